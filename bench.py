@@ -9,7 +9,15 @@ graph; one K-wide sweep = 16 topic-iterations = one "step"), the top-k half
 one batch = one step) is reported under "topk" in the same line, BASELINE config 2
 (2^20 nodes / 5M edges, one vector, to eps 1e-6) under "config2".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run measures only the headline: it builds the inputs, runs W untimed steps, times exactly K steps of the workload
+that `value` is read from and prints the line.  --full adds everything else the line can report: five timed blocks
+instead of one (min / median), the to-convergence and end-to-end calls, the two-vector form, the gather probes, the CPU
+baselines, BASELINE config 2, the top-k half next to the PageRank one and, at N>1, the variants that are never `value`.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy in float64 (of the rank
+table a fixed, seeded sample of DUMP_COLUMNS node columns; of top-k every field of the hits), so that two builds can be
+compared output for output.
 
 N>1: one process per GPU.  Started without a launcher (WORLD_SIZE unset) this script spawns the N
 ranks itself with torch.distributed.run — before it touches the GPU — relays rank 0's line and exits
@@ -84,7 +92,8 @@ os.environ["OMP_NUM_THREADS"] = str(OMP_THREADS)
 TFIDF_KERNELS = ("k_weight_count", "k_scatter", "k_bucket_sum")   # the three passes over the body table's postings
 SCORE_WARM = 50         # untimed scoring batches in front of every timed scoring region, whatever --warmup says (see timed_blocks)
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
-N_BLOCKS = 5            # timed blocks of --steps per measurement: the first is `value`, all give min/median
+N_BLOCKS = 5            # timed blocks of --steps per measurement under --full: the first is `value`, all give min/median
+DUMP_COLUMNS = 1 << 18  # node columns of the rank table written by --dump-outputs: 16 topics x 2^18 x 8 B = 32 MB
 
 
 def profiled_traffic(kernel: str, pick: str = "median"):
@@ -160,7 +169,14 @@ def main() -> None:
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget per half")
     ap.add_argument("--settle", type=float, default=float(os.environ.get("SS_BENCH_SETTLE_S", "8")),
                     help="seconds to wait before the first GPU call (outside every timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (repeat blocks, convergence and end-to-end calls, CPU baselines, "
+                         "config 2, the top-k half, N>1 variants that are never `value`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -216,16 +232,18 @@ def main() -> None:
         return float(t.item())
 
     K, W = args.steps, args.warmup
+    head_blocks = N_BLOCKS if args.full else 1
 
-    def timed_blocks(step_k, warm=None, n_blocks=N_BLOCKS, min_warm=0):
-        """W untimed warm-up steps, then N_BLOCKS blocks of EXACTLY K steps, each bracketed by barrier + synchronize on
-        both sides and reduced with max over ranks.  -> (seconds of the first block, [ms per step of every block]).
+    def timed_blocks(step_k, warm=None, n_blocks=None, min_warm=0):
+        """W untimed warm-up steps, then `n_blocks` blocks (default: N_BLOCKS under --full, else one) of EXACTLY K steps, each
+        bracketed by barrier + synchronize on both sides and reduced with max over ranks.  -> (seconds of the first block,
+        [ms per step of every block]).
         `min_warm`: the scoring sections ask for at least SCORE_WARM untimed batches whatever --warmup says — back-to-back batches
         take ~40 calls after an idle stream to reach their steady rate (0.375 / 0.355 / 0.343 ms for the first three blocks of 20),
         and the driver's command has --warmup 5; the line says so (`topk.untimed_warmup_batches`)."""
         (warm or step_k)(max(W, 1, min_warm))
         secs = []
-        for _ in range(n_blocks):
+        for _ in range(n_blocks or head_blocks):
             barrier()
             t0 = time.perf_counter()
             step_k(K)
@@ -246,6 +264,7 @@ def main() -> None:
     ctx.set_stream(stream.cuda_stream)
     result: dict = {}
     invalid: list = []
+    dumps: dict = {}                             # --dump-outputs: name -> float64 array
 
     def emit() -> None:
         if rank != 0:
@@ -343,8 +362,11 @@ def main() -> None:
                 pr.begin()
                 dt, blocks = timed_blocks(pr.step)
                 st = pr.status()
-                assert st["sweeps"] == max(W, 1) + N_BLOCKS * K, st
+                assert st["sweeps"] == max(W, 1) + len(blocks) * K, st
                 kern_ms = ctx.last_kernel_ms(0) / K     # HIP events on the library's stream around the K launches of the last block
+                if args.dump_outputs:
+                    cols = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_COLUMNS), replace=False))
+                    dumps["pagerank_ranks"] = pr.read()[:, cols]       # [topics][sampled nodes] after the last timed sweep
                 result.update({
                     "metric": "pagerank_iters_per_sec", "value": kt * K / dt, "unit": "topic-iterations/s",
                     "ms_per_step": dt * 1e3 / K, "ms_per_step_blocks": summarize(blocks),
@@ -359,7 +381,7 @@ def main() -> None:
                                       "kernel_ms": kern_ms, "algorithmic_bytes": algo_bytes}
                 if tr:
                     result["roofline"]["traffic_detail"] = tr
-                if kt >= 5:
+                if kt >= 5 and args.full:
                     # what the sweep's access pattern alone costs on this chip: gather-only passes over the same index
                     # stream and table (ss_pr_probe), beside a hub-free and a streamed variant
                     gc = {name: pr.probe(mode, 5) for mode, name in ((0, "graph_index_stream"), (1, "uniform_random_rows"), (2, "consecutive_rows"))}
@@ -370,7 +392,7 @@ def main() -> None:
                 # Several GPUs.  The headline is the doc-range split with its per-sweep RCCL exchange (BASELINE config 4);
                 # the collective-free topic split is kept under "decompositions" for comparison only.
                 decomp = {}
-                if kt % world == 0:
+                if kt % world == 0 and args.full:
                     try:
                         g1 = engine.Graph(ctx, n, out_ptr, out_dst)
                         mine = n_topic[rank * (kt // world):(rank + 1) * (kt // world)]
@@ -404,7 +426,7 @@ def main() -> None:
 
                         dt_, blocks_ = timed_blocks(sweeps)
                         stat = st_.status()
-                        assert stat["sweeps"] == max(W, 1) + N_BLOCKS * K, stat
+                        assert stat["sweeps"] == max(W, 1) + len(blocks_) * K, stat
                         sp, sb, rp, rb = st_.exchange_buffers()
                         # xGMI is point-to-point: a rank receives (world-1)/world of the table over its 7 links (~50 GB/s each
                         # achievable of 64 GB/s per direction), so the exchange alone costs at least this much per sweep
@@ -449,55 +471,57 @@ def main() -> None:
                                "sweeps_per_sec": head["value"] / kt, "parallelism": head["parallelism"]},
                     "decompositions": decomp,
                 })
-            # to-convergence run at the BASELINE eps (not timed into `value`)
-            try:
-                prc = engine.PageRankState(g, d, 1e-6, n_topic)
-                exc = sharding.DistExchange(prc, dev, host_staged=rehearsal) if world > 1 else None
-                barrier()
-                t0 = time.perf_counter()
-                if world == 1:
-                    prc.begin()
-                    stc = prc.status()
-                    while stc["n_active"] > 0:
-                        prc.step(4)
+            prc = None
+            if args.full:
+                # to-convergence run at the BASELINE eps (not timed into `value`)
+                try:
+                    prc = engine.PageRankState(g, d, 1e-6, n_topic)
+                    exc = sharding.DistExchange(prc, dev, host_staged=rehearsal) if world > 1 else None
+                    barrier()
+                    t0 = time.perf_counter()
+                    if world == 1:
+                        prc.begin()
                         stc = prc.status()
-                else:
-                    stc = sharding.iterate([prc], exc, batch=4)
-                barrier()
-                result["config"]["to_convergence_eps1e-6"] = {"iters": [int(x) for x in stc["iters"]],
-                                                              "seconds": time.perf_counter() - t0}
-            except Exception as exc_:
+                        while stc["n_active"] > 0:
+                            prc.step(4)
+                            stc = prc.status()
+                    else:
+                        stc = sharding.iterate([prc], exc, batch=4)
+                    barrier()
+                    result["config"]["to_convergence_eps1e-6"] = {"iters": [int(x) for x in stc["iters"]],
+                                                                  "seconds": time.perf_counter() - t0}
+                except Exception as exc_:
+                    if world == 1:
+                        raise
+                    result["to_convergence_error"] = repr(exc_)
+                    prc = None
+                if world == 1 and args.workload == "both" and n == args.docs:
+                    c4_ranks = prc.read()                   # [K][N] converged ranks: the prior of the blended top-k run (config 5)
                 if world == 1:
-                    raise
-                result["to_convergence_error"] = repr(exc_)
-                prc = None
-            if world == 1 and args.workload == "both" and n == args.docs:
-                c4_ranks = prc.read()                   # [K][N] converged ranks: the prior of the blended top-k run (config 5)
-            if world == 1:
-                # the other damping factor SURVEY.md §8d asks for (a sweep costs the same; only the iteration counts move)
-                p85 = engine.PageRankState(g, 0.85, 1e-6, n_topic)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                p85.begin()
-                s85 = p85.status()
-                while s85["n_active"] > 0:
-                    p85.step(4)
+                    # the other damping factor SURVEY.md §8d asks for (a sweep costs the same; only the iteration counts move)
+                    p85 = engine.PageRankState(g, 0.85, 1e-6, n_topic)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    p85.begin()
                     s85 = p85.status()
-                torch.cuda.synchronize()
-                result["config"]["to_convergence_eps1e-6_d0.85"] = {"iters": [int(x) for x in s85["iters"]], "seconds": time.perf_counter() - t0}
-                p85.close()
-                # the reference's own call (start_crawl.go:175: d=0.75, eps=1e-20 — to the floating-point fixed point)
-                pref = engine.PageRankState(g, 0.75, 1e-20, n_topic, max_iter=500)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                pref.begin()
-                sref = pref.status()
-                while sref["n_active"] > 0:
-                    pref.step(4)
+                    while s85["n_active"] > 0:
+                        p85.step(4)
+                        s85 = p85.status()
+                    torch.cuda.synchronize()
+                    result["config"]["to_convergence_eps1e-6_d0.85"] = {"iters": [int(x) for x in s85["iters"]], "seconds": time.perf_counter() - t0}
+                    p85.close()
+                    # the reference's own call (start_crawl.go:175: d=0.75, eps=1e-20 — to the floating-point fixed point)
+                    pref = engine.PageRankState(g, 0.75, 1e-20, n_topic, max_iter=500)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pref.begin()
                     sref = pref.status()
-                torch.cuda.synchronize()
-                result["config"]["to_convergence_reference_eps1e-20"] = {"iters": [int(x) for x in sref["iters"]], "seconds": time.perf_counter() - t0}
-                pref.close()
+                    while sref["n_active"] > 0:
+                        pref.step(4)
+                        sref = pref.status()
+                    torch.cuda.synchronize()
+                    result["config"]["to_convergence_reference_eps1e-20"] = {"iters": [int(x) for x in sref["iters"]], "seconds": time.perf_counter() - t0}
+                    pref.close()
             if prc is not None:
                 prc.close()
 
@@ -529,7 +553,7 @@ def main() -> None:
                 del r_dev
                 return out_
 
-            if world == 1:
+            if world == 1 and args.full:
                 e2e = end_to_end(n, out_ptr, out_dst, n_topic)
                 result["pagerank_end_to_end"] = {
                     "what": "out-edge CSR -> ss_graph_create -> ss_pagerank_run (ranks left in HBM), synchronised wall clock, best of 3",
@@ -537,7 +561,7 @@ def main() -> None:
 
             # ---- the two-vector form (option pr.affine; opt-in, never the headline): the reference's topics differ only in their start
             #      value 1/n_k and its recurrence maps x = (p*u + q) / (r*u + s) onto itself, so two vectors carry all K topics
-            if world == 1:
+            if world == 1 and args.full:
                 ge = engine.Graph(ctx, n, out_ptr, out_dst)
                 r_ref = torch.empty((len(n_topic), n), dtype=torch.float64, device=dev)
                 r_aff = torch.empty((len(n_topic), n), dtype=torch.float64, device=dev)
@@ -587,7 +611,7 @@ def main() -> None:
                 del r_ref, r_aff
 
             # ---- CPU baseline: the oracle on the same graph, bounded sample
-            if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
                 from oracle import pyoracle
                 log("cpu baseline (PageRank): flat port, reference-shaped, OpenMP ...")
                 h_ptr = out_ptr.cpu().numpy().view(np.uint64)
@@ -645,7 +669,7 @@ def main() -> None:
             torch.cuda.empty_cache()
 
             # ---- BASELINE config 2: 2^20 nodes / 5M edges, ONE vector (the K=1 kernel classes), to eps = 1e-6
-            if world == 1 and not args.no_config2:
+            if world == 1 and args.full and not args.no_config2:
                 n2, e2 = 1 << 20, 5_000_000
                 o2p, o2d = synth.rmat_graph_torch(n2, e2, seed=42, device=dev)
                 g2 = engine.Graph(ctx, n2, o2p, o2d)
@@ -686,7 +710,7 @@ def main() -> None:
                 torch.cuda.empty_cache()
 
         # ------------------------------------------------------------------ top-k half
-        if args.workload in ("both", "topk"):
+        if args.workload == "topk" or (args.workload == "both" and args.full):
             nd, nt, k, nq = args.docs, args.terms, args.k, args.queries
             t0 = time.time()
             b_ptr, b_doc, b_tf = synth.zipf_index_torch(nd, nt, args.body_postings, seed=44, device=dev)
@@ -699,13 +723,13 @@ def main() -> None:
             h_bptr = b_ptr.cpu().numpy().view(np.uint64)
             h_tptr = t_ptr.cpu().numpy().view(np.uint64)
             Pb, Pt = int(b_doc.numel()), int(t_doc.numel())
-            keep_host = rank == 0 and world == 1 and not args.no_cpu_baseline
+            keep_host = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
             if keep_host:
                 h_bdoc = b_doc.cpu().numpy().view(np.uint32)
                 h_tdoc = t_doc.cpu().numpy().view(np.uint32)
             shard = None
             shard_error = None
-            if world > 1:
+            if world > 1 and args.full:
                 try:
                     # doc-range shard of the same index: this rank's slice of every posting list
                     lo, hi = sharding.doc_range(nd, rank, world)
@@ -724,10 +748,11 @@ def main() -> None:
             # the build is timed ONCE (it weights the table in place), right behind seconds of host-side copies during which the GPU
             # has clocked down: an untimed build of a throwaway copy of the body table first, as every other section warms up
             # (tools/tfidf_place.py: the same build 5.3 ms warm, 5.5 behind a 5 s pause)
-            wi = engine.InvertedIndex(ctx, nd, b_ptr, b_doc, b_tf.clone())
-            wi.tfidf_build(nd, want_w=False, want_mag=False, want_idf=False)
-            wi.close()
-            del wi
+            if args.full:
+                wi = engine.InvertedIndex(ctx, nd, b_ptr, b_doc, b_tf.clone())
+                wi.tfidf_build(nd, want_w=False, want_mag=False, want_idf=False)
+                wi.close()
+                del wi
             del b_ptr, b_doc, b_tf, t_ptr, t_doc, t_tf
             torch.cuda.empty_cache()
             wt, mt, _ = ti.tfidf_build(nd, want_w=keep_host, want_mag=keep_host, want_idf=False)   # title first (start_crawl.go:176)
@@ -756,287 +781,297 @@ def main() -> None:
             ctx.set_option("score.timing", 0)        # the timed regions run without the library's two timing events per call
             dt, blocks = timed_blocks(batches, min_warm=SCORE_WARM)       # (instrumentation: each costs the stream a few us; they are switched on again for
             ctx.set_option("score.timing", None)     #  the kernel-time loop below and for everything that reads ss_last_kernel_ms)
-            # Device time per batch of the SAME back-to-back calls, by HIP events on the stream the hits are produced on (the merge of
-            # every batch runs on it, in call order: the interval from the first call's start to the last merge's end is the time the
-            # device spent on K batches with its pipelining as it is in production) — the roofline's `achieved` uses this figure ...
-            ctx.set_option("score.timing", 0)
-            batches(max(W, 1, SCORE_WARM))
-            ctx.synchronize(); torch.cuda.synchronize()
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record(stream)
-            batches(K)
-            ev1.record(stream)
-            ev1.synchronize()
-            period_ms = ev0.elapsed_time(ev1) / K
-            ctx.set_option("score.timing", None)
-            # ... and the kernels of ONE batch on its own (device query arrays: each call waits for the stream before it plans, so
-            # nothing overlaps): prep + wave + merge one after the other, the figure a kernel trace of `score.pipeline` = 0 gives
-            kms = []
-            for _ in range(min(K, 10)):
-                sc.score_topk(d_qptr, d_qterms, k, out=(d_hits, d_nhits))
-                kms.append(ctx.last_kernel_ms(1))
-            kern_ms = sum(kms) / len(kms)
-            # option "score.pipeline" = 0 for comparison: every scoring kernel on the one stream (round 3's default).  Same batches,
-            # same hits.  [The default since round 4 keeps the stream-order contract: the merge — the kernel that writes the hits —
-            # stays on the caller's stream, k_score_wave moves to an internal one.]
-            pipelined = None
-            if world == 1:
-                ctx.synchronize(); torch.cuda.synchronize()
-                ref_h, ref_n = d_hits.clone(), d_nhits.clone()
-                ctx.set_option("score.timing", 0)
-                ctx.set_option("score.pipeline", 0)
-                dtp, blocks_p = timed_blocks(batches, min_warm=SCORE_WARM)
-                ctx.synchronize(); torch.cuda.synchronize()
-                same_p = bool(torch.equal(ref_h, d_hits) and torch.equal(ref_n, d_nhits))
-                ctx.set_option("score.pipeline", None)
-                ctx.set_option("score.timing", None)
-                pipelined = {"value": nq * K / dtp, "unit": "queries/s", "ms_per_step": dtp * 1e3 / K, "ms_per_step_blocks": summarize(blocks_p),
-                             "hits_equal_default": same_p,
-                             "what": "option score.pipeline=0: k_wave_prep, k_score_wave and k_merge_flat of a batch all on the caller's stream, "
-                                     "one batch after the other (the default runs k_score_wave of batch i+1 on an internal stream under k_merge_flat of batch i)"}
-                assert same_p
-                del ref_h, ref_n
-            t0 = time.perf_counter()
-            for _ in range(K):
-                hits, n_hits = sc.score_topk(q_ptr, q_terms, k)      # host in, host out: PCIe-inclusive
-            dt_pcie = time.perf_counter() - t0
-            # the same host-in / host-out batches with three in flight (ss_score_topk_submit / _collect): what a server with the
-            # next requests ready gets; the hits must be the synchronous call's
-            outs3 = [(np.zeros((nq, k), dtype=hits.dtype), np.zeros(nq, dtype=np.int32)) for _ in range(3)]
-            def in_flight(n):
-                fl = []
-                for i in range(n):
-                    if len(fl) == 3:
-                        tk, o = fl.pop(0); sc.collect(tk, out=o)
-                    fl.append((sc.submit(q_ptr, q_terms, k), outs3[i % 3]))
-                for tk, o in fl: sc.collect(tk, out=o)
-            in_flight(6)
-            t0 = time.perf_counter()
-            in_flight(K)
-            dt_flight = time.perf_counter() - t0
-            assert all(np.array_equal(o[0], hits) and np.array_equal(o[1], n_hits) for o in outs3)
-            algo_q = 8 * sum_df + 36 * k * nq           # SURVEY.md §8d B_q without the per-candidate magnitude term
-            ach = algo_q / (period_ms * 1e-3) / 1e9      # steady state: device time per batch of K overlapping batches
-            ach1 = algo_q / (kern_ms * 1e-3) / 1e9       # one batch's kernels alone
-            full = (nd, nt, nq, k) == (10_000_000, 1_000_000, 1024, 100)
-            algo_tw = 12 * Pb + 8 * nt + 8 * nd         # SURVEY.md §8d B_tw = 12P + 8T + 8N (body table)
-            ach_tw = algo_tw / (tfidf_ms * 1e-3) / 1e9
-            tw_traffic = None
-            tw_detail = None
-            sc_traffic = None
-            if full:
-                parts = [profiled_traffic(kn, pick="max") for kn in TFIDF_KERNELS]
-                if all(parts):
-                    tw_traffic = sum(p["bytes"] for p in parts)
-                    tw_detail = {kn: {"fetch_size_raw_bytes": p["fetch_size_raw_bytes"], "write_size_bytes": p["write_size_bytes"]} for kn, p in zip(TFIDF_KERNELS, parts)}
-                    tw_detail["source"] = parts[0]["source"]
-                    tw_detail["dispatch"] = parts[0]["dispatch"]
-                    # a full pass cannot move fewer bytes than it must read and write: such a figure is a selection error
-                    if tw_traffic < algo_tw:
-                        invalid.append(f"tfidf roofline.traffic {tw_traffic:.3e} B below the algorithmic bytes {algo_tw:.3e} B")
-                parts = [profiled_traffic(kn) for kn in ("k_wave_prep", "k_score_wave", "k_merge_flat")]
-                if all(parts):
-                    sc_traffic = sum(p["bytes"] for p in parts)
             topk = {"metric": "topk_queries_per_sec", "value": world * nq * K / dt, "unit": "queries/s",
                     "ms_per_step": dt * 1e3 / K, "ms_per_step_blocks": summarize(blocks), "scaling": "weak",
                     "config": {"workload": f"{nd} docs / {nt} terms, body P={Pb}, title P={Pt}, {nq} x 3-term OR queries "
                                            f"(term ranks U[1,10000]), cosine top-{k} (BASELINE config 3)",
                                "postings_per_query": sum_df / nq,
                                "parallelism": "single GPU" if world == 1 else f"query-split replicas x{world}"},
-                    "roofline": {"bound": "hbm", "achieved": ach1, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": ach1 / HBM_PEAK_GBS,
-                                 "traffic": sc_traffic,
-                                 "kernel": "scoring kernels of one batch (k_wave_prep + k_score_wave + k_merge_flat); `kernel_ms` = their summed device time "
-                                           "for ONE batch with nothing beside it (HIP events on the library's stream; what a kernel trace of score.pipeline=0 "
-                                           "shows per kernel, summed).  Back-to-back batches overlap (k_score_wave of batch i+1 runs under k_merge_flat of "
-                                           "batch i): that steady-state period is `pipelined_period_ms` / `frac_steady_state`, not a kernel time",
-                                 "kernel_ms": kern_ms, "kernel_ms_min": min(kms), "algorithmic_bytes": algo_q,
-                                 "pipelined_period_ms": period_ms, "achieved_steady_state": ach, "frac_steady_state": ach / HBM_PEAK_GBS},
-                    "untimed_warmup_batches": max(W, 1, SCORE_WARM),
-                    "tfidf": {"ms": tfidf_ms, "title_ms": tfidf_title_ms,
-                              "what": "ss_tfidf_build of the body table: device time between HIP events (allocations outside), after one untimed build of a throwaway copy of the table",
-                              "roofline": {"bound": "hbm", "achieved": ach_tw, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_tw / HBM_PEAK_GBS,
-                                           "traffic": tw_traffic, "traffic_detail": tw_detail,
-                                           "kernel": "k_idf + head-list set-up + k_weight_count + k_scatter + k_bucket_sum",
-                                           "kernel_ms": tfidf_ms, "algorithmic_bytes": algo_tw}},
-                    "tfidf_build_ms": tfidf_ms, "scorer_create_ms": scorer_create_ms,
-                    "queries_per_sec_host_in_host_out": nq * K / dt_pcie,
-                    "queries_per_sec_host_in_host_out_3_in_flight": nq * K / dt_flight}
-            if pipelined is not None:
-                topk["one_stream_option"] = pipelined
-
-            # ---- one query through the ABI, host in / host out (the reference's call shape: one Retrieve per request,
-            #      k = 50, main_retrieve.go:99-100)
-            lat = []
-            for i in range(40):
-                q1p = np.array([0, 3], dtype=np.uint32)
-                q1t = q_terms[3 * (i % nq):3 * (i % nq) + 3]
+                    "untimed_warmup_batches": max(W, 1, SCORE_WARM)}
+            if args.dump_outputs:
+                # the hits of the last timed batch, as the caller's records: one array per field, empty slots doc -1 / score 0
+                hh = d_hits.cpu().numpy().view(engine.HIT_DTYPE).reshape(nq, k)
+                nh = d_nhits.cpu().numpy()
+                filled = np.arange(k)[None, :] < nh[:, None]
+                dumps["topk_n_hits"] = nh.astype(np.float64)
+                for f_ in ("doc", "title", "body", "pagerank", "final"):
+                    dumps["topk_" + f_] = np.where(filled, hh[f_], -1 if f_ == "doc" else 0).astype(np.float64)
+            if args.full:
+                # Device time per batch of the SAME back-to-back calls, by HIP events on the stream the hits are produced on (the merge of
+                # every batch runs on it, in call order: the interval from the first call's start to the last merge's end is the time the
+                # device spent on K batches with its pipelining as it is in production) — the roofline's `achieved` uses this figure ...
+                ctx.set_option("score.timing", 0)
+                batches(max(W, 1, SCORE_WARM))
+                ctx.synchronize(); torch.cuda.synchronize()
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record(stream)
+                batches(K)
+                ev1.record(stream)
+                ev1.synchronize()
+                period_ms = ev0.elapsed_time(ev1) / K
+                ctx.set_option("score.timing", None)
+                # ... and the kernels of ONE batch on its own (device query arrays: each call waits for the stream before it plans, so
+                # nothing overlaps): prep + wave + merge one after the other, the figure a kernel trace of `score.pipeline` = 0 gives
+                kms = []
+                for _ in range(min(K, 10)):
+                    sc.score_topk(d_qptr, d_qterms, k, out=(d_hits, d_nhits))
+                    kms.append(ctx.last_kernel_ms(1))
+                kern_ms = sum(kms) / len(kms)
+                # option "score.pipeline" = 0 for comparison: every scoring kernel on the one stream (round 3's default).  Same batches,
+                # same hits.  [The default since round 4 keeps the stream-order contract: the merge — the kernel that writes the hits —
+                # stays on the caller's stream, k_score_wave moves to an internal one.]
+                pipelined = None
+                if world == 1:
+                    ctx.synchronize(); torch.cuda.synchronize()
+                    ref_h, ref_n = d_hits.clone(), d_nhits.clone()
+                    ctx.set_option("score.timing", 0)
+                    ctx.set_option("score.pipeline", 0)
+                    dtp, blocks_p = timed_blocks(batches, min_warm=SCORE_WARM)
+                    ctx.synchronize(); torch.cuda.synchronize()
+                    same_p = bool(torch.equal(ref_h, d_hits) and torch.equal(ref_n, d_nhits))
+                    ctx.set_option("score.pipeline", None)
+                    ctx.set_option("score.timing", None)
+                    pipelined = {"value": nq * K / dtp, "unit": "queries/s", "ms_per_step": dtp * 1e3 / K, "ms_per_step_blocks": summarize(blocks_p),
+                                 "hits_equal_default": same_p,
+                                 "what": "option score.pipeline=0: k_wave_prep, k_score_wave and k_merge_flat of a batch all on the caller's stream, "
+                                         "one batch after the other (the default runs k_score_wave of batch i+1 on an internal stream under k_merge_flat of batch i)"}
+                    assert same_p
+                    del ref_h, ref_n
                 t0 = time.perf_counter()
-                sc.score_topk(q1p, q1t, 50)
-                lat.append((time.perf_counter() - t0) * 1e3)
-            lat = lat[5:]
-            topk["latency_single_query_ms"] = {"median": statistics.median(lat), "min": min(lat), "p90": sorted(lat)[int(len(lat) * 0.9)],
-                                               "what": "one 3-term OR query, k=50, host buffers in and out through ss_score_topk"}
+                for _ in range(K):
+                    hits, n_hits = sc.score_topk(q_ptr, q_terms, k)      # host in, host out: PCIe-inclusive
+                dt_pcie = time.perf_counter() - t0
+                # the same host-in / host-out batches with three in flight (ss_score_topk_submit / _collect): what a server with the
+                # next requests ready gets; the hits must be the synchronous call's
+                outs3 = [(np.zeros((nq, k), dtype=hits.dtype), np.zeros(nq, dtype=np.int32)) for _ in range(3)]
+                def in_flight(n):
+                    fl = []
+                    for i in range(n):
+                        if len(fl) == 3:
+                            tk, o = fl.pop(0); sc.collect(tk, out=o)
+                        fl.append((sc.submit(q_ptr, q_terms, k), outs3[i % 3]))
+                    for tk, o in fl: sc.collect(tk, out=o)
+                in_flight(6)
+                t0 = time.perf_counter()
+                in_flight(K)
+                dt_flight = time.perf_counter() - t0
+                assert all(np.array_equal(o[0], hits) and np.array_equal(o[1], n_hits) for o in outs3)
+                algo_q = 8 * sum_df + 36 * k * nq           # SURVEY.md §8d B_q without the per-candidate magnitude term
+                ach = algo_q / (period_ms * 1e-3) / 1e9      # steady state: device time per batch of K overlapping batches
+                ach1 = algo_q / (kern_ms * 1e-3) / 1e9       # one batch's kernels alone
+                full = (nd, nt, nq, k) == (10_000_000, 1_000_000, 1024, 100)
+                algo_tw = 12 * Pb + 8 * nt + 8 * nd         # SURVEY.md §8d B_tw = 12P + 8T + 8N (body table)
+                ach_tw = algo_tw / (tfidf_ms * 1e-3) / 1e9
+                tw_traffic = None
+                tw_detail = None
+                sc_traffic = None
+                if full:
+                    parts = [profiled_traffic(kn, pick="max") for kn in TFIDF_KERNELS]
+                    if all(parts):
+                        tw_traffic = sum(p["bytes"] for p in parts)
+                        tw_detail = {kn: {"fetch_size_raw_bytes": p["fetch_size_raw_bytes"], "write_size_bytes": p["write_size_bytes"]} for kn, p in zip(TFIDF_KERNELS, parts)}
+                        tw_detail["source"] = parts[0]["source"]
+                        tw_detail["dispatch"] = parts[0]["dispatch"]
+                        # a full pass cannot move fewer bytes than it must read and write: such a figure is a selection error
+                        if tw_traffic < algo_tw:
+                            invalid.append(f"tfidf roofline.traffic {tw_traffic:.3e} B below the algorithmic bytes {algo_tw:.3e} B")
+                    parts = [profiled_traffic(kn) for kn in ("k_wave_prep", "k_score_wave", "k_merge_flat")]
+                    if all(parts):
+                        sc_traffic = sum(p["bytes"] for p in parts)
+                topk.update({
+                        "roofline": {"bound": "hbm", "achieved": ach1, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": ach1 / HBM_PEAK_GBS,
+                                     "traffic": sc_traffic,
+                                     "kernel": "scoring kernels of one batch (k_wave_prep + k_score_wave + k_merge_flat); `kernel_ms` = their summed device time "
+                                               "for ONE batch with nothing beside it (HIP events on the library's stream; what a kernel trace of score.pipeline=0 "
+                                               "shows per kernel, summed).  Back-to-back batches overlap (k_score_wave of batch i+1 runs under k_merge_flat of "
+                                               "batch i): that steady-state period is `pipelined_period_ms` / `frac_steady_state`, not a kernel time",
+                                     "kernel_ms": kern_ms, "kernel_ms_min": min(kms), "algorithmic_bytes": algo_q,
+                                     "pipelined_period_ms": period_ms, "achieved_steady_state": ach, "frac_steady_state": ach / HBM_PEAK_GBS},
+                        "tfidf": {"ms": tfidf_ms, "title_ms": tfidf_title_ms,
+                                  "what": "ss_tfidf_build of the body table: device time between HIP events (allocations outside), after one untimed build of a throwaway copy of the table",
+                                  "roofline": {"bound": "hbm", "achieved": ach_tw, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_tw / HBM_PEAK_GBS,
+                                               "traffic": tw_traffic, "traffic_detail": tw_detail,
+                                               "kernel": "k_idf + head-list set-up + k_weight_count + k_scatter + k_bucket_sum",
+                                               "kernel_ms": tfidf_ms, "algorithmic_bytes": algo_tw}},
+                        "tfidf_build_ms": tfidf_ms, "scorer_create_ms": scorer_create_ms,
+                        "queries_per_sec_host_in_host_out": nq * K / dt_pcie,
+                        "queries_per_sec_host_in_host_out_3_in_flight": nq * K / dt_flight})
+                if pipelined is not None:
+                    topk["one_stream_option"] = pipelined
 
-            # ---- tail queries: term ranks uniform over the whole vocabulary, reported separately
-            tq_ptr, tq_terms = synth.make_queries(nq, 3, nt, seed=1045 + rank)
-            # ... one at a time and eight at a time first (a web query hits tail terms: a call whose queries are all small takes
-            # k_score_small — one launch that writes the hits; option "score.small" = 0 is the slices kernel + merge)
-            def small_calls(n_per_call):
-                ms_ = []
-                qp_ = (np.arange(n_per_call + 1) * 3).astype(np.uint32)
+                # ---- one query through the ABI, host in / host out (the reference's call shape: one Retrieve per request,
+                #      k = 50, main_retrieve.go:99-100)
+                lat = []
                 for i in range(40):
-                    qt_ = tq_terms[3 * n_per_call * (i % (nq // n_per_call)):3 * n_per_call * (i % (nq // n_per_call) + 1)]
+                    q1p = np.array([0, 3], dtype=np.uint32)
+                    q1t = q_terms[3 * (i % nq):3 * (i % nq) + 3]
                     t0 = time.perf_counter()
-                    sc.score_topk(qp_, qt_, 50)
-                    ms_.append((time.perf_counter() - t0) * 1e3)
-                return statistics.median(ms_[5:])
-            lat_tail = {"one_query_ms": small_calls(1), "eight_queries_ms": small_calls(8)}
-            ctx.set_option("score.small", 0)
-            lat_tail["one_query_ms_small_kernel_off"] = small_calls(1)
-            lat_tail["eight_queries_ms_small_kernel_off"] = small_calls(8)
-            ctx.set_option("score.small", None)
-            lat_tail["what"] = "3-term OR queries of term ranks U[1,1000000], k=50, host buffers in and out through ss_score_topk; medians of 35 calls"
-            topk["latency_tail_queries_ms"] = lat_tail
-            ctx.set_option("score.timing", 0)
-            # (three blocks of K batches, the median one reported: a single block of these 0.1 ms batches is at the mercy of one host hiccup —
-            #  r05h_bench_full: 0.167 ms in a run whose neighbours measured 0.090-0.096)
-            _, tblocks = timed_blocks(lambda m: batches(m, tq_ptr, tq_terms), n_blocks=3, min_warm=SCORE_WARM)
-            dtt = statistics.median(tblocks) * K / 1e3
-            ctx.set_option("score.timing", None)
-            tail_df = int(sum((h_bptr[t + 1] - h_bptr[t]) + (h_tptr[t + 1] - h_tptr[t]) for t in tq_terms.astype(np.int64)))
-            topk["tail_queries"] = {"value": world * nq * K / dtt, "unit": "queries/s", "ms_per_step": dtt * 1e3 / K, "ms_per_step_blocks": summarize(tblocks),
-                                    "workload": f"{nq} x 3-term OR queries, term ranks U[1,{nt}]", "postings_per_query": tail_df / nq}
+                    sc.score_topk(q1p, q1t, 50)
+                    lat.append((time.perf_counter() - t0) * 1e3)
+                lat = lat[5:]
+                topk["latency_single_query_ms"] = {"median": statistics.median(lat), "min": min(lat), "p90": sorted(lat)[int(len(lat) * 0.9)],
+                                                   "what": "one 3-term OR query, k=50, host buffers in and out through ss_score_topk"}
 
-            # ---- mixed batches: term ranks over the first 100k terms (long and short lists in one query: the batch runs in
-            #      k_score_slices), and a batch that is half head / half tail queries (split per query between the two scoring kernels,
-            #      which run side by side on two streams)
-            mq_ptr, mq_terms = synth.make_queries(nq, 3, min(100_000, nt), seed=2045 + rank)
-            hq = nq // 2
-            hh_ptr = np.concatenate([q_ptr[:hq + 1], tq_ptr[1:nq - hq + 1] + q_ptr[hq]]).astype(np.uint32)
-            hh_terms = np.concatenate([q_terms[:q_ptr[hq]], tq_terms[:tq_ptr[nq - hq]]]).astype(np.uint32)
-            ctx.set_option("score.timing", 0)
-            for key_, (qp_, qt_), what_ in (("mixed_queries", (mq_ptr, mq_terms), f"{nq} x 3-term OR queries, term ranks U[1,{min(100_000, nt)}]"),
-                                            ("half_head_half_tail", (hh_ptr, hh_terms), f"{hq} queries of term ranks U[1,10000] + {nq - hq} of U[1,{nt}] in one batch")):
-                _, mblocks = timed_blocks(lambda m: batches(m, qp_, qt_), n_blocks=3, min_warm=SCORE_WARM)
-                dtm = statistics.median(mblocks) * K / 1e3
-                dfm = int(sum((h_bptr[t + 1] - h_bptr[t]) + (h_tptr[t + 1] - h_tptr[t]) for t in qt_.astype(np.int64)))
-                topk[key_] = {"value": world * nq * K / dtm, "unit": "queries/s", "ms_per_step": dtm * 1e3 / K, "ms_per_step_blocks": summarize(mblocks), "workload": what_, "postings_per_query": dfm / nq}
-            ctx.set_option("score.timing", None)
+                # ---- tail queries: term ranks uniform over the whole vocabulary, reported separately
+                tq_ptr, tq_terms = synth.make_queries(nq, 3, nt, seed=1045 + rank)
+                # ... one at a time and eight at a time first (a web query hits tail terms: a call whose queries are all small takes
+                # k_score_small — one launch that writes the hits; option "score.small" = 0 is the slices kernel + merge)
+                def small_calls(n_per_call):
+                    ms_ = []
+                    qp_ = (np.arange(n_per_call + 1) * 3).astype(np.uint32)
+                    for i in range(40):
+                        qt_ = tq_terms[3 * n_per_call * (i % (nq // n_per_call)):3 * n_per_call * (i % (nq // n_per_call) + 1)]
+                        t0 = time.perf_counter()
+                        sc.score_topk(qp_, qt_, 50)
+                        ms_.append((time.perf_counter() - t0) * 1e3)
+                    return statistics.median(ms_[5:])
+                lat_tail = {"one_query_ms": small_calls(1), "eight_queries_ms": small_calls(8)}
+                ctx.set_option("score.small", 0)
+                lat_tail["one_query_ms_small_kernel_off"] = small_calls(1)
+                lat_tail["eight_queries_ms_small_kernel_off"] = small_calls(8)
+                ctx.set_option("score.small", None)
+                lat_tail["what"] = "3-term OR queries of term ranks U[1,1000000], k=50, host buffers in and out through ss_score_topk; medians of 35 calls"
+                topk["latency_tail_queries_ms"] = lat_tail
+                ctx.set_option("score.timing", 0)
+                # (three blocks of K batches, the median one reported: a single block of these 0.1 ms batches is at the mercy of one host hiccup —
+                #  r05h_bench_full: 0.167 ms in a run whose neighbours measured 0.090-0.096)
+                _, tblocks = timed_blocks(lambda m: batches(m, tq_ptr, tq_terms), n_blocks=3, min_warm=SCORE_WARM)
+                dtt = statistics.median(tblocks) * K / 1e3
+                ctx.set_option("score.timing", None)
+                tail_df = int(sum((h_bptr[t + 1] - h_bptr[t]) + (h_tptr[t + 1] - h_tptr[t]) for t in tq_terms.astype(np.int64)))
+                topk["tail_queries"] = {"value": world * nq * K / dtt, "unit": "queries/s", "ms_per_step": dtt * 1e3 / K, "ms_per_step_blocks": summarize(tblocks),
+                                        "workload": f"{nq} x 3-term OR queries, term ranks U[1,{nt}]", "postings_per_query": tail_df / nq}
 
-            # ---- blended run (BASELINE config 5): same index and queries + PageRank prior, per-query topicProbs
-            kt5 = args.topics
-            if c4_ranks is not None:
-                prior5, prior_src = c4_ranks, "converged ranks of the PageRank half (config 4 graph, node i = doc i)"
-            else:
-                g5 = torch.Generator(device="cpu").manual_seed(46)
-                prior5 = (torch.rand((kt5, nd), generator=g5, dtype=torch.float64) * 1e-6).numpy()
-                prior_src = "synthetic uniform ranks (N>1, or the PageRank half did not run)"
-            sc.set_prior(prior5)
-            probs5 = np.random.default_rng(46 + rank).dirichlet(np.ones(kt5), size=nq)
-            ctx.set_option("score.timing", 0)
-            dt5, blocks5 = timed_blocks(lambda m: batches(m, topic_probs=probs5), min_warm=SCORE_WARM)
-            ctx.set_option("score.timing", None)
-            topk["blended_config5"] = {"value": world * nq * K / dt5, "unit": "queries/s", "ms_per_step": dt5 * 1e3 / K,
-                                       "ms_per_step_blocks": summarize(blocks5),
-                                       "k_topics": kt5, "prior": prior_src, "topic_probs": "Dirichlet(1) per query"}
-            if keep_host:
-                from oracle import pyoracle
-                nb = 16
-                h5, n5 = sc.score_topk(q_ptr[:nb + 1], q_terms[:3 * nb], k, topic_probs=probs5[:nb])
-                r5, rn5 = pyoracle.score_topk_batch(nd, (h_tptr, h_tdoc, wt), (h_bptr, h_bdoc, wb), mt, mb, q_ptr[:nb + 1], q_terms[:3 * nb], k,
-                                                    prior=np.ascontiguousarray(prior5.T), topic_probs=probs5[:nb])
-                same5 = all(h5["doc"][q, :n5[q]].tolist() == r5["doc"][q, :rn5[q]].tolist() and
-                            np.array_equal(h5["final"][q, :n5[q]], r5["final"][q, :rn5[q]]) for q in range(nb))
-                topk["blended_config5"]["gpu_matches_oracle"] = bool(same5)
-                assert same5
-                del r5
-            sc.set_prior(None)
-            del prior5
+                # ---- mixed batches: term ranks over the first 100k terms (long and short lists in one query: the batch runs in
+                #      k_score_slices), and a batch that is half head / half tail queries (split per query between the two scoring kernels,
+                #      which run side by side on two streams)
+                mq_ptr, mq_terms = synth.make_queries(nq, 3, min(100_000, nt), seed=2045 + rank)
+                hq = nq // 2
+                hh_ptr = np.concatenate([q_ptr[:hq + 1], tq_ptr[1:nq - hq + 1] + q_ptr[hq]]).astype(np.uint32)
+                hh_terms = np.concatenate([q_terms[:q_ptr[hq]], tq_terms[:tq_ptr[nq - hq]]]).astype(np.uint32)
+                ctx.set_option("score.timing", 0)
+                for key_, (qp_, qt_), what_ in (("mixed_queries", (mq_ptr, mq_terms), f"{nq} x 3-term OR queries, term ranks U[1,{min(100_000, nt)}]"),
+                                                ("half_head_half_tail", (hh_ptr, hh_terms), f"{hq} queries of term ranks U[1,10000] + {nq - hq} of U[1,{nt}] in one batch")):
+                    _, mblocks = timed_blocks(lambda m: batches(m, qp_, qt_), n_blocks=3, min_warm=SCORE_WARM)
+                    dtm = statistics.median(mblocks) * K / 1e3
+                    dfm = int(sum((h_bptr[t + 1] - h_bptr[t]) + (h_tptr[t + 1] - h_tptr[t]) for t in qt_.astype(np.int64)))
+                    topk[key_] = {"value": world * nq * K / dtm, "unit": "queries/s", "ms_per_step": dtm * 1e3 / K, "ms_per_step_blocks": summarize(mblocks), "workload": what_, "postings_per_query": dfm / nq}
+                ctx.set_option("score.timing", None)
 
-            # ---- doc-range-sharded scoring (N>1): one batch replicated, local top-k, one all-gather, merge
-            if shard is not None:
-                try:
-                    sti, sbi, ssc = shard
-                    dsc = sharding.DocShardedScorer(ssc, ctx.merge_hits, nd, rank, world, device=dev, host_staged=rehearsal)
-                    g_qptr, g_qterms = synth.make_queries(nq, 3, min(10_000, nt), seed=45)       # rank 0's batch on every rank
-                    dg = (torch.from_numpy(g_qptr.view(np.int32)).to(dev), torch.from_numpy(g_qterms.view(np.int32)).to(dev))
-                    m_hits = torch.empty(nq * k * 40, dtype=torch.uint8, device=dev)
-                    m_n = torch.empty(nq, dtype=torch.int32, device=dev)
+                # ---- blended run (BASELINE config 5): same index and queries + PageRank prior, per-query topicProbs
+                kt5 = args.topics
+                if c4_ranks is not None:
+                    prior5, prior_src = c4_ranks, "converged ranks of the PageRank half (config 4 graph, node i = doc i)"
+                else:
+                    g5 = torch.Generator(device="cpu").manual_seed(46)
+                    prior5 = (torch.rand((kt5, nd), generator=g5, dtype=torch.float64) * 1e-6).numpy()
+                    prior_src = "synthetic uniform ranks (N>1, or the PageRank half did not run)"
+                sc.set_prior(prior5)
+                probs5 = np.random.default_rng(46 + rank).dirichlet(np.ones(kt5), size=nq)
+                ctx.set_option("score.timing", 0)
+                dt5, blocks5 = timed_blocks(lambda m: batches(m, topic_probs=probs5), min_warm=SCORE_WARM)
+                ctx.set_option("score.timing", None)
+                topk["blended_config5"] = {"value": world * nq * K / dt5, "unit": "queries/s", "ms_per_step": dt5 * 1e3 / K,
+                                           "ms_per_step_blocks": summarize(blocks5),
+                                           "k_topics": kt5, "prior": prior_src, "topic_probs": "Dirichlet(1) per query"}
+                if keep_host:
+                    from oracle import pyoracle
+                    nb = 16
+                    h5, n5 = sc.score_topk(q_ptr[:nb + 1], q_terms[:3 * nb], k, topic_probs=probs5[:nb])
+                    r5, rn5 = pyoracle.score_topk_batch(nd, (h_tptr, h_tdoc, wt), (h_bptr, h_bdoc, wb), mt, mb, q_ptr[:nb + 1], q_terms[:3 * nb], k,
+                                                        prior=np.ascontiguousarray(prior5.T), topic_probs=probs5[:nb])
+                    same5 = all(h5["doc"][q, :n5[q]].tolist() == r5["doc"][q, :rn5[q]].tolist() and
+                                np.array_equal(h5["final"][q, :n5[q]], r5["final"][q, :rn5[q]]) for q in range(nb))
+                    topk["blended_config5"]["gpu_matches_oracle"] = bool(same5)
+                    assert same5
+                    del r5
+                sc.set_prior(None)
+                del prior5
 
-                    def sharded(m):
-                        for _ in range(m):
-                            dsc.score_topk(dg[0], dg[1], k, out=(m_hits, m_n))
+                # ---- doc-range-sharded scoring (N>1): one batch replicated, local top-k, one all-gather, merge
+                if shard is not None:
+                    try:
+                        sti, sbi, ssc = shard
+                        dsc = sharding.DocShardedScorer(ssc, ctx.merge_hits, nd, rank, world, device=dev, host_staged=rehearsal)
+                        g_qptr, g_qterms = synth.make_queries(nq, 3, min(10_000, nt), seed=45)       # rank 0's batch on every rank
+                        dg = (torch.from_numpy(g_qptr.view(np.int32)).to(dev), torch.from_numpy(g_qterms.view(np.int32)).to(dev))
+                        m_hits = torch.empty(nq * k * 40, dtype=torch.uint8, device=dev)
+                        m_n = torch.empty(nq, dtype=torch.int32, device=dev)
 
-                    dts, _ = timed_blocks(sharded, n_blocks=1)
-                    sc.score_topk(dg[0], dg[1], k, out=(d_hits, d_nhits))                         # the full replica, same batch
-                    same_s = bool(torch.equal(m_hits, d_hits) and torch.equal(m_n, d_nhits))
-                    topk["doc_sharded"] = {"value": nq * K / dts, "unit": "queries/s", "ms_per_step": dts * 1e3 / K, "scaling": "strong",
-                                           "parallelism": f"doc-range shards x{world}: batch replicated, local top-{k}, 1 all-gather of "
-                                                          f"{nq * k * 40} B/rank + merge", "matches_unsharded_replica": same_s}
-                    assert same_s
-                    ssc.close()
-                    sti.close()
-                    sbi.close()
-                except Exception as exc_:            # the replica number must survive a failing collective
-                    topk["doc_sharded_error"] = repr(exc_)
+                        def sharded(m):
+                            for _ in range(m):
+                                dsc.score_topk(dg[0], dg[1], k, out=(m_hits, m_n))
 
-            if keep_host:
-                from oracle import pyoracle
-                log("cpu baseline (top-k): flat port, reference-shaped, OpenMP ...")
-                title = (h_tptr, h_tdoc, wt)
-                body = (h_bptr, h_bdoc, wb)
-                ns = 64
-                t0 = time.perf_counter()
-                ref, ref_n = pyoracle.score_topk_batch(nd, title, body, mt, mb, q_ptr[:ns + 1], q_terms[:3 * ns], k)
-                cdt = time.perf_counter() - t0
-                if cdt < args.cpu_seconds / 3 and nq > ns:
-                    ns = int(min(nq, ns * args.cpu_seconds / max(cdt, 1e-3) / 1.5))
+                        dts, _ = timed_blocks(sharded, n_blocks=1)
+                        sc.score_topk(dg[0], dg[1], k, out=(d_hits, d_nhits))                         # the full replica, same batch
+                        same_s = bool(torch.equal(m_hits, d_hits) and torch.equal(m_n, d_nhits))
+                        topk["doc_sharded"] = {"value": nq * K / dts, "unit": "queries/s", "ms_per_step": dts * 1e3 / K, "scaling": "strong",
+                                               "parallelism": f"doc-range shards x{world}: batch replicated, local top-{k}, 1 all-gather of "
+                                                              f"{nq * k * 40} B/rank + merge", "matches_unsharded_replica": same_s}
+                        assert same_s
+                        ssc.close()
+                        sti.close()
+                        sbi.close()
+                    except Exception as exc_:            # the replica number must survive a failing collective
+                        topk["doc_sharded_error"] = repr(exc_)
+
+                if keep_host:
+                    from oracle import pyoracle
+                    log("cpu baseline (top-k): flat port, reference-shaped, OpenMP ...")
+                    title = (h_tptr, h_tdoc, wt)
+                    body = (h_bptr, h_bdoc, wb)
+                    ns = 64
                     t0 = time.perf_counter()
                     ref, ref_n = pyoracle.score_topk_batch(nd, title, body, mt, mb, q_ptr[:ns + 1], q_terms[:3 * ns], k)
                     cdt = time.perf_counter() - t0
-                flat = {"value": ns / cdt, "unit": "queries/s", "cores": 1,
-                        "sample": f"first {ns} queries of the same batch, flat-array single-thread C restatement of "
-                                  f"main_retrieve.go:50-103 + get_metadata.go:31-69 (oracle/oracle.c:orc_score_topk_batch)"}
-                # reference-shaped: string-keyed maps, appended weight slices, insertion-sort appendSort
-                # (util.go:48-54 is quadratic in the candidates — every insert shifts half of a ~100k-row slice of 152-byte
-                # Rank_combined structs: 10-80 s per head query on one core — so the sample is one query, more if time allows)
-                mm = pyoracle.MagMap(mt, mb)
-                log(f"cpu baseline (top-k): flat port done ({ns} queries in {cdt:.1f}s); reference-shaped sample ...")
-                # appendSort is quadratic in a query's candidates, so the sample is sized by candidates, not by queries:
-                # time the first query, then take the longest prefix of the batch whose estimated cost (~ postings^2) fits
-                h_bp, h_tp = body[0].astype(np.int64), title[0].astype(np.int64)
-                qt = q_terms.astype(np.int64).reshape(-1, 3)
-                posts = ((h_bp[qt + 1] - h_bp[qt]) + (h_tp[qt + 1] - h_tp[qt])).sum(axis=1).astype(np.float64)
-                nb1 = 1
-                t0 = time.perf_counter()
-                hb1, nb1n, th1 = pyoracle.score_topk_batch_hashed(mm, title, body, q_ptr[:nb1 + 1], q_terms[:3 * nb1], k, threads=False)
-                bdt = time.perf_counter() - t0
-                est = bdt * np.maximum((posts / posts[0]) ** 2, posts / posts[0])
-                more = int(min(ns, 64, np.searchsorted(np.cumsum(est), args.cpu_seconds)))
-                if more > 1 and bdt < args.cpu_seconds:
-                    nb1 = more
+                    if cdt < args.cpu_seconds / 3 and nq > ns:
+                        ns = int(min(nq, ns * args.cpu_seconds / max(cdt, 1e-3) / 1.5))
+                        t0 = time.perf_counter()
+                        ref, ref_n = pyoracle.score_topk_batch(nd, title, body, mt, mb, q_ptr[:ns + 1], q_terms[:3 * ns], k)
+                        cdt = time.perf_counter() - t0
+                    flat = {"value": ns / cdt, "unit": "queries/s", "cores": 1,
+                            "sample": f"first {ns} queries of the same batch, flat-array single-thread C restatement of "
+                                      f"main_retrieve.go:50-103 + get_metadata.go:31-69 (oracle/oracle.c:orc_score_topk_batch)"}
+                    # reference-shaped: string-keyed maps, appended weight slices, insertion-sort appendSort
+                    # (util.go:48-54 is quadratic in the candidates — every insert shifts half of a ~100k-row slice of 152-byte
+                    # Rank_combined structs: 10-80 s per head query on one core — so the sample is one query, more if time allows)
+                    mm = pyoracle.MagMap(mt, mb)
+                    log(f"cpu baseline (top-k): flat port done ({ns} queries in {cdt:.1f}s); reference-shaped sample ...")
+                    # appendSort is quadratic in a query's candidates, so the sample is sized by candidates, not by queries:
+                    # time the first query, then take the longest prefix of the batch whose estimated cost (~ postings^2) fits
+                    h_bp, h_tp = body[0].astype(np.int64), title[0].astype(np.int64)
+                    qt = q_terms.astype(np.int64).reshape(-1, 3)
+                    posts = ((h_bp[qt + 1] - h_bp[qt]) + (h_tp[qt + 1] - h_tp[qt])).sum(axis=1).astype(np.float64)
+                    nb1 = 1
                     t0 = time.perf_counter()
                     hb1, nb1n, th1 = pyoracle.score_topk_batch_hashed(mm, title, body, q_ptr[:nb1 + 1], q_terms[:3 * nb1], k, threads=False)
                     bdt = time.perf_counter() - t0
-                mm.close()
-                chk = min(nb1, ns)
-                b1_same = bool(np.array_equal(hb1["final"][:chk], ref["final"][:chk]))
-                topk["cpu_baseline"] = {"value": nb1 / bdt, "unit": "queries/s", "cores": 1, "kind": "port",
-                                        "sample": f"reference-shaped restatement (B1) of main_retrieve.go:61-97 + get_metadata.go:46-69 + "
-                                                  f"util.go:48-54 on the first {nb1} queries of the same batch ({int(posts[:nb1].sum())} postings; appendSort is quadratic "
-                                                  f"in a query's candidates), single thread "
-                                                  f"(oracle/oracle.c:orc_score_topk_batch_hashed); forw[4] map built outside the timing",
-                                        "final_ranks_match_flat_port": b1_same, "flat_port": flat}
-                t0 = time.perf_counter()
-                _, _, th = pyoracle.score_topk_batch(nd, title, body, mt, mb, q_ptr, q_terms, k, omp=True)
-                odt = time.perf_counter() - t0
-                topk["cpu_baseline"]["strong_cpu"] = {"value": nq / odt, "unit": "queries/s", "cores": th,
-                                                      "sample": f"all {nq} queries, one query per thread, oracle/oracle.c:orc_score_topk_batch_omp; threads = {OMP_HOW}"}
-                same = all(hits["doc"][q, :n_hits[q]].tolist() == ref["doc"][q, :ref_n[q]].tolist() for q in range(ns))
-                same &= all(np.array_equal(hits["final"][q, :n_hits[q]], ref["final"][q, :ref_n[q]]) for q in range(ns))
-                topk["cpu_baseline"]["gpu_matches_oracle"] = bool(same)
-                assert same and b1_same
+                    est = bdt * np.maximum((posts / posts[0]) ** 2, posts / posts[0])
+                    more = int(min(ns, 64, np.searchsorted(np.cumsum(est), args.cpu_seconds)))
+                    if more > 1 and bdt < args.cpu_seconds:
+                        nb1 = more
+                        t0 = time.perf_counter()
+                        hb1, nb1n, th1 = pyoracle.score_topk_batch_hashed(mm, title, body, q_ptr[:nb1 + 1], q_terms[:3 * nb1], k, threads=False)
+                        bdt = time.perf_counter() - t0
+                    mm.close()
+                    chk = min(nb1, ns)
+                    b1_same = bool(np.array_equal(hb1["final"][:chk], ref["final"][:chk]))
+                    topk["cpu_baseline"] = {"value": nb1 / bdt, "unit": "queries/s", "cores": 1, "kind": "port",
+                                            "sample": f"reference-shaped restatement (B1) of main_retrieve.go:61-97 + get_metadata.go:46-69 + "
+                                                      f"util.go:48-54 on the first {nb1} queries of the same batch ({int(posts[:nb1].sum())} postings; appendSort is quadratic "
+                                                      f"in a query's candidates), single thread "
+                                                      f"(oracle/oracle.c:orc_score_topk_batch_hashed); forw[4] map built outside the timing",
+                                            "final_ranks_match_flat_port": b1_same, "flat_port": flat}
+                    t0 = time.perf_counter()
+                    _, _, th = pyoracle.score_topk_batch(nd, title, body, mt, mb, q_ptr, q_terms, k, omp=True)
+                    odt = time.perf_counter() - t0
+                    topk["cpu_baseline"]["strong_cpu"] = {"value": nq / odt, "unit": "queries/s", "cores": th,
+                                                          "sample": f"all {nq} queries, one query per thread, oracle/oracle.c:orc_score_topk_batch_omp; threads = {OMP_HOW}"}
+                    same = all(hits["doc"][q, :n_hits[q]].tolist() == ref["doc"][q, :ref_n[q]].tolist() for q in range(ns))
+                    same &= all(np.array_equal(hits["final"][q, :n_hits[q]], ref["final"][q, :ref_n[q]]) for q in range(ns))
+                    topk["cpu_baseline"]["gpu_matches_oracle"] = bool(same)
+                    assert same and b1_same
             if shard_error:
                 topk["doc_sharded_error"] = shard_error
             if result:
@@ -1076,7 +1111,7 @@ def main() -> None:
                 sharding.drain_pipelined(pst, pex, hnd)
                 # the same number of plain sweeps: the ranks must agree (other kernel width: 1e-12, not bitwise)
                 pu = engine.PageRankState(g2, d, -1.0, n_topic, max_iter=0)
-                sharding.iterate([pu], sharding.DistExchange(pu, dev, host_staged=rehearsal), batch=4, max_sweeps=max(W, 1) + N_BLOCKS * K)
+                sharding.iterate([pu], sharding.DistExchange(pu, dev, host_staged=rehearsal), batch=4, max_sweeps=max(W, 1) + len(pblocks) * K)
                 ids_p, x_p = pst[0].read_local()
                 ids_u, x_u = pu.read_local()
                 ok = bool(np.array_equal(ids_p, ids_u) and np.allclose(x_p, x_u[:kt // 2], rtol=1e-12, atol=0))
@@ -1135,22 +1170,23 @@ def main() -> None:
                         del rk_lib
                     except Exception as exc:
                         decomp["doc_range_shards_lib_pipelined"] = {"value": 0.0, "error": repr(exc)}
-                    # the same loop with float32 on the wire (option "pr.wire_f32": half the bytes per link; inside the 1e-6 gate but not
-                    # the reference's float64 arithmetic) — reported here only, never as `value`
-                    try:
-                        ctx.set_option("pr.wire_f32", 1)
-                        ent, rk32 = lib_pipelined(g2, n_topic, f"doc-range shards x{world}, topic blocks pipelined inside the library, contribution "
-                                                               f"slices as FLOAT32 on the wire (opt-in pr.wire_f32; not eligible as the headline)")
-                        if ent.get("exchange_bytes_per_rank"):
-                            ent["exchange_bytes_per_rank"] /= 2
-                            ent["predicted_exchange_ms_at_7x50GBs"] /= 2
-                        ent["never_the_headline"] = True
-                        decomp["f32_wire_doc_range_shards_lib_pipelined"] = ent
-                        del rk32
-                    except Exception as exc:
-                        decomp["f32_wire_doc_range_shards_lib_pipelined"] = {"value": 0.0, "error": repr(exc)}
-                    finally:
-                        ctx.set_option("pr.wire_f32", None)
+                    if args.full:
+                        # the same loop with float32 on the wire (option "pr.wire_f32": half the bytes per link; inside the 1e-6 gate but not
+                        # the reference's float64 arithmetic) — reported here only, never as `value`
+                        try:
+                            ctx.set_option("pr.wire_f32", 1)
+                            ent, rk32 = lib_pipelined(g2, n_topic, f"doc-range shards x{world}, topic blocks pipelined inside the library, contribution "
+                                                                   f"slices as FLOAT32 on the wire (opt-in pr.wire_f32; not eligible as the headline)")
+                            if ent.get("exchange_bytes_per_rank"):
+                                ent["exchange_bytes_per_rank"] /= 2
+                                ent["predicted_exchange_ms_at_7x50GBs"] /= 2
+                            ent["never_the_headline"] = True
+                            decomp["f32_wire_doc_range_shards_lib_pipelined"] = ent
+                            del rk32
+                        except Exception as exc:
+                            decomp["f32_wire_doc_range_shards_lib_pipelined"] = {"value": 0.0, "error": repr(exc)}
+                        finally:
+                            ctx.set_option("pr.wire_f32", None)
                     for G in (2, 4):
                         S = world // G
                         if world % G or S < 2 or kt % G:
@@ -1191,25 +1227,26 @@ def main() -> None:
                     # the doc range and exchange per sweep, as measured in this run — not a fixed variant
                     result["config"]["value_is"] = ("the fastest float64 doc-range / topic-group x doc-shard variant of this run (" +
                                                     str(decomp.get("headline", "doc_range_shards")) + "); every variant's own number is under `decompositions`")
-                    # the two-vector form on the shards (option "pr.affine": a TWO-column exchange per iteration whatever K is — 2/kt of the
-                    # table's bytes per link; opt-in, not the reference's operation order) — reported here only, never as `value`
-                    # (after the choice above and last of all: this variant is the newest code on the multi-rank path — if it stalls, the watchdog
-                    # prints everything measured before it)
-                    try:
-                        ctx.set_option("pr.affine", 1)
-                        ent, rk2 = lib_pipelined(g2, n_topic, f"doc-range shards x{world}, two-vector form (opt-in pr.affine): all {kt} topics from two "
-                                                              f"vectors, a 2-column exchange per iteration; not eligible as the headline")
-                        if ent.get("exchange_bytes_per_rank"):
-                            ent["exchange_bytes_per_rank"] *= 2.0 / kt
-                            ent["predicted_exchange_ms_at_7x50GBs"] *= 2.0 / kt
-                        ent["never_the_headline"] = True
-                        ent["topic_blocks"] = "none (one K = 2 state per shard)"
-                        decomp["two_vector_form_doc_range_shards"] = ent
-                        del rk2
-                    except Exception as exc:
-                        decomp["two_vector_form_doc_range_shards"] = {"value": 0.0, "error": repr(exc)}
-                    finally:
-                        ctx.set_option("pr.affine", None)
+                    if args.full:
+                        # the two-vector form on the shards (option "pr.affine": a TWO-column exchange per iteration whatever K is — 2/kt of the
+                        # table's bytes per link; opt-in, not the reference's operation order) — reported here only, never as `value`
+                        # (after the choice above and last of all: this variant is the newest code on the multi-rank path — if it stalls, the watchdog
+                        # prints everything measured before it)
+                        try:
+                            ctx.set_option("pr.affine", 1)
+                            ent, rk2 = lib_pipelined(g2, n_topic, f"doc-range shards x{world}, two-vector form (opt-in pr.affine): all {kt} topics from two "
+                                                                  f"vectors, a 2-column exchange per iteration; not eligible as the headline")
+                            if ent.get("exchange_bytes_per_rank"):
+                                ent["exchange_bytes_per_rank"] *= 2.0 / kt
+                                ent["predicted_exchange_ms_at_7x50GBs"] *= 2.0 / kt
+                            ent["never_the_headline"] = True
+                            ent["topic_blocks"] = "none (one K = 2 state per shard)"
+                            decomp["two_vector_form_doc_range_shards"] = ent
+                            del rk2
+                        except Exception as exc:
+                            decomp["two_vector_form_doc_range_shards"] = {"value": 0.0, "error": repr(exc)}
+                        finally:
+                            ctx.set_option("pr.affine", None)
                 g2.close()
         except Exception as exc:
             result["pipelined_error"] = repr(exc)
@@ -1218,6 +1255,11 @@ def main() -> None:
     torch.cuda.synchronize()
     ctx.set_stream(None)
     ctx.close()
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumps.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(sorted(dumps))}")
     emit()
     if world > 1:
         dist.barrier()

@@ -1,6 +1,6 @@
 """bench.py --gpus N as the driver launches it (torch.distributed.run, one process per rank), rehearsed on ONE GPU:
 SS_BENCH_REHEARSAL=1 puts every rank on cuda:0 with gloo and a host-staged exchange in place of RCCL.  The numbers mean nothing;
-the test checks that the multi-rank flow of every section runs to the end and that rank 0's JSON line has the shape the driver
+the test (with --full) checks that the multi-rank flow of every section runs to the end and that rank 0's JSON line has the shape the driver
 parses.  Four ranks, not eight: the GPU boxes admit at most 6 processes on the card at once (this pytest process is one of
 them); the 8-rank arithmetic itself is covered in-process by tests/test_gpu_world8.py and on the CPU by the gloo tests."""
 import json
@@ -27,7 +27,7 @@ def test_four_rank_rehearsal_prints_the_drivers_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
            "--nodes", "200000", "--edges", "1000000", "--topics", "16", "--docs", "200000", "--terms", "20000",
-           "--body-postings", "2000000", "--title-postings", "200000", "--queries", "64", "--k", "10", "--no-cpu-baseline"]
+           "--body-postings", "2000000", "--title-postings", "200000", "--queries", "64", "--k", "10", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])

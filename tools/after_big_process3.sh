@@ -13,5 +13,5 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('settle_s', d['settle_s'], 'ms_per_sweep', round(d['ms_per_step'],4), 'kernel_ms', round(d['roofline']['kernel_ms'],4), 'gather probe', round(d['roofline']['gather_ceiling_ms'],4))"; }
 for s in 8 0 4 8 0; do
   big; echo "== behind a 128 GB process, --settle $s"
-  python3 bench.py --workload pagerank --no-cpu-baseline --no-config2 --steps 20 --warmup 5 --settle $s 2>/dev/null | digest
+  python3 bench.py --full --workload pagerank --no-cpu-baseline --no-config2 --steps 20 --warmup 5 --settle $s 2>/dev/null | digest
 done

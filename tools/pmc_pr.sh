@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/pmcpr_$2
 rm -rf $out
-timeout -k 10 250 rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $out -o pmc -- python3 bench.py --workload pagerank --no-cpu-baseline --steps 10 --warmup 2 > $out.log 2>&1
+timeout -k 10 250 rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $out -o pmc -- python3 bench.py --full --workload pagerank --no-cpu-baseline --steps 10 --warmup 2 > $out.log 2>&1
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)
