@@ -397,6 +397,36 @@ func (s *Scorer) SetPrior(kTopics int, rank []float64) {
 	check(s.ctx, C.ss_scorer_set_prior(s.h, C.int32_t(kTopics), f64p(rank)), "ss_scorer_set_prior")
 }
 
+// SetDocMasks registers allow-lists: words [nMasks][(nDocs+31)/32], bit (d & 31) of word d >> 5 = doc d allowed (nil clears).
+func (s *Scorer) SetDocMasks(nMasks int, words []uint32) {
+	check(s.ctx, C.ss_scorer_set_doc_masks(s.h, C.int32_t(nMasks), u32p(words)), "ss_scorer_set_doc_masks")
+}
+
+// ScoreTopKMasked = ScoreTopKPhrase with one allow-list per query: maskID[q] (-1 = the whole index; nil = all -1); pPtr nil = no
+// phrases.  Row q holds the first k docs of query q's ranking that its mask allows.
+func (s *Scorer) ScoreTopKMasked(qPtr, qTerms, pPtr, pTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32, k int) ([][]Hit, error) {
+	nq := len(qPtr) - 1
+	if nq == 0 {
+		return nil, nil
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	rc := C.ss_score_topk_masked(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), u32p(pPtr), u32p(pTerms), i32p(queryLen),
+		f64p(topicProbs), i32p(maskID), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	if err := statusErr(s.ctx, rc, "ss_score_topk_masked"); err != nil {
+		return nil, err
+	}
+	out := make([][]Hit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Hit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*k+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
 // ScoreTopKPhrase = ScoreTopK plus one (concatenated) quoted phrase per query (retrieval/phrase.go).
 func (s *Scorer) ScoreTopKPhrase(qPtr, qTerms, pPtr, pTerms []uint32, queryLen []int32, topicProbs []float64, k int) ([][]Hit, error) {
 	nq := len(qPtr) - 1

@@ -34,7 +34,8 @@ extern "C" {
 /* 4 (round 5): ss_score_topk_submit / ss_score_topk_collect exist; ss_graph_create may return while its last build kernels
  * still run on the context's stream (everything that reads the graph is ordered behind them); "score.pipeline" defaults to 2
  * internal wave streams and ss_last_kernel_ms(1) is the device time of the last scoring call's kernels on the stream that
- * carries its merge.  A binding checks ss_abi_version() == SS_ABI_VERSION at load. */
+ * carries its merge.  A binding checks ss_abi_version() == SS_ABI_VERSION at load.
+ * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -356,6 +357,24 @@ int32_t ss_score_topk_collect(ss_scorer* s, uint64_t ticket, ss_hit* hits_out, i
 int32_t ss_score_topk_phrase(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
                              const uint32_t* p_ptr, const uint32_t* p_terms, const int32_t* query_len,
                              const double* topic_probs, int32_t k, ss_hit* hits_out, int32_t* n_hits_out);
+
+/* Doc masks: top-k over PART of the corpus ("results in category X only", "hide these pages").  No reference counterpart.
+ * Register allow-lists on a scorer: words [n_masks][(n_docs+31)/32], bit (d & 31) of word d >> 5 = doc d allowed
+ * (n_docs = the scorer's; bits past n_docs ignored).  Host or device memory, copied.  n_masks = 0 / NULL clears.
+ * Replaces the previous set after the scorer's outstanding work (pipelined batches, tickets) has finished with it.
+ * The masks live as long as the scorer: after an index update (destroy scorers before, re-create after) register them again. */
+int32_t ss_scorer_set_doc_masks(ss_scorer* s, int32_t n_masks, const uint32_t* words);
+
+/* ss_score_topk_phrase with a per-query allow-list: mask_id [n_q] (-1 = unrestricted; NULL = all -1), p_ptr NULL = no phrases.
+ * Row q = the first min(k, m) rows of query q's unrestricted ranking (FinalRank desc, ties doc asc, NaN last)
+ * restricted to the docs its mask allows -- NOT a post-filter of the unrestricted top-k.
+ * Outputs as ss_score_topk (device outputs: the call only enqueues, pipelined like any other batch).  A mask_id below -1
+ * or at / above n_masks is SS_ERR_INVALID and nothing is enqueued.  With no masked query the call IS ss_score_topk_phrase /
+ * ss_score_topk (same kernels, bit-identical rows).  There is no masked form of ss_score_topk_submit / _collect. */
+int32_t ss_score_topk_masked(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                             const uint32_t* p_ptr, const uint32_t* p_terms, const int32_t* query_len,
+                             const double* topic_probs, const int32_t* mask_id, int32_t k,
+                             ss_hit* hits_out, int32_t* n_hits_out);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

@@ -135,6 +135,7 @@ __device__ __forceinline__ void score_owned(const SliceLds& S, const TopK& tk, c
     uint64_t e_key = 0;
     if (slot != EMPTY) {
         e_doc = doc;
+        const bool allowed = doc_allowed(Q.mask, doc);
         const uint32_t fr = S.ht_rec[slot];
         // no posting of a field => its sum is 0 and 0/(m*q) is 0 (or NaN -> 0) for every m
         double2 rb = make_double2(0.0, 1.0), rt = make_double2(0.0, 1.0);
@@ -151,7 +152,8 @@ __device__ __forceinline__ void score_owned(const SliceLds& S, const TopK& tk, c
         // v_rcp_f32 (1 ulp) instead of an IEEE division: the 1e-4 margin below covers it; 0*inf = NaN falls through
         const float ea = 38.0f * ((float)T * __builtin_amdgcn_rcpf((float)mt * Q.qmag_f)), eb = 29.0f * ((float)B * __builtin_amdgcn_rcpf((float)mb * Q.qmag_f)),
                     ec = 33.0f * Q.sqd_ub_f;
-        if ((ea + eb + ec) + (fabsf(ea) + fabsf(eb) + fabsf(ec)) * 1e-4f + 1e-30f < thr_f) {
+        // a doc outside the query's allow-list never enters the running top-k: the threshold comes from allowed docs only
+        if (!allowed || (ea + eb + ec) + (fabsf(ea) + fabsf(eb) + fabsf(ec)) * 1e-4f + 1e-30f < thr_f) {
             e_doc = EMPTY;
         } else {
             double title, body, fin;
@@ -615,6 +617,8 @@ __device__ __forceinline__ void merge_query(const ScoreParams& p, const uint32_t
 }
 
 
+// MASKED: the instantiation for calls in which some query has an allow-list (ss_score_topk_masked); the other one has no trace of it
+template <bool MASKED>
 __global__ __launch_bounds__(TPB, (TPB / 256) * SS_WGS_PER_CU) void k_score_slices(ScoreParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const ScoreLds lo_ = score_lds_layout(p.cb);
@@ -664,6 +668,8 @@ __global__ __launch_bounds__(TPB, (TPB / 256) * SS_WGS_PER_CU) void k_score_slic
     Q.sqd_ub = Q.probs ? p.sqd_ub[q] : 0.0;
     Q.sqd_ub_f = Q.probs ? __double2float_ru(Q.sqd_ub) : 0.0f;
     Q.qmag_f = (float)Q.qmag;
+    const int32_t mask_id = MASKED ? p.q_mask[q] : -1;
+    Q.mask = mask_id >= 0 ? p.masks + (size_t)mask_id * p.mask_words : nullptr;
     // filter: upper bound of the prior's share of FinalRank, 0.33*sqd*100 (get_metadata.go:69), with the filter's margin
     const float r_ub = Q.probs ? __double2float_ru(33.0 * Q.sqd_ub * (1.0 + 0x1p-12)) : 0.0f;
     const bool exact_all = p.exact_all != 0;
@@ -711,13 +717,14 @@ __global__ __launch_bounds__(TPB, (TPB / 256) * SS_WGS_PER_CU) void k_score_slic
         const float coef = __double2float_ru(share * (1.0 + 0x1p-12));
         S.l_coef[tid] = coef;
         if (coef > 0.0f && coef < INFINITY) atomicMax(coef_max_bits, __float_as_uint(coef));
-        if (!exact_all && kth > 0.0f) {
+        // (no floor under an allow-list: the k' best postings of a list need not be k' docs the query may return)
+        if (!exact_all && !Q.mask && kth > 0.0f) {
             const float floor_l = __double2float_rd(share * (1.0 - 0x1p-12) * (double)kth);
             if (floor_l > 0.0f) atomicMax(thr0_bits, __float_as_uint(floor_l));
         }
     }
 #ifdef SS_EXP_FLOOR      // variant build only (tools/floor_exp.py): a per-query floor handed in by the host
-    if (tid == 0 && p.q_floor && !exact_all) {
+    if (tid == 0 && p.q_floor && !exact_all && !Q.mask) {
         const float f = p.q_floor[q];
         if (f > 0.0f) atomicMax(thr0_bits, __float_as_uint(f));
     }
@@ -1407,7 +1414,10 @@ struct ss_scorer {
     ss::DevBuf<double> prior;
     std::vector<double> prior_max, prior_min;   // per topic
     int k_topics = 0;
-    int lds_attr = 0;
+    ss::DevBuf<uint32_t> masks;                 // ss_scorer_set_doc_masks: [n_masks][mask_words] allow-lists
+    int32_t n_masks = 0;
+    uint64_t mask_words = 0;
+    int lds_attr = 0, lds_attr_masked = 0;
     // per-call workspaces, grow-only (no hipMalloc/hipFree on the steady-state query path)
     // Turns of per-batch buffers: the host runs at most TURNS batches ahead.  (Three were measured for the pipelined mode, so that a
     // batch's plan upload and k_wave_prep — which do not fit beside k_score_wave's three waves of 168 VGPRs per SIMD — are enqueued
@@ -1648,9 +1658,37 @@ int32_t ss_scorer_set_prior(ss_scorer* s, int32_t k_topics, const double* rank) 
     return SS_OK;
 }
 
+int32_t ss_scorer_set_doc_masks(ss_scorer* s, int32_t n_masks, const uint32_t* words) {
+    if (!s) return SS_ERR_INVALID;
+    ss_ctx* ctx = s->ctx;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    SS_HIP(ctx, hipSetDevice(ctx->device));
+    if (n_masks < 0 || (n_masks > 0 && !words)) return ctx->fail(SS_ERR_INVALID, "ss_scorer_set_doc_masks: n_masks < 0 or words is NULL");
+    // the scorer's outstanding batches (pipelined calls, tickets) read the old set: their kernels are on the context's stream or
+    // a wave stream, every one of which is drained before the set is replaced
+    SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (hipStream_t ws : ctx->wave_stream)
+        if (ws) SS_HIP(ctx, hipStreamSynchronize(ws));
+    const uint64_t n_words = (s->n_docs + 31) / 32;
+    if (n_masks == 0 || n_words == 0) {
+        s->masks.release();
+        s->n_masks = n_masks;                   // (n_docs = 0: ids 0 .. n_masks-1 stay valid, there is no doc to allow)
+        s->mask_words = n_words;
+        return SS_OK;
+    }
+    ss::DevBuf<uint32_t> nb;
+    SS_HIP(ctx, nb.alloc((size_t)n_masks * n_words));
+    SS_HIP(ctx, hipMemcpyAsync(nb.p, words, (size_t)n_masks * n_words * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
+    SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->masks = std::move(nb);
+    s->n_masks = n_masks;
+    s->mask_words = n_words;
+    return SS_OK;
+}
+
 static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                           const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out);
+                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id = nullptr);
 
 int32_t ss_score_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
                       const double* topic_probs, int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
@@ -1662,6 +1700,12 @@ int32_t ss_score_topk_phrase(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
                              ss_hit* hits_out, int32_t* n_hits_out) {
     if (s && !p_ptr) return s->ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_ptr is NULL");
     return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out);
+}
+
+int32_t ss_score_topk_masked(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
+                             const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
+                             int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
+    return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id);
 }
 
 // Batches in flight with HOST results: submit runs the batch like a call with device outputs (nothing waits, consecutive batches
@@ -1787,15 +1831,15 @@ int32_t ss_score_topk_collect(ss_scorer* s, uint64_t ticket, ss_hit* hits_out, i
 
 static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                                 const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out);
+                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id);
 
 // no C++ exception may cross the C ABI: host allocation failures come back as SS_ERR_OOM
 static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                           const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out) {
+                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id) {
     if (!s) return SS_ERR_INVALID;
     try {
-        return score_impl_inner(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out);
+        return score_impl_inner(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id);
     } catch (const std::bad_alloc&) {
         return s->ctx->fail(SS_ERR_OOM, "ss_score_topk: host allocation failed");
     } catch (const std::exception& e) {
@@ -1805,7 +1849,7 @@ static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, cons
 
 static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                                 const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out) {
+                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id) {
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1815,6 +1859,18 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     if (k > SS_MAX_TOPK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk: k %d > SS_MAX_TOPK %d", k, SS_MAX_TOPK);
     if (topic_probs && s->k_topics == 0) return ctx->fail(SS_ERR_STATE, "ss_score_topk: topic_probs given but no prior set (ss_scorer_set_prior)");
     if (n_q == 0) return SS_OK;
+    // allow-lists (ss_score_topk_masked): checked before anything is enqueued; a call without a masked query is the unmasked call
+    std::vector<int32_t> h_mask;
+    bool any_mask = false;
+    if (mask_id) {
+        h_mask.resize(n_q);
+        SS_HIP(ctx, ss::copy_in(ctx->stream, h_mask.data(), mask_id, n_q * sizeof(int32_t)));
+        for (int q = 0; q < n_q; q++) {
+            if (h_mask[q] < -1 || h_mask[q] >= s->n_masks)
+                return ctx->fail(SS_ERR_INVALID, "ss_score_topk_masked: query %d has mask id %d (the scorer has %d masks)", q, h_mask[q], s->n_masks);
+            any_mask = any_mask || h_mask[q] >= 0;
+        }
+    }
 
     const bool trace = ctx->opt("score.trace", 0) != 0;
     auto t_now = [] { return std::chrono::steady_clock::now(); };
@@ -2005,6 +2061,10 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
         // after the other)
         const uint64_t share = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(100, ctx->opt("score.wave_share_pct", 90)));
         batch_wave = wml == 0 ? fit > 0 : (fit * 100 >= all * share && fit >= 400000);
+        // a query with an allow-list has no threshold floor, which the wave kernel's routing rests on: k_score_slices.  (After the
+        // batch's choice: the unmasked queries of the batch go where they would without the masked ones.)
+        for (int q = 0; q < n_q && any_mask; q++)
+            if (h_mask[q] >= 0) h_suits[q] = 0;
     }
     std::vector<uint8_t> h_fast(n_q, 0);
     // k_score_small (one workgroup per query, every posting scored exactly, no slices and no merge: score_small.hip) takes queries without
@@ -2093,7 +2153,7 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
             }
             if (fits) {
                 SmallEnt en;
-                en.h = SmallHdr{(uint32_t)q, nl, run, 0u, h_qmag[q], 0.0};
+                en.h = SmallHdr{(uint32_t)q, nl, run, any_mask ? (uint32_t)(h_mask[q] + 1) : 0u, h_qmag[q], 0.0};
                 en.loff = (uint32_t)h_small_lists.size();
                 h_small_lists.insert(h_small_lists.end(), tmp, tmp + nl);
                 small_lmax = std::max(small_lmax, nl);
@@ -2201,6 +2261,7 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     const size_t o_mergeq = o; o = align16(o + h_mergeq.size() * sizeof(uint32_t));
     const size_t o_qfast = o;  o = align16(o + (size_t)n_q);
     const size_t o_smalltab = o; o = align16(o + n_small * small_stride);
+    const size_t o_qmask = o;  o = align16(o + (any_mask ? (size_t)n_q * sizeof(int32_t) : 0));
 #ifdef SS_EXP_FLOOR
     const bool use_floor = ctx->opt("score.debug_floor", 0) != 0 && s->dbg_floor.size() == (size_t)n_q;
 #else
@@ -2251,6 +2312,7 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     if (!h_mergeq.empty()) std::memcpy(hp + o_mergeq, h_mergeq.data(), h_mergeq.size() * sizeof(uint32_t));
     std::memcpy(hp + o_qfast, h_fast.data(), (size_t)n_q);
     if (use_floor) std::memcpy(hp + o_qfloor, s->dbg_floor.data(), (size_t)n_q * sizeof(float));
+    if (any_mask) std::memcpy(hp + o_qmask, h_mask.data(), (size_t)n_q * sizeof(int32_t));
     {
         unsigned char* w = hp + o_smalltab;              // the 1024-slot queries first, then the larger ones (launch_score_small)
         for (const std::vector<SmallEnt>* v : {&h_small_a, &h_small_b})
@@ -2368,6 +2430,9 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     p.small_stage_n = small_staged ? s->d_small_stage_n[pb].p : nullptr;
     p.hits = dev_out ? hits_out : s->d_hits.p;
     p.n_hits = dev_out ? n_hits_out : one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + res_rows) : s->d_nhits.p;
+    p.q_mask = any_mask ? reinterpret_cast<const int32_t*>(dp + o_qmask) : nullptr;
+    p.masks = any_mask ? s->masks.p : nullptr;
+    p.mask_words = s->mask_words;
 
     // "score.pipeline" (default): a batch that is all k_score_wave, results in device memory.  Its k_wave_prep and k_score_wave go
     // to the context's WAVE stream, its k_merge_flat to the caller's stream behind an event: the next batch's k_score_wave (which
@@ -2406,8 +2471,12 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     }
     const auto th4 = t_now();
     const size_t lds_score = score_lds_bytes(cb), lds_merge = merge_lds_bytes(k, cb);
+    if (any_mask && s->lds_attr_masked < cb) {
+        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
+        s->lds_attr_masked = cb;
+    }
     if (s->lds_attr < cb) {
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
+        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
         SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)merge_lds_bytes(SS_MAX_TOPK, cb)));
         s->lds_attr = cb;
@@ -2446,7 +2515,8 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     if (n_slices > n_fast_slices) {
         ScoreParams ps = p;
         ps.order = p.order + n_fast_slices;
-        hipLaunchKernelGGL(k_score_slices, dim3((unsigned)(n_slices - n_fast_slices)), dim3(TPB), lds_score, sst, ps);
+        if (any_mask) hipLaunchKernelGGL(k_score_slices<true>, dim3((unsigned)(n_slices - n_fast_slices)), dim3(TPB), lds_score, sst, ps);
+        else hipLaunchKernelGGL(k_score_slices<false>, dim3((unsigned)(n_slices - n_fast_slices)), dim3(TPB), lds_score, sst, ps);
     }
     if (pipe_s) {                                // the merge, on the caller's stream, behind this batch's k_score_slices
         SS_HIP(ctx, hipEventRecord(s->wave_ev[pb], wst));

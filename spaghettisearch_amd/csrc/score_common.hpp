@@ -146,11 +146,16 @@ struct ScoreParams {
     const float* q_floor;             // experiment ("score.debug_floor"): a per-query lower bound of the k-th best FinalRank, or null
     ss_hit* small_stage;              // null: k_score_small writes row q of `hits`; else row b of this block (k_small_copy moves it on the caller's stream)
     int32_t* small_stage_n;
+    // doc masks (ss_score_topk_masked): query q may only return the docs whose bit is set in allow-list q_mask[q] (-1: any doc);
+    // q_mask = null: no query of the call has one.  k_score_small reads the list's number from its SmallHdr instead.
+    const int32_t* q_mask;
+    const uint32_t* masks;            // [n_masks][mask_words]: bit (d & 31) of word d >> 5 = doc d allowed
+    uint64_t mask_words;
 };
 
 // k_score_small's view of a query, resolved by the host (which holds term_ptr)
 #define SS_SMALL_MAX_LISTS 16
-struct __attribute__((aligned(16))) SmallHdr { uint32_t q, n_lists, tot, pad; double qmag, pad2; };
+struct __attribute__((aligned(16))) SmallHdr { uint32_t q, n_lists, tot, mask1; double qmag, pad2; };   // mask1: the query's allow-list + 1 (0: none)
 struct __attribute__((aligned(16))) SmallList { uint64_t start; uint32_t end, mf; };    // first posting in its table; postings of lists 0..this one; multiplicity << 1 | field (1 = title)
 static_assert(sizeof(SmallHdr) == 32 && sizeof(SmallList) == 16, "small-query table layout");
 
@@ -565,7 +570,11 @@ struct SliceQuery {      // per-query constants of the exact stage
     double qmag, sqd_ub;
     float qmag_f, sqd_ub_f;
     const double* probs;
+    const uint32_t* mask;   // the query's allow-list, or null
 };
+
+// a doc passes the query's allow-list (mask = null: every doc does); one word load, one bit test
+__device__ __forceinline__ bool doc_allowed(const uint32_t* mask, uint32_t doc) { return !mask || ((mask[doc >> 5] >> (doc & 31u)) & 1u); }
 
 // the running threshold in the filter's units, rounded down: a slot below it cannot hold a doc of the top-k.
 // thr_f = -inf (no threshold yet) -> 0: everything survives; never above FX_CLAMP: clamped shares always survive.

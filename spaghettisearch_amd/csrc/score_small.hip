@@ -51,7 +51,8 @@ __device__ __forceinline__ uint32_t sel_digit(uint64_t key, uint32_t doc, int sh
     return (uint32_t)w & 255u;
 }
 
-template <int NS>
+// MASKED: the instantiation for calls in which some query has an allow-list (its check costs the kernel registers)
+template <int NS, bool MASKED>
 __global__ __launch_bounds__(ST) void k_score_small(ScoreParams p, uint32_t first) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* accT = reinterpret_cast<double*>(smem);                       // [NS]
@@ -76,6 +77,7 @@ __global__ __launch_bounds__(ST) void k_score_small(ScoreParams p, uint32_t firs
     const unsigned char* const ent = p.small_tab + (size_t)(first + blockIdx.x) * p.small_stride;
     const SmallHdr hd = *reinterpret_cast<const SmallHdr*>(ent);
     const uint32_t q = hd.q, L = hd.n_lists, tot = hd.tot;
+    const uint32_t* const mask = MASKED && hd.mask1 ? p.masks + (size_t)(hd.mask1 - 1u) * p.mask_words : nullptr;   // the query's allow-list, or null
     TopK tk{cd_key, cd_doc, &sc32[0], &sc64[0], reinterpret_cast<float*>(&sc32[2]), 0ull, -INFINITY, (uint32_t)SCB};
     if ((uint32_t)tid < L) {
         const SmallList sl = reinterpret_cast<const SmallList*>(ent + sizeof(SmallHdr))[tid];
@@ -136,6 +138,7 @@ __global__ __launch_bounds__(ST) void k_score_small(ScoreParams p, uint32_t firs
     uint32_t alive = 0;                     // bit j: candidate j is still in the running for the k-th place
     {
         double T[PT], B[PT], mt[PT], mb[PT];
+        uint32_t mw[PT];                    // MASKED: the candidate's word of the allow-list (all ones without one)
 #pragma unroll
         for (int j = 0; j < PT; j++) {
             const int s = j * ST + tid;
@@ -150,11 +153,13 @@ __global__ __launch_bounds__(ST) void k_score_small(ScoreParams p, uint32_t firs
             const uint32_t d = e_doc[j] != EMPTY ? e_doc[j] : 0u;
             mt[j] = p.t_mag[T[j] != 0.0 ? d : 0u];
             mb[j] = p.b_mag[B[j] != 0.0 ? d : 0u];
+            mw[j] = MASKED && mask ? mask[d >> 5] : ~0u;
         }
 #pragma unroll
         for (int j = 0; j < PT; j++) {
             e_key[j] = 0ull;
-            if (e_doc[j] != EMPTY) {
+            // a doc outside the query's allow-list is dropped before the selection
+            if (e_doc[j] != EMPTY && (!MASKED || ((mw[j] >> (e_doc[j] & 31u)) & 1u))) {
                 const double sqd = probs ? topic_dot(p.prior, probs, p.k_topics, e_doc[j]) : 0.0;
                 double title, body, fin;
                 final_rank(T[j], B[j], T[j] != 0.0 ? mt[j] : 1.0, B[j] != 0.0 ? mb[j] : 1.0, qmag, sqd, title, body, fin);
@@ -333,14 +338,21 @@ int32_t launch_score_small(const void* params, unsigned n_a, unsigned n_b, hipSt
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_B>());
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_A>());
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_B, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_B>());
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_A, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_A>());
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_B, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_B>());
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_small<S_A, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds_bytes<S_A>());
         if (e != hipSuccess) return (int32_t)e;
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const ScoreParams& p = *static_cast<const ScoreParams*>(params);
-    if (n_b) hipLaunchKernelGGL(k_score_small<S_B>, dim3(n_b), dim3(ST), small_lds_bytes<S_B>(), st, p, (uint32_t)n_a);    // the larger queries first
-    if (n_a) hipLaunchKernelGGL(k_score_small<S_A>, dim3(n_a), dim3(ST), small_lds_bytes<S_A>(), st, p, 0u);
+    if (p.q_mask) {                        // (a call with an allow-list: the host sets q_mask)
+        if (n_b) hipLaunchKernelGGL((k_score_small<S_B, true>), dim3(n_b), dim3(ST), small_lds_bytes<S_B>(), st, p, (uint32_t)n_a);
+        if (n_a) hipLaunchKernelGGL((k_score_small<S_A, true>), dim3(n_a), dim3(ST), small_lds_bytes<S_A>(), st, p, 0u);
+        return 0;
+    }
+    if (n_b) hipLaunchKernelGGL((k_score_small<S_B, false>), dim3(n_b), dim3(ST), small_lds_bytes<S_B>(), st, p, (uint32_t)n_a);    // the larger queries first
+    if (n_a) hipLaunchKernelGGL((k_score_small<S_A, false>), dim3(n_a), dim3(ST), small_lds_bytes<S_A>(), st, p, 0u);
     return 0;
 }
 

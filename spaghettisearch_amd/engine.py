@@ -443,6 +443,25 @@ class InvertedIndex:
             self.h = None
 
 
+def pack_doc_masks(sets, n_docs: int) -> np.ndarray:
+    """Allow-lists for Scorer.set_doc_masks -> uint32 words [n_masks][(n_docs + 31) // 32], bit (d & 31) of word d >> 5 = doc d.
+    `sets`: a list of doc-id arrays (ids outside 0 .. n_docs-1 are an error), or a bool array [n_masks][n_docs]."""
+    n_words = (int(n_docs) + 31) // 32
+    if isinstance(sets, np.ndarray) and sets.dtype == np.bool_:
+        if sets.ndim != 2 or sets.shape[1] != n_docs:
+            raise ValueError(f"bool masks must have shape [n_masks][{n_docs}], got {sets.shape}")
+        bits = np.zeros((sets.shape[0], n_words * 32), dtype=np.bool_)
+        bits[:, :n_docs] = sets
+    else:
+        bits = np.zeros((len(sets), n_words * 32), dtype=np.bool_)
+        for i, docs in enumerate(sets):
+            docs = np.asarray(docs, dtype=np.int64).ravel()
+            if docs.size and (docs.min() < 0 or docs.max() >= n_docs):
+                raise ValueError(f"mask {i}: doc id outside 0 .. {n_docs - 1}")
+            bits[i, docs] = True
+    return np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(bits.shape[0], n_words).astype(np.uint32)
+
+
 class Scorer:
     """Batched OR-query cosine scorer + PageRank blend + top-k (ss_score_topk)."""
 
@@ -464,6 +483,40 @@ class Scorer:
         self.k_topics = int(rank.shape[0])
         self.ctx.ready(rank)
         check(self.ctx.lib.ss_scorer_set_prior(self.h, self.k_topics, _ptr(rank)), self.ctx.h)
+
+    def set_doc_masks(self, masks) -> None:
+        """ss_scorer_set_doc_masks: register allow-lists (uint32 words [n_masks][(n_docs + 31) // 32] as pack_doc_masks gives,
+        numpy or torch), or None / an empty set to clear.  Replaces the previous set once the scorer's outstanding work is done."""
+        if masks is None or len(masks) == 0:
+            check(self.ctx.lib.ss_scorer_set_doc_masks(self.h, 0, None), self.ctx.h)
+            return
+        masks = _as(masks, "uint32")
+        self.ctx.ready(masks)
+        check(self.ctx.lib.ss_scorer_set_doc_masks(self.h, int(masks.shape[0]), _ptr(masks)), self.ctx.h)
+
+    def score_topk_masked(self, q_ptr, q_terms, mask_id, k: int, p_ptr=None, p_terms=None, query_len=None, topic_probs=None, out=None):
+        """ss_score_topk_masked: query q's top-k restricted to the docs of allow-list mask_id[q] (-1: unrestricted; None: all -1).
+        p_ptr / p_terms: quoted phrases as in score_topk_phrase (None: plain OR queries).  out: device outputs as in score_topk."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        mask_id = _as(mask_id, "int32")
+        p_ptr = _as(p_ptr, "uint32")
+        p_terms = _as(p_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        n_q = int(q_ptr.shape[0]) - 1
+        self.ctx.ready(q_ptr, q_terms, mask_id, p_ptr, p_terms, query_len, topic_probs)
+        if out is not None:
+            hits, n_hits = out
+            if hits.numel() * hits.element_size() < n_q * k * HIT_DTYPE.itemsize or n_hits.numel() < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            hits, n_hits = np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32)
+        check(self.ctx.lib.ss_score_topk_masked(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(p_ptr), _ptr(p_terms), _ptr(query_len),
+                                                _ptr(topic_probs), _ptr(mask_id), k, _ptr(hits), _ptr(n_hits)), self.ctx.h)
+        if out is not None and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return hits, n_hits
 
     def score_topk_phrase(self, q_ptr, q_terms, p_ptr, p_terms, k: int, query_len=None, topic_probs=None):
         """ss_score_topk_phrase: OR terms + one concatenated quoted phrase per query."""
@@ -537,4 +590,4 @@ class Scorer:
             self.h = None
 
 
-__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "SsHit"]
+__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "SsHit", "pack_doc_masks"]

@@ -114,6 +114,13 @@ PYBIND11_MODULE(_host, m) {
             auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
             return di.RetrieveBatch(queries, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("RetrieveBatch", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, const std::vector<std::string>& masks,
+                                 int k, py::object topic_probs, bool live_topic_probs) {
+            if (topic_probs.is_none()) return di.RetrieveBatch(queries, masks, k, nullptr, live_topic_probs);
+            auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
+            return di.RetrieveBatch(queries, masks, k, &tp, live_topic_probs);
+        }, py::arg("queries"), py::arg("masks"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("SetDocMasks", &retrieval::DeviceIndex::SetDocMasks, py::arg("sets"))
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;
             auto f = as_dbs(forw), i = as_dbs(inv);

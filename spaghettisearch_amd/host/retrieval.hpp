@@ -191,6 +191,11 @@ public:
     std::function<std::vector<std::string>(const std::string&)> laundry = defaultLaundry;
     bool mags_resident = false;      // squared magnitudes resident on the device: deltas keep them up to date
     bool flat_stale = false;         // deltas were applied since `flat` was filled
+    // Named doc allow-lists (no reference counterpart): "search within a category" (TopicTeleportSets' doc set of an ODP
+    // category used as a result restriction), "hide these pages".  Kept by doc hash: every scorer this index creates (upload,
+    // ApplyDelta) gets them again, with the ids as they stand then.
+    std::map<std::string, std::vector<std::string>> mask_sets;
+    std::map<std::string, int32_t> mask_index;      // name -> the scorer's mask id
 
     ~DeviceIndex() {
         if (scorer) ss_scorer_destroy(scorer);
@@ -285,6 +290,33 @@ public:
         categories = flat.categories;
         const size_t K = categories.size();
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
+        register_masks();
+    }
+
+    // Replace the named allow-lists: name -> doc hashes (hashes the index does not hold are ignored).
+    void SetDocMasks(const std::map<std::string, std::vector<std::string>>& sets) {
+        mask_sets = sets;
+        register_masks();
+    }
+    // mask_sets -> the scorer's doc masks (ss_scorer_set_doc_masks), in name order
+    void register_masks() {
+        using namespace spaghetti;
+        mask_index.clear();
+        if (!scorer || !title) return;
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        const size_t W = (size_t)((n + 31) / 32);
+        std::vector<uint32_t> words(mask_sets.size() * W, 0u);
+        int32_t m = 0;
+        for (auto& kv : mask_sets) {
+            uint32_t* row = words.data() + (size_t)m * W;
+            for (auto& d : kv.second) {
+                auto it = docs.id.find(d);
+                if (it != docs.id.end() && it->second < n) row[it->second >> 5] |= 1u << (it->second & 31);
+            }
+            mask_index[kv.first] = m++;
+        }
+        check(ss_scorer_set_doc_masks(scorer, m, m ? words.data() : nullptr), "ss_scorer_set_doc_masks");
     }
 
     // On-disk snapshot of the flattened tables with the md5-hex <-> dense-id maps: written once after
@@ -357,6 +389,7 @@ public:
                 const size_t K = di.categories.size(), nd = di.docs.name.size();
                 if (ss_scorer_create(spaghetti::default_ctx(), di.title, di.body, &di.scorer) != SS_OK) { di.scorer = nullptr; return; }
                 if (K > 0 && K <= SS_MAX_TOPICS && di.flat.prior.size() == K * nd) (void)ss_scorer_set_prior(di.scorer, (int32_t)K, di.flat.prior.data());
+                try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
             }
         } scorer_guard{*this};
         bool resized = false;
@@ -472,6 +505,7 @@ public:
         const size_t K = categories.size();
         check(ss_scorer_create(default_ctx(), title, body, &scorer), "ss_scorer_create");
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
+        register_masks();                                                 // the new scorer, the ids as they stand now
     }
 
     // forw[3] was rewritten (UpdateTopicSensitivePagerank / ResidentPagerank::Run): refresh the scorer's PageRank table.
@@ -644,6 +678,28 @@ public:
         std::vector<int32_t> n_hits(t.nq);
         check(ss_score_topk_phrase(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
                                    t.probs.empty() ? nullptr : t.probs.data(), k, hits.data(), n_hits.data()), "ss_score_topk_phrase");
+        return to_ranks(t.nq, k, hits, n_hits);
+    }
+    // RetrieveBatch with one allow-list per query: masks[q] names a set of SetDocMasks, "" = the whole index.  Row q holds
+    // the first k docs of query q's ranking that the set allows (not a filter of the unrestricted top k).
+    std::vector<std::vector<Rank_combined>> RetrieveBatch(const std::vector<std::string>& queries, const std::vector<std::string>& masks,
+                                                          int k = 50, const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                          bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (masks.size() != queries.size()) throw std::runtime_error("RetrieveBatch: one mask name per query");
+        std::vector<int32_t> mask_id(queries.size(), -1);
+        for (size_t q = 0; q < masks.size(); q++) {
+            if (masks[q].empty()) continue;
+            auto it = mask_index.find(masks[q]);
+            if (it == mask_index.end()) throw std::runtime_error("RetrieveBatch: no doc mask named '" + masks[q] + "' (SetDocMasks)");
+            mask_id[q] = it->second;
+        }
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        std::vector<ss_hit> hits((size_t)t.nq * k);
+        std::vector<int32_t> n_hits(t.nq);
+        check(ss_score_topk_masked(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                   t.probs.empty() ? nullptr : t.probs.data(), mask_id.data(), k, hits.data(), n_hits.data()),
+              "ss_score_topk_masked");
         return to_ranks(t.nq, k, hits, n_hits);
     }
     // The same in two halves, for a caller that has the next batch ready while this one runs (RetrieveBatcher): BeginBatch tokenises
