@@ -427,6 +427,34 @@ func (s *Scorer) ScoreTopKMasked(qPtr, qTerms, pPtr, pTerms []uint32, queryLen [
 	return out, nil
 }
 
+// ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every
+// result contains it, title or body), excPtr/excTerms its excluded ones ("-word": no result does); nil pointers = none.  The
+// constraint terms only filter; put a required word in qTerms too for it to be scored.
+func (s *Scorer) ScoreTopKConstrained(qPtr, qTerms, pPtr, pTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32,
+	reqPtr, reqTerms, excPtr, excTerms []uint32, k int) ([][]Hit, error) {
+	nq := len(qPtr) - 1
+	if nq == 0 {
+		return nil, nil
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	rc := C.ss_score_topk_constrained(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), u32p(pPtr), u32p(pTerms), i32p(queryLen),
+		f64p(topicProbs), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr), u32p(excTerms), C.int32_t(k),
+		(*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	if err := statusErr(s.ctx, rc, "ss_score_topk_constrained"); err != nil {
+		return nil, err
+	}
+	out := make([][]Hit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Hit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*k+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
 // ScoreTopKPhrase = ScoreTopK plus one (concatenated) quoted phrase per query (retrieval/phrase.go).
 func (s *Scorer) ScoreTopKPhrase(qPtr, qTerms, pPtr, pTerms []uint32, queryLen []int32, topicProbs []float64, k int) ([][]Hit, error) {
 	nq := len(qPtr) - 1

@@ -35,7 +35,8 @@ extern "C" {
  * still run on the context's stream (everything that reads the graph is ordered behind them); "score.pipeline" defaults to 2
  * internal wave streams and ss_last_kernel_ms(1) is the device time of the last scoring call's kernels on the stream that
  * carries its merge.  A binding checks ss_abi_version() == SS_ABI_VERSION at load.
- * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists). */
+ * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists);
+ * ss_score_topk_constrained (required and excluded query terms). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -53,6 +54,7 @@ enum {
 #define SS_MAX_TOPK 1024     /* largest k accepted by ss_score_topk */
 #define SS_MAX_TOPICS 64     /* largest k_topics accepted by every entry point (also by the opt-in two-vector form, "pr.affine") */
 #define SS_MAX_QUERY_TERMS 64
+#define SS_MAX_CONSTRAINT_TERMS 16   /* required + excluded terms per query, after de-duplication (ss_score_topk_constrained) */
 #define SS_UNKNOWN_TERM 0xFFFFFFFFu /* term id for "key not found" (main_retrieve.go:193,218) */
 
 typedef struct ss_ctx ss_ctx;
@@ -375,6 +377,30 @@ int32_t ss_score_topk_masked(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
                              const uint32_t* p_ptr, const uint32_t* p_terms, const int32_t* query_len,
                              const double* topic_probs, const int32_t* mask_id, int32_t k,
                              ss_hit* hits_out, int32_t* n_hits_out);
+
+/* Query operators: ss_score_topk_masked plus required ("+word") and excluded ("-word") terms per query.  No reference counterpart.
+ * Doc d CONTAINS term t if d has a posting of t in the title or the body table (any weight, zero included).  Doc d is allowed for
+ * query q iff d is in mask(q) (the allow-list mask_id[q], every doc for -1), contains every term of req_terms[req_ptr[q] ..
+ * req_ptr[q+1]) and no term of exc_terms[exc_ptr[q] .. exc_ptr[q+1]).  Row q = the first min(k, m) rows of query q's unrestricted
+ * ranking (FinalRank desc, ties doc asc, NaN last) restricted to its allowed docs: byte for byte what ss_score_topk_masked returns
+ * with that allowed set registered as the query's allow-list.
+ * Constraint terms only filter: they add nothing to the score, to query_len or to the candidates (a caller who wants "+foo" scored
+ * too puts foo in q_terms as well).  A term id >= n_terms (SS_UNKNOWN_TERM included) has no postings: an unknown required term
+ * leaves the row empty, an unknown excluded term does nothing; a term both required and excluded leaves the row empty; duplicates
+ * change nothing.  req_ptr / exc_ptr [n_q+1] (NULL = none) start at 0 and never decrease, else SS_ERR_INVALID; more than
+ * SS_MAX_CONSTRAINT_TERMS distinct required + excluded ids in one query is SS_ERR_UNSUPPORTED; a bad mask_id is SS_ERR_INVALID as
+ * in ss_score_topk_masked.  Every check comes before anything is enqueued and leaves the outputs untouched.
+ * Inputs are read on the host like the query arrays (device pointers cost one blocking copy each); outputs as ss_score_topk (device
+ * outputs: the call only enqueues, pipelined like any other batch).  The allowed sets are built on the device for the call, one
+ * per distinct (mask, required, excluded) combination: n_docs / 8 bytes each (1.25 MB at 10M docs), SS_ERR_OOM if that memory
+ * cannot be had.  A call without a constraint IS ss_score_topk_masked (same kernels, bit-identical rows).
+ * There is no constrained form of ss_score_topk_submit / _collect. */
+int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                                  const uint32_t* p_ptr, const uint32_t* p_terms, const int32_t* query_len,
+                                  const double* topic_probs, const int32_t* mask_id,
+                                  const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                                  const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                                  int32_t k, ss_hit* hits_out, int32_t* n_hits_out);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

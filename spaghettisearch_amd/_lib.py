@@ -101,6 +101,7 @@ PROTOTYPES = {
     "ss_score_topk_collect": (_i32, [_vp, C.c_uint64, _vp, _vp]),
     "ss_scorer_set_doc_masks": (_i32, [_vp, _i32, _vp]),
     "ss_score_topk_masked": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ss_score_topk_constrained": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

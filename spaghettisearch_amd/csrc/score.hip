@@ -1393,6 +1393,8 @@ int32_t launch_score_small(const void* params, unsigned n_a, unsigned n_b, hipSt
 void launch_small_copy(const void* params, unsigned n_small, hipStream_t st);
 void score_small_report();
 void score_wave_diag_dump();
+uint32_t constraint_blocks(uint64_t n_words);
+void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st);
 }  // namespace ss
 
 struct ss_scorer {
@@ -1448,6 +1450,8 @@ struct ss_scorer {
     ss::DevBuf<uint32_t> d_so_doc2[TURNS], d_so_cnt2[TURNS], d_qticket, d_qcnt2[TURNS];
     ss::DevBuf<ss_hit> d_small_stage[TURNS];         // k_score_small's rows of a pipelined batch (k_small_copy moves them on the caller's stream)
     ss::DevBuf<int32_t> d_small_stage_n[TURNS];
+    ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
+    hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
     hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
@@ -1485,6 +1489,7 @@ struct ss_scorer {
             if (batch_ev[i]) (void)hipEventDestroy(batch_ev[i]);
             if (wave_ev[i]) (void)hipEventDestroy(wave_ev[i]);
             if (slice_ev[i]) (void)hipEventDestroy(slice_ev[i]);
+            if (set_ev[i]) (void)hipEventDestroy(set_ev[i]);
         }
     }
 };
@@ -1686,9 +1691,13 @@ int32_t ss_scorer_set_doc_masks(ss_scorer* s, int32_t n_masks, const uint32_t* w
     return SS_OK;
 }
 
+// the constraint arrays of ss_score_topk_constrained (NULL pointers: none)
+struct QueryConstraints { const uint32_t *req_ptr, *req_terms, *exc_ptr, *exc_terms; };
+
 static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                           const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id = nullptr);
+                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id = nullptr,
+                          const QueryConstraints* cons = nullptr);
 
 int32_t ss_score_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
                       const double* topic_probs, int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
@@ -1706,6 +1715,14 @@ int32_t ss_score_topk_masked(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
                              const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
                              int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
     return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id);
+}
+
+int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
+                                  const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
+                                  const uint32_t* req_ptr, const uint32_t* req_terms, const uint32_t* exc_ptr, const uint32_t* exc_terms,
+                                  int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
+    const QueryConstraints cons{req_ptr, req_terms, exc_ptr, exc_terms};
+    return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, &cons);
 }
 
 // Batches in flight with HOST results: submit runs the batch like a call with device outputs (nothing waits, consecutive batches
@@ -1831,15 +1848,15 @@ int32_t ss_score_topk_collect(ss_scorer* s, uint64_t ticket, ss_hit* hits_out, i
 
 static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                                 const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id);
+                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons);
 
 // no C++ exception may cross the C ABI: host allocation failures come back as SS_ERR_OOM
 static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                           const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id) {
+                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons) {
     if (!s) return SS_ERR_INVALID;
     try {
-        return score_impl_inner(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id);
+        return score_impl_inner(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, cons);
     } catch (const std::bad_alloc&) {
         return s->ctx->fail(SS_ERR_OOM, "ss_score_topk: host allocation failed");
     } catch (const std::exception& e) {
@@ -1849,7 +1866,7 @@ static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, cons
 
 static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
                                 const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id) {
+                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons) {
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1869,6 +1886,86 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
             if (h_mask[q] < -1 || h_mask[q] >= s->n_masks)
                 return ctx->fail(SS_ERR_INVALID, "ss_score_topk_masked: query %d has mask id %d (the scorer has %d masks)", q, h_mask[q], s->n_masks);
             any_mask = any_mask || h_mask[q] >= 0;
+        }
+    }
+    // query operators (ss_score_topk_constrained): required / excluded terms, checked here too, and resolved to one allowed set per
+    // distinct (mask, required, excluded) combination, which k_constraint_masks builds on the device in the call's set buffer.  The
+    // scoring kernels take the sets as the masked call takes registered allow-lists: q_mask / SmallHdr carry the set's index.
+    std::vector<ConstraintSet> h_csets;
+    std::vector<ConstraintTerm> h_cterms;
+    if (cons && (cons->req_ptr || cons->exc_ptr)) {
+        const std::vector<uint64_t>& tp = s->title->h_term_ptr;
+        const std::vector<uint64_t>& bp = s->body->h_term_ptr;
+        std::vector<uint32_t> rp(n_q + 1, 0), rt, ep(n_q + 1, 0), et;
+        auto load = [&](const uint32_t* ptr, const uint32_t* terms, std::vector<uint32_t>& hp, std::vector<uint32_t>& ht, const char* what) -> int32_t {
+            if (!ptr) return SS_OK;
+            SS_HIP(ctx, ss::copy_in(ctx->stream, hp.data(), ptr, (n_q + 1) * sizeof(uint32_t)));
+            if (hp[0] != 0) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr[0] is %u, not 0", what, hp[0]);
+            for (int q = 0; q < n_q; q++)
+                if (hp[q + 1] < hp[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr not non-decreasing", what);
+            ht.resize(hp[n_q]);
+            if (hp[n_q] && !terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_terms is NULL", what);
+            if (hp[n_q]) SS_HIP(ctx, ss::copy_in(ctx->stream, ht.data(), terms, ht.size() * sizeof(uint32_t)));
+            return SS_OK;
+        };
+        int32_t rc = load(cons->req_ptr, cons->req_terms, rp, rt, "req");
+        if (rc == SS_OK) rc = load(cons->exc_ptr, cons->exc_terms, ep, et, "exc");
+        if (rc != SS_OK) return rc;
+        auto df = [&](uint32_t t) -> uint64_t { return (uint64_t)t < s->n_terms ? (tp[t + 1] - tp[t]) + (bp[t + 1] - bp[t]) : 0; };
+        // a query's set key: {CS_EMPTY} (no doc can be allowed), {mask + 1, n_req, required ids, excluded ids}, or none at all
+        std::vector<std::vector<uint32_t>> keys(n_q);
+        bool constrained = false;
+        std::vector<uint32_t> req, exc;
+        for (int q = 0; q < n_q; q++) {
+            req.assign(rt.begin() + rp[q], rt.begin() + rp[q + 1]);
+            exc.assign(et.begin() + ep[q], et.begin() + ep[q + 1]);
+            std::sort(req.begin(), req.end());
+            req.erase(std::unique(req.begin(), req.end()), req.end());
+            std::sort(exc.begin(), exc.end());
+            exc.erase(std::unique(exc.begin(), exc.end()), exc.end());
+            if (req.size() + exc.size() > SS_MAX_CONSTRAINT_TERMS)
+                return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk_constrained: query %d has %zu distinct required + excluded terms (max %d)", q,
+                                 req.size() + exc.size(), SS_MAX_CONSTRAINT_TERMS);
+            // a term without postings (unknown ids included): required, no doc contains it; excluded, it excludes nothing
+            bool empty = false;
+            for (uint32_t t : req) empty = empty || df(t) == 0 || std::binary_search(exc.begin(), exc.end(), t);
+            exc.erase(std::remove_if(exc.begin(), exc.end(), [&](uint32_t t) { return df(t) == 0; }), exc.end());
+            if (empty) keys[q] = {CS_EMPTY};
+            else if (!req.empty() || !exc.empty()) {
+                keys[q] = {(uint32_t)((mask_id ? h_mask[q] : -1) + 1), (uint32_t)req.size()};
+                keys[q].insert(keys[q].end(), req.begin(), req.end());
+                keys[q].insert(keys[q].end(), exc.begin(), exc.end());
+            }
+            constrained = constrained || !keys[q].empty();
+        }
+        if (constrained) {
+            // every query with a set: the constrained ones and, since the sets replace the registered masks for the call, the ones
+            // with an allow-list alone (a set without terms: the builder copies the list)
+            h_mask.resize(n_q);
+            std::map<std::vector<uint32_t>, int32_t> set_of;
+            for (int q = 0; q < n_q; q++) {
+                const int32_t m = mask_id ? h_mask[q] : -1;
+                if (keys[q].empty() && m >= 0) keys[q] = {(uint32_t)(m + 1), 0u};
+                if (keys[q].empty()) { h_mask[q] = -1; continue; }
+                auto it = set_of.find(keys[q]);
+                if (it == set_of.end()) {
+                    const std::vector<uint32_t>& key = keys[q];
+                    ConstraintSet cs{CS_EMPTY, 0u, 0u, (uint32_t)h_cterms.size()};
+                    if (key[0] != CS_EMPTY) {
+                        cs.mask1 = key[0];
+                        cs.n_req = key[1];
+                        cs.n_exc = (uint32_t)key.size() - 2 - key[1];
+                        // the required terms rarest first: a block that one of them empties skips the others
+                        std::vector<uint32_t> order(key.begin() + 2, key.end());
+                        std::stable_sort(order.begin(), order.begin() + cs.n_req, [&](uint32_t a, uint32_t b) { return df(a) < df(b); });
+                        for (uint32_t t : order) h_cterms.push_back(ConstraintTerm{tp[t], tp[t + 1], bp[t], bp[t + 1]});
+                    }
+                    it = set_of.emplace(key, (int32_t)h_csets.size()).first;
+                    h_csets.push_back(cs);
+                }
+                h_mask[q] = it->second;
+            }
+            any_mask = true;
         }
     }
 
@@ -2262,6 +2359,9 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     const size_t o_qfast = o;  o = align16(o + (size_t)n_q);
     const size_t o_smalltab = o; o = align16(o + n_small * small_stride);
     const size_t o_qmask = o;  o = align16(o + (any_mask ? (size_t)n_q * sizeof(int32_t) : 0));
+    const size_t n_csets = h_csets.size();
+    const size_t o_csets = o;  o = align16(o + n_csets * sizeof(ConstraintSet));
+    const size_t o_cterms = o; o = align16(o + h_cterms.size() * sizeof(ConstraintTerm));
 #ifdef SS_EXP_FLOOR
     const bool use_floor = ctx->opt("score.debug_floor", 0) != 0 && s->dbg_floor.size() == (size_t)n_q;
 #else
@@ -2291,6 +2391,18 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
         s->batch_ev_pending[pb] = false;
     }
     SS_HIP(ctx, ensure(s->d_plan2[pb], plan_bytes));
+    // the call's allowed sets: this turn's buffer, free since the wait above (the batch that last read it is done); exactly the size
+    // needed (1.25 MB per set at 10M docs), not grown by half like the other workspaces
+    const uint64_t set_stride = std::max<uint64_t>(4, ((s->n_docs + 31) / 32 + 3) & ~(uint64_t)3);
+    if (n_csets && s->d_sets[pb].n < n_csets * set_stride) {
+        const hipError_t e = s->d_sets[pb].alloc(n_csets * set_stride);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->d_sets[pb].release();
+            return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "ss_score_topk_constrained: no device memory for %zu allowed sets of %llu bytes",
+                             n_csets, (unsigned long long)(set_stride * sizeof(uint32_t)));
+        }
+    }
     unsigned char* hp = s->h_plan[pb];
     std::memcpy(hp + o_qoff, h_qoff.data(), (n_q + 1) * sizeof(uint32_t));
     if (n_d) {
@@ -2313,6 +2425,10 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     std::memcpy(hp + o_qfast, h_fast.data(), (size_t)n_q);
     if (use_floor) std::memcpy(hp + o_qfloor, s->dbg_floor.data(), (size_t)n_q * sizeof(float));
     if (any_mask) std::memcpy(hp + o_qmask, h_mask.data(), (size_t)n_q * sizeof(int32_t));
+    if (n_csets) {
+        std::memcpy(hp + o_csets, h_csets.data(), n_csets * sizeof(ConstraintSet));
+        if (!h_cterms.empty()) std::memcpy(hp + o_cterms, h_cterms.data(), h_cterms.size() * sizeof(ConstraintTerm));
+    }
     {
         unsigned char* w = hp + o_smalltab;              // the 1024-slot queries first, then the larger ones (launch_score_small)
         for (const std::vector<SmallEnt>* v : {&h_small_a, &h_small_b})
@@ -2431,8 +2547,8 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
     p.hits = dev_out ? hits_out : s->d_hits.p;
     p.n_hits = dev_out ? n_hits_out : one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + res_rows) : s->d_nhits.p;
     p.q_mask = any_mask ? reinterpret_cast<const int32_t*>(dp + o_qmask) : nullptr;
-    p.masks = any_mask ? s->masks.p : nullptr;
-    p.mask_words = s->mask_words;
+    p.masks = n_csets ? s->d_sets[pb].p : any_mask ? s->masks.p : nullptr;
+    p.mask_words = n_csets ? set_stride : s->mask_words;
 
     // "score.pipeline" (default): a batch that is all k_score_wave, results in device memory.  Its k_wave_prep and k_score_wave go
     // to the context's WAVE stream, its k_merge_flat to the caller's stream behind an event: the next batch's k_score_wave (which
@@ -2499,6 +2615,24 @@ static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
         }
     }
     if (pipe_s) sst = wst;
+    if (n_csets) {                               // the allowed sets, in front of the kernels that read them (never k_score_wave)
+        ConstraintParams cp{};
+        cp.t_doc = s->title->post_doc.p; cp.b_doc = s->body->post_doc.p;
+        cp.sets = reinterpret_cast<const ConstraintSet*>(dp + o_csets);
+        cp.terms = reinterpret_cast<const ConstraintTerm*>(dp + o_cterms);
+        cp.reg_masks = s->masks.p; cp.reg_words = s->mask_words;
+        cp.out = s->d_sets[pb].p;
+        cp.stride = set_stride;
+        cp.n_words = (s->n_docs + 31) / 32;
+        cp.n_blocks = ss::constraint_blocks(set_stride);
+        ss::launch_constraint_masks(&cp, (uint32_t)n_csets, sst);
+        hipStream_t small_st = !small_staged ? st : small_alone ? wst : sst;
+        if (n_small && small_st != sst) {
+            if (!s->set_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->set_ev[pb], hipEventDisableTiming));
+            SS_HIP(ctx, hipEventRecord(s->set_ev[pb], sst));
+            SS_HIP(ctx, hipStreamWaitEvent(small_st, s->set_ev[pb], 0));
+        }
+    }
     if (n_small) {                     // writes its queries' hits itself: the caller's stream, like every kernel that does — or stages them
         const int32_t rc_s = ss::launch_score_small(&p, (unsigned)n_small_a, (unsigned)n_small_b, !small_staged ? st : small_alone ? wst : sst);
         if (rc_s != 0) return ctx->fail(SS_ERR_HIP, "k_score_small: %s", hipGetErrorString((hipError_t)rc_s));

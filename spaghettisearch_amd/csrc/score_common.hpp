@@ -159,6 +159,24 @@ struct __attribute__((aligned(16))) SmallHdr { uint32_t q, n_lists, tot, mask1; 
 struct __attribute__((aligned(16))) SmallList { uint64_t start; uint32_t end, mf; };    // first posting in its table; postings of lists 0..this one; multiplicity << 1 | field (1 = title)
 static_assert(sizeof(SmallHdr) == 32 && sizeof(SmallList) == 16, "small-query table layout");
 
+// k_constraint_masks (constraint.hip, ss_score_topk_constrained): one allow-list per distinct (mask, required, excluded) set of a call
+#define CS_EMPTY 0xFFFFFFFFu
+struct __attribute__((aligned(16))) ConstraintSet { uint32_t mask1, n_req, n_exc, t0; };   // mask1: registered allow-list + 1 it starts from (0: every doc, CS_EMPTY: no doc); terms t0 .. t0+n_req+n_exc, required first
+struct __attribute__((aligned(16))) ConstraintTerm { uint64_t t_b, t_e, b_b, b_e; };      // the term's title and body postings [b, e)
+static_assert(sizeof(ConstraintSet) == 16 && sizeof(ConstraintTerm) == 32, "constraint table layout");
+struct ConstraintParams {
+    const uint32_t* t_doc;            // the tables' post_doc (strictly ascending inside a term)
+    const uint32_t* b_doc;
+    const ConstraintSet* sets;
+    const ConstraintTerm* terms;
+    const uint32_t* reg_masks;        // the scorer's registered allow-lists [n_masks][reg_words]
+    uint64_t reg_words;
+    uint32_t* out;                    // [n_sets][stride]
+    uint64_t stride;                  // words per set: n_words rounded up to 4
+    uint64_t n_words;                 // (n_docs + 31) / 32
+    uint32_t n_blocks;                // workgroups per set
+};
+
 using ss::fkey;
 using ss::funkey;
 using ss::better;

@@ -518,6 +518,35 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return hits, n_hits
 
+    def score_topk_constrained(self, q_ptr, q_terms, k: int, req=None, exc=None, mask_id=None, p_ptr=None, p_terms=None,
+                               query_len=None, topic_probs=None, out=None):
+        """ss_score_topk_constrained: score_topk_masked where every doc of row q must also contain each REQUIRED term of query q
+        (title or body posting) and none of its EXCLUDED terms.  req / exc: (ptr [n_q + 1], terms) pairs or None.  Constraint
+        terms only filter (they are not scored).  out: device outputs as in score_topk."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        p_ptr = _as(p_ptr, "uint32")
+        p_terms = _as(p_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        n_q = int(q_ptr.shape[0]) - 1
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, p_ptr, p_terms, query_len, topic_probs)
+        if out is not None:
+            hits, n_hits = out
+            if hits.numel() * hits.element_size() < n_q * k * HIT_DTYPE.itemsize or n_hits.numel() < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            hits, n_hits = np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32)
+        check(self.ctx.lib.ss_score_topk_constrained(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(p_ptr), _ptr(p_terms), _ptr(query_len),
+                                                     _ptr(topic_probs), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                                     _ptr(exc_terms), k, _ptr(hits), _ptr(n_hits)), self.ctx.h)
+        if out is not None and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return hits, n_hits
+
     def score_topk_phrase(self, q_ptr, q_terms, p_ptr, p_terms, k: int, query_len=None, topic_probs=None):
         """ss_score_topk_phrase: OR terms + one concatenated quoted phrase per query."""
         q_ptr = _as(q_ptr, "uint32")

@@ -91,6 +91,10 @@ PYBIND11_MODULE(_host, m) {
         ranking::UpdateTermWeights(ctx, &i, f, info);
     }, py::arg("inv"), py::arg("forw"), py::arg("info"));
     m.def("md5_hex", &md5::hex);
+    m.def("parseQueryOperators", [](const std::string& query) {
+        const retrieval::QueryOperators op = retrieval::parseQueryOperators(query);
+        return py::make_tuple(op.query, op.required, op.excluded);
+    }, py::arg("query"));
     m.def("computeTopicProbs", [as_dbs](std::vector<db::MemDB*> inv, std::vector<db::MemDB*> forw, const std::vector<std::string>& tokens, bool as_written) {
         db::Context ctx;
         auto i = as_dbs(inv), f = as_dbs(forw);
@@ -121,6 +125,7 @@ PYBIND11_MODULE(_host, m) {
             return di.RetrieveBatch(queries, masks, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("masks"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetDocMasks", &retrieval::DeviceIndex::SetDocMasks, py::arg("sets"))
+        .def("SetQueryOperators", &retrieval::DeviceIndex::SetQueryOperators, py::arg("on"))
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;
             auto f = as_dbs(forw), i = as_dbs(inv);

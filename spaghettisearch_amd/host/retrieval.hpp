@@ -55,6 +55,45 @@ inline std::vector<std::string> defaultLaundry(const std::string& s) {
     return out;
 }
 
+// Query operators (no reference counterpart; DeviceIndex::SetQueryOperators, default off).  Outside quoted phrases (the `".*?"`
+// pairs of getPhrase), a whitespace-separated token whose first character is '+' or '-' and whose second is one that `laundry`
+// keeps is an operator token: every word it launders to is REQUIRED ('+': each result must contain it) or EXCLUDED ('-': no result
+// may).  `query` is the string the scorer tokenises: '+' tokens stay in it (their words are scored and counted in query_len, as any
+// word), '-' tokens are taken out.  "e-mail", a lone "-", "--x" and everything between quotes are no operators.
+struct QueryOperators {
+    std::string query;
+    std::vector<std::string> required, excluded;
+};
+inline QueryOperators parseQueryOperators(const std::string& query,
+                                          const std::function<std::vector<std::string>(const std::string&)>& laundry = defaultLaundry) {
+    QueryOperators out;
+    std::vector<size_t> quotes;                          // the quotes that pair up as getPhrase's matches do: 0-1, 2-3, ...
+    for (size_t i = 0; i < query.size(); i++)
+        if (query[i] == '"') quotes.push_back(i);
+    if (quotes.size() % 2) quotes.pop_back();
+    size_t qi = 0, i = 0;
+    while (i < query.size()) {
+        if (qi < quotes.size() && i == quotes[qi]) {     // a quoted phrase: copied as it is
+            out.query.append(query, i, quotes[qi + 1] + 1 - i);
+            i = quotes[qi + 1] + 1;
+            qi += 2;
+            continue;
+        }
+        if (std::isspace((unsigned char)query[i])) { out.query += query[i++]; continue; }
+        size_t j = i;                                    // a token: up to whitespace or the next phrase
+        while (j < query.size() && !std::isspace((unsigned char)query[j]) && !(qi < quotes.size() && j == quotes[qi])) j++;
+        const std::string tok = query.substr(i, j - i);
+        const bool op = tok.size() > 1 && (tok[0] == '+' || tok[0] == '-') && !laundry(tok.substr(1, 1)).empty();
+        if (op) {
+            std::vector<std::string>& dst = tok[0] == '+' ? out.required : out.excluded;
+            for (auto& w : laundry(tok.substr(1))) dst.push_back(w);
+        }
+        if (!op || tok[0] == '+') out.query += tok;
+        i = j;
+    }
+    return out;
+}
+
 // computeTopicProbs, retrieval/main_retrieve.go:106-159 — DISABLED in the reference (the call at :43 is commented out and
 // :87 passes a nil map, so sqd = 0); restated so that the PageRank blend of get_metadata.go:39-42,69 can be switched on.
 //   queryTokenised: md5-hex word hashes as Retrieve makes them (:33-36);
@@ -196,6 +235,7 @@ public:
     // ApplyDelta) gets them again, with the ids as they stand then.
     std::map<std::string, std::vector<std::string>> mask_sets;
     std::map<std::string, int32_t> mask_index;      // name -> the scorer's mask id
+    bool query_operators = false;                   // SetQueryOperators: "+word" / "-word" in RetrieveBatch's query strings
 
     ~DeviceIndex() {
         if (scorer) ss_scorer_destroy(scorer);
@@ -669,10 +709,42 @@ public:
             }
         return out;
     }
+    // Query operators on (default off): RetrieveBatch reads "+word" / "-word" (parseQueryOperators) and answers through
+    // ss_score_topk_constrained.  Off, every query string is tokenised as it always was, '+' and '-' included.
+    void SetQueryOperators(bool on) { query_operators = on; }
+    // RetrieveBatch with query operators: mask_id as for ss_score_topk_masked (NULL: none)
+    std::vector<std::vector<Rank_combined>> retrieve_constrained(const std::vector<std::string>& queries, const int32_t* mask_id, int k,
+                                                                 const std::vector<std::map<std::string, double>>* topicProbs,
+                                                                 bool live_topic_probs) {
+        using namespace spaghetti;
+        std::vector<std::string> rewritten;
+        std::vector<uint32_t> req_ptr{0}, req_terms, exc_ptr{0}, exc_terms;
+        auto id_of = [&](const std::string& w) {
+            auto it = terms.id.find(md5::hex(w));
+            return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+        };
+        for (auto& q : queries) {
+            const QueryOperators op = parseQueryOperators(q, laundry);
+            rewritten.push_back(op.query);
+            for (auto& w : op.required) req_terms.push_back(id_of(w));
+            for (auto& w : op.excluded) exc_terms.push_back(id_of(w));
+            req_ptr.push_back((uint32_t)req_terms.size());
+            exc_ptr.push_back((uint32_t)exc_terms.size());
+        }
+        const Tokenised t = tokenise(rewritten, topicProbs, live_topic_probs);
+        std::vector<ss_hit> hits((size_t)t.nq * k);
+        std::vector<int32_t> n_hits(t.nq);
+        check(ss_score_topk_constrained(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                        t.probs.empty() ? nullptr : t.probs.data(), mask_id, req_ptr.data(), req_terms.data(),
+                                        exc_ptr.data(), exc_terms.data(), k, hits.data(), n_hits.data()),
+              "ss_score_topk_constrained");
+        return to_ranks(t.nq, k, hits, n_hits);
+    }
     std::vector<std::vector<Rank_combined>> RetrieveBatch(const std::vector<std::string>& queries, int k = 50,
                                                           const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
                                                           bool live_topic_probs = false) {
         using namespace spaghetti;
+        if (query_operators) return retrieve_constrained(queries, nullptr, k, topicProbs, live_topic_probs);
         const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
         std::vector<ss_hit> hits((size_t)t.nq * k);
         std::vector<int32_t> n_hits(t.nq);
@@ -694,6 +766,7 @@ public:
             if (it == mask_index.end()) throw std::runtime_error("RetrieveBatch: no doc mask named '" + masks[q] + "' (SetDocMasks)");
             mask_id[q] = it->second;
         }
+        if (query_operators) return retrieve_constrained(queries, mask_id.data(), k, topicProbs, live_topic_probs);
         const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
         std::vector<ss_hit> hits((size_t)t.nq * k);
         std::vector<int32_t> n_hits(t.nq);
