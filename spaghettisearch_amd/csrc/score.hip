@@ -1268,7 +1268,9 @@ __global__ __launch_bounds__(CM_TPB) void k_merge_lists(const uint64_t* __restri
         // fields in k_score_wave's inner loop (get_metadata.go:69 weighs title 0.38, body 0.29) — still an upper bound
         if (my_field) {
             const float v = r.imp * 1.3103449f;                          // 1.3103449f > 38/29; then two ulps up: above the real product
-            c.imp = v > 0.0f ? __uint_as_float(__float_as_uint(v) + 2u) : v;
+            // (never past +Inf: the bit patterns behind it are NaNs, whose share fx_share counts as ONE unit — for a title impact
+            //  beyond FLT_MAX / 1.31 the filter then dropped the very documents that win; +Inf saturates to FX_CLAMP and survives)
+            c.imp = v > 0.0f ? __uint_as_float(min(__float_as_uint(v) + 2u, 0x7F800000u)) : v;
         }
         c_rec[pos] = c;
         c_w[pos] = my_w[i];
