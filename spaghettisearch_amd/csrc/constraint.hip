@@ -7,7 +7,7 @@
 // list, found by two binary searches per list and block.  A workgroup owns one block of words of one set; it ORs a term's runs into
 // an LDS image of the block, combines the image into the words it keeps in registers, and writes every word exactly once with
 // vector stores.  No global atomics, no order dependence: the words are a function of the lists alone.
-#include "score_common.hpp"
+#include "scorer.hpp"
 
 namespace {
 

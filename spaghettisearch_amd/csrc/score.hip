@@ -16,7 +16,7 @@
 //   * scoring layout: one 8-byte record per posting {doc u32, impact f32}, impact = float32 UPPER bound of
 //     w / magnitude(doc, field).  The float32 weights and float64 magnitudes stay in the index's own arrays and
 //     are only read for documents that can still enter the top-k.
-//   * the host plans (it keeps df per term): duplicates -> multiplicities, unknown terms dropped, each query's
+//   * the host plans (score_call.hip; it keeps df per term): duplicates -> multiplicities, unknown terms dropped, each query's
 //     doc range cut into slices, longest first; one 512-thread workgroup per (query, slice).
 //   * k_score_slices builds the slice's window plan in LDS (window = a doc range holding <= CAP records; every
 //     record of a doc lies in one window), then streams the windows, window j+1's records in flight while window
@@ -40,15 +40,11 @@
 //   * k_merge_topk: one workgroup per query merges its slices' top-k lists, re-derives
 //     title/body/pagerank of the k winners by binary search and writes ss_hit rows.
 //   Ties: ascending doc id (Q10); NaN finals last.
-#include <chrono>
-#include "score_common.hpp"
+#include "scorer.hpp"
 
 namespace {
 
 // ---- K4: score one (query, doc-range slice) --------------------------------------
-#ifndef SS_WGS_PER_CU
-#define SS_WGS_PER_CU 2
-#endif
 struct ScoreLds {                     // byte offsets into the dynamic LDS block
     size_t s_rec, l_rec, l_w, sc64, cd_key, cd_doc, ht_key, ht_rec, sk, tbl, l_mult, l_field, f_cur, f_nxt, l_coef, sc32, sel, sel64, off, total;
 };
@@ -1058,7 +1054,6 @@ __device__ __forceinline__ float impact_of(float w, double mag) {
     return __double2float_ru((double)w / mag);
 }
 
-constexpr uint32_t PH_PART = 8192;   // candidates per k_phrase_match workgroup
 __global__ __launch_bounds__(PH_TPB) void k_phrase_match(ScoreParams p) {
     __shared__ int32_t s_pb[PH_MAX * PH_TPB];     // body posting index of term i for this thread's doc, -1 = none
     __shared__ int32_t s_pt[PH_MAX * PH_TPB];
@@ -1380,130 +1375,43 @@ double unkey(uint64_t k) {
 }  // namespace
 
 namespace ss {
-// score_wave.hip
-size_t score_wave_prep_bytes(unsigned n_slices);
-void launch_wave_prep(const void* params, unsigned n_slices, void* prep, hipStream_t st);
-void launch_score_wave(const void* params, unsigned n_slices, const void* prep, hipStream_t st);
-int score_wave_max_lists();
-int score_wave_max_k();
-// score_small.hip: one workgroup per small query (every posting scored exactly, hits written by the kernel itself)
-uint32_t score_small_cap();
-uint32_t score_small_cap_a();
-int score_small_max_k();
-int score_small_max_lists();
-int32_t launch_score_small(const void* params, unsigned n_a, unsigned n_b, hipStream_t st);
-void launch_small_copy(const void* params, unsigned n_small, hipStream_t st);
-void score_small_report();
-void score_wave_diag_dump();
-uint32_t constraint_blocks(uint64_t n_words);
-void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st);
-}  // namespace ss
-
-struct ss_scorer {
-    ss_ctx* ctx = nullptr;
-    ss_index* title = nullptr;
-    ss_index* body = nullptr;
-    uint64_t n_docs = 0, n_terms = 0;
-    ss::DevBuf<Rec> t_rec, b_rec;              // scoring records {doc, impact}
-    // combined lists (k_score_wave): title + body postings of a term merged by doc, field in bit 31 of the doc word
-    ss::DevBuf<Rec> c_rec;
-    ss::DevBuf<uint32_t> c_skip;
-    ss::DevBuf<float> c_w;
-    ss::DevBuf<uint64_t> c_ptr;
-    bool has_combined = false;
-    uint64_t c_pad_block = 0;
-    ss::DevBuf<float> t_kth, b_kth;             // [T][KTH_N] k'-th largest impact per term (threshold floor)
-    bool clean = true;                          // weights >= 0 and finite, magnitudes positive and finite where a weight is not 0
-    bool prior_clean = true;                    // every prior value >= 0 and finite
-    ss::DevBuf<double> prior;
-    std::vector<double> prior_max, prior_min;   // per topic
-    int k_topics = 0;
-    ss::DevBuf<uint32_t> masks;                 // ss_scorer_set_doc_masks: [n_masks][mask_words] allow-lists
-    int32_t n_masks = 0;
-    uint64_t mask_words = 0;
-    int lds_attr = 0, lds_attr_masked = 0;
-    // per-call workspaces, grow-only (no hipMalloc/hipFree on the steady-state query path)
-    // Turns of per-batch buffers: the host runs at most TURNS batches ahead.  (Three were measured for the pipelined mode, so that a
-    // batch's plan upload and k_wave_prep — which do not fit beside k_score_wave's three waves of 168 VGPRs per SIMD — are enqueued
-    // one batch earlier: 0.395 against 0.399 ms per batch, not worth a third set of buffers.)
-#ifndef SS_TURNS
-#define SS_TURNS 3
-#endif
-    static constexpr int TURNS = SS_TURNS;
-    unsigned wave_turn = 0;                    // which wave stream the next pipelined batch takes
-    ss::DevBuf<unsigned char> d_plan2[TURNS], d_wprep2[TURNS];   // the plan on the device, one buffer per turn: batch i+1's upload runs beside batch i's kernels
-    // pinned staging for the plan, double-buffered: a call that returns results in device memory does not wait
-    // for the GPU, so the next call plans (and fills the other buffer) while this one's copy and kernels run
-    unsigned char* h_plan[TURNS] = {};
-    size_t h_plan_cap[TURNS] = {};
-    std::vector<float> dbg_floor;    // experiment "score.debug_floor": the k-th best FinalRank of every query of the last host-output call, rounded down
-    unsigned char* h_res = nullptr;  // pinned landing block of small host results (one device-to-host copy for hits + counts)
-    static constexpr size_t H_RES_BYTES = 128 << 10;
-    hipEvent_t plan_ev[TURNS] = {}; // recorded after the H2D copy of the buffer (on the context's second stream)
-    hipEvent_t batch_ev[TURNS] = {};// recorded behind the kernels of the batch that read device buffer [turn]
-    bool batch_ev_pending[TURNS] = {};
-    size_t qcnt_zeroed2[TURNS] = {};           // counters known to be zero (k_merge_flat leaves its query's counter at zero)
-    bool plan_ev_pending[TURNS] = {};
-    int plan_turn = 0;
-    ss::DevBuf<Rec> d_x[TURNS][4];              // phrase result lists: scoring records (one set per turn: batches overlap)
-    ss::DevBuf<float> d_xw[TURNS][4];           // ... and their float32 weight sums
-    ss::DevBuf<uint32_t> d_xcnt[TURNS], d_pcnt[TURNS];
-    ss::DevBuf<uint64_t> d_so_key2[TURNS];           // the slices' candidates, one set per turn ("score.pipeline": batch i's merge reads its set while batch i+1 fills the other)
-    ss::DevBuf<uint32_t> d_so_doc2[TURNS], d_so_cnt2[TURNS], d_qticket, d_qcnt2[TURNS];
-    ss::DevBuf<ss_hit> d_small_stage[TURNS];         // k_score_small's rows of a pipelined batch (k_small_copy moves them on the caller's stream)
-    ss::DevBuf<int32_t> d_small_stage_n[TURNS];
-    ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
-    hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
-    hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
-    hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
-    size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
-    ss::DevBuf<ss_hit> d_hits;
-    // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
-    // an event behind them.
-    static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;
-    struct AsyncSlot {
-        ss::DevBuf<ss_hit> hits;
-        ss::DevBuf<int32_t> n_hits;
-        hipEvent_t ev = nullptr;             // behind the batch's kernels on the caller's stream
-        void* pin = nullptr;                 // "score.collect_pinned": the copy-out lands here first
-        size_t pin_cap = 0;
-        bool pin_mode = false;
-        uint64_t ticket = 0;                 // 0 = free
-        bool collecting = false;             // a collect call is waiting for / copying this slot outside the lock
-        void* pin_n = nullptr;               // pinned landing block of the counts (a small copy into pageable memory costs ~20 us more)
-        size_t pin_n_cap = 0;
-        int32_t n_q = 0, k = 0;
-    } aslot[INFLIGHT];
-    uint64_t next_ticket = 1;
-    hipStream_t out_stream = nullptr;        // collect's copies
-    ss::DevBuf<int32_t> d_nhits;
-    ~ss_scorer() {
-        if (out_stream) { (void)hipStreamSynchronize(out_stream); (void)hipStreamDestroy(out_stream); }
-        for (auto& a : aslot) {
-            if (a.ev) (void)hipEventDestroy(a.ev);
-            if (a.pin) ctx->pin_free(a.pin, a.pin_cap);
-            if (a.pin_n) ctx->pin_free(a.pin_n, a.pin_n_cap);
-        }
-        for (int i = 0; i < TURNS; i++) {
-            if (h_plan[i]) (void)hipHostFree(h_plan[i]);
-            if (i == 0 && h_res) (void)hipHostFree(h_res);
-            if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);
-            if (batch_ev[i]) (void)hipEventDestroy(batch_ev[i]);
-            if (wave_ev[i]) (void)hipEventDestroy(wave_ev[i]);
-            if (slice_ev[i]) (void)hipEventDestroy(slice_ev[i]);
-            if (set_ev[i]) (void)hipEventDestroy(set_ev[i]);
-        }
+hipError_t launch_score_slices(const void* params, unsigned first, unsigned n, bool masked, int* lds_attr, int* lds_attr_masked, hipStream_t st) {
+    ScoreParams p = *reinterpret_cast<const ScoreParams*>(params);
+    const int cb = p.cb;
+    const size_t lds_score = score_lds_bytes(cb);
+    hipError_t e = hipSuccess;
+    if (masked && *lds_attr_masked < cb) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score);
+        if (e != hipSuccess) return e;
+        *lds_attr_masked = cb;
     }
-};
-
-namespace {
-template <typename T>
-hipError_t ensure(ss::DevBuf<T>& b, size_t n) {
-    if (b.p && b.n >= n) return hipSuccess;
-    return b.alloc(n + n / 2 + 16);
+    if (*lds_attr < cb) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)merge_lds_bytes(SS_MAX_TOPK, cb));
+        if (e != hipSuccess) return e;
+        *lds_attr = cb;
+    }
+    p.order += first;
+    if (masked) hipLaunchKernelGGL(k_score_slices<true>, dim3(n), dim3(TPB), lds_score, st, p);
+    else hipLaunchKernelGGL(k_score_slices<false>, dim3(n), dim3(TPB), lds_score, st, p);
+    return hipSuccess;
 }
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-}  // namespace
+void launch_phrase(const void* params, unsigned n_parts, unsigned n_q, hipStream_t st) {
+    const ScoreParams& p = *reinterpret_cast<const ScoreParams*>(params);
+    if (n_parts) hipLaunchKernelGGL(k_phrase_match, dim3(n_parts), dim3(PH_TPB), 0, st, p);
+    hipLaunchKernelGGL(k_phrase_close, dim3(n_q), dim3(PH_TPB), 0, st, p);
+}
+void launch_merge_topk(const void* params, unsigned n_q, hipStream_t st) {
+    const ScoreParams& p = *reinterpret_cast<const ScoreParams*>(params);
+    hipLaunchKernelGGL(k_merge_topk, dim3(n_q), dim3(TPB_M), merge_lds_bytes(p.k, p.cb), st, p);
+}
+void launch_merge_flat(const void* params, unsigned n_merge, hipStream_t st) {
+    const ScoreParams& p = *reinterpret_cast<const ScoreParams*>(params);
+    hipLaunchKernelGGL(k_merge_flat, dim3(n_merge), dim3(TPB_MF), merge_lds_bytes(p.k, p.cb_flat), st, p);
+}
+}  // namespace ss
 
 extern "C" {
 
@@ -1690,1039 +1598,6 @@ int32_t ss_scorer_set_doc_masks(ss_scorer* s, int32_t n_masks, const uint32_t* w
     s->masks = std::move(nb);
     s->n_masks = n_masks;
     s->mask_words = n_words;
-    return SS_OK;
-}
-
-// the constraint arrays of ss_score_topk_constrained (NULL pointers: none)
-struct QueryConstraints { const uint32_t *req_ptr, *req_terms, *exc_ptr, *exc_terms; };
-
-static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                          const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id = nullptr,
-                          const QueryConstraints* cons = nullptr);
-
-int32_t ss_score_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
-                      const double* topic_probs, int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
-    return score_impl(s, n_q, q_ptr, q_terms, nullptr, nullptr, query_len, topic_probs, k, hits_out, n_hits_out);
-}
-
-int32_t ss_score_topk_phrase(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                             const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                             ss_hit* hits_out, int32_t* n_hits_out) {
-    if (s && !p_ptr) return s->ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_ptr is NULL");
-    return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out);
-}
-
-int32_t ss_score_topk_masked(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                             const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
-                             int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
-    return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id);
-}
-
-int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                                  const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
-                                  const uint32_t* req_ptr, const uint32_t* req_terms, const uint32_t* exc_ptr, const uint32_t* exc_terms,
-                                  int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
-    const QueryConstraints cons{req_ptr, req_terms, exc_ptr, exc_terms};
-    return score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, &cons);
-}
-
-// Batches in flight with HOST results: submit runs the batch like a call with device outputs (nothing waits, consecutive batches
-// overlap on the device) into the slot's own device buffers; collect waits for that batch alone and copies its rows to the caller.
-// The host's plan for batch i+1 and the copy-out of batch i-1 then run under the kernels of batch i.
-int32_t ss_score_topk_submit(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                             const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k, uint64_t* ticket_out) {
-    if (!s) return SS_ERR_INVALID;
-    ss_ctx* ctx = s->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!ticket_out) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_submit: ticket_out is NULL");
-    *ticket_out = 0;
-    if (n_q < 0 || k < 1 || k > SS_MAX_TOPK) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_submit: n_q < 0 or k outside 1 .. %d", SS_MAX_TOPK);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    ss_scorer::AsyncSlot* a = nullptr;
-    for (auto& c : s->aslot)
-        if (!c.ticket) { a = &c; break; }
-    if (!a) return ctx->fail(SS_ERR_STATE, "ss_score_topk_submit: %d batches in flight already (ss_score_topk_collect one first)", (int)ss_scorer::INFLIGHT);
-    const size_t rows = (size_t)n_q * (size_t)k;
-    if (a->hits.n < rows) SS_HIP(ctx, a->hits.alloc(rows + rows / 4));
-    if (a->n_hits.n < (size_t)n_q) SS_HIP(ctx, a->n_hits.alloc((size_t)n_q + 64));
-    if (!a->ev) SS_HIP(ctx, hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
-    a->pin_mode = ctx->opt("score.collect_pinned", 0) != 0;
-    if (a->pin_mode) {
-        const size_t bytes = rows * sizeof(ss_hit) + (size_t)n_q * sizeof(int32_t);
-        if (a->pin_cap < bytes) {
-            ctx->pin_free(a->pin, a->pin_cap);
-            a->pin = ctx->pin_alloc(bytes, &a->pin_cap);
-            if (!a->pin) { a->pin_cap = 0; return ctx->fail(SS_ERR_OOM, "ss_score_topk_submit: no pinned host memory for %zu bytes of results", bytes); }
-        }
-        if (!s->out_stream) SS_HIP(ctx, hipStreamCreateWithFlags(&s->out_stream, hipStreamNonBlocking));
-    }
-    if (a->pin_n_cap < (size_t)n_q * sizeof(int32_t)) {
-        if (a->pin_n) ctx->pin_free(a->pin_n, a->pin_n_cap);
-        a->pin_n = ctx->pin_alloc(std::max<size_t>((size_t)n_q * sizeof(int32_t), 4096), &a->pin_n_cap);
-        if (!a->pin_n) a->pin_n_cap = 0;                                   // (no pinned memory: collect copies the counts straight out)
-    }
-    if (n_q) {
-        const int32_t rc = score_impl(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, a->hits.p, a->n_hits.p);
-        if (rc != SS_OK) return rc;
-        // Only an event behind the batch's kernels is recorded here; the rows are copied when they are COLLECTED.  [Enqueued at
-        // submit, the device-to-host copy waits in the copy engine's in-order queue for this batch's merge and holds up the NEXT
-        // batch's plan upload behind it (submit then took 0.41 ms instead of 0.13); done by a kernel on the caller's stream it sat
-        // between two merges that the wave kernel stretches (period 0.48 ms instead of 0.345), on a stream of its own it shared a
-        // hardware queue with a wave stream (0.59).  At collect time the batch is finished, the copy takes its 85 us and blocks
-        // nothing: the host spends 0.13 ms in submit and 0.09 in collect per batch, under the 0.345 ms the device needs.]
-        SS_HIP(ctx, hipEventRecord(a->ev, ctx->stream));
-    }
-    a->n_q = n_q;
-    a->k = k;
-    a->ticket = s->next_ticket++;
-    *ticket_out = a->ticket;
-    return SS_OK;
-}
-
-int32_t ss_score_topk_collect(ss_scorer* s, uint64_t ticket, ss_hit* hits_out, int32_t* n_hits_out) {
-    if (!s) return SS_ERR_INVALID;
-    ss_ctx* ctx = s->ctx;
-    ss_scorer::AsyncSlot* a = nullptr;
-    // everything the unlocked part needs is read HERE, under the context's lock: the options map, the slot's fields and the scorer's
-    // stream may be written by a thread that submits or sets an option meanwhile (ctx->opt() is an unlocked map lookup)
-    bool trace = false, pin_mode = false;
-    int32_t n_q = 0, k = 0;
-    hipEvent_t ev = nullptr;
-    hipStream_t out_stream = nullptr;
-    const ss_hit* d_hits = nullptr;
-    const int32_t* d_n = nullptr;
-    void* pin = nullptr;
-    void* pin_n = nullptr;
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        if (!hits_out || !n_hits_out) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_collect: NULL output");
-        for (auto& c : s->aslot)
-            if (ticket && c.ticket == ticket && !c.collecting) { a = &c; break; }
-        if (!a) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_collect: no batch in flight with ticket %llu", (unsigned long long)ticket);
-        SS_HIP(ctx, hipSetDevice(ctx->device));
-        a->collecting = true;                   // (a second collect of the same ticket from another thread is refused, not raced)
-        trace = ctx->opt("score.trace", 0) != 0;
-        pin_mode = a->pin_mode;
-        n_q = a->n_q; k = a->k; ev = a->ev; out_stream = s->out_stream;
-        d_hits = a->hits.p; d_n = a->n_hits.p; pin = a->pin; pin_n = a->pin_n;
-    }
-    // (the wait and the copies run outside the context's lock: another thread may submit the next batch meanwhile; the slot itself
-    // stays this call's until its ticket is cleared below)
-    if (n_q) {
-        const auto tw0 = std::chrono::steady_clock::now();
-        hipError_t e = hipEventSynchronize(ev);
-        const auto tw1 = std::chrono::steady_clock::now();
-        const size_t rows = (size_t)n_q * (size_t)k;
-        const size_t hb = rows * sizeof(ss_hit), nb = (size_t)n_q * sizeof(int32_t);
-        if (pin_mode) {
-            // through the slot's pinned block on the copy engine, then a host memcpy
-            if (e == hipSuccess) e = hipMemcpyAsync(pin, d_hits, hb, hipMemcpyDeviceToHost, out_stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(static_cast<unsigned char*>(pin) + hb, d_n, nb, hipMemcpyDeviceToHost, out_stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(out_stream);
-            if (e == hipSuccess) {
-                std::memcpy(hits_out, pin, hb);
-                std::memcpy(n_hits_out, static_cast<unsigned char*>(pin) + hb, nb);
-            }
-        } else {
-            if (e == hipSuccess) e = hipMemcpy(hits_out, d_hits, hb, hipMemcpyDeviceToHost);
-            if (pin_n) {                                                   // the counts: device -> the slot's pinned block -> the caller
-                if (e == hipSuccess) e = hipMemcpy(pin_n, d_n, nb, hipMemcpyDeviceToHost);
-                if (e == hipSuccess) std::memcpy(n_hits_out, pin_n, nb);
-            } else if (e == hipSuccess) {
-                e = hipMemcpy(n_hits_out, d_n, nb, hipMemcpyDeviceToHost);
-            }
-        }
-        if (trace) fprintf(stderr, "[score trace] collect: waited %.0f us for the batch, copies %.0f us\n", std::chrono::duration<double, std::micro>(tw1 - tw0).count(),
-                           std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw1).count());
-        if (e != hipSuccess) {
-            std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-            a->ticket = 0;
-            a->collecting = false;
-            return ctx->fail(SS_ERR_HIP, "ss_score_topk_collect: %s", hipGetErrorString(e));
-        }
-    }
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    a->ticket = 0;
-    a->collecting = false;
-    return SS_OK;
-}
-
-static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                                const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons);
-
-// no C++ exception may cross the C ABI: host allocation failures come back as SS_ERR_OOM
-static int32_t score_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                          const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                          ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return score_impl_inner(s, n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, cons);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_score_topk: host allocation failed");
-    } catch (const std::exception& e) {
-        return s->ctx->fail(SS_ERR_INVALID, "ss_score_topk: %s", e.what());
-    }
-}
-
-static int32_t score_impl_inner(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
-                                const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, int32_t k,
-                                ss_hit* hits_out, int32_t* n_hits_out, const int32_t* mask_id, const QueryConstraints* cons) {
-    ss_ctx* ctx = s->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (n_q < 0 || !q_ptr || !hits_out || !n_hits_out) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: NULL argument or n_q < 0");
-    if (k < 1) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: k < 1");
-    if (k > SS_MAX_TOPK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk: k %d > SS_MAX_TOPK %d", k, SS_MAX_TOPK);
-    if (topic_probs && s->k_topics == 0) return ctx->fail(SS_ERR_STATE, "ss_score_topk: topic_probs given but no prior set (ss_scorer_set_prior)");
-    if (n_q == 0) return SS_OK;
-    // allow-lists (ss_score_topk_masked): checked before anything is enqueued; a call without a masked query is the unmasked call
-    std::vector<int32_t> h_mask;
-    bool any_mask = false;
-    if (mask_id) {
-        h_mask.resize(n_q);
-        SS_HIP(ctx, ss::copy_in(ctx->stream, h_mask.data(), mask_id, n_q * sizeof(int32_t)));
-        for (int q = 0; q < n_q; q++) {
-            if (h_mask[q] < -1 || h_mask[q] >= s->n_masks)
-                return ctx->fail(SS_ERR_INVALID, "ss_score_topk_masked: query %d has mask id %d (the scorer has %d masks)", q, h_mask[q], s->n_masks);
-            any_mask = any_mask || h_mask[q] >= 0;
-        }
-    }
-    // query operators (ss_score_topk_constrained): required / excluded terms, checked here too, and resolved to one allowed set per
-    // distinct (mask, required, excluded) combination, which k_constraint_masks builds on the device in the call's set buffer.  The
-    // scoring kernels take the sets as the masked call takes registered allow-lists: q_mask / SmallHdr carry the set's index.
-    std::vector<ConstraintSet> h_csets;
-    std::vector<ConstraintTerm> h_cterms;
-    if (cons && (cons->req_ptr || cons->exc_ptr)) {
-        const std::vector<uint64_t>& tp = s->title->h_term_ptr;
-        const std::vector<uint64_t>& bp = s->body->h_term_ptr;
-        std::vector<uint32_t> rp(n_q + 1, 0), rt, ep(n_q + 1, 0), et;
-        auto load = [&](const uint32_t* ptr, const uint32_t* terms, std::vector<uint32_t>& hp, std::vector<uint32_t>& ht, const char* what) -> int32_t {
-            if (!ptr) return SS_OK;
-            SS_HIP(ctx, ss::copy_in(ctx->stream, hp.data(), ptr, (n_q + 1) * sizeof(uint32_t)));
-            if (hp[0] != 0) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr[0] is %u, not 0", what, hp[0]);
-            for (int q = 0; q < n_q; q++)
-                if (hp[q + 1] < hp[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr not non-decreasing", what);
-            ht.resize(hp[n_q]);
-            if (hp[n_q] && !terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_terms is NULL", what);
-            if (hp[n_q]) SS_HIP(ctx, ss::copy_in(ctx->stream, ht.data(), terms, ht.size() * sizeof(uint32_t)));
-            return SS_OK;
-        };
-        int32_t rc = load(cons->req_ptr, cons->req_terms, rp, rt, "req");
-        if (rc == SS_OK) rc = load(cons->exc_ptr, cons->exc_terms, ep, et, "exc");
-        if (rc != SS_OK) return rc;
-        auto df = [&](uint32_t t) -> uint64_t { return (uint64_t)t < s->n_terms ? (tp[t + 1] - tp[t]) + (bp[t + 1] - bp[t]) : 0; };
-        // a query's set key: {CS_EMPTY} (no doc can be allowed), {mask + 1, n_req, required ids, excluded ids}, or none at all
-        std::vector<std::vector<uint32_t>> keys(n_q);
-        bool constrained = false;
-        std::vector<uint32_t> req, exc;
-        for (int q = 0; q < n_q; q++) {
-            req.assign(rt.begin() + rp[q], rt.begin() + rp[q + 1]);
-            exc.assign(et.begin() + ep[q], et.begin() + ep[q + 1]);
-            std::sort(req.begin(), req.end());
-            req.erase(std::unique(req.begin(), req.end()), req.end());
-            std::sort(exc.begin(), exc.end());
-            exc.erase(std::unique(exc.begin(), exc.end()), exc.end());
-            if (req.size() + exc.size() > SS_MAX_CONSTRAINT_TERMS)
-                return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk_constrained: query %d has %zu distinct required + excluded terms (max %d)", q,
-                                 req.size() + exc.size(), SS_MAX_CONSTRAINT_TERMS);
-            // a term without postings (unknown ids included): required, no doc contains it; excluded, it excludes nothing
-            bool empty = false;
-            for (uint32_t t : req) empty = empty || df(t) == 0 || std::binary_search(exc.begin(), exc.end(), t);
-            exc.erase(std::remove_if(exc.begin(), exc.end(), [&](uint32_t t) { return df(t) == 0; }), exc.end());
-            if (empty) keys[q] = {CS_EMPTY};
-            else if (!req.empty() || !exc.empty()) {
-                keys[q] = {(uint32_t)((mask_id ? h_mask[q] : -1) + 1), (uint32_t)req.size()};
-                keys[q].insert(keys[q].end(), req.begin(), req.end());
-                keys[q].insert(keys[q].end(), exc.begin(), exc.end());
-            }
-            constrained = constrained || !keys[q].empty();
-        }
-        if (constrained) {
-            // every query with a set: the constrained ones and, since the sets replace the registered masks for the call, the ones
-            // with an allow-list alone (a set without terms: the builder copies the list)
-            h_mask.resize(n_q);
-            std::map<std::vector<uint32_t>, int32_t> set_of;
-            for (int q = 0; q < n_q; q++) {
-                const int32_t m = mask_id ? h_mask[q] : -1;
-                if (keys[q].empty() && m >= 0) keys[q] = {(uint32_t)(m + 1), 0u};
-                if (keys[q].empty()) { h_mask[q] = -1; continue; }
-                auto it = set_of.find(keys[q]);
-                if (it == set_of.end()) {
-                    const std::vector<uint32_t>& key = keys[q];
-                    ConstraintSet cs{CS_EMPTY, 0u, 0u, (uint32_t)h_cterms.size()};
-                    if (key[0] != CS_EMPTY) {
-                        cs.mask1 = key[0];
-                        cs.n_req = key[1];
-                        cs.n_exc = (uint32_t)key.size() - 2 - key[1];
-                        // the required terms rarest first: a block that one of them empties skips the others
-                        std::vector<uint32_t> order(key.begin() + 2, key.end());
-                        std::stable_sort(order.begin(), order.begin() + cs.n_req, [&](uint32_t a, uint32_t b) { return df(a) < df(b); });
-                        for (uint32_t t : order) h_cterms.push_back(ConstraintTerm{tp[t], tp[t + 1], bp[t], bp[t + 1]});
-                    }
-                    it = set_of.emplace(key, (int32_t)h_csets.size()).first;
-                    h_csets.push_back(cs);
-                }
-                h_mask[q] = it->second;
-            }
-            any_mask = true;
-        }
-    }
-
-    const bool trace = ctx->opt("score.trace", 0) != 0;
-    auto t_now = [] { return std::chrono::steady_clock::now(); };
-    auto t_us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::micro>(b - a).count();
-    };
-    const auto th0 = t_now();
-    // ---- host-side plan (the host keeps df per term; queries are tiny) -------------
-    std::vector<uint32_t> h_qptr(n_q + 1);
-    SS_HIP(ctx, ss::copy_in(ctx->stream, h_qptr.data(), q_ptr, (n_q + 1) * sizeof(uint32_t)));
-    const uint32_t n_tok = h_qptr[n_q];
-    for (int q = 0; q < n_q; q++)
-        if (h_qptr[q + 1] < h_qptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: q_ptr not non-decreasing");
-    if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: q_terms is NULL");
-    std::vector<uint32_t> h_terms(n_tok);
-    if (n_tok) SS_HIP(ctx, ss::copy_in(ctx->stream, h_terms.data(), q_terms, n_tok * sizeof(uint32_t)));
-    // phrase part (retrieval/phrase.go): tokens of all quoted phrases of a query, concatenated
-    std::vector<uint32_t> h_pptr(n_q + 1, 0), h_pterms, h_pdrv(n_q, 0xFFFFFFFFu), h_xoff(n_q + 1, 0), h_pbase(n_q + 1, 0);
-    std::vector<uint4> h_parts;                 // k_phrase_match work: {query, pass, first candidate, candidates}
-    if (p_ptr) {
-        if (!s->title->pos_ptr.p || !s->body->pos_ptr.p)
-            return ctx->fail(SS_ERR_STATE, "ss_score_topk_phrase: positional postings not loaded (ss_index_set_positions on both tables)");
-        SS_HIP(ctx, ss::copy_in(ctx->stream, h_pptr.data(), p_ptr, (n_q + 1) * sizeof(uint32_t)));
-        for (int q = 0; q < n_q; q++)
-            if (h_pptr[q + 1] < h_pptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_ptr not non-decreasing");
-        h_pterms.resize(h_pptr[n_q]);
-        if (h_pptr[n_q]) {
-            if (!p_terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_terms is NULL");
-            SS_HIP(ctx, ss::copy_in(ctx->stream, h_pterms.data(), p_terms, h_pterms.size() * sizeof(uint32_t)));
-        }
-    }
-    std::vector<int32_t> h_qlen(n_q);
-    if (query_len) SS_HIP(ctx, ss::copy_in(ctx->stream, h_qlen.data(), query_len, n_q * sizeof(int32_t)));
-    else for (int q = 0; q < n_q; q++)     // len(queryTokenised)+len(phraseTokenised), main_retrieve.go:90
-        h_qlen[q] = (int32_t)(h_qptr[q + 1] - h_qptr[q]) + (int32_t)(h_pptr[q + 1] - h_pptr[q]);
-    std::vector<double> h_probs;
-    const int K = s->k_topics;
-    if (topic_probs) {
-        h_probs.resize((size_t)n_q * K);
-        SS_HIP(ctx, ss::copy_in(ctx->stream, h_probs.data(), topic_probs, h_probs.size() * sizeof(double)));
-    }
-
-    // The filter of k_score_slices assumes non-negative finite addends (see there).  Anything else — tables or priors
-    // flagged at creation, a negative / non-finite topic probability, queryLength <= 0 — switches it off for this call:
-    // every record then goes through the exact stage, which restates the reference's arithmetic for any input.
-    bool exact_all = !s->clean || (topic_probs && !s->prior_clean);
-    for (int q = 0; q < n_q && !exact_all; q++) exact_all = h_qlen[q] <= 0;
-    for (size_t i = 0; i < h_probs.size() && !exact_all; i++) exact_all = !(h_probs[i] >= 0.0) || !std::isfinite(h_probs[i]);
-    int kth_j = 0;
-    while ((1 << kth_j) < k) kth_j++;
-    const auto th1 = t_now();
-
-    const std::vector<uint64_t>& tp = s->title->h_term_ptr;
-    const std::vector<uint64_t>& bp = s->body->h_term_ptr;
-    bool any_phrase = false;
-    for (int q = 0; q < n_q && p_ptr; q++) {
-        const uint32_t m = h_pptr[q + 1] - h_pptr[q];
-        h_xoff[q + 1] = h_xoff[q];
-        h_pbase[q + 1] = (uint32_t)h_parts.size();
-        if (m == 0) continue;
-        any_phrase = true;
-        if (m > 16) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk_phrase: query %d has a phrase of %u terms (max 16)", q, m);
-        uint64_t best = ~0ull;
-        bool known = true;
-        for (uint32_t i = 0; i < m; i++) {
-            const uint32_t t = h_pterms[h_pptr[q] + i];
-            if ((uint64_t)t >= s->n_terms) { known = false; break; }    // a doc must contain EVERY phrase term (phrase.go:63)
-            const uint64_t df = (tp[t + 1] - tp[t]) + (bp[t + 1] - bp[t]);
-            if (df < best) { best = df; h_pdrv[q] = i; }
-        }
-        h_pbase[q + 1] = (uint32_t)h_parts.size();
-        if (!known) { h_pdrv[q] = 0xFFFFFFFFu; continue; }
-        if ((uint64_t)h_xoff[q] + best >= (1ull << 32))
-            return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk_phrase: the phrases of this batch have more than 2^32 candidate documents (split the batch)");
-        h_xoff[q + 1] = h_xoff[q] + (uint32_t)best;   // matches <= docs of the rarest term
-        // candidates = the rarest term's body postings (pass 0), then its title postings (pass 1), PH_PART per workgroup
-        const uint32_t dt = h_pterms[h_pptr[q] + h_pdrv[q]];
-        const uint64_t nbody = bp[dt + 1] - bp[dt], ntitle = tp[dt + 1] - tp[dt];
-        for (int pass = 0; pass < 2; pass++) {
-            const uint64_t nc = pass == 0 ? nbody : ntitle;
-            for (uint64_t c = 0; c < nc; c += PH_PART)
-                h_parts.push_back(make_uint4((uint32_t)q, (uint32_t)pass, (uint32_t)c, (uint32_t)std::min<uint64_t>(PH_PART, nc - c)));
-        }
-        h_pbase[q + 1] = (uint32_t)h_parts.size();
-    }
-    // results straight into the caller's buffers when both live in device memory (then the call does not wait either)
-    bool dev_out = false;
-    {
-        hipPointerAttribute_t a1{}, a2{};
-        const bool d1 = hipPointerGetAttributes(&a1, hits_out) == hipSuccess && a1.type == hipMemoryTypeDevice;
-        const bool d2 = hipPointerGetAttributes(&a2, n_hits_out) == hipSuccess && a2.type == hipMemoryTypeDevice;
-        (void)hipGetLastError();                 // plain host memory is reported as an error: not one
-        dev_out = d1 && d2;
-    }
-    // Slice size: SLICE_TARGET postings when the batch fills the chip several times over; smaller (down to
-    // SLICE_MIN) for small batches, so that one query's lists are spread over many CUs instead of being
-    // walked by a single workgroup (latency of a lone query: 0.72 ms -> see DESIGN.md K4).
-    uint64_t slice_target = SLICE_TARGET;
-    uint64_t grade_tot = 0, grade_seen = 0;
-    const bool grade_slices = ctx->opt("score.grade_slices", 0) != 0;
-    // The tokens' list lengths, looked up ONCE: the two host copies of term_ptr are 8 MB each at config 3 and a batch's terms are
-    // scattered over them, so every look-up is a cache miss — and the plan used to make them in three passes (batch total, the
-    // wave kernel's suitability test, the per-query slicing): 37k misses per 1024-query batch, most of the 43 us the plan took for a
-    // batch of tail queries (round 5: `score.trace`, tools/host_tail.py).  0 / 0 for unknown terms.
-    static thread_local std::vector<uint32_t> tok_lt, tok_lb;
-    tok_lt.resize(n_tok);
-    tok_lb.resize(n_tok);
-    uint64_t tok_tot = 0;
-    for (uint32_t i = 0; i < n_tok; i++) {
-        const uint32_t t = h_terms[i];
-        const bool known = (uint64_t)t < s->n_terms;
-        tok_lt[i] = known ? (uint32_t)(tp[t + 1] - tp[t]) : 0u;       // (a posting list is shorter than 2^32: ss_index_create)
-        tok_lb[i] = known ? (uint32_t)(bp[t + 1] - bp[t]) : 0u;
-        tok_tot += (uint64_t)tok_lt[i] + tok_lb[i];
-    }
-    {
-        const uint64_t batch_tot = tok_tot;
-        const uint64_t slots = (uint64_t)std::max(ctx->cu_count, 1) * SS_WGS_PER_CU;
-        // measured (10M docs, 3-term head queries, batches of 1..4096): one partial wave of slices is best — about
-        // 1.5x the batch's postings per resident workgroup slot, never below SLICE_MIN (a slice costs ~45 us of
-        // threshold warm-up whatever its size) nor above SLICE_TARGET
-        slice_target = std::min<uint64_t>(SLICE_TARGET, std::max<uint64_t>(SLICE_MIN, batch_tot * 3 / (2 * slots)));
-        // (results in device memory: consecutive batches overlap — "score.pipeline_slices" —, the next batch's kernel fills this one's
-        //  tail and larger slices pay: mixed batch 0.164 ms at 2.6x this target against 0.170)
-        if (dev_out && ctx->opt("score.pipeline", 2) != 0 && ctx->opt("score.pipeline_slices", 1) != 0)
-            slice_target = std::min<uint64_t>(SLICE_TARGET, slice_target * 5 / 2);
-        slice_target = (uint64_t)std::max<int64_t>(1024, ctx->opt("score.slice_target", (int64_t)slice_target));   // experiments only
-        grade_tot = batch_tot;
-    }
-    // k_score_wave (one wave per slice) takes the plain OR queries: few lists, no phrase part, small k, inputs for which the
-    // filter's assumptions hold, and a list long enough for the threshold floor (k'-th largest impact, k' >= k) to exist;
-    // everything else runs k_score_slices.  Option "score.wave" = 0 switches the wave kernel off (tests, A/B).
-    const bool wave_ok = ctx->opt("score.wave", 1) != 0 && s->has_combined && !exact_all && k <= ss::score_wave_max_k();
-    uint64_t wave_target = 0;
-    // (85 / 115 / 40 suited one batch at a time; with consecutive batches overlapping the next batch's kernel fills this one's tail
-    //  and fewer, larger tail slices pay: 0.334-0.338 ms per batch at config 3 against 0.341-0.345, `tools/score_wall.py` with OPTS)
-    const int64_t grade_pct = ctx->opt("score.wave_big_pct", 92), grade_big = ctx->opt("score.wave_big_x100", 115),
-                  grade_small = ctx->opt("score.wave_small_x100", 60);
-    if (wave_ok) {
-        // about 5.5 slices per nine-wave-per-CU slot (four rounds of the 12 waves a CU holds), 8k .. 48k postings each
-        const uint64_t slots = (uint64_t)std::max(ctx->cu_count, 1) * 9;
-        const uint64_t batch_tot = tok_tot;
-        wave_target = std::min<uint64_t>(49152, std::max<uint64_t>(8192, batch_tot * 2 / (11 * slots)));          // (config 3, ms per batch at 6k / 8k / 10k / 12k / 14k / 17k / 21k postings: 0.661 / 0.635 / 0.616 / 0.623 / 0.655 / 0.649 / 0.639)
-        wave_target = (uint64_t)std::max<int64_t>(1024, ctx->opt("score.wave_slice_target", (int64_t)wave_target));
-    }
-    // Which queries suit k_score_wave: no phrase part, few lists, a list long enough for the threshold floor (k'-th largest
-    // impact, k' = k rounded up to 2^j) to exist — and EVERY list long enough for that floor to be selective: the k'-th largest of
-    // n impacts lets k'/n of a list's records through until the real threshold has risen (measured: batches of term ranks
-    // U[1,100k] — long and short lists mixed — ran 3.5x slower here than in k_score_slices, with 100x the overflow events per
-    // slice).  Option "score.wave_min_list" x k' postings (default 16; 0 = no such demand: tests reach the kernel with small tables).
-    // The kernel is taken per BATCH: two scoring kernels one after the other each pay their ramp-up and tail (a batch split
-    // between them measured slower than either alone), so it runs only when the queries it suits carry 90 % of the batch.
-    // ... and few lists: a window is cut so that its blocks number 16 - 3 - (lists), every list adding a boundary block; with
-    // 12 dense lists a window is one driver block and most windows overflow into the slow path (soak on the config-3 index,
-    // wave / slices time: 0.4-0.9 at <= 5 terms, 1.0-1.1 at 9, 2-3 at 12).  Option "score.wave_max_terms", default 6.
-    const uint32_t wave_max_terms = (uint32_t)std::min<int64_t>(ss::score_wave_max_lists(), std::max<int64_t>(1, ctx->opt("score.wave_max_terms", 6)));
-    const int64_t wml = std::max<int64_t>(0, ctx->opt("score.wave_min_list", 16));
-    const uint64_t wave_min_list = (uint64_t)wml << kth_j;
-    std::vector<uint8_t> h_suits(n_q, 0);
-    bool batch_wave = false;
-    if (wave_ok) {
-        uint64_t fit = 0, all = 0;
-        for (int q = 0; q < n_q; q++) {
-            uint64_t tot = 0, shortest = ~0ull, longest = 0;
-            uint32_t n_known = 0;
-            for (uint32_t i = h_qptr[q]; i < h_qptr[q + 1]; i++) {
-                const uint32_t t = h_terms[i];
-                if ((uint64_t)t >= s->n_terms) continue;
-                n_known++;
-                tot += (uint64_t)tok_lt[i] + tok_lb[i];
-                const uint64_t len = std::max(tok_lt[i], tok_lb[i]);
-                shortest = std::min(shortest, len);
-                longest = std::max(longest, len);
-            }
-            all += tot;
-            const bool phrase_q = p_ptr && h_pptr[q + 1] > h_pptr[q];
-            // (n_known counts duplicate tokens too: an upper bound of the distinct terms, good enough for the choice)
-            if (n_known && n_known <= wave_max_terms && !phrase_q && longest >= (uint64_t)4 * (uint64_t)k && longest >= 1024 &&
-                shortest >= wave_min_list) {
-                h_suits[q] = 1;
-                fit += tot;
-            }
-        }
-        // (a lone query or two — under ~400k postings — finish sooner in k_score_slices: 0.143 against 0.166 ms for two head queries,
-        //  host in / host out; from four queries on the wave kernel leads, 0.21 against 0.31 ms)
-        // "score.wave_share_pct": the share of the batch's postings the suited queries must carry (default 90; with device outputs
-        // the two kernels of a split batch run side by side on two streams, so a split no longer pays two ramp-ups and tails one
-        // after the other)
-        const uint64_t share = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(100, ctx->opt("score.wave_share_pct", 90)));
-        batch_wave = wml == 0 ? fit > 0 : (fit * 100 >= all * share && fit >= 400000);
-        // a query with an allow-list has no threshold floor, which the wave kernel's routing rests on: k_score_slices.  (After the
-        // batch's choice: the unmasked queries of the batch go where they would without the masked ones.)
-        for (int q = 0; q < n_q && any_mask; q++)
-            if (h_mask[q] >= 0) h_suits[q] = 0;
-    }
-    std::vector<uint8_t> h_fast(n_q, 0);
-    // k_score_small (one workgroup per query, every posting scored exactly, no slices and no merge: score_small.hip) takes queries without
-    // a phrase part whose lists hold at most score_small_cap() postings in all.  Bit-identical hits.  Round 5 measured both ways: a
-    // workgroup is a chain of short phases (list table, postings -> hash table, magnitudes -> scores, radix selection, placement, hits:
-    // ~20 us with nothing to overlap), so a 1024-query tail batch is SLOWER there than in the slices pipeline that runs batches side by
-    // side (0.14 against 0.09 ms), while a short call — where latency is all there is — is faster (1 .. 32 tail queries host to host
-    // 0.068-0.074 -> 0.050-0.058 ms): DESIGN K4c.
-    // "score.small": 1 = every query that fits (tests, A/B); 2 (default) = only a call that consists of such queries and is at most
-    // "score.small_max_batch" queries long: ONE launch that writes the hits, against a slices kernel and a merge — what a lone query or
-    // a handful gain in latency a 1024-query batch loses in overlap (the slices pipeline runs batches side by side); 0 = never.
-    const int64_t small_mode = ctx->opt("score.small", 2);
-    const uint64_t small_cap = (uint64_t)std::min<int64_t>(ss::score_small_cap(), std::max<int64_t>(0, ctx->opt("score.small_cap", ss::score_small_cap())));
-    bool small_ok = small_mode == 1 && k <= ss::score_small_max_k();
-    // "score.small_batch" = 1 (with "score.small" = 2): in a LONGER call with device outputs every query that fits goes there too, the
-    // kernel on an internal stream beside the neighbouring batches like the slices kernel, its rows staged and copied on the caller's stream
-    const bool small_batch = small_mode == 2 && dev_out && k <= ss::score_small_max_k() && ctx->opt("score.pipeline", 2) != 0 &&
-                             ctx->opt("score.small_batch", 0) != 0 && n_q > ctx->opt("score.small_max_batch", 64);
-    if (small_batch) small_ok = true;
-    if (small_mode == 2 && k <= ss::score_small_max_k() && n_q <= ctx->opt("score.small_max_batch", 64) && !p_ptr) {
-        small_ok = true;                                    // (tokens counted with their repeats: an upper bound of a query's postings)
-        for (int q = 0; q < n_q && small_ok; q++) {
-            uint64_t tq = 0;
-            for (uint32_t i = h_qptr[q]; i < h_qptr[q + 1]; i++) tq += (uint64_t)tok_lt[i] + tok_lb[i];
-            small_ok = tq <= small_cap && h_qptr[q + 1] - h_qptr[q] <= (uint32_t)(ss::score_small_max_lists() / 2);
-        }
-    }
-    struct SmallEnt { SmallHdr h; uint32_t loff; };
-    std::vector<SmallEnt> h_small_a, h_small_b;         // by table size: up to score_small_cap_a() postings, and beyond
-    std::vector<SmallList> h_small_lists;
-    uint32_t small_lmax = 0;
-    std::vector<uint32_t> h_qoff(n_q + 1, 0), h_dterm, h_dmult, h_sbase(n_q + 1, 0);
-    std::vector<double> h_qmag(n_q), h_ub(n_q, 0.0);
-    std::vector<SliceDesc> h_slices;
-    std::vector<uint64_t> h_qcost(n_q, 0);          // postings per slice of the query (all its slices cost the same)
-    h_slices.reserve((size_t)n_q * 16);
-    h_dterm.reserve(n_tok);
-    h_dmult.reserve(n_tok);
-    for (int q = 0; q < n_q; q++) {
-        const size_t d0 = h_dterm.size();
-        uint64_t tot = 0;
-        for (uint32_t i = h_qptr[q]; i < h_qptr[q + 1]; i++) {
-            const uint32_t t = h_terms[i];
-            if ((uint64_t)t >= s->n_terms) continue;            // unknown word: ErrKeyNotFound -> no postings (main_retrieve.go:193,218)
-            size_t j = d0;
-            while (j < h_dterm.size() && h_dterm[j] != t) j++;
-            if (j < h_dterm.size()) { h_dmult[j]++; continue; } // duplicate token: counted again (Q8)
-            h_dterm.push_back(t);
-            h_dmult.push_back(1);
-            tot += (uint64_t)tok_lt[i] + tok_lb[i];
-        }
-        if (h_dterm.size() - d0 > SS_MAX_QUERY_TERMS)
-            return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk: query %d has more than %d distinct terms", q, SS_MAX_QUERY_TERMS);
-        h_qoff[q + 1] = (uint32_t)h_dterm.size();
-        h_qmag[q] = std::sqrt((double)h_qlen[q]);               // get_metadata.go:53
-        if (topic_probs) {
-            // upper bound of sqd over all docs, same operation order as topic_dot (monotone)
-            double ub = 0.0;
-            for (int t = 0; t < K; t++) {
-                const double pt = h_probs[(size_t)q * K + t];
-                ub += pt * (pt >= 0.0 ? s->prior_max[t] : s->prior_min[t]);
-            }
-            h_ub[q] = ub != ub ? INFINITY : ub;
-        }
-        // the window plan holds (n_win + 1) * L cursors: keep a slice within what the plan can cut into regular windows
-        const uint64_t n_lists = 2 * (h_dterm.size() - d0) + 4;
-        const uint64_t plan_cap = std::max<uint64_t>(TARGET, (uint64_t)(TBL_CAP / n_lists > 2 ? TBL_CAP / n_lists - 2 : 1) * TARGET * 7 / 8);
-        uint64_t q_target = slice_target;
-        uint64_t max_slices = MAX_SLICES_PER_Q;
-        if (small_ok && tot <= small_cap && !(p_ptr && h_pptr[q + 1] > h_pptr[q])) {
-            // no slices: k_score_small reads the lists whole and writes the hits.  Its list table is made here — the host holds
-            // term_ptr, and the kernel's own walk (query -> terms -> term_ptr) was three dependent loads at the head of every workgroup
-            SmallList tmp[SS_SMALL_MAX_LISTS];
-            uint32_t nl = 0, run = 0;
-            bool fits = true;
-            for (size_t j = d0; j < h_dterm.size() && fits; j++) {
-                const uint32_t t = h_dterm[j];
-                for (uint32_t field = 0; field < 2; field++) {
-                    const uint64_t* pp = field ? tp.data() : bp.data();
-                    const uint64_t b = pp[t], e = pp[t + 1];
-                    if (e == b) continue;
-                    if (nl == SS_SMALL_MAX_LISTS) { fits = false; break; }
-                    run += (uint32_t)(e - b);
-                    tmp[nl++] = SmallList{b, run, h_dmult[j] << 1 | field};
-                }
-            }
-            if (fits) {
-                SmallEnt en;
-                en.h = SmallHdr{(uint32_t)q, nl, run, any_mask ? (uint32_t)(h_mask[q] + 1) : 0u, h_qmag[q], 0.0};
-                en.loff = (uint32_t)h_small_lists.size();
-                h_small_lists.insert(h_small_lists.end(), tmp, tmp + nl);
-                small_lmax = std::max(small_lmax, nl);
-                (run <= ss::score_small_cap_a() ? h_small_a : h_small_b).push_back(en);
-                h_fast[q] = 2;
-                h_sbase[q + 1] = (uint32_t)h_slices.size();
-                continue;
-            }
-        }
-        const bool fast = batch_wave && h_suits[q] && h_dterm.size() > d0 && (h_dterm.size() - d0) <= (size_t)ss::score_wave_max_lists();
-        if (fast) {
-            h_fast[q] = 1;
-            q_target = wave_target;
-            max_slices = 4096;
-        }
-        // graded slices: the first part of the batch's postings in larger slices, the rest in smaller ones — launched
-        // longest first, the small ones fill the kernel's tail (both kernels; see DESIGN K4b)
-        if (grade_pct > 0 && (fast || grade_slices)) {
-            q_target = grade_seen * 100 < grade_tot * (uint64_t)grade_pct ? q_target * (uint64_t)grade_big / 100 : q_target * (uint64_t)grade_small / 100;
-            q_target = std::max<uint64_t>(q_target, 1024);
-            grade_seen += tot;
-        }
-        if (!fast) q_target = std::min<uint64_t>(q_target, plan_cap);
-        uint64_t ns = std::max<uint64_t>(1, (tot + q_target - 1) / q_target);
-        ns = std::min<uint64_t>(ns, std::min<uint64_t>(max_slices, s->n_docs));
-        h_qcost[q] = tot / ns;
-        for (uint64_t j = 0; j < ns; j++) {
-            SliceDesc sd;
-            sd.q = (uint32_t)q;
-            sd.dlo = (uint32_t)(s->n_docs * j / ns);
-            sd.dhi = j + 1 == ns ? 0xFFFFFFFFu : (uint32_t)(s->n_docs * (j + 1) / ns);
-            sd.pad = 0;
-            h_slices.push_back(sd);
-        }
-        h_sbase[q + 1] = (uint32_t)h_slices.size();
-    }
-    if (small_mode == 2 && !(small_batch && ctx->opt("score.small_batch", 0) == 2) && !h_small_a.empty() && !h_small_b.empty()) {      // one launch: the larger table takes them all
-        h_small_b.insert(h_small_b.end(), h_small_a.begin(), h_small_a.end());
-        h_small_a.clear();
-    }
-    const size_t n_small_a = h_small_a.size(), n_small_b = h_small_b.size(), n_small = n_small_a + n_small_b;
-    const size_t small_stride = sizeof(SmallHdr) + (size_t)small_lmax * sizeof(SmallList);
-    const size_t n_slices = h_slices.size();
-    const size_t n_d = h_dterm.size();
-    // launch order: the wave kernel's slices first, then k_score_slices' (each group longest first); merge list = the wave queries
-    // (the slices of a query are consecutive and cost the same, so the order is that of the QUERIES, stably sorted, with every
-    //  query's slices in a row: sorting 14.6k slice indices took two thirds of the 0.22 ms a config-3 batch is planned in)
-    std::vector<uint32_t> h_order(n_slices), h_mergeq;
-    {
-        // (a counting sort by a coarse cost class — the leading bit of the cost and the four bits behind it, 6 % steps — instead of
-        //  std::stable_sort by the exact cost: the order only decides which slices are LAUNCHED first, and the comparison sort with its
-        //  temporary buffer was most of the 35 us the plan of a 1024-query batch took (round 5); stable inside a class)
-        std::vector<uint32_t> q_order(n_q);
-        {
-            constexpr int NCLS = 2048;
-            auto cls_of = [&](uint32_t q) -> int {
-                const uint64_t c = h_qcost[q];
-                int kc = 0;
-                if (c) {
-                    const int msb = 63 - __builtin_clzll(c);
-                    const uint64_t frac = msb >= 4 ? (c >> (msb - 4)) & 15u : (c << (4 - msb)) & 15u;
-                    kc = (msb << 4 | (int)frac) + 1;                    // <= 64 * 16
-                }
-                return ((h_fast[q] & 1) ? 1024 : 0) + std::min(kc, 1023);
-            };
-            uint32_t cnt[NCLS + 1] = {};
-            for (int q = 0; q < n_q; q++) cnt[NCLS - 1 - cls_of((uint32_t)q)]++;      // descending classes
-            uint32_t run = 0;
-            for (int c = 0; c < NCLS; c++) { const uint32_t v = cnt[c]; cnt[c] = run; run += v; }
-            for (int q = 0; q < n_q; q++) q_order[cnt[NCLS - 1 - cls_of((uint32_t)q)]++] = (uint32_t)q;
-        }
-        size_t o = 0;
-        for (int i = 0; i < n_q; i++)
-            for (uint32_t sl = h_sbase[q_order[i]]; sl < h_sbase[q_order[i] + 1]; sl++) h_order[o++] = sl;
-    }
-    size_t n_fast_slices = 0;
-    for (size_t i = 0; i < n_slices; i++) n_fast_slices += h_fast[h_slices[i].q] & 1;
-    for (int q = 0; q < n_q; q++)
-        if (h_fast[q] & 1) h_mergeq.push_back((uint32_t)q);
-
-    int cb = SS_CB_MIN;
-    while (cb < 2 * k) cb <<= 1;
-    // k_merge_flat gathers ALL of a query's candidates before it sorts once (config 3: ~300 per query at k = 100; with room for
-    // 2k only it sorted 2.6 times per query, and the sorts' barriers were half of the merge)
-    const int cb_flat = std::max(cb, 512);
-    const auto th2 = t_now();
-
-    // ---- one pinned staging buffer, one H2D copy -------------------------------------
-    size_t o = 0;
-    const size_t o_qoff = o;   o = align16(o + (n_q + 1) * sizeof(uint32_t));
-    const size_t o_dterm = o;  o = align16(o + n_d * sizeof(uint32_t));
-    const size_t o_dmult = o;  o = align16(o + n_d * sizeof(uint32_t));
-    const size_t o_sbase = o;  o = align16(o + (n_q + 1) * sizeof(uint32_t));
-    const size_t o_order = o;  o = align16(o + n_slices * sizeof(uint32_t));
-    const size_t o_qmag = o;   o = align16(o + n_q * sizeof(double));
-    const size_t o_ub = o;     o = align16(o + n_q * sizeof(double));
-    const size_t o_slices = o; o = align16(o + n_slices * sizeof(SliceDesc));
-    const size_t o_pptr = o;   o = align16(o + (n_q + 1) * sizeof(uint32_t));
-    const size_t o_pterms = o; o = align16(o + h_pterms.size() * sizeof(uint32_t));
-    const size_t o_pdrv = o;   o = align16(o + n_q * sizeof(uint32_t));
-    const size_t o_xoff = o;   o = align16(o + (n_q + 1) * sizeof(uint32_t));
-    const size_t o_pbase = o;  o = align16(o + (n_q + 1) * sizeof(uint32_t));
-    const size_t o_parts = o;  o = align16(o + h_parts.size() * sizeof(uint4));
-    const size_t o_probs = o;  o = align16(o + h_probs.size() * sizeof(double));
-    const size_t o_mergeq = o; o = align16(o + h_mergeq.size() * sizeof(uint32_t));
-    const size_t o_qfast = o;  o = align16(o + (size_t)n_q);
-    const size_t o_smalltab = o; o = align16(o + n_small * small_stride);
-    const size_t o_qmask = o;  o = align16(o + (any_mask ? (size_t)n_q * sizeof(int32_t) : 0));
-    const size_t n_csets = h_csets.size();
-    const size_t o_csets = o;  o = align16(o + n_csets * sizeof(ConstraintSet));
-    const size_t o_cterms = o; o = align16(o + h_cterms.size() * sizeof(ConstraintTerm));
-#ifdef SS_EXP_FLOOR
-    const bool use_floor = ctx->opt("score.debug_floor", 0) != 0 && s->dbg_floor.size() == (size_t)n_q;
-#else
-    const bool use_floor = false;
-#endif
-    const size_t o_qfloor = o; o = align16(o + (use_floor ? (size_t)n_q * sizeof(float) : 0));
-    const size_t plan_bytes = o;
-    const int pb = s->plan_turn;
-    s->plan_turn = (s->plan_turn + 1) % ss_scorer::TURNS;
-    if (!s->plan_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->plan_ev[pb], hipEventDisableTiming));
-    if (s->plan_ev_pending[pb]) {                // the copy that last read this buffer (two calls ago) must be over
-        SS_HIP(ctx, hipEventSynchronize(s->plan_ev[pb]));
-        s->plan_ev_pending[pb] = false;
-    }
-    if (s->h_plan_cap[pb] < plan_bytes) {
-        if (s->h_plan[pb]) (void)hipHostFree(s->h_plan[pb]);
-        s->h_plan[pb] = nullptr;
-        s->h_plan_cap[pb] = 0;
-        SS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_plan[pb]), plan_bytes * 2, hipHostMallocDefault));
-        s->h_plan_cap[pb] = plan_bytes * 2;
-    }
-    if (!s->batch_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->batch_ev[pb], hipEventDisableTiming));
-    // the batch two calls ago used this turn's device buffers (plan, prep, candidates) and may still be running — in pipelined mode its
-    // merge certainly may: the host runs at most two batches ahead, and waits here BEFORE any of those buffers is grown or rewritten
-    if (s->batch_ev_pending[pb]) {
-        SS_HIP(ctx, hipEventSynchronize(s->batch_ev[pb]));
-        s->batch_ev_pending[pb] = false;
-    }
-    SS_HIP(ctx, ensure(s->d_plan2[pb], plan_bytes));
-    // the call's allowed sets: this turn's buffer, free since the wait above (the batch that last read it is done); exactly the size
-    // needed (1.25 MB per set at 10M docs), not grown by half like the other workspaces
-    const uint64_t set_stride = std::max<uint64_t>(4, ((s->n_docs + 31) / 32 + 3) & ~(uint64_t)3);
-    if (n_csets && s->d_sets[pb].n < n_csets * set_stride) {
-        const hipError_t e = s->d_sets[pb].alloc(n_csets * set_stride);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            s->d_sets[pb].release();
-            return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "ss_score_topk_constrained: no device memory for %zu allowed sets of %llu bytes",
-                             n_csets, (unsigned long long)(set_stride * sizeof(uint32_t)));
-        }
-    }
-    unsigned char* hp = s->h_plan[pb];
-    std::memcpy(hp + o_qoff, h_qoff.data(), (n_q + 1) * sizeof(uint32_t));
-    if (n_d) {
-        std::memcpy(hp + o_dterm, h_dterm.data(), n_d * sizeof(uint32_t));
-        std::memcpy(hp + o_dmult, h_dmult.data(), n_d * sizeof(uint32_t));
-    }
-    std::memcpy(hp + o_sbase, h_sbase.data(), (n_q + 1) * sizeof(uint32_t));
-    std::memcpy(hp + o_order, h_order.data(), n_slices * sizeof(uint32_t));
-    std::memcpy(hp + o_qmag, h_qmag.data(), n_q * sizeof(double));
-    std::memcpy(hp + o_ub, h_ub.data(), n_q * sizeof(double));
-    std::memcpy(hp + o_slices, h_slices.data(), n_slices * sizeof(SliceDesc));
-    std::memcpy(hp + o_pptr, h_pptr.data(), (n_q + 1) * sizeof(uint32_t));
-    if (!h_pterms.empty()) std::memcpy(hp + o_pterms, h_pterms.data(), h_pterms.size() * sizeof(uint32_t));
-    std::memcpy(hp + o_pdrv, h_pdrv.data(), n_q * sizeof(uint32_t));
-    std::memcpy(hp + o_xoff, h_xoff.data(), (n_q + 1) * sizeof(uint32_t));
-    std::memcpy(hp + o_pbase, h_pbase.data(), (n_q + 1) * sizeof(uint32_t));
-    if (!h_parts.empty()) std::memcpy(hp + o_parts, h_parts.data(), h_parts.size() * sizeof(uint4));
-    if (!h_probs.empty()) std::memcpy(hp + o_probs, h_probs.data(), h_probs.size() * sizeof(double));
-    if (!h_mergeq.empty()) std::memcpy(hp + o_mergeq, h_mergeq.data(), h_mergeq.size() * sizeof(uint32_t));
-    std::memcpy(hp + o_qfast, h_fast.data(), (size_t)n_q);
-    if (use_floor) std::memcpy(hp + o_qfloor, s->dbg_floor.data(), (size_t)n_q * sizeof(float));
-    if (any_mask) std::memcpy(hp + o_qmask, h_mask.data(), (size_t)n_q * sizeof(int32_t));
-    if (n_csets) {
-        std::memcpy(hp + o_csets, h_csets.data(), n_csets * sizeof(ConstraintSet));
-        if (!h_cterms.empty()) std::memcpy(hp + o_cterms, h_cterms.data(), h_cterms.size() * sizeof(ConstraintTerm));
-    }
-    {
-        unsigned char* w = hp + o_smalltab;              // the 1024-slot queries first, then the larger ones (launch_score_small)
-        for (const std::vector<SmallEnt>* v : {&h_small_a, &h_small_b})
-            for (const SmallEnt& en : *v) {
-                std::memcpy(w, &en.h, sizeof(SmallHdr));
-                std::memcpy(w + sizeof(SmallHdr), h_small_lists.data() + en.loff, (size_t)en.h.n_lists * sizeof(SmallList));
-                w += small_stride;
-            }
-    }
-    const auto th3 = t_now();
-    if (any_phrase) {
-        for (int x = 0; x < 4; x++) {
-            SS_HIP(ctx, ensure(s->d_x[pb][x], (size_t)h_xoff[n_q]));
-            SS_HIP(ctx, ensure(s->d_xw[pb][x], (size_t)h_xoff[n_q]));
-        }
-        SS_HIP(ctx, ensure(s->d_xcnt[pb], (size_t)n_q * 4));
-        SS_HIP(ctx, ensure(s->d_pcnt[pb], std::max<size_t>(h_parts.size(), 1) * 2));
-    }
-    SS_HIP(ctx, ensure(s->d_so_key2[pb], n_slices * k));
-    SS_HIP(ctx, ensure(s->d_so_doc2[pb], n_slices * k));
-    SS_HIP(ctx, ensure(s->d_so_cnt2[pb], n_slices));
-    // A batch that is all k_score_slices, results in device memory ("score.pipeline" != 0 and "score.pipeline_slices", default on):
-    // pipelined like the wave batches — the slices kernel on an internal stream, the merge (k_merge_topk, the kernel that writes
-    // the hits) as a launch of its own on the caller's stream behind an event.  Small slices leave the last third of their kernel
-    // on a thinning machine; the next batch's kernel now starts under it.  (The fused merge — the last slice of a query merges it
-    // inside k_score_slices — cannot move off the caller's stream: it writes the hits, and a consumer the caller enqueued between
-    // two calls must see the first call's hits before the second call's kernel touches the buffer.)
-    const bool pipe_s = dev_out && n_fast_slices == 0 && n_slices > 0 && ctx->opt("score.pipeline", 2) != 0 &&
-                        ctx->opt("score.pipeline_slices", 1) != 0;       // (phrase queries included: their match kernels go in front of the slices kernel)
-    // ... and the k_score_slices part of a SPLIT batch (some queries on the wave kernel, the rest here): on a second internal stream
-    // beside the wave kernel, unfused, its k_merge_topk on the caller's stream in front of the wave queries' k_merge_flat
-    const bool pipe_split = dev_out && n_fast_slices > 0 && n_slices > n_fast_slices && !h_mergeq.empty() && ctx->opt("score.pipeline", 2) >= 2 &&
-                            ctx->opt("score.pipeline_slices", 1) != 0;
-    const bool fused = ctx->opt("score.separate_merge", 0) == 0 && !pipe_s && !pipe_split;
-    // k_score_small of a pipelined batch: on the slices kernel's stream if there is one, else on a side stream beside the wave kernel,
-    // else (every query small) on a wave stream of its own
-    const bool small_staged = small_batch && n_small > 0;
-    const bool small_side = small_staged && !pipe_split && dev_out && n_fast_slices > 0 && !h_mergeq.empty() && ctx->opt("score.pipeline", 2) >= 2;
-    const bool small_alone = small_staged && !pipe_s && !pipe_split && !small_side;
-    if (small_staged) {
-        SS_HIP(ctx, ensure(s->d_small_stage[pb], n_small * (size_t)k));
-        SS_HIP(ctx, ensure(s->d_small_stage_n[pb], n_small));
-    }
-    if (fused && s->qticket_zeroed < (size_t)n_q) {
-        SS_HIP(ctx, ensure(s->d_qticket, (size_t)n_q));
-        SS_HIP(ctx, hipMemsetAsync(s->d_qticket.p, 0, (size_t)n_q * sizeof(uint32_t), st));
-        s->qticket_zeroed = (size_t)n_q;
-    }
-    if (!h_mergeq.empty() && s->qcnt_zeroed2[pb] < (size_t)n_q) {    // k_merge_flat hands every counter back at zero
-        SS_HIP(ctx, ensure(s->d_qcnt2[pb], (size_t)n_q));
-        SS_HIP(ctx, hipMemsetAsync(s->d_qcnt2[pb].p, 0, s->d_qcnt2[pb].bytes(), st));
-        SS_HIP(ctx, hipStreamSynchronize(st));                        // (first use or growth only) k_score_wave may run on another stream
-        s->qcnt_zeroed2[pb] = s->d_qcnt2[pb].n;
-    }
-    // Small results that go back to the host (a lone query, a handful): hits and counts in ONE device block, one copy into the context's
-    // pinned scratch, two host memcpys — a second device-to-host copy costs a lone query ~8 us of its ~0.12 ms (round 5)
-    const size_t res_rows = (size_t)n_q * k;
-    const size_t res_bytes = res_rows * sizeof(ss_hit) + (size_t)n_q * sizeof(int32_t);
-    // (up to 128 KB — 32 queries at k = 100 —: beyond that the extra host copy costs more than the second transfer; a 4 MB batch through
-    //  a pinned block measured 0.79 against 0.655 ms in round 4)
-    bool one_copy = !dev_out && res_bytes <= ss_scorer::H_RES_BYTES;
-    if (one_copy && !s->h_res && hipHostMalloc(reinterpret_cast<void**>(&s->h_res), ss_scorer::H_RES_BYTES, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        s->h_res = nullptr;
-        one_copy = false;
-    }
-    SS_HIP(ctx, ensure(s->d_hits, res_rows + (one_copy ? ((size_t)n_q * sizeof(int32_t) + sizeof(ss_hit) - 1) / sizeof(ss_hit) : 0)));
-    SS_HIP(ctx, ensure(s->d_nhits, n_q));
-
-    const unsigned char* dp = s->d_plan2[pb].p;
-    ScoreParams p{};
-    p.t_ptr = s->title->term_ptr.p; p.t_rec = s->t_rec.p; p.t_w = s->title->post_w.p; p.t_mag = s->title->mag.p; p.t_kth = s->t_kth.p;
-    p.b_ptr = s->body->term_ptr.p; p.b_rec = s->b_rec.p; p.b_w = s->body->post_w.p; p.b_mag = s->body->mag.p; p.b_kth = s->b_kth.p;
-    p.c_ptr = s->c_ptr.p; p.c_rec = s->c_rec.p; p.c_w = s->c_w.p; p.c_skip = s->c_skip.p;
-    p.c_pad_block = (uint32_t)s->c_pad_block;
-    p.t_pos_ptr = s->title->pos_ptr.p; p.t_pos = s->title->pos.p;
-    p.b_pos_ptr = s->body->pos_ptr.p; p.b_pos = s->body->pos.p;
-    if (any_phrase) {
-        p.ph_off = reinterpret_cast<const uint32_t*>(dp + o_pptr);
-        p.ph_terms = reinterpret_cast<const uint32_t*>(dp + o_pterms);
-        p.ph_drv = reinterpret_cast<const uint32_t*>(dp + o_pdrv);
-        p.x_off = reinterpret_cast<const uint32_t*>(dp + o_xoff);
-        for (int x = 0; x < 4; x++) { p.x_rec[x] = s->d_x[pb][x].p; p.x_w[x] = s->d_xw[pb][x].p; }
-        p.x_cnt = s->d_xcnt[pb].p;
-        p.ph_parts = reinterpret_cast<const uint4*>(dp + o_parts);
-        p.ph_pbase = reinterpret_cast<const uint32_t*>(dp + o_pbase);
-        p.ph_pcnt = s->d_pcnt[pb].p;
-    }
-    p.prior = K ? s->prior.p : nullptr;
-    p.k_topics = K;
-    p.q_off = reinterpret_cast<const uint32_t*>(dp + o_qoff);
-    p.dterm = reinterpret_cast<const uint32_t*>(dp + o_dterm);
-    p.dmult = reinterpret_cast<const uint32_t*>(dp + o_dmult);
-    p.qmag = reinterpret_cast<const double*>(dp + o_qmag);
-    p.probs = topic_probs ? reinterpret_cast<const double*>(dp + o_probs) : nullptr;
-    p.sqd_ub = reinterpret_cast<const double*>(dp + o_ub);
-    p.slice_base = reinterpret_cast<const uint32_t*>(dp + o_sbase);
-    p.slices = reinterpret_cast<const SliceDesc*>(dp + o_slices);
-    p.order = reinterpret_cast<const uint32_t*>(dp + o_order);
-    p.k = k;
-    p.cb = cb;
-    p.cb_flat = cb_flat;
-    p.kth_j = kth_j;
-    p.exact_all = exact_all ? 1 : 0;
-    p.so_key = s->d_so_key2[pb].p; p.so_doc = s->d_so_doc2[pb].p; p.so_cnt = s->d_so_cnt2[pb].p;
-    p.q_ticket = fused ? s->d_qticket.p : nullptr;
-    p.qc_cnt = s->d_qcnt2[pb].p;
-    p.merge_q = reinterpret_cast<const uint32_t*>(dp + o_mergeq);
-    p.q_fast = reinterpret_cast<const uint8_t*>(dp + o_qfast);
-    p.small_q = nullptr;
-    p.small_tab = dp + o_smalltab;
-    p.small_stride = (uint32_t)small_stride;
-    p.q_floor = use_floor ? reinterpret_cast<const float*>(dp + o_qfloor) : nullptr;
-    p.small_stage = small_staged ? s->d_small_stage[pb].p : nullptr;
-    p.small_stage_n = small_staged ? s->d_small_stage_n[pb].p : nullptr;
-    p.hits = dev_out ? hits_out : s->d_hits.p;
-    p.n_hits = dev_out ? n_hits_out : one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + res_rows) : s->d_nhits.p;
-    p.q_mask = any_mask ? reinterpret_cast<const int32_t*>(dp + o_qmask) : nullptr;
-    p.masks = n_csets ? s->d_sets[pb].p : any_mask ? s->masks.p : nullptr;
-    p.mask_words = n_csets ? set_stride : s->mask_words;
-
-    // "score.pipeline" (default): a batch that is all k_score_wave, results in device memory.  Its k_wave_prep and k_score_wave go
-    // to the context's WAVE stream, its k_merge_flat to the caller's stream behind an event: the next batch's k_score_wave (which
-    // needs nothing the caller's stream produces — queries arrive in host memory, the index is immutable while a scorer holds it,
-    // candidate lists and counters exist once per turn) starts under this batch's merge, and since the merge — the kernel that
-    // writes the hits — sits on the caller's stream, the results are complete in stream order like before.  [Round 3 had it the
-    // other way round (merge on a side stream that the caller's stream did not wait for): faster by the same amount, but the hits
-    // were only complete after ss_synchronize.]
-    // A batch split between the two scoring kernels (queries that do not suit k_score_wave: short lists, phrases, many terms) is
-    // pipelined too: its k_score_slices part — which writes its queries' hits itself — runs on the caller's stream BESIDE the wave
-    // kernel, the wave queries' merge follows behind both.
-    const bool pipe = dev_out && n_fast_slices > 0 && !h_mergeq.empty() && ctx->opt("score.pipeline", 2) != 0;
-    // The upload goes out on the context's SECOND stream as soon as the plan is staged — beside the kernels of the previous
-    // batch, which read the other device buffer.  (On the one stream the copy sat
-    // between two batches: 39 us per batch in the kernel trace with the counter memset, 6 % of the wall time at config 3.)
-    if (n_fast_slices) SS_HIP(ctx, ensure(s->d_wprep2[pb], ss::score_wave_prep_bytes((unsigned)n_fast_slices)));
-    bool prep_done = false;
-    if (!dev_out) {
-        // results go back to the host: the call waits for them anyway, and a second wait in the middle would only add to a lone
-        // query's latency (0.15 ms, of which 0.08 are kernels): copy, kernels and read-back follow each other on the one stream
-        SS_HIP(ctx, hipMemcpyAsync(s->d_plan2[pb].p, hp, plan_bytes, hipMemcpyHostToDevice, st));
-    } else {
-        SS_HIP(ctx, hipMemcpyAsync(s->d_plan2[pb].p, hp, plan_bytes, hipMemcpyHostToDevice, ctx->comm_stream));
-        // k_wave_prep reads the plan and the index, nothing of an earlier batch.  Unpipelined it follows the copy on the second
-        // stream and so runs beside the previous batch's kernels (12 us of kernel and one launch gap per batch off the caller's
-        // stream); pipelined it is enqueued on the wave stream in front of its k_score_wave (it finds no room beside the previous
-        // batch's k_score_wave anyway: 3 x 168 VGPRs per SIMD).
-        if (n_fast_slices && !pipe) {
-            ss::launch_wave_prep(&p, (unsigned)n_fast_slices, s->d_wprep2[pb].p, ctx->comm_stream);
-            prep_done = true;
-        }
-        // ... and the HOST waits for the second stream (~30 us; it has 0.4 ms to spare per batch): the kernels then go out with no
-        // cross-stream dependency in front of them (a hipStreamWaitEvent there left 21 us between two batches, and two of
-        // them per batch ran the runtime out of signals every ~80 batches: an 8 ms stall)
-        SS_HIP(ctx, hipStreamSynchronize(ctx->comm_stream));
-    }
-    const auto th4 = t_now();
-    const size_t lds_score = score_lds_bytes(cb), lds_merge = merge_lds_bytes(k, cb);
-    if (any_mask && s->lds_attr_masked < cb) {
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
-        s->lds_attr_masked = cb;
-    }
-    if (s->lds_attr < cb) {
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_score_slices<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_topk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)merge_lds_bytes(SS_MAX_TOPK, cb)));
-        s->lds_attr = cb;
-    }
-    const bool timed = ctx->opt("score.timing", 1) != 0;       // the two timing events of ss_last_kernel_ms(1) (each costs the stream a few us)
-    if (timed) SS_HIP(ctx, hipEventRecord(ctx->ev[1][0], st));
-    hipStream_t wst = st;                        // where k_wave_prep / k_score_wave go
-    hipStream_t sst = st;                        // ... and k_score_slices (with the phrase kernels in front of it)
-    if (pipe || pipe_s || small_alone) {
-        const int n_ws = (int)std::min<int64_t>(ss_ctx::N_WAVE_STREAMS, std::max<int64_t>(1, ctx->opt("score.pipeline", 2)));
-        const int wi = (int)(s->wave_turn++ % (unsigned)n_ws);
-        if (!ctx->wave_stream[wi]) SS_HIP(ctx, hipStreamCreateWithFlags(&ctx->wave_stream[wi], hipStreamNonBlocking));
-        if (!s->wave_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->wave_ev[pb], hipEventDisableTiming));
-        wst = ctx->wave_stream[wi];
-        if (pipe_split || small_side) {
-            const int si = (wi + 1) % n_ws;                        // (n_ws >= 2: "score.pipeline" >= 2)
-            if (!ctx->wave_stream[si]) SS_HIP(ctx, hipStreamCreateWithFlags(&ctx->wave_stream[si], hipStreamNonBlocking));
-            if (!s->slice_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->slice_ev[pb], hipEventDisableTiming));
-            sst = ctx->wave_stream[si];
-        }
-    }
-    if (pipe_s) sst = wst;
-    if (n_csets) {                               // the allowed sets, in front of the kernels that read them (never k_score_wave)
-        ConstraintParams cp{};
-        cp.t_doc = s->title->post_doc.p; cp.b_doc = s->body->post_doc.p;
-        cp.sets = reinterpret_cast<const ConstraintSet*>(dp + o_csets);
-        cp.terms = reinterpret_cast<const ConstraintTerm*>(dp + o_cterms);
-        cp.reg_masks = s->masks.p; cp.reg_words = s->mask_words;
-        cp.out = s->d_sets[pb].p;
-        cp.stride = set_stride;
-        cp.n_words = (s->n_docs + 31) / 32;
-        cp.n_blocks = ss::constraint_blocks(set_stride);
-        ss::launch_constraint_masks(&cp, (uint32_t)n_csets, sst);
-        hipStream_t small_st = !small_staged ? st : small_alone ? wst : sst;
-        if (n_small && small_st != sst) {
-            if (!s->set_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->set_ev[pb], hipEventDisableTiming));
-            SS_HIP(ctx, hipEventRecord(s->set_ev[pb], sst));
-            SS_HIP(ctx, hipStreamWaitEvent(small_st, s->set_ev[pb], 0));
-        }
-    }
-    if (n_small) {                     // writes its queries' hits itself: the caller's stream, like every kernel that does — or stages them
-        const int32_t rc_s = ss::launch_score_small(&p, (unsigned)n_small_a, (unsigned)n_small_b, !small_staged ? st : small_alone ? wst : sst);
-        if (rc_s != 0) return ctx->fail(SS_ERR_HIP, "k_score_small: %s", hipGetErrorString((hipError_t)rc_s));
-    }
-    if (any_phrase) {                            // the phrase matches, in front of the kernel that merges them in (k_score_slices)
-        hipStream_t pst = sst;
-        if (!h_parts.empty()) hipLaunchKernelGGL(k_phrase_match, dim3((unsigned)h_parts.size()), dim3(PH_TPB), 0, pst, p);
-        hipLaunchKernelGGL(k_phrase_close, dim3((unsigned)n_q), dim3(PH_TPB), 0, pst, p);
-    }
-    if (n_fast_slices) {
-        if (!prep_done) ss::launch_wave_prep(&p, (unsigned)n_fast_slices, s->d_wprep2[pb].p, wst);
-        ss::launch_score_wave(&p, (unsigned)n_fast_slices, s->d_wprep2[pb].p, wst);
-    }
-    if (n_slices > n_fast_slices) {
-        ScoreParams ps = p;
-        ps.order = p.order + n_fast_slices;
-        if (any_mask) hipLaunchKernelGGL(k_score_slices<true>, dim3((unsigned)(n_slices - n_fast_slices)), dim3(TPB), lds_score, sst, ps);
-        else hipLaunchKernelGGL(k_score_slices<false>, dim3((unsigned)(n_slices - n_fast_slices)), dim3(TPB), lds_score, sst, ps);
-    }
-    if (pipe_s) {                                // the merge, on the caller's stream, behind this batch's k_score_slices
-        SS_HIP(ctx, hipEventRecord(s->wave_ev[pb], wst));
-        SS_HIP(ctx, hipStreamWaitEvent(st, s->wave_ev[pb], 0));
-    }
-    if (pipe_split || small_side) {
-        SS_HIP(ctx, hipEventRecord(s->slice_ev[pb], sst));
-        SS_HIP(ctx, hipStreamWaitEvent(st, s->slice_ev[pb], 0));
-    }
-    if (small_alone) {
-        SS_HIP(ctx, hipEventRecord(s->wave_ev[pb], wst));
-        SS_HIP(ctx, hipStreamWaitEvent(st, s->wave_ev[pb], 0));
-    }
-    if (small_staged) ss::launch_small_copy(&p, (unsigned)n_small, st);
-    if (!fused && n_slices > n_fast_slices) hipLaunchKernelGGL(k_merge_topk, dim3((unsigned)n_q), dim3(TPB_M), lds_merge, st, p);
-    if (pipe) {                                  // the merge, on the caller's stream, behind this batch's k_score_wave
-        SS_HIP(ctx, hipEventRecord(s->wave_ev[pb], wst));
-        SS_HIP(ctx, hipStreamWaitEvent(st, s->wave_ev[pb], 0));
-    }
-    if (!h_mergeq.empty()) hipLaunchKernelGGL(k_merge_flat, dim3((unsigned)h_mergeq.size()), dim3(TPB_MF), merge_lds_bytes(k, cb_flat), st, p);
-    if (timed) {                                 // (pipelined: from the end of the previous batch's merge to the end of this one's)
-        SS_HIP(ctx, hipEventRecord(ctx->ev[1][1], st));
-        ctx->ev_valid[1] = true;
-    }
-    SS_HIP(ctx, hipEventRecord(s->batch_ev[pb], st));
-    s->batch_ev_pending[pb] = true;
-    SS_HIP(ctx, hipGetLastError());
-    if (trace)
-        fprintf(stderr, "[score trace] copies in + checks %.0f us, plan (%zu slices) %.0f us, staging %.0f us, H2D + allocs + params %.0f us, launches %.0f us%s\n",
-                t_us(th0, th1), n_slices, t_us(th1, th2), t_us(th2, th3), t_us(th3, th4), t_us(th4, t_now()), pipe ? " (k_score_wave on the wave stream)" : "");
-    if (dev_out) return SS_OK;                   // ordered on the ctx stream; ss_synchronize (or the stream's owner) waits
-    auto capture_floor = [&]() {                 // experiment only: the next call of the same batch starts from these thresholds
-#ifndef SS_EXP_FLOOR
-        return;
-#endif
-        if (ctx->opt("score.debug_floor", 0) == 0) return;
-        s->dbg_floor.assign((size_t)n_q, 0.0f);
-        for (int q = 0; q < n_q; q++)
-            if (n_hits_out[q] == k) {
-                const double f = hits_out[(size_t)q * k + (k - 1)].final;
-                float ff = (float)f;
-                if ((double)ff > f) ff = std::nextafterf(ff, -INFINITY);
-                if (ff > 0.0f && f == f) s->dbg_floor[q] = ff;
-            }
-    };
-    if (one_copy) {
-        unsigned char* const hp1 = s->h_res;
-        SS_HIP(ctx, hipMemcpyAsync(hp1, s->d_hits.p, res_bytes, hipMemcpyDeviceToHost, st));
-        SS_HIP(ctx, hipStreamSynchronize(st));
-        std::memcpy(hits_out, hp1, res_rows * sizeof(ss_hit));
-        std::memcpy(n_hits_out, hp1 + res_rows * sizeof(ss_hit), (size_t)n_q * sizeof(int32_t));
-        capture_floor();
-        return SS_OK;
-    }
-    SS_HIP(ctx, hipMemcpyAsync(hits_out, s->d_hits.p, (size_t)n_q * k * sizeof(ss_hit), hipMemcpyDefault, st));
-    // (the counts through the context's pinned scratch: a small copy into pageable memory is staged and waited for by the runtime on its
-    //  own, ~20 us that a copy into pinned memory does not cost)
-    const size_t nh_bytes = (size_t)n_q * sizeof(int32_t);
-    if (nh_bytes <= ss_ctx::PIN_SCRATCH) {
-        ctx->pin_used = 0;
-        int32_t* const hn = ctx->pin<int32_t>((size_t)n_q);
-        SS_HIP(ctx, hipMemcpyAsync(hn, s->d_nhits.p, nh_bytes, hipMemcpyDeviceToHost, st));
-        SS_HIP(ctx, hipStreamSynchronize(st));
-        std::memcpy(n_hits_out, hn, nh_bytes);
-        capture_floor();
-        return SS_OK;
-    }
-    SS_HIP(ctx, hipMemcpyAsync(n_hits_out, s->d_nhits.p, nh_bytes, hipMemcpyDefault, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    capture_floor();
     return SS_OK;
 }
 

@@ -1,5 +1,5 @@
-// score_common.hpp — declarations shared by the scoring kernels (score.hip: workgroup-per-slice kernel, phrase search, merge,
-// host side; score_wave.hip: wave-per-slice kernel).  Everything sits in an anonymous namespace: each translation unit
+// score_common.hpp — declarations shared by the scoring kernels (score.hip: workgroup-per-slice kernel, phrase search, merge;
+// score_wave.hip: wave-per-slice kernel) and the host side of a scoring call (score_call.hip).  Everything sits in an anonymous namespace: each translation unit
 // gets its own copy and its own register allocation.
 #pragma once
 #include "index.hpp"
@@ -60,6 +60,10 @@ constexpr uint32_t NOREC = 0xFFFFu;                  // "no first record" in a p
 #endif
 constexpr uint64_t SLICE_TARGET = SS_SLICE_TARGET;
 constexpr uint32_t MAX_SLICES_PER_Q = 256;
+#ifndef SS_WGS_PER_CU
+#define SS_WGS_PER_CU 2                              // k_score_slices workgroups resident per CU (its launch bounds; the planner's slot count)
+#endif
+constexpr uint32_t PH_PART = 8192;                   // candidates per k_phrase_match workgroup
 #ifndef SS_SLICE_MIN
 #define SS_SLICE_MIN 8192
 #endif

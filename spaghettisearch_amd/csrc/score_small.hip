@@ -11,8 +11,8 @@
 // FinalRank descending, ties by ascending doc id, NaN last) and writes the ss_hit rows itself: no filter, no slices, no merge
 // launch, no second look at the lists.  No assumption about the inputs either (negative or non-finite weights, zero magnitudes,
 // hostile priors): what the filter of the other kernels needs "clean" inputs for does not exist here.
-// Routed per query by the host (score.hip: option "score.small", default on): no phrase part, <= SMALL_CAP postings, k <= SMALL_MAX_K.
-#include "score_common.hpp"
+// Routed per query by the host (score_call.hip: option "score.small", default on): no phrase part, <= SMALL_CAP postings, k <= SMALL_MAX_K.
+#include "scorer.hpp"
 
 namespace {
 

@@ -29,7 +29,7 @@
 // The host routes a query here when it has at most WL lists, no phrase part, k <= WK_MAX, clean inputs (the filter's
 // assumptions hold) and a list long enough for the threshold floor to be meaningful; everything else runs k_score_slices.
 // The slices' top-k lists are merged per query by k_merge_topk.
-#include "score_common.hpp"
+#include "scorer.hpp"
 
 namespace {
 

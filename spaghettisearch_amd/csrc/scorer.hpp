@@ -1,0 +1,147 @@
+// scorer.hpp — the scorer object and everything of the scoring path that crosses a translation unit: score.hip (slice, phrase
+// and merge kernels, scorer lifecycle), score_wave.hip, score_small.hip and constraint.hip (their kernels and launchers) and
+// score_call.hip (the host side of a scoring call).  Every file that defines one of the ss:: functions below includes this
+// header, so a definition is checked against the one prototype its callers see.
+// Launchers take the kernel parameters as `const void* params`: ScoreParams / ConstraintParams live in score_common.hpp's
+// anonymous namespace (every translation unit has its own copy of the device code) and cannot appear in a shared prototype.
+#pragma once
+#include "score_common.hpp"
+
+namespace ss {
+// score.hip: thin launchers of its kernels (params: ScoreParams)
+// k_score_slices over `n` slices from launch position `first` of params' order; raises the dynamic-LDS limits of the kernel (and of
+// k_merge_topk, which goes with the unmasked kernel's mark) when the call's candidate buffer outgrows what the marks record.
+// That happens here, at the launch — behind the call's timing event and whatever the call has enqueued before its slices kernel
+// (allowed sets, k_score_small, phrase and wave kernels), and only in a call that launches a slices kernel; k_merge_topk is only
+// ever launched behind one.  It matters on a scorer's first such call and when cb grows: a failure then returns the error with
+// those earlier kernels already enqueued (they write this turn's workspaces and, for k_score_small, hits of a call that fails).
+hipError_t launch_score_slices(const void* params, unsigned first, unsigned n, bool masked, int* lds_attr, int* lds_attr_masked, hipStream_t st);
+void launch_phrase(const void* params, unsigned n_parts, unsigned n_q, hipStream_t st);   // k_phrase_match (n_parts > 0) + k_phrase_close
+void launch_merge_topk(const void* params, unsigned n_q, hipStream_t st);
+void launch_merge_flat(const void* params, unsigned n_merge, hipStream_t st);
+
+// score_wave.hip
+size_t score_wave_prep_bytes(unsigned n_slices);
+void launch_wave_prep(const void* params, unsigned n_slices, void* prep, hipStream_t st);
+void launch_score_wave(const void* params, unsigned n_slices, const void* prep, hipStream_t st);
+int score_wave_max_lists();
+int score_wave_max_k();
+// score_small.hip: one workgroup per small query (every posting scored exactly, hits written by the kernel itself)
+uint32_t score_small_cap();
+uint32_t score_small_cap_a();
+int score_small_max_k();
+int score_small_max_lists();
+int32_t launch_score_small(const void* params, unsigned n_a, unsigned n_b, hipStream_t st);
+void launch_small_copy(const void* params, unsigned n_small, hipStream_t st);
+void score_small_report();
+void score_wave_diag_dump();
+uint32_t constraint_blocks(uint64_t n_words);
+void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st);
+}  // namespace ss
+
+struct ss_scorer {
+    ss_ctx* ctx = nullptr;
+    ss_index* title = nullptr;
+    ss_index* body = nullptr;
+    uint64_t n_docs = 0, n_terms = 0;
+    ss::DevBuf<Rec> t_rec, b_rec;              // scoring records {doc, impact}
+    // combined lists (k_score_wave): title + body postings of a term merged by doc, field in bit 31 of the doc word
+    ss::DevBuf<Rec> c_rec;
+    ss::DevBuf<uint32_t> c_skip;
+    ss::DevBuf<float> c_w;
+    ss::DevBuf<uint64_t> c_ptr;
+    bool has_combined = false;
+    uint64_t c_pad_block = 0;
+    ss::DevBuf<float> t_kth, b_kth;             // [T][KTH_N] k'-th largest impact per term (threshold floor)
+    bool clean = true;                          // weights >= 0 and finite, magnitudes positive and finite where a weight is not 0
+    bool prior_clean = true;                    // every prior value >= 0 and finite
+    ss::DevBuf<double> prior;
+    std::vector<double> prior_max, prior_min;   // per topic
+    int k_topics = 0;
+    ss::DevBuf<uint32_t> masks;                 // ss_scorer_set_doc_masks: [n_masks][mask_words] allow-lists
+    int32_t n_masks = 0;
+    uint64_t mask_words = 0;
+    int lds_attr = 0, lds_attr_masked = 0;
+    // per-call workspaces, grow-only (no hipMalloc/hipFree on the steady-state query path)
+    // Turns of per-batch buffers: the host runs at most TURNS batches ahead.  (Three were measured for the pipelined mode, so that a
+    // batch's plan upload and k_wave_prep — which do not fit beside k_score_wave's three waves of 168 VGPRs per SIMD — are enqueued
+    // one batch earlier: 0.395 against 0.399 ms per batch, not worth a third set of buffers.)
+#ifndef SS_TURNS
+#define SS_TURNS 3
+#endif
+    static constexpr int TURNS = SS_TURNS;
+    unsigned wave_turn = 0;                    // which wave stream the next pipelined batch takes
+    ss::DevBuf<unsigned char> d_plan2[TURNS], d_wprep2[TURNS];   // the plan on the device, one buffer per turn: batch i+1's upload runs beside batch i's kernels
+    // pinned staging for the plan, double-buffered: a call that returns results in device memory does not wait
+    // for the GPU, so the next call plans (and fills the other buffer) while this one's copy and kernels run
+    unsigned char* h_plan[TURNS] = {};
+    size_t h_plan_cap[TURNS] = {};
+    std::vector<float> dbg_floor;    // experiment "score.debug_floor": the k-th best FinalRank of every query of the last host-output call, rounded down
+    unsigned char* h_res = nullptr;  // pinned landing block of small host results (one device-to-host copy for hits + counts)
+    static constexpr size_t H_RES_BYTES = 128 << 10;
+    hipEvent_t plan_ev[TURNS] = {}; // recorded after the H2D copy of the buffer (on the context's second stream)
+    hipEvent_t batch_ev[TURNS] = {};// recorded behind the kernels of the batch that read device buffer [turn]
+    bool batch_ev_pending[TURNS] = {};
+    size_t qcnt_zeroed2[TURNS] = {};           // counters known to be zero (k_merge_flat leaves its query's counter at zero)
+    bool plan_ev_pending[TURNS] = {};
+    int plan_turn = 0;
+    ss::DevBuf<Rec> d_x[TURNS][4];              // phrase result lists: scoring records (one set per turn: batches overlap)
+    ss::DevBuf<float> d_xw[TURNS][4];           // ... and their float32 weight sums
+    ss::DevBuf<uint32_t> d_xcnt[TURNS], d_pcnt[TURNS];
+    ss::DevBuf<uint64_t> d_so_key2[TURNS];           // the slices' candidates, one set per turn ("score.pipeline": batch i's merge reads its set while batch i+1 fills the other)
+    ss::DevBuf<uint32_t> d_so_doc2[TURNS], d_so_cnt2[TURNS], d_qticket, d_qcnt2[TURNS];
+    ss::DevBuf<ss_hit> d_small_stage[TURNS];         // k_score_small's rows of a pipelined batch (k_small_copy moves them on the caller's stream)
+    ss::DevBuf<int32_t> d_small_stage_n[TURNS];
+    ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
+    hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
+    hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
+    hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
+    size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
+    ss::DevBuf<ss_hit> d_hits;
+    // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
+    // an event behind them.
+    static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;
+    struct AsyncSlot {
+        ss::DevBuf<ss_hit> hits;
+        ss::DevBuf<int32_t> n_hits;
+        hipEvent_t ev = nullptr;             // behind the batch's kernels on the caller's stream
+        void* pin = nullptr;                 // "score.collect_pinned": the copy-out lands here first
+        size_t pin_cap = 0;
+        bool pin_mode = false;
+        uint64_t ticket = 0;                 // 0 = free
+        bool collecting = false;             // a collect call is waiting for / copying this slot outside the lock
+        void* pin_n = nullptr;               // pinned landing block of the counts (a small copy into pageable memory costs ~20 us more)
+        size_t pin_n_cap = 0;
+        int32_t n_q = 0, k = 0;
+    } aslot[INFLIGHT];
+    uint64_t next_ticket = 1;
+    hipStream_t out_stream = nullptr;        // collect's copies
+    ss::DevBuf<int32_t> d_nhits;
+    ~ss_scorer() {
+        if (out_stream) { (void)hipStreamSynchronize(out_stream); (void)hipStreamDestroy(out_stream); }
+        for (auto& a : aslot) {
+            if (a.ev) (void)hipEventDestroy(a.ev);
+            if (a.pin) ctx->pin_free(a.pin, a.pin_cap);
+            if (a.pin_n) ctx->pin_free(a.pin_n, a.pin_n_cap);
+        }
+        for (int i = 0; i < TURNS; i++) {
+            if (h_plan[i]) (void)hipHostFree(h_plan[i]);
+            if (i == 0 && h_res) (void)hipHostFree(h_res);
+            if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);
+            if (batch_ev[i]) (void)hipEventDestroy(batch_ev[i]);
+            if (wave_ev[i]) (void)hipEventDestroy(wave_ev[i]);
+            if (slice_ev[i]) (void)hipEventDestroy(slice_ev[i]);
+            if (set_ev[i]) (void)hipEventDestroy(set_ev[i]);
+        }
+    }
+};
+
+template <typename T>
+inline hipError_t ensure(ss::DevBuf<T>& b, size_t n) {
+    if (b.p && b.n >= n) return hipSuccess;
+    return b.alloc(n + n / 2 + 16);
+}
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// the constraint arrays of ss_score_topk_constrained (NULL pointers: none)
+struct QueryConstraints { const uint32_t *req_ptr, *req_terms, *exc_ptr, *exc_terms; };

@@ -1,4 +1,4 @@
-"""Constructed inputs for the quoted-phrase path (k_phrase_match / k_phrase_close and their host plan in csrc/score.hip).
+"""Constructed inputs for the quoted-phrase path (k_phrase_match / k_phrase_close and their host plan in csrc/score_call.hip).
 
 Every table is built from explicit per-term doc sets and position lists, so the phrase's driver (its rarest term, whose
 postings are the candidates), the driver's list lengths, the split of the candidates into workgroup parts of PH_PART and
