@@ -1,6 +1,6 @@
 // graph.hip — build the PageRank graph layout on the device (see graph.hpp).
 // Setup code: runs once per UpdateTopicSensitivePagerank call.  Sorting and
-// scanning use rocPRIM device primitives; the hot loop lives in pagerank.hip.
+// scanning use rocPRIM device primitives; the hot loop lives in pagerank.hip (work plan: pr_plan.hpp).
 #include "graph.hpp"
 
 #include <rocprim/rocprim.hpp>

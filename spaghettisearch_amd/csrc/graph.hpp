@@ -16,6 +16,7 @@
 //     sorted by (row, source): the SpMV needs no atomics and is deterministic.
 #pragma once
 #include "common.hpp"
+#include "sorted_degrees.hpp"
 
 // world > 1: rows of a rank's all-gather piece in front of its two tail rows that can carry further partial sums of the rank (the
 // two-vector form's per-topic L1 sums ride there: 32 rows of two doubles = SS_MAX_TOPICS sums); zero unless somebody writes them
@@ -44,31 +45,8 @@ struct ss_graph {
     ss::DevBuf<uint32_t> in_ptr;  // [sl_nd + sl_d + 1]
     ss::DevBuf<uint32_t> in_src;  // [e_local] internal ids, all < nd_int
     ss::DevBuf<uint32_t> outdeg;  // [sl_nd] out-degree of the local non-dangling rows
-    // The local in-degrees, sorted descending per class, as the HOST sees them for work-table building: run-length encoded on the
-    // device (a few thousand distinct values at 10M rows: a few KB over PCIe instead of 40 MB, and a table the host's searches
-    // find in its L1 instead of a 40 MB array they miss in).  val[j] = in-degree of rows [start[j], start[j + 1]).
-    struct SortedDegrees {
-        std::vector<uint32_t> val, start;     // start has val.size() + 1 entries; start.back() = number of rows
-        size_t size() const { return start.empty() ? 0 : start.back(); }
-        size_t run_of(size_t i) const {        // the run that holds row i (i < size())
-            size_t lo = 0, hi = val.size();
-            while (hi - lo > 1) {
-                const size_t mid = (lo + hi) >> 1;
-                if (start[mid] <= i) lo = mid; else hi = mid;
-            }
-            return lo;
-        }
-        uint32_t operator[](size_t i) const { return val[run_of(i)]; }
-        // number of rows with in-degree > lim = index of the first row whose in-degree is <= lim
-        uint32_t first_at_most(uint32_t lim) const {
-            size_t lo = 0, hi = val.size();   // first run with val <= lim (val is strictly descending)
-            while (lo < hi) {
-                const size_t mid = (lo + hi) >> 1;
-                if (val[mid] > lim) lo = mid + 1; else hi = mid;
-            }
-            return start.empty() ? 0u : start[lo];
-        }
-    };
+    // the local in-degrees, sorted descending per class, as the HOST sees them for work-table building (sorted_degrees.hpp)
+    using SortedDegrees = ss::SortedDegrees;
     SortedDegrees h_indeg_nd, h_indeg_d;
 
     // Temporaries of the build that its last kernels may still be reading when ss_graph_create returns (option "graph.late_free"):

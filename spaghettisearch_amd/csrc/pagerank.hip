@@ -26,108 +26,18 @@
 // per iteration.
 //
 // Algorithmic bytes per sweep: 4E + 8N + 16*K*N.
-#include "graph.hpp"
+//
+// This file: the sweep kernels, their launchers (ss::pr_launch_*), ss_pr_create and the ss_pr_* stepping API.  The state and the
+// kernel parameters are in pr_state.hpp, the work plan (items, deal, placement: host-only) in pr_plan.hpp, the one-call drivers
+// (ss_pagerank_run*), the two-vector kernels and float32 on the wire in pagerank_run.hip.
+#include "pr_state.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <memory>
-#include <queue>
 
 namespace {
-
-constexpr int TPB = 256;
-constexpr int WAVES = TPB / 64;
-constexpr int MAXK = 16;
-
-struct PrCtl {
-    double S[MAXK];       // normaliser (`totalValue`) for the next sweep
-    double delta[MAXK];   // last L1 change
-    double csum[MAXK];    // last contribution sum (diagnostics)
-    double xz[MAXK];      // rank of EVERY row without in-edges (they all share one value per topic)
-    double xz_in[MAXK];   // topic-sensitive teleport only: that rank for the rows INSIDE the topic's teleport set (xz: outside)
-    double tele[MAXK];    // two-vector form only ("pr.affine"): the teleport of each COLUMN for the next sweep
-    int32_t active[MAXK];
-    int32_t iters[MAXK];
-    int32_t sweep;        // sweeps completed
-    int32_t n_active;
-    uint32_t ticket;      // last-group arrival counter
-    uint32_t stuck;       // k_pr_multi_n: a wait between two sweeps ran out of patience (the grid was not resident): the state is void
-    uint32_t gticket[8];  // last-block-of-a-group arrival counters
-};
-
-// The two-vector form of the reference's recurrence (option "pr.affine", opt-in; DESIGN K1b).  Every topic of pagerank.go:85-124 runs
-// the SAME linear map on the same graph and differs only in its start value u_k = 1/n_k (:104); with x = (p*u + q) / (r*u + s)
-// elementwise (p, q vectors over the nodes, r, s scalars) one iteration maps (p, q, r, s) to
-//     p' = M p + tau*r*1,  q' = M q + tau*s*1,  r' = W p + tau*N*r,  s' = W q + tau*N*s        (M: the inherited part, W: the sum of
-// the contributions, tau = 1 - d; iteration 1 adds the start vector: p += 1) — so TWO vectors carry every topic, whatever K is.
-// The state is kept scaled to r + s = 1.  Per-topic ranks, L1 changes and stop decisions are evaluated from (p, q, r) by streaming
-// kernels; a topic's ranks are written out in the iteration it stops.  Not the reference's float64 operation order: ranks agree
-// with the oracle to ~1e-13, iteration counts where the stop rule is not at a rounding tie.
-constexpr int AFF_MAXK = 256;
-struct AffCtl {
-    double u[AFF_MAXK];       // 1 / n_topic
-    double delta[AFF_MAXK];   // last L1 change of the topic
-    int32_t active[AFF_MAXK], iters[AFF_MAXK], just[AFF_MAXK];   // just: stopped in the iteration that has just been evaluated
-    double r_x, r_prev, r_next;      // r of the stored vectors, of the previous ones, of the next sweep's result
-    double s_x, s_prev, s_next;      // ... and s (the state is kept scaled to r + s = 1: s alone vanishes when d = 1)
-    double xz_prev[2];               // the edge-less rows' (p, q) before the last sweep
-    int32_t n_active, n_just, k_real, it;
-};
-
-enum : uint32_t { W_SEG = 0, W_WAVE = 1, W_GROUP = 2, W_ZERO = 3,   // GW < 8 (k_pr_step): block-owned items
-                  // GW >= 8 (k_pr_sweep): every item belongs to ONE wave
-                  V_SEG = 8,     // a <= SEGW-edge piece of a row with more than T_MULTI in-edges (partials + ticket)
-                  V_ROWW = 9,    // a whole row, T_QUAD < in-edges <= T_MULTI
-                  V_QUAD = 10,   // `count` rows, one per lane group and turn, each `nseg` (= chunks per row) 16-edge chunks long
-                  V_DEG = 11,    // `count` rows of EXACTLY `nseg` (<= 8) in-edges: several rows per lane group and chunk
-                  V_ZERO = 12 }; // `count` non-dangling rows without in-edges
-
-struct WorkItem {
-    uint32_t kind;
-    uint32_t row;     // first local row
-    uint32_t count;   // rows (WAVE/GROUP/ZERO) or segment index (SEG)
-    uint32_t nseg;    // SEG: segments of this row
-    uint32_t sbase;   // SEG: index of the row's first segment partial
-    uint32_t tix;     // SEG: per-row ticket index
-    uint32_t beg, end; // k_pr_sweep items: the item's in-edges are in_src[beg .. end)
-};
-
-struct PrParams {
-    const uint32_t* in_ptr;
-    const uint32_t* in_src;
-    const uint32_t* outdeg;
-    double* x;
-    const double* tab_rd[2];
-    double* tab_wr[2];
-    const WorkItem* work;
-    double* partials;     // [nblocks][2][GW]
-    double* segpart;      // [nsegs][GW]
-    uint32_t* rowticket;  // [n multi-segment rows]
-    PrCtl* ctl;
-    const double* x0;     // [GW] 1/n_topic
-    double d, teleport, eps, tele_n;
-    int32_t max_iter, k_topics, world;
-    uint32_t sl_nd, cnt_nd, sl_d, cnt_d, seg_edges, n_items;
-    uint32_t pos_nd, pos_d;   // rows WITH in-edges per class (they come first: rows are in-degree sorted)
-    // opt-in true topic-sensitive teleport (ss_pr_set_teleport; null = the reference's uniform teleport):
-    const uint32_t* memb;     // [n_local] bit k: the row's node is in topic k's teleport set
-    const double* tin;        // [MAXK] teleport of a member: (1-d) * N / |set_k|
-    const double* nz_in;      // [MAXK] rows without in-edges (this rank) inside topic k's set
-    uint32_t ts_mask;         // bit k: topic k has a teleport set (others keep the uniform teleport)
-    uint32_t zrow;            // index of the table's all-zero row (= nd_int): where the unused slots of a chunk gather from
-    const uint32_t* woff;     // k_pr_sweep: [waves][8]: wave w's items of class c are work[woff[8w+c] .. woff[8w+c+1])
-    uint32_t stagger_div;     // k_pr_sweep: blocks per arrival round (= CUs); 0 = every block walks the classes in the same order
-    uint32_t stagger_code;    // start classes of the rounds as base-6 digits (0 = round r starts at position r of the class order)
-    uint32_t class_order;     // k_pr_sweep: the order in which a wave walks its six work classes, 3 bits per position
-    uint32_t n_order;         // k_pr_sweep_n: the order of its four phases, 2 bits per position
-    double* x_alt;            // two-vector form: sweep s reads x (s even) / x_alt (s odd) and writes the other one; null otherwise
-    AffCtl* aff;              // two-vector form ("pr.affine"): its control block; null otherwise
-    const double* tele_col;   // ... and the per-column teleport (ctl->tele); null = the uniform p.teleport
-#ifdef SS_PR_EXP_KINDMASK
-    uint32_t kind_mask;       // experiment builds only: run just these work classes (bit = kind)
-#endif
-};
 
 // ---- reductions --------------------------------------------------------------
 
@@ -416,7 +326,6 @@ __device__ __forceinline__ double tab_at(const double* __restrict__ T, uint32_t 
 
 
 constexpr uint32_t SRC_MASK = 0x7FFFFFFFu;   // in_src bit 31 = "last in-edge of its row" (graph.hip)
-constexpr int CH = 16;                       // edges per chunk of the GW=16 path
 
 // sum of T[src][t] over edges beg+first, beg+first+stride, ... < end; 4 gathers in flight
 template <int GW>
@@ -571,7 +480,6 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
 //   V_DEG<R>         R rows of exactly D <= 16/R in-edges per lane group and turn, at fixed slots
 // Measured on the 10M/50M R-MAT, K=16 (MI355X): 1.41 ms per sweep for the block-per-item / flag-driven kernel this
 // replaces; every class alone was latency-bound (0.60 + 0.53 + 0.57 + 0.16 ms, tools/pr_kmask.sh).
-constexpr uint32_t SEGW = 2048;      // edges per V_SEG piece
 
 // TS: the state holds teleport sets (ss_pr_set_teleport).  A kernel of its own, so that the reference's path carries no
 // membership loads (a load under a branch in finish_row makes the compiler drain the loads in flight: s_waitcnt vmcnt(0)).
@@ -944,7 +852,7 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
 //   V_QUAD   9 .. 256 in-edges: one row per 8-lane group, the lanes stride the row's edges, three-step butterfly at its end;
 //   V_ROWW / V_SEG   long rows and 2048-edge pieces of the longest: the wave strides the edges, six-step butterfly;
 //   V_ZERO   one lane per row.
-// The items, their classes and the static deal to the waves are those of the 8-wide sweep (build_work with NS = 8).  Nothing is
+// The items, their classes and the static deal to the waves are those of the 8-wide sweep (cut_items with 8-lane groups).  Nothing is
 // software-pipelined: a lane holds a handful of registers, so eight waves per SIMD hide the latency instead.
 // Summation order: a row's in-edges are added in a fixed order that depends only on the row's class — deterministic, and
 // within the last bits of the other kernels' orders (parity gate 1e-6; iteration counts as the oracle's).
@@ -1493,30 +1401,6 @@ __global__ __launch_bounds__(TPB) void k_pr_probe(const double* __restrict__ T, 
 
 }  // namespace
 
-// ------------------------------------------------------------------------------
-
-struct ss_pr {
-    ss_graph* g = nullptr;
-    int gw = 1;            // lane-group width = padded topic count
-    ss::DevBuf<float> wire_send, wire_recv;   // option "pr.wire_f32": the contribution slice as float32 on the wire
-    bool nwave = false;    // K <= 2 on the wave-item kernel k_pr_sweep_n (gw = K; the work items are those of the 8-wide sweep)
-    int persist_mode = 1;  // 1: write-through hand-offs, 2: release / acquire fences around the wait
-    bool persist = false;  // ... with ss_pr_step's sweeps inside ONE launch (k_pr_multi_n): small graphs, whose sweep is mostly fixed cost
-    int k = 1;
-    PrParams prm{};
-    unsigned nblocks = 0;
-    ss::DevBuf<double> x, tab0, tab1, send, partials, segpart, x0;
-    ss::DevBuf<uint32_t> rowticket;
-    ss::DevBuf<uint32_t> memb;          // topic-sensitive teleport (optional)
-    ss::DevBuf<double> tin, nz_in;
-    ss::DevBuf<WorkItem> work;
-    ss::DevBuf<uint32_t> woff;          // k_pr_sweep: per-wave class offsets into work
-    ss::DevBuf<PrCtl> ctl;
-    bool begun = false;
-    bool need_finalize = false;   // world>1: a begin/step is waiting for its exchange + finalize
-    bool finalize_is_begin = false;
-};
-
 namespace {
 
 int pick_gw(int k, uint64_t table_rows, bool force_narrow, bool narrow_wave) {
@@ -1530,138 +1414,6 @@ int pick_gw(int k, uint64_t table_rows, bool force_narrow, bool narrow_wave) {
     if (k <= 2 && table_rows * 64 <= (64ull << 20)) return 8;
     if (k <= 2) return k;
     return 16;
-}
-
-void build_work(const ss_graph* g, int gw, bool lane_rows, int64_t item_turns_default, std::vector<WorkItem>& items, uint32_t& nsegs, uint32_t& nmulti,
-                uint32_t& seg_edges, uint32_t& pos_nd, uint32_t& pos_d, uint32_t (&vbeg)[7]) {
-    const uint32_t NSLOT = 64 / gw;
-    // gw < 8: rows above T_SEG in-edges get block(s) of their own, then wave-per-row / group-per-row classes.
-    // gw >= 8: emit_v below.
-    const uint32_t T_SEG = 32 * NSLOT;
-    const uint32_t T_WAVE = 2 * NSLOT;
-    seg_edges = 128 * NSLOT;
-    nsegs = 0;
-    nmulti = 0;
-    // (scratch kept per thread across calls: freshly reserved vectors of a few MB cost more in page faults — 0.7 ms at 10M nodes — than
-    //  the items cost to make)
-    static thread_local std::vector<WorkItem> seg, rwg, wav, grp, zer;
-
-    // gw >= 8: wave-owned items of k_pr_sweep.  deg is sorted descending.
-    static thread_local std::vector<WorkItem> vseg, vroww, vquad, vdeg[3], vzero;
-    for (auto* v : {&seg, &rwg, &wav, &grp, &zer, &vseg, &vroww, &vquad, &vdeg[0], &vdeg[1], &vdeg[2], &vzero}) v->clear();
-    auto emit_v = [&](const ss_graph::SortedDegrees& deg, uint32_t row0, bool non_dangling, uint32_t& n_pos) {
-        const uint32_t cnt = (uint32_t)deg.size();
-        const uint32_t T_MULTI = 4096, T_DEG = 8;
-        const uint32_t T_QUAD = (uint32_t)g->ctx->opt("pr.t_quad", lane_rows ? 256 : 128);   // (k_pr_sweep_n keeps 256)
-        // turns per V_DEG item (a V_QUAD item: twice that): small graphs want finer items — with ~20 turns per wave in all, an
-        // item of 16 leaves the deal nothing to balance ("pr.item_turns"; default from the graph's size, see ss_pr_create)
-        const uint32_t item_turns = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(64, g->ctx->opt("pr.item_turns", item_turns_default)));
-        // (rows and limits only move forward: two cursors over the degree runs instead of a bisection per item — the bisections were
-        //  most of the 0.8 ms this took at config 4)
-        size_t j_at = 0, j_lim = 0;
-        const size_t n_run = deg.val.size();
-        auto deg_at = [&](uint32_t r) -> uint32_t {              // in-degree of row r (r < cnt, never smaller than the last call's)
-            while (deg.start[j_at + 1] <= r) j_at++;
-            return deg.val[j_at];
-        };
-        auto end_above = [&](uint32_t lim) -> uint32_t {         // first row with in-degree <= lim (lim never larger than the last call's)
-            while (j_lim < n_run && deg.val[j_lim] > lim) j_lim++;
-            return deg.start[j_lim];
-        };
-        uint32_t r = 0;
-        for (; r < cnt && deg_at(r) > T_MULTI; r++) {
-            const uint32_t ns = (deg_at(r) + SEGW - 1) / SEGW;
-            const uint32_t tix = nmulti++;
-            for (uint32_t s = 0; s < ns; s++) vseg.push_back({V_SEG, row0 + r, s, ns, nsegs, tix});
-            nsegs += ns;
-        }
-        {
-            const uint32_t end = std::min(cnt, end_above(T_QUAD));
-            for (; r < end; r++) vroww.push_back({V_ROWW, row0 + r, 0, 0, 0, 0});
-        }
-        // one row per lane group and turn; an item's rows all take nch = ceil(longest / 16) turns, at most gw row groups
-        // and about 32 turns per item
-        while (r < cnt && deg_at(r) > T_DEG) {
-            const uint32_t nch = (deg_at(r) + CH - 1) / CH;
-            const uint32_t max_groups = std::min<uint32_t>((uint32_t)gw, std::max<uint32_t>(1u, 2u * item_turns / nch));
-            // rows of the same turn count nch: in-degree > (nch - 1) * CH (and > T_DEG)
-            const uint32_t lim = std::max<uint32_t>(T_DEG, (nch - 1) * CH);
-            const uint32_t end = end_above(lim);
-            const uint32_t same = end > r ? end - r : 0u;
-            const uint32_t rows = std::min<uint32_t>(same, max_groups * NSLOT);
-            vquad.push_back({V_QUAD, row0 + r, rows, nch, 0, 0});
-            r += rows;
-        }
-        // exact-degree runs
-        while (r < cnt && deg_at(r) > 0) {
-            const uint32_t D = deg_at(r);
-            // deg is sorted descending and run-length encoded: the rows with exactly D in-edges end with r's run
-            const uint32_t run = deg.start[j_at + 1] - r;
-            const uint32_t R = D <= 2 ? 8 : D <= 4 ? 4 : 2;
-            // (k_pr_sweep_n gives every LANE a row: whole waves of 64 rows per item there)
-            const uint32_t per_item = lane_rows ? 64u * item_turns : NSLOT * R * item_turns;
-            auto& out = vdeg[R == 2 ? 0 : R == 4 ? 1 : 2];
-            for (uint32_t o = 0; o < run; o += per_item) out.push_back({V_DEG, row0 + r + o, std::min(per_item, run - o), D, 0, 0});
-            r += run;
-        }
-        n_pos = r;
-        const uint32_t ZERO_ROWS = 16 * NSLOT;
-        if (non_dangling)
-            for (uint32_t o = r; o < cnt; o += ZERO_ROWS) vzero.push_back({V_ZERO, row0 + o, std::min<uint32_t>(ZERO_ROWS, cnt - o), 0, 0, 0});
-    };
-    auto emit = [&](const ss_graph::SortedDegrees& deg, uint32_t row0, bool non_dangling, uint32_t& n_pos) {
-        if (gw >= 8) { emit_v(deg, row0, non_dangling, n_pos); return; }
-        const uint32_t cnt = (uint32_t)deg.size();
-        // deg is sorted descending: class boundaries
-        const uint32_t a = deg.first_at_most(T_SEG);
-        const uint32_t c = std::max(a, deg.first_at_most(0));
-        for (uint32_t r = 0; r < a; r++) {
-            const uint32_t ns = (deg[r] + seg_edges - 1) / seg_edges;
-            const uint32_t tix = ns > 1 ? nmulti++ : 0;
-            for (uint32_t s = 0; s < ns; s++) seg.push_back({W_SEG, row0 + r, s, ns, nsegs, tix});
-            nsegs += ns;
-        }
-        {
-            const uint32_t b = std::min(c, std::max(a, deg.first_at_most(T_WAVE)));
-            for (uint32_t r = a; r < b; r += WAVES) wav.push_back({W_WAVE, row0 + r, std::min<uint32_t>(WAVES, b - r), 0, 0, 0});
-            const uint32_t GROUP_ROWS = WAVES * NSLOT * 4;   // 4 rows per lane group per block
-            for (uint32_t r = b; r < c; r += GROUP_ROWS) grp.push_back({W_GROUP, row0 + r, std::min<uint32_t>(GROUP_ROWS, c - r), 0, 0, 0});
-        }
-        n_pos = c;
-        // rows without in-edges all share one rank (zero_row_rank): only the non-dangling ones have work
-        // (their next contribution); 8 elements per thread
-        const uint32_t ZERO_ROWS = (TPB * 8) / gw;
-        if (non_dangling)
-            for (uint32_t r = c; r < cnt; r += ZERO_ROWS) zer.push_back({W_ZERO, row0 + r, std::min<uint32_t>(ZERO_ROWS, cnt - r), 0, 0, 0});
-    };
-    emit(g->h_indeg_nd, 0, true, pos_nd);
-    const size_t vquad_split = vquad.size();            // the non-dangling rows' groups (falling length), then the dangling rows'
-    emit(g->h_indeg_d, g->sl_nd, false, pos_d);
-    items.clear();
-    items.reserve(seg.size() + rwg.size() + wav.size() + grp.size() + zer.size());
-    // heavy work first
-    items.insert(items.end(), seg.begin(), seg.end());
-    items.insert(items.end(), rwg.begin(), rwg.end());
-    items.insert(items.end(), wav.begin(), wav.end());
-    items.insert(items.end(), grp.begin(), grp.end());
-    items.insert(items.end(), zer.begin(), zer.end());
-    // k_pr_sweep: longest first (pieces of the hubs, whole long rows, then the row groups by falling length)
-    vbeg[0] = (uint32_t)items.size();
-    items.insert(items.end(), vseg.begin(), vseg.end());
-    items.insert(items.end(), vroww.begin(), vroww.end());
-    vbeg[1] = (uint32_t)items.size();
-    // row groups by falling length (the dangling class was appended after the non-dangling one)
-    // (each of the two classes is in falling length already: one stable merge, not a sort)
-    std::inplace_merge(vquad.begin(), vquad.begin() + (ptrdiff_t)vquad_split, vquad.end(),
-                       [](const WorkItem& a, const WorkItem& b) { return a.nseg > b.nseg; });
-    items.insert(items.end(), vquad.begin(), vquad.end());
-    for (int k = 0; k < 3; k++) {
-        vbeg[2 + k] = (uint32_t)items.size();
-        items.insert(items.end(), vdeg[k].begin(), vdeg[k].end());
-    }
-    vbeg[5] = (uint32_t)items.size();
-    items.insert(items.end(), vzero.begin(), vzero.end());
-    vbeg[6] = (uint32_t)items.size();
 }
 
 template <int GW>
@@ -1730,189 +1482,6 @@ __global__ __launch_bounds__(TPB) void k_pr_read_orig(const double* __restrict__
         if (k < k_topics) out[(size_t)k * n + v] = r[k];
 }
 
-
-// ---- two-vector form: per-topic L1 change, stop rule, write-out ("pr.affine"; see AffCtl) ---------------------------------------
-// x holds (p, q) of the rows WITH in-edges; the edge-less rows share one (p, q) per class position (ctl->xz).  A topic's rank
-// of a row is (p*u + q) / (r*u + s).
-constexpr int AFF_KC = 16;        // topics a thread accumulates per pass over the rows
-constexpr unsigned AFF_NB = 512;  // blocks of k_aff_delta (their partial sums are added in a fixed order)
-__global__ __launch_bounds__(TPB) void k_aff_delta(const double2* __restrict__ xp, const double2* __restrict__ xn, const AffCtl* __restrict__ a,
-                                                   uint32_t sl_nd, uint32_t pos_nd, uint32_t pos_d, double* __restrict__ partials) {
-    __shared__ double red[WAVES][AFF_KC];
-    if (a->n_active == 0) return;                                     // every topic has stopped: the enqueued iterations are no-ops
-    const int k_real = a->k_real;
-    const double r_old = a->r_prev, r_new = a->r_x, s_old = a->s_prev, s_new = a->s_x;
-    const uint32_t n_rows = pos_nd + pos_d;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int k0 = 0; k0 < k_real; k0 += AFF_KC) {
-        double u[AFF_KC], d_old[AFF_KC], d_new[AFF_KC], acc[AFF_KC];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < AFF_KC; j++) {
-            const bool on = k0 + j < k_real && a->active[k0 + j] != 0;
-            any = any || on;
-            u[j] = on ? a->u[k0 + j] : 0.0;
-            d_old[j] = on ? r_old * u[j] + s_old : 1.0;
-            d_new[j] = on ? r_new * u[j] + s_new : 1.0;
-            acc[j] = 0.0;
-        }
-        if (any) {
-            for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < n_rows; i += gridDim.x * TPB) {
-                const uint32_t lrow = i < pos_nd ? i : sl_nd + (i - pos_nd);
-                const double2 o = xp[lrow], n = xn[lrow];
-#pragma unroll
-                for (int j = 0; j < AFF_KC; j++) acc[j] += fabs((n.x * u[j] + n.y) / d_new[j] - (o.x * u[j] + o.y) / d_old[j]);   // pagerank.go:118
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < AFF_KC; j++) {
-            double v = acc[j];
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-            if (lane == 0) red[wave][j] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < AFF_KC && k0 + (int)threadIdx.x < k_real) {
-            double v = 0.0;
-            for (int w = 0; w < WAVES; w++) v += red[w][threadIdx.x];
-            partials[(size_t)blockIdx.x * AFF_MAXK + k0 + threadIdx.x] = v;
-        }
-        __syncthreads();
-    }
-}
-// one block: the topics' L1 changes (block partials in block order + the edge-less rows, which all hold one value), pagerank.go:93
-// and the max_iter cut, per topic
-// `stride`: doubles between two blocks' (ranks') rows of sums — AFF_MAXK for a partials / gather buffer, sl_nd * 2 when the ranks' sums are
-// read where they arrived: in the spare tail rows of the all-gathered contribution table
-__global__ __launch_bounds__(AFF_MAXK) void k_aff_ctl(AffCtl* __restrict__ a, PrCtl* __restrict__ ctl, const double* __restrict__ partials, unsigned nb,
-                                                      double n_zero, double eps, int max_iter, size_t stride) {
-    __shared__ int s_na, s_nj;
-    __shared__ double s_part[16][AFF_KC];
-    __shared__ double s_dl[AFF_MAXK];
-    const int k = threadIdx.x;
-    if (a->n_active == 0) {
-        if (k == 0) a->n_just = 0;
-        return;
-    }
-    if (k == 0) { s_na = 0; s_nj = 0; }
-    const int k_real = a->k_real;
-    // the blocks' partial sums, 16 topics at a time: thread (part, j) adds blocks part, part + 16, ... of topic j in block order, thread
-    // j then adds the 16 parts in order — fixed order, and nobody adds 256 numbers alone
-    for (int k0 = 0; k0 < k_real; k0 += AFF_KC) {
-        const int j = k & (AFF_KC - 1), part = k >> 4;
-        double v = 0.0;
-        if (k0 + j < k_real)
-            for (unsigned b = (unsigned)part; b < nb; b += 16) v += partials[(size_t)b * stride + k0 + j];
-        s_part[part][j] = v;
-        __syncthreads();
-        if (k < AFF_KC) {
-            double t = 0.0;
-            for (int q = 0; q < 16; q++) t += s_part[q][k];
-            s_dl[k0 + k] = t;
-        }
-        __syncthreads();
-    }
-    const int it = a->it + 1;
-    if (k < k_real) {
-        a->just[k] = 0;
-        if (a->active[k]) {
-            double dl = s_dl[k];
-            const double u = a->u[k];
-            const double z_new = (ctl->xz[0] * u + ctl->xz[1]) / (a->r_x * u + a->s_x);
-            const double z_old = (a->xz_prev[0] * u + a->xz_prev[1]) / (a->r_prev * u + a->s_prev);
-            dl += n_zero * fabs(z_new - z_old);
-            a->delta[k] = dl;
-            a->iters[k] = it;
-            bool cont = dl > eps;                                       // pagerank.go:93
-            if (max_iter > 0 && it >= max_iter) cont = false;
-            if (cont) atomicAdd(&s_na, 1);
-            else { a->active[k] = 0; a->just[k] = 1; atomicAdd(&s_nj, 1); }
-        }
-    }
-    __syncthreads();
-    if (k == 0) {
-        a->it = it;
-        a->n_active = s_na;
-        a->n_just = s_nj;
-        if (s_na == 0) ctl->n_active = 0;                             // the sweeps that are already enqueued return at once
-    }
-}
-// ranks of the topics that have just stopped, by ORIGINAL id (rank_out[k][v]): one thread per node, its row's (p, q) once
-__global__ __launch_bounds__(TPB) void k_aff_emit(const double2* __restrict__ x, const PrCtl* __restrict__ ctl, const AffCtl* __restrict__ a,
-                                                  const uint32_t* __restrict__ new_id, uint64_t n, uint32_t sl_nd, uint32_t pos_nd, uint32_t pos_d,
-                                                  double* __restrict__ out) {
-    if (a->n_just == 0) return;
-    const double r = a->r_x, sx = a->s_x;
-    const int k_real = a->k_real;
-    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t lrow = new_id[v];
-        const bool zero = lrow < sl_nd ? lrow >= pos_nd : (lrow - sl_nd) >= pos_d;
-        double2 pq;
-        if (zero) pq = make_double2(ctl->xz[0], ctl->xz[1]);
-        else pq = x[lrow];
-        for (int k = 0; k < k_real; k++)
-            if (a->just[k]) {
-                const double u = a->u[k];
-                out[(size_t)k * n + v] = (pq.x * u + pq.y) / (r * u + sx);
-            }
-    }
-}
-
-// sharded two-vector form: this rank's per-topic sums (its blocks' partials in a fixed order + its own edge-less rows); the ranks'
-// sums are all-gathered and k_aff_ctl adds them in rank order (nb = world, n_zero = 0), so every rank decides alike
-__global__ __launch_bounds__(AFF_MAXK) void k_aff_local(const AffCtl* __restrict__ a, const PrCtl* __restrict__ ctl, const double* __restrict__ partials, unsigned nb,
-                                                        double n_zero, double* __restrict__ loc) {
-    __shared__ double s_part[16][AFF_KC];
-    const int k = threadIdx.x;
-    const int k_real = a->k_real;
-    if (a->n_active == 0) return;
-    for (int k0 = 0; k0 < k_real; k0 += AFF_KC) {
-        const int j = k & (AFF_KC - 1), part = k >> 4;
-        double v = 0.0;
-        if (k0 + j < k_real)
-            for (unsigned b = (unsigned)part; b < nb; b += 16) v += partials[(size_t)b * AFF_MAXK + k0 + j];
-        s_part[part][j] = v;
-        __syncthreads();
-        if (k < AFF_KC && k0 + k < k_real) {
-            double t = 0.0;
-            for (int q = 0; q < 16; q++) t += s_part[q][k];
-            const int kk = k0 + k;
-            if (a->active[kk]) {
-                const double u = a->u[kk];
-                const double z_new = (ctl->xz[0] * u + ctl->xz[1]) / (a->r_x * u + a->s_x);
-                const double z_old = (a->xz_prev[0] * u + a->xz_prev[1]) / (a->r_prev * u + a->s_prev);
-                t += n_zero * fabs(z_new - z_old);
-            }
-            loc[kk] = t;
-        }
-        __syncthreads();
-    }
-}
-// ... and the ranks of the topics that have just stopped, for this rank's rows in local order (out[k][row], as ss_pr_read_local)
-__global__ __launch_bounds__(TPB) void k_aff_emit_local(const double2* __restrict__ x, const PrCtl* __restrict__ ctl, const AffCtl* __restrict__ a,
-                                                        uint32_t sl_nd, uint32_t cnt_nd, uint32_t cnt_d, uint32_t pos_nd, uint32_t pos_d,
-                                                        double* __restrict__ out, int lag) {
-    if (a->n_just == 0) return;
-    // lag: the decision arrives one exchange late (its sums rode on the next iteration's all-gather): `x` are the vectors BEFORE the last
-    // sweep, and their r, s and edge-less rows are the control block's "previous" ones
-    const double r = lag ? a->r_prev : a->r_x, sx = lag ? a->s_prev : a->s_x;
-    const double xz0 = lag ? a->xz_prev[0] : ctl->xz[0], xz1 = lag ? a->xz_prev[1] : ctl->xz[1];
-    const int k_real = a->k_real;
-    const uint32_t n_rows = cnt_nd + cnt_d;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += gridDim.x * blockDim.x) {
-        const uint32_t lrow = i < cnt_nd ? i : sl_nd + (i - cnt_nd);
-        const bool zero = lrow < sl_nd ? lrow >= pos_nd : (lrow - sl_nd) >= pos_d;
-        double2 pq;
-        if (zero) pq = make_double2(xz0, xz1);
-        else pq = x[lrow];
-        for (int k = 0; k < k_real; k++)
-            if (a->just[k]) {
-                const double u = a->u[k];
-                out[(size_t)k * n_rows + i] = (pq.x * u + pq.y) / (r * u + sx);
-            }
-    }
-}
-
 template <int GW>
 void launch_read(ss_pr* pr, hipStream_t st, int by_orig, uint64_t stride, uint32_t* ids, double* out) {
     const ss_graph* g = pr->g;
@@ -1930,52 +1499,6 @@ void launch_read(ss_pr* pr, hipStream_t st, int by_orig, uint64_t stride, uint32
                        pr->prm.memb, pr->prm.ts_mask);
 }
 
-// ---- float32 on the wire (option "pr.wire_f32", opt-in; bench.py reports it under `decompositions` only) --------------------
-// The doc-range-sharded sweep is bound by the bytes a rank receives per sweep over its point-to-point xGMI links (VERDICT r3:
-// 52 MB per link at K = 16 whatever the world size).  With this option a rank's contribution slice travels as float32 — half the
-// bytes — and is widened again on arrival; the two tail rows of the slice (the rank's partial sums: normaliser and L1 change,
-// which every rank must combine identically and which decide the stop rule) travel as (hi, lo) float pairs, i.e. to ~2^-48.
-// Every rank decodes the SAME gathered floats, its own slice included, so the ranks stay in lockstep.  The ranks differ from the
-// float64 exchange by the rounding of the contributions (2^-24 relative each, averaging out in the sums): inside the 1e-6 parity
-// gate, not the reference's float64 arithmetic — which is why it is not the default.  Arithmetic on the device stays float64.
-__global__ void k_wire_pack(const double* __restrict__ send, uint32_t n_body, uint32_t n_tail, float* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_body) out[i] = (float)send[i];
-    else if (i < n_body + n_tail) {
-        const double d = send[i];
-        const float hi = (float)d;
-        out[n_body + 2 * (i - n_body)] = hi;
-        out[n_body + 2 * (i - n_body) + 1] = (float)(d - (double)hi);
-    }
-}
-// in: [world][n_body + 2 n_tail] floats -> table [world][n_body + n_tail] doubles
-__global__ void k_wire_unpack(const float* __restrict__ in, uint32_t world, uint32_t n_body, uint32_t n_tail, double* __restrict__ table) {
-    const uint64_t per_out = (uint64_t)n_body + n_tail, per_in = (uint64_t)n_body + 2ull * n_tail;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= per_out * world) return;
-    const uint64_t r = i / per_out, j = i % per_out;
-    const float* src = in + r * per_in;
-    table[i] = j < n_body ? (double)src[j] : (double)src[n_body + 2 * (j - n_body)] + (double)src[n_body + 2 * (j - n_body) + 1];
-}
-// floats a rank sends: the slice's body rows + its tail rows (the two sums rows and the TAIL_SUM_ROWS in front of them) as pairs
-constexpr uint32_t WIRE_TAIL_ROWS = 2u + TAIL_SUM_ROWS;
-size_t wire_floats(const ss_pr* pr) { return (size_t)pr->g->sl_nd * pr->gw + (size_t)WIRE_TAIL_ROWS * (size_t)pr->gw; }
-hipError_t wire_alloc(ss_pr* pr) {
-    if (pr->wire_send.p) return hipSuccess;
-    hipError_t e = pr->wire_send.alloc(wire_floats(pr));
-    if (e == hipSuccess) e = pr->wire_recv.alloc(wire_floats(pr) * (size_t)pr->g->world);
-    return e;
-}
-void wire_pack(ss_pr* pr, hipStream_t st) {
-    const uint32_t n_tail = WIRE_TAIL_ROWS * (uint32_t)pr->gw, n_body = pr->g->sl_nd * (uint32_t)pr->gw - n_tail;
-    hipLaunchKernelGGL(k_wire_pack, dim3(ss::div_up((size_t)n_body + n_tail, TPB)), dim3(TPB), 0, st, (const double*)pr->send.p, n_body, n_tail, pr->wire_send.p);
-}
-void wire_unpack(ss_pr* pr, hipStream_t st) {
-    const uint32_t n_tail = WIRE_TAIL_ROWS * (uint32_t)pr->gw, n_body = pr->g->sl_nd * (uint32_t)pr->gw - n_tail;
-    hipLaunchKernelGGL(k_wire_unpack, dim3(ss::div_up(((size_t)n_body + n_tail) * pr->g->world, TPB)), dim3(TPB), 0, st, (const float*)pr->wire_recv.p,
-                       (uint32_t)pr->g->world, n_body, n_tail, pr->tab0.p);
-}
-
 #define SS_GW_DISPATCH(gw, fn, ...)          \
     switch (gw) {                            \
         case 1: fn<1>(__VA_ARGS__); break;   \
@@ -1986,85 +1509,79 @@ void wire_unpack(ss_pr* pr, hipStream_t st) {
 
 }  // namespace
 
-extern "C" {
+namespace ss {
+unsigned begin_blocks(const ss_pr* pr) { return std::max(1u, std::min(2048u, ss::div_up((size_t)pr->g->n_local() * pr->gw, TPB))); }
+void pr_launch_begin(ss_pr* pr, hipStream_t st, unsigned nb) { SS_GW_DISPATCH(pr->gw, launch_begin, pr, st, nb); }
+void pr_launch_step(ss_pr* pr, hipStream_t st) { SS_GW_DISPATCH(pr->gw, launch_step, pr, st); }
+void pr_launch_finalize(ss_pr* pr, hipStream_t st, int is_begin) { SS_GW_DISPATCH(pr->gw, launch_finalize, pr, st, is_begin); }
+}  // namespace ss
 
-int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, int32_t k_topics,
-                     const int32_t* n_topic, ss_pr** out) {
-    if (!g) return SS_ERR_INVALID;
-    ss_ctx* ctx = g->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!out) return ctx->fail(SS_ERR_INVALID, "ss_pr_create: out is NULL");
-    *out = nullptr;
-    if (k_topics < 1 || !n_topic) return ctx->fail(SS_ERR_INVALID, "ss_pr_create: k_topics < 1 or n_topic NULL");
-    if (k_topics > MAXK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pr_create: k_topics %d > %d per state (ss_pagerank_run splits larger K)", k_topics, MAXK);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+namespace {
 
-    ss_pr* pr = new (std::nothrow) ss_pr();
-    if (!pr) return ctx->fail(SS_ERR_OOM, "ss_pr_create: host OOM");
-    std::unique_ptr<ss_pr> guard(pr);
-    pr->g = g;
-    pr->k = k_topics;
-    const bool force_narrow = ctx->opt("pr.force_narrow", 0) != 0;
-    pr->gw = pick_gw(k_topics, g->nd_int, force_narrow, ctx->opt("pr.narrow_wave", 1) != 0);
-    pr->nwave = pr->gw <= 2 && !force_narrow && ctx->opt("pr.narrow_wave", 1) != 0;
-    const int GW = pr->gw;
-    const bool vitems = GW >= 8 || pr->nwave;          // wave-owned items (k_pr_sweep / k_pr_sweep_n); otherwise k_pr_step's block items
-    const int GI = pr->nwave ? 8 : GW;                 // lane-group width the ITEMS are cut for
-    const size_t n_local = g->n_local();
-
-    const bool trace = ctx->opt("pr.trace", 0) != 0;
-    auto t_now = [] { return std::chrono::steady_clock::now(); };
-    auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    // the large tables first: the device zeroes them (gigabytes at config 4) while the host builds and deals the work items below
-    if (((uint64_t)g->nd_int + 1) * GW * 8 >= (1ull << 32))
-        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pr_create: contribution table of %llu rows x %d topics exceeds 4 GiB (shard the graph over more ranks)",
-                         (unsigned long long)g->nd_int, GW);
-    SS_HIP(ctx, pr->x.alloc_streaming(n_local * GW));
-    // + the all-zero row k_pr_sweep's unused slots gather from (never written: the exchange and the sweeps stop at nd_int)
-    SS_HIP(ctx, pr->tab0.alloc(((size_t)g->nd_int + 1) * GW));
-    SS_HIP(ctx, hipMemsetAsync(pr->tab0.p, 0, std::max<size_t>(pr->tab0.bytes(), 8), st));
-    if (g->world == 1) {
-        SS_HIP(ctx, pr->tab1.alloc(((size_t)g->nd_int + 1) * GW));
-        SS_HIP(ctx, hipMemsetAsync(pr->tab1.p, 0, std::max<size_t>(pr->tab1.bytes(), 8), st));
-    } else {
-        SS_HIP(ctx, pr->send.alloc((size_t)g->sl_nd * GW));
-        SS_HIP(ctx, hipMemsetAsync(pr->send.p, 0, std::max<size_t>(pr->send.bytes(), 8), st));
-    }
-    const auto tc0 = t_now();
-    static thread_local std::vector<WorkItem> items, dealt;       // (scratch kept per thread across calls, see build_work)
-    static thread_local std::vector<double> cost;
-    static thread_local std::vector<uint32_t> owner;
-    uint32_t nsegs = 0, nmulti = 0, seg_edges = 0, pos_nd = 0, pos_d = 0;
-    uint32_t vbeg[7] = {0};
+// ---- ss_pr_create's steps ---------------------------------------------------------------------------------------------------
+// What the context's "pr.*" options say about the plan: the one place they are read.  The defaults depend on the kernel and on
+// the graph's size.
+PlanOptions plan_options(const ss_ctx* ctx, const ss_pr* pr, size_t n_local) {
+    const bool small = n_local <= ((size_t)4 << 20);
+    PlanOptions o;
+    o.t_quad = (uint32_t)ctx->opt("pr.t_quad", pr->nwave ? 256 : 128);
     // item granularity (measured, sweep ms at 2 / 4 / 8 / 16 / 32 turns per V_DEG item): 2^20 nodes, 5M edges, K=1: 0.078 / 0.077 / 0.096 /
     // 0.102 / 0.158; 10M nodes, 50M edges, K=16: 0.973 / 0.968 / 0.968 / 0.988 / 1.013 — a small graph gives every wave ~20 turns in all,
     // and the deal can only balance what the items let it; the large one pays for more items in the deal itself (host time)
-    build_work(g, GI, pr->nwave, pr->nwave ? (n_local <= ((size_t)4 << 20) ? 1 : 4) : (n_local <= ((size_t)4 << 20) ? 4 : 8), items, nsegs, nmulti, seg_edges, pos_nd, pos_d, vbeg);
-    const auto tc1 = t_now();
-    if (items.empty()) items.push_back({W_ZERO, 0, 0, 0, 0, 0});
-    // persistent grid, each block (gw < 8) or wave (gw >= 8) walks the work table round-robin: gw < 8: 8 blocks per CU at
-    // most; gw >= 8: exactly the waves the chip holds at once
-    int per_cu = 8;
-    {
-        // (the occupancy query is a runtime call of ~0.3 ms: asked once per kernel width and process)
-        static std::mutex occ_mu;
-        static int occ_cache[17] = {0};
-        std::lock_guard<std::mutex> lk_occ(occ_mu);
-        const int slot = pr->nwave ? 2 + GW : GW;      // (3, 4: the narrow wave-item kernels)
-        if (!occ_cache[slot]) {
-            if (pr->nwave) {
-                if (GW == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_n<1, false>, TPB, 0);
-                else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_n<2, false>, TPB, 0);
-            } else {
-                SS_GW_DISPATCH(GW, sweep_occupancy, &per_cu);
-            }
-            occ_cache[slot] = per_cu < 1 ? 1 : per_cu;
+    o.item_turns = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(64, ctx->opt("pr.item_turns", pr->nwave ? (small ? 1 : 4) : (small ? 4 : 8))));
+    // How many waves: k_pr_sweep gives every wave at least one item; k_pr_sweep_n at least "pr.items_per_wave" (default 4: 0.0537 / 0.0531 / 0.0522 / 0.0483 / 0.0523 ms at 1 / 2 / 3 / 4 / 6) — on a small
+    // graph what a sweep costs is mostly per WAVE (launch, control-block and offset reads, the hand-in of the partial sums), and a wave
+    // with a single pass of 64 rows is all overhead.  Config 2 (2^20 nodes / 5M edges, K = 1), ms per sweep by resident blocks per CU:
+    // 8: 0.0533, 6: 0.0513, 4: 0.0485, 3: 0.0461, 2: 0.0468.  [Built, measured, removed: the same waves in 1024-thread blocks (a quarter
+    // of the arrivals at the hand-in): 0.067 against 0.054 — sixteen waves wait for their slowest at every workgroup barrier.]
+    o.items_per_wave = pr->nwave ? (size_t)std::max<int64_t>(1, ctx->opt("pr.items_per_wave", 4)) : 1;
+    o.deal_snake = ctx->opt("pr.deal_snake", PlanOptions::AUTO);
+    o.deal_global = ctx->opt("pr.deal_global", pr->nwave && pr->gw == 1 ? 1 : 2);
+    o.blocks_per_cu = ctx->opt("pr.blocks_per_cu", PlanOptions::AUTO);
+    o.class_order = ctx->opt("pr.class_order", 235401);
+    o.n_class_order = ctx->opt("pr.n_class_order", small ? 2310 : 123);
+    o.stagger = ctx->opt("pr.stagger", 0);
+    return o;
+}
+
+// blocks per CU the runtime admits of the state's sweep kernel
+// (the occupancy query is a runtime call of ~0.3 ms: asked once per kernel width and process)
+int sweep_blocks_per_cu(const ss_pr* pr) {
+    static std::mutex occ_mu;
+    static int occ_cache[17] = {0};
+    std::lock_guard<std::mutex> lk_occ(occ_mu);
+    const int GW = pr->gw;
+    const int slot = pr->nwave ? 2 + GW : GW;      // (3, 4: the narrow wave-item kernels)
+    if (!occ_cache[slot]) {
+        int per_cu = 8;
+        if (pr->nwave) {
+            if (GW == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_n<1, false>, TPB, 0);
+            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep_n<2, false>, TPB, 0);
+        } else {
+            SS_GW_DISPATCH(GW, sweep_occupancy, &per_cu);
         }
-        per_cu = occ_cache[slot];
+        occ_cache[slot] = per_cu < 1 ? 1 : per_cu;
     }
-    const auto tc1a = t_now();
-    per_cu = (int)std::max<int64_t>(1, ctx->opt("pr.blocks_per_cu", per_cu));
+    return occ_cache[slot];
+}
+// ... and of k_pr_multi_n (gw = 1, 2)
+int multi_blocks_per_cu(int gw) {
+    static std::mutex occ2_mu;
+    static int occ_multi[3] = {0, 0, 0};
+    std::lock_guard<std::mutex> lk2(occ2_mu);
+    int& occ = occ_multi[gw <= 2 ? gw : 0];
+    if (!occ) {
+        int o = 0;
+        if (gw == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_pr_multi_n<1, 1>, TPB, 0);
+        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_pr_multi_n<2, 1>, TPB, 0);
+        occ = std::max(o, 1);
+    }
+    return occ;
+}
+// The grid: persistent, each block (gw < 8) or wave (gw >= 8) walks the work table round-robin: gw < 8: 8 blocks per CU at
+// most; gw >= 8: exactly the waves the chip holds at once (per_cu: sweep_blocks_per_cu).  Decides pr->persist on the way.
+unsigned grid_for(const ss_ctx* ctx, ss_pr* pr, const PlanOptions& opt, int per_cu, bool vitems, size_t n_items) {
+    per_cu = (int)std::max<int64_t>(1, opt.blocks_per_cu == PlanOptions::AUTO ? per_cu : opt.blocks_per_cu);
     // Several sweeps per launch (k_pr_multi_n), OPT-IN ("pr.persistent" = 1: write-through hand-offs, 2: release / acquire fences): one
     // rank, the reference's uniform teleport, K <= 2 on the wave-item kernel.  The blocks wait for each other between two sweeps, so ALL
     // of them must be resident: half of what the occupancy query admits per CU, at most "pr.persistent_blocks" (default 4).
@@ -2072,252 +1589,21 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     // sweep against 0.113 (write-through) / 0.152 (fences) inside one launch at 4 blocks per CU, 0.075 / 0.094 at 2, 0.078 / 0.082 at 1 —
     // the wait costs ~25 us per 256 resident blocks, far more than the 33 us an empty launch of this sweep costs in all; 10M / 50M:
     // 0.38 against 0.51 ms.  Results are bit-identical in every mode (test_sweeps_inside_one_launch_are_bit_identical).
-    {
-        const int64_t want = ctx->opt("pr.persistent", 0);
-        pr->persist_mode = want == 2 ? 2 : 1;
-        pr->persist = pr->nwave && g->world == 1 && !ctx->opt("pr.affine", 0) && want > 0;
-        if (pr->persist) {
-            // what the runtime admits of k_pr_multi_n itself, less two: the query answers one block per CU too many for kernels with
-            // 97-112 SGPRs (MI355X_MICROARCH.md, residency), and a block that is not resident would be waited for in vain
-            static std::mutex occ2_mu;
-            static int occ_multi[3] = {0, 0, 0};
-            std::lock_guard<std::mutex> lk2(occ2_mu);
-            if (!occ_multi[GW <= 2 ? GW : 0]) {
-                int o = 0;
-                if (GW == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_pr_multi_n<1, 1>, TPB, 0);
-                else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_pr_multi_n<2, 1>, TPB, 0);
-                occ_multi[GW <= 2 ? GW : 0] = std::max(o, 1);
-            }
-            const int admit = std::max(1, occ_multi[GW <= 2 ? GW : 0] - 2);
-            per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(admit, std::max(1, per_cu / 2)), ctx->opt("pr.persistent_blocks", 4)));
-        }
+    const int64_t want = ctx->opt("pr.persistent", 0);
+    pr->persist_mode = want == 2 ? 2 : 1;
+    pr->persist = pr->nwave && pr->g->world == 1 && !ctx->opt("pr.affine", 0) && want > 0;
+    if (pr->persist) {
+        // what the runtime admits of k_pr_multi_n itself, less two: the query answers one block per CU too many for kernels with
+        // 97-112 SGPRs (MI355X_MICROARCH.md, residency), and a block that is not resident would be waited for in vain
+        const int admit = std::max(1, multi_blocks_per_cu(pr->gw) - 2);
+        per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(admit, std::max(1, per_cu / 2)), ctx->opt("pr.persistent_blocks", 4)));
     }
-    // How many waves: k_pr_sweep gives every wave at least one item; k_pr_sweep_n at least "pr.items_per_wave" (default 4: 0.0537 / 0.0531 / 0.0522 / 0.0483 / 0.0523 ms at 1 / 2 / 3 / 4 / 6) — on a small
-    // graph what a sweep costs is mostly per WAVE (launch, control-block and offset reads, the hand-in of the partial sums), and a wave
-    // with a single pass of 64 rows is all overhead.  Config 2 (2^20 nodes / 5M edges, K = 1), ms per sweep by resident blocks per CU:
-    // 8: 0.0533, 6: 0.0513, 4: 0.0485, 3: 0.0461, 2: 0.0468.  [Built, measured, removed: the same waves in 1024-thread blocks (a quarter
-    // of the arrivals at the hand-in): 0.067 against 0.054 — sixteen waves wait for their slowest at every workgroup barrier.]
-    const size_t ipw = pr->nwave ? (size_t)std::max<int64_t>(1, ctx->opt("pr.items_per_wave", 4)) : 1;
-    pr->nblocks = vitems ? (unsigned)std::min<size_t>(std::max<size_t>(1, ss::div_up(items.size(), (size_t)WAVES * ipw)), (size_t)ctx->cu_count * per_cu)
-                          : (unsigned)std::min<size_t>(items.size(), (size_t)ctx->cu_count * 8);
-    static thread_local std::vector<uint32_t> woff, cnt;
-    woff.clear();
-    if (vitems) {
-        // k_pr_sweep: the items' turn counts (from the sorted in-degrees the graph keeps on the host), then the items dealt to the
-        // grid's waves; the edge ranges are filled in on the device (k_pr_item_ranges)
-        const uint32_t NS = 64 / GI;
-        // (rows rise inside a class's items: a cursor per degree table, a bisection only when a row steps back)
-        struct DegCursor {
-            const ss_graph::SortedDegrees* d;
-            size_t j = 0;
-            uint32_t at(uint32_t r) {
-                if (r >= d->size()) return 0u;
-                if (d->start[j] > r) j = d->run_of(r);
-                while (d->start[j + 1] <= r) j++;
-                return d->val[j];
-            }
-        } cur_nd{&g->h_indeg_nd}, cur_d{&g->h_indeg_d};
-        auto deg_of = [&](uint32_t lrow) -> uint32_t { return lrow < g->sl_nd ? cur_nd.at(lrow) : cur_d.at(lrow - g->sl_nd); };
-        cost.assign(items.size(), 0.0);
-        const auto td0 = t_now();
-        for (size_t i = 0; i < items.size(); i++) {
-            const WorkItem& w = items[i];
-            double turns = 1.0;
-            switch (w.kind) {
-                case V_ROWW: turns = ss::div_up(deg_of(w.row), NS * CH); break;
-                case V_SEG: turns = ss::div_up(std::min<uint32_t>(SEGW, deg_of(w.row) - w.count * SEGW), NS * CH) + 2.0; break;
-                case V_QUAD: turns = (double)ss::div_up(w.count, NS) * w.nseg; break;
-                case V_DEG: {
-                    if (pr->nwave) { turns = (double)ss::div_up(w.count, 64u) * (0.6 + 0.2 * (w.nseg <= 2 ? 2 : w.nseg <= 4 ? 4 : 8)); break; }   // a pass of 64 rows: 2, 4 or 8 gathers per lane + a row each
-                    const uint32_t R = w.nseg <= 2 ? 8 : w.nseg <= 4 ? 4 : 2;
-                    turns = (double)ss::div_up(w.count, NS * R) * (R == 8 ? 2.5 : R == 4 ? 1.7 : 1.3);   // a turn finishes R rows per lane group
-                    break;
-                }
-                default: turns = 0.5; break;
-            }
-            cost[i] = turns + 1.0;                                   // + the item's own overhead
-        }
-        const auto td0a = t_now();
-        // Longest-processing-time deal: items in table order (classes by falling item length), each to the wave with the
-        // least work so far — every wave ends up with the same number of turns (+- one item), whatever the degree mix.
-        const uint32_t nw = pr->nblocks * WAVES;
-        // The items come in falling cost inside each class.  Deal them nw at a time: the waves ordered by their load so far, the
-        // chunk's items in table order (costliest first inside a class) to the least loaded waves first — the longest-processing-
-        // time rule applied per chunk, one sort of nw loads per chunk instead of a heap operation per item (3 ms -> 0.4 ms at
-        // 60k items / 3072 waves, same balance: every wave ends within one item of the mean).
-        owner.assign(items.size(), 0u);
-        {
-            static thread_local std::vector<double> load;
-            static thread_local std::vector<uint32_t> by_load, idx;
-            static thread_local std::vector<std::pair<double, uint32_t>> key;
-            load.assign(nw, 0.0);
-            by_load.resize(nw);
-            for (uint32_t w = 0; w < nw; w++) by_load[w] = w;
-            // Many chunks (a large graph): the loads are not sorted between chunks, every other chunk is dealt in reverse — costs fall
-            // smoothly inside a class, so the snake ends as level as the sorted deal (config 4: sweep 0.960 against 0.963 ms) and the
-            // deal takes 0.3 ms of host time instead of 2.8.  Few chunks: least-loaded-first as before (config 2 on k_pr_sweep<8>: 0.075
-            // against 0.077 ms); k_pr_sweep_n's finer items sweep the same either way and the update is 0.1 ms shorter with the snake.
-            const bool snake = ctx->opt("pr.deal_snake", items.size() >= (size_t)8 * nw || pr->nwave ? 1 : 0) != 0;
-            // All items by falling cost first ("pr.deal_global": 1 = one order over all classes, 2 = class by class in table order): a
-            // counting sort on the cost in sixteenths of a turn, stable (table order inside a bucket), O(items).  The chunks below
-            // then come sorted.  [Sorting each chunk took 0.2 of
-            // config 2's 0.4 ms here: inside a class the costs fall, but every run of equal rows ends in a short item, so a chunk
-            // is dozens of falling runs, not one.]
-            static thread_local std::vector<uint32_t> order, bucket;
-            // (`tools/pr_deal.py`, sweep ms at 10M / 50M: K = 16 chunks 0.959, global 0.963, class-major 0.955; K = 1 chunks 0.383, global
-            //  0.379, class-major 0.389 — k_pr_sweep and k_pr_sweep_n<2> take class-major, k_pr_sweep_n<1> the one global order)
-            // (K = 2 on k_pr_sweep_n at 10M / 50M: class-major 0.471, global 0.481, chunks 0.483)
-            const int64_t deal_mode = ctx->opt("pr.deal_global", pr->nwave && pr->gw == 1 ? 1 : 2);
-            const bool global_order = deal_mode != 0;
-            if (global_order) {
-                constexpr uint32_t NB = 1u << 14;
-                // (mode 2: class-major — the table's class order kept, falling cost inside a class)
-                const auto key = [&](size_t i) { return NB - 1 - (uint32_t)std::min<double>(cost[i] * 16.0, (double)(NB - 1)); };
-                bucket.assign(NB + 1, 0u);
-                order.resize(items.size());
-                size_t c0 = 0;
-                for (int kcls = 0; kcls < (deal_mode == 2 ? 6 : 1); kcls++) {
-                    const size_t c1 = deal_mode == 2 ? (kcls < 5 ? std::min<size_t>(vbeg[kcls + 1], items.size()) : items.size()) : items.size();
-                    if (kcls) std::fill(bucket.begin(), bucket.end(), 0u);
-                    for (size_t i = c0; i < c1; i++) bucket[key(i) + 1]++;
-                    for (uint32_t b = 0; b < NB; b++) bucket[b + 1] += bucket[b];
-                    for (size_t i = c0; i < c1; i++) order[c0 + bucket[key(i)]++] = (uint32_t)i;
-                    c0 = c1;
-                }
-            }
-            // (Equal modelled loads do not end together: the hardware issues oldest-first, so of a CU's four resident blocks the one
-            //  that arrived first is out of items after 623 us at config 4 and the last one after 906 — -DSS_PR_WAVETIME,
-            //  tools/pr_wavetime.py.  Shares weighted by those speeds were tried and dropped: the late blocks end where they ended
-            //  before, the early ones later, the sweep 0.985-1.0 ms instead of 0.955 — the sweep is bound by the memory system's
-            //  throughput, and who finishes first is the scheduler's business.)
-#ifdef SS_PR_WAVETIME
-            // experiment (SS_PR_HEAP="123,106,92,85"): exact weighted longest-first — every item to the wave whose load / share is least
-            bool heap_done = false;
-            if (const char* ws = getenv("SS_PR_HEAP")) {
-                double wg[8] = {100, 100, 100, 100, 100, 100, 100, 100};
-                sscanf(ws, "%lf,%lf,%lf,%lf", &wg[0], &wg[1], &wg[2], &wg[3]);
-                const uint32_t wpr = (uint32_t)std::max(ctx->cu_count, 1) * WAVES;
-                typedef std::pair<double, uint32_t> E;
-                std::priority_queue<E, std::vector<E>, std::greater<E>> pq;
-                for (uint32_t w = 0; w < nw; w++) pq.push({0.0, w});
-                for (size_t j = 0; j < items.size(); j++) {
-                    const uint32_t it = global_order ? order[j] : (uint32_t)j;
-                    const E top = pq.top(); pq.pop();
-                    owner[it] = top.second;
-                    load[top.second] += cost[it];
-                    pq.push({load[top.second] / wg[std::min<uint32_t>(7, top.second / wpr)], top.second});
-                }
-                heap_done = true;
-            }
-            for (size_t i0 = 0; i0 < items.size() && !heap_done; i0 += nw) {
-#else
-            for (size_t i0 = 0; i0 < items.size(); i0 += nw) {
-#endif
-                const size_t n_chunk = std::min<size_t>(nw, items.size() - i0);
-                if (i0 && snake) {
-                    std::reverse(by_load.begin(), by_load.end());
-                } else if (i0) {
-                    // (load, wave) pairs sorted by value: several times faster than a comparator that reads load[] through the ids
-                    key.resize(nw);
-#ifdef SS_PR_WAVETIME
-                    // experiment: loads normalised by the share of the wave's block round (SS_PR_WEIGHTS="123,106,92,85")
-                    if (const char* ws = getenv("SS_PR_WEIGHTS")) {
-                        double wg[8] = {100, 100, 100, 100, 100, 100, 100, 100};
-                        sscanf(ws, "%lf,%lf,%lf,%lf", &wg[0], &wg[1], &wg[2], &wg[3]);
-                        const uint32_t wpr = (uint32_t)std::max(ctx->cu_count, 1) * WAVES;
-                        for (uint32_t w = 0; w < nw; w++) key[w] = {load[w] / wg[std::min<uint32_t>(7, w / wpr)], w};
-                    } else
-#endif
-                    for (uint32_t w = 0; w < nw; w++) key[w] = {load[w], w};
-                    std::sort(key.begin(), key.end());
-                    for (uint32_t w = 0; w < nw; w++) by_load[w] = key[w].second;
-                }
-                // the chunk's costliest item to the least loaded wave: order the chunk by falling cost (it already is, except
-                // where it crosses a class boundary)
-                // (a few falling runs: merged pairwise, O(chunk) per boundary — a full stable_sort of the chunk through cost[] took
-                //  0.15 ms a chunk, most of config 2's deal)
-                idx.resize(n_chunk);
-                for (size_t j = 0; j < n_chunk; j++) idx[j] = global_order ? order[i0 + j] : (uint32_t)(i0 + j);
-                const auto falling = [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; };
-                size_t run_end = 0, n_merge = 0;
-                for (size_t j = 1; j <= n_chunk && !global_order; j++) {
-                    if (j < n_chunk && !(cost[i0 + j] > cost[i0 + j - 1])) continue;     // still falling (or level)
-                    if (run_end) {
-                        if (++n_merge > 8) { std::stable_sort(idx.begin(), idx.end(), falling); break; }
-                        std::inplace_merge(idx.begin(), idx.begin() + (ptrdiff_t)run_end, idx.begin() + (ptrdiff_t)j, falling);
-                    }
-                    run_end = j;
-                }
-                for (size_t j = 0; j < n_chunk; j++) {
-                    owner[idx[j]] = by_load[j];
-                    load[by_load[j]] += cost[idx[j]];
-                }
-            }
-        }
-#ifdef SS_PR_WAVETIME
-        if (FILE* f = fopen("gpurun_out/pr_load.csv", "w")) {
-            static thread_local std::vector<double> wl, wcls;
-            wl.assign(nw, 0.0); wcls.assign((size_t)nw * 6, 0.0);
-            for (size_t i = 0; i < items.size(); i++) {
-                int kc = 0; while (kc < 5 && i >= vbeg[kc + 1]) kc++;
-                wl[owner[i]] += cost[i]; wcls[(size_t)owner[i] * 6 + kc] += cost[i];
-            }
-            fprintf(f, "wave,load,c0,c1,c2,c3,c4,c5\n");
-            for (uint32_t w = 0; w < nw; w++) fprintf(f, "%u,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f\n", w, wl[w], wcls[(size_t)w * 6], wcls[(size_t)w * 6 + 1], wcls[(size_t)w * 6 + 2], wcls[(size_t)w * 6 + 3], wcls[(size_t)w * 6 + 4], wcls[(size_t)w * 6 + 5]);
-            fclose(f);
-        }
-#endif
-        const auto td1 = t_now();
-        if (trace) fprintf(stderr, "[pr trace]   deal: occupancy query %.2f ms, costs %.3f ms, owners %.3f ms\n", t_ms(tc1, tc1a), t_ms(td0, td0a), t_ms(td0a, td1));
-        // table order inside a wave's list = item order = class order: count per (wave, class), offsets, place
-        // (the items are in class order: owner[i] * 8 + class, computed once per class range)
-        woff.assign((size_t)nw * 8, 0);
-        cnt.assign((size_t)nw * 8, 0);
-        for (int k = 0; k < 6; k++) {
-            const size_t i1 = k < 5 ? std::min<size_t>(vbeg[k + 1], items.size()) : items.size();
-            for (size_t i = std::min<size_t>(vbeg[k], i1); i < i1; i++) { owner[i] = owner[i] * 8 + (uint32_t)k; cnt[owner[i]]++; }
-        }
-        uint32_t run_off = 0;
-        for (uint32_t w = 0; w < nw; w++) {
-            for (int k = 0; k < 8; k++) {
-                woff[(size_t)w * 8 + k] = run_off;
-                run_off += cnt[(size_t)w * 8 + k];
-                cnt[(size_t)w * 8 + k] = woff[(size_t)w * 8 + k];       // becomes the write cursor of (wave, class)
-            }
-        }
-        dealt.resize(items.size());
-        for (size_t i = 0; i < items.size(); i++) dealt[cnt[owner[i]]++] = items[i];
-        dealt.push_back({V_ZERO, 0, 0, 0, 0, 0, 0, 0});              // the pipelines read two items ahead
-        dealt.push_back({V_ZERO, 0, 0, 0, 0, 0, 0, 0});
-        items.swap(dealt);
-        if (trace) fprintf(stderr, "[pr trace]   deal: placement %.3f ms\n", t_ms(td1, t_now()));
-    }
+    return vitems ? (unsigned)std::min<size_t>(std::max<size_t>(1, ss::div_up(n_items, (size_t)WAVES * opt.items_per_wave)), (size_t)ctx->cu_count * per_cu)
+                  : (unsigned)std::min<size_t>(n_items, (size_t)ctx->cu_count * 8);
+}
 
-    // the graph's build temporaries (ss_graph::late_free): its last kernels ran under the host work above
-    g->settle();
-    const auto tc2 = t_now();
-    const unsigned begin_blocks = std::max(1u, std::min(2048u, ss::div_up(n_local * GW, TPB)));
-    SS_HIP(ctx, pr->partials.alloc(((size_t)std::max(pr->nblocks, begin_blocks) + 8) * 2 * GW));   // block rows + 8 group rows
-    SS_HIP(ctx, pr->segpart.alloc((size_t)std::max(nsegs, 1u) * GW));
-    SS_HIP(ctx, pr->rowticket.alloc(std::max(nmulti, 1u)));
-    SS_HIP(ctx, hipMemsetAsync(pr->rowticket.p, 0, pr->rowticket.bytes(), st));
-    SS_HIP(ctx, pr->woff.alloc(std::max<size_t>(woff.size(), 8)));
-    if (!woff.empty()) SS_HIP(ctx, hipMemcpyAsync(pr->woff.p, woff.data(), woff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    SS_HIP(ctx, pr->work.alloc(items.size()));
-    SS_HIP(ctx, hipMemcpyAsync(pr->work.p, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
-    if (vitems)
-        hipLaunchKernelGGL(k_pr_item_ranges, dim3(ss::div_up(items.size(), TPB)), dim3(TPB), 0, st, pr->work.p, (uint32_t)items.size(), (const uint32_t*)g->in_ptr.p);
-    SS_HIP(ctx, pr->ctl.alloc(1));
-    SS_HIP(ctx, hipMemsetAsync(pr->ctl.p, 0, sizeof(PrCtl), st));
-    double h_x0[MAXK];
-    for (int k = 0; k < MAXK; k++) h_x0[k] = k < k_topics ? 1.0 / (double)n_topic[k] : 0.0;   // pagerank.go:104
-    SS_HIP(ctx, pr->x0.alloc(MAXK));
-    SS_HIP(ctx, hipMemcpyAsync(pr->x0.p, h_x0, sizeof(h_x0), hipMemcpyHostToDevice, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));   // items / h_x0 are stack/host temporaries
-    if (trace) fprintf(stderr, "[pr trace] ss_pr_create: build_work %.2f ms (%zu items), edge ranges + deal %.2f ms, alloc + upload %.2f ms\n", t_ms(tc0, tc1), items.size(), t_ms(tc1, tc2), t_ms(tc2, t_now()));
-    if (trace) fprintf(stderr, "[pr trace] where the state lives: x %p  tab0 %p  tab1 %p  in_src %p  in_ptr %p  outdeg %p  work %p  woff %p\n", (void*)pr->x.p, (void*)pr->tab0.p,
-                       (void*)pr->tab1.p, (void*)g->in_src.p, (void*)g->in_ptr.p, (void*)g->outdeg.p, (void*)pr->work.p, (void*)pr->woff.p);
-
+void fill_params(ss_pr* pr, const Cut& cut, const PlanOptions& opt, double damping, double eps, int32_t max_iter, int32_t k_topics) {
+    const ss_graph* g = pr->g;
     PrParams& p = pr->prm;
     p.in_ptr = g->in_ptr.p;
     p.in_src = g->in_src.p;
@@ -2348,41 +1634,181 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     p.cnt_nd = g->cnt_nd;
     p.sl_d = g->sl_d;
     p.cnt_d = g->cnt_d;
-    p.seg_edges = seg_edges;
-    p.n_items = (uint32_t)items.size();
-    p.pos_nd = pos_nd;
-    p.pos_d = pos_d;
+    p.seg_edges = cut.seg_edges;
+    p.n_items = (uint32_t)cut.items.size();
+    p.pos_nd = cut.pos_nd;
+    p.pos_d = cut.pos_d;
     p.zrow = (uint32_t)g->nd_int;
     p.woff = pr->woff.p;
-    p.stagger_div = ctx->opt("pr.stagger", 0) != 0 ? (uint32_t)std::max(ctx->cu_count, 1) : 0u;
-    p.stagger_code = ctx->opt("pr.stagger", 0) >= 10 ? (uint32_t)(ctx->opt("pr.stagger", 0) - 10) : 0u;
-    {
-        // "pr.class_order": six decimal digits, position by position (012345 = long rows, mid rows, the three short-row classes,
-        // edge-less rows); anything that is not a permutation of 0..5 falls back to that order
-        int64_t code = ctx->opt("pr.class_order", 235401);
-        uint32_t packed = 0, seen = 0;
-        for (int pos = 5; pos >= 0; pos--) {
-            const uint32_t c = (uint32_t)(code % 10);
-            code /= 10;
-            packed |= (c & 7u) << (3 * pos);
-            if (c < 6) seen |= 1u << c;
-        }
-        p.class_order = seen == 0x3Fu ? packed : (0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12 | 5u << 15);
-        // "pr.n_class_order": four digits for k_pr_sweep_n's phases (0 = long rows, 1 = mid rows, 2 = rows of <= 8 in-edges, 3 = edge-less rows)
-        // (all 24 orders, round 5: 2^20 nodes / 5M edges 0.0472 ms for 2-3-1-0 against 0.0492 for 0-1-2-3, the worst; at 10M / 50M the
-        //  numbering order is within 0.2 % of the best and short-rows-first among the worst: 0.3796 against 0.379 / 0.389)
-        int64_t c4 = ctx->opt("pr.n_class_order", (size_t)g->n_local() <= ((size_t)4 << 20) ? 2310 : 123);
-        uint32_t p4 = 0, s4 = 0;
-        for (int pos = 3; pos >= 0; pos--) {
-            const uint32_t c = (uint32_t)(c4 % 10);
-            c4 /= 10;
-            p4 |= (c & 3u) << (2 * pos);
-            if (c < 4) s4 |= 1u << c;
-        }
-        p.n_order = s4 == 0xFu ? p4 : (0u | 1u << 2 | 2u << 4 | 3u << 6);
+    p.stagger_div = opt.stagger != 0 ? (uint32_t)std::max(g->ctx->cu_count, 1) : 0u;
+    p.stagger_code = opt.stagger >= 10 ? (uint32_t)(opt.stagger - 10) : 0u;
+    p.class_order = pack_class_order(opt.class_order);
+    p.n_order = pack_n_order(opt.n_class_order);
+}
+
+// pr.trace: 64-bit FNV-1a hashes of the plan (the host work table as uploaded, the per-wave offsets, the scalar fields of PrParams): two
+// builds that plan alike print the same line
+uint64_t fnv1a(const void* q, size_t n, uint64_t h = 0xcbf29ce484222325ull) {
+    const unsigned char* b = static_cast<const unsigned char*>(q);
+    for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; }
+    return h;
+}
+void trace_plan(const ss_pr* pr, const std::vector<WorkItem>& work, const std::vector<uint32_t>& woff) {
+    const PrParams& p = pr->prm;
+    const double sd[] = {p.d, p.teleport, p.eps, p.tele_n};
+    const uint32_t su[] = {(uint32_t)p.max_iter, (uint32_t)p.k_topics, (uint32_t)p.world, p.sl_nd, p.cnt_nd, p.sl_d, p.cnt_d, p.seg_edges, p.n_items,
+                           p.pos_nd, p.pos_d, p.ts_mask, p.zrow, p.stagger_div, p.stagger_code, p.class_order, p.n_order};
+    fprintf(stderr, "[pr trace] plan: work %016llx (%zu items)  woff %016llx  params %016llx  nblocks %u\n",
+            (unsigned long long)fnv1a(work.data(), work.size() * sizeof(WorkItem)), work.size(),
+            (unsigned long long)fnv1a(woff.data(), woff.size() * sizeof(uint32_t)),
+            (unsigned long long)fnv1a(su, sizeof(su), fnv1a(sd, sizeof(sd))), pr->nblocks);
+}
+
+#ifdef SS_PR_WAVETIME
+// the variant build's two dumps go to the directory the environment names in SS_PR_WAVETIME_DIR (default: the working directory)
+FILE* open_dump(const char* name) {
+    const char* dir = getenv("SS_PR_WAVETIME_DIR");
+    return fopen((std::string(dir && *dir ? dir : ".") + "/" + name).c_str(), "w");
+}
+// variant build: the modelled load of every wave, in all and per class (tools/pr_wavetime.py)
+void dump_wave_loads(const Cut& cut, const std::vector<double>& cost, const std::vector<uint32_t>& owner, uint32_t nw) {
+    FILE* f = open_dump("pr_load.csv");
+    if (!f) return;
+    std::vector<double> wl(nw, 0.0), wcls((size_t)nw * 6, 0.0);
+    for (size_t i = 0; i < cut.items.size(); i++) {
+        int kc = 0; while (kc < 5 && i >= cut.vbeg[kc + 1]) kc++;
+        wl[owner[i]] += cost[i]; wcls[(size_t)owner[i] * 6 + kc] += cost[i];
     }
+    fprintf(f, "wave,load,c0,c1,c2,c3,c4,c5\n");
+    for (uint32_t w = 0; w < nw; w++) fprintf(f, "%u,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f\n", w, wl[w], wcls[(size_t)w * 6], wcls[(size_t)w * 6 + 1], wcls[(size_t)w * 6 + 2], wcls[(size_t)w * 6 + 3], wcls[(size_t)w * 6 + 4], wcls[(size_t)w * 6 + 5]);
+    fclose(f);
+}
+// ... and when every wave of the last sweep started and ran out of items (k_pr_sweep's timestamps)
+void dump_wave_times(const ss_pr* pr) {
+    if (pr->gw < 8) return;
+    (void)hipDeviceSynchronize();
+    const uint32_t nwv = std::min<uint32_t>(65536u, pr->nblocks * WAVES);
+    std::vector<unsigned long long> h((size_t)nwv * 2);
+    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_pr_wt), h.size() * sizeof(unsigned long long)) != hipSuccess || !nwv) return;
+    unsigned long long t0 = ~0ull;
+    for (uint32_t w = 0; w < nwv; w++) t0 = std::min(t0, h[2 * w]);
+    std::vector<double> st(nwv), en(nwv);
+    for (uint32_t w = 0; w < nwv; w++) { st[w] = (double)(h[2 * w] - t0) / 100.0; en[w] = (double)(h[2 * w + 1] - t0) / 100.0; }
+    std::sort(st.begin(), st.end()); std::sort(en.begin(), en.end());
+    if (FILE* f = open_dump("pr_wt.csv")) {
+        fprintf(f, "wave,start_us,end_us\n");
+        for (uint32_t w = 0; w < nwv; w++) fprintf(f, "%u,%.2f,%.2f\n", w, (double)(h[2 * w] - t0) / 100.0, (double)(h[2 * w + 1] - t0) / 100.0);
+        fclose(f);
+    }
+    fprintf(stderr, "[pr wavetime] %u waves: start us median %.1f max %.1f | out of items us min %.1f p10 %.1f median %.1f p90 %.1f p99 %.1f max %.1f\n", nwv,
+            st[nwv / 2], st[nwv - 1], en[0], en[nwv / 10], en[nwv / 2], en[nwv * 9 / 10], en[(size_t)nwv * 99 / 100], en[nwv - 1]);
+}
+#endif
+
+}  // namespace
+
+extern "C" {
+
+int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, int32_t k_topics,
+                     const int32_t* n_topic, ss_pr** out) {
+    if (!g) return SS_ERR_INVALID;
+    ss_ctx* ctx = g->ctx;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!out) return ctx->fail(SS_ERR_INVALID, "ss_pr_create: out is NULL");
+    *out = nullptr;
+    if (k_topics < 1 || !n_topic) return ctx->fail(SS_ERR_INVALID, "ss_pr_create: k_topics < 1 or n_topic NULL");
+    if (k_topics > MAXK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pr_create: k_topics %d > %d per state (ss_pagerank_run splits larger K)", k_topics, MAXK);
+    SS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+
+    ss_pr* pr = new (std::nothrow) ss_pr();
+    if (!pr) return ctx->fail(SS_ERR_OOM, "ss_pr_create: host OOM");
+    std::unique_ptr<ss_pr> guard(pr);
+    pr->g = g;
+    pr->k = k_topics;
+    const bool force_narrow = ctx->opt("pr.force_narrow", 0) != 0;
+    pr->gw = pick_gw(k_topics, g->nd_int, force_narrow, ctx->opt("pr.narrow_wave", 1) != 0);
+    pr->nwave = pr->gw <= 2 && !force_narrow && ctx->opt("pr.narrow_wave", 1) != 0;
+    const int GW = pr->gw;
+    const bool vitems = GW >= 8 || pr->nwave;          // wave-owned items (k_pr_sweep / k_pr_sweep_n); otherwise k_pr_step's block items
+    const int GI = pr->nwave ? 8 : GW;                 // lane-group width the ITEMS are cut for
+    const size_t n_local = g->n_local();
+    if (((uint64_t)g->nd_int + 1) * GW * 8 >= (1ull << 32))
+        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pr_create: contribution table of %llu rows x %d topics exceeds 4 GiB (shard the graph over more ranks)",
+                         (unsigned long long)g->nd_int, GW);
+
+    const bool trace = ctx->opt("pr.trace", 0) != 0;
+    auto t_now = [] { return std::chrono::steady_clock::now(); };
+    auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    // the large tables first: the device zeroes them (gigabytes at config 4) while the host builds and deals the work items below
+    SS_HIP(ctx, pr->x.alloc_streaming(n_local * GW));
+    // + the all-zero row k_pr_sweep's unused slots gather from (never written: the exchange and the sweeps stop at nd_int)
+    SS_HIP(ctx, pr->tab0.alloc(((size_t)g->nd_int + 1) * GW));
+    SS_HIP(ctx, hipMemsetAsync(pr->tab0.p, 0, std::max<size_t>(pr->tab0.bytes(), 8), st));
+    if (g->world == 1) {
+        SS_HIP(ctx, pr->tab1.alloc(((size_t)g->nd_int + 1) * GW));
+        SS_HIP(ctx, hipMemsetAsync(pr->tab1.p, 0, std::max<size_t>(pr->tab1.bytes(), 8), st));
+    } else {
+        SS_HIP(ctx, pr->send.alloc((size_t)g->sl_nd * GW));
+        SS_HIP(ctx, hipMemsetAsync(pr->send.p, 0, std::max<size_t>(pr->send.bytes(), 8), st));
+    }
+
+    // the plan (pr_plan.hpp): rows cut into items, the grid, and for the wave-item kernels the items dealt to the grid's waves — the
+    // items' turn counts come from the sorted in-degrees the graph keeps on the host, their edge ranges are filled in on the device
+    // (k_pr_item_ranges)
+    const auto tc0 = t_now();
+    const PlanOptions opt = plan_options(ctx, pr, n_local);
+    Cut cut = cut_items(g->h_indeg_nd, g->h_indeg_d, g->sl_nd, GI, pr->nwave, opt);
+    const auto tc1 = t_now();
+    const int per_cu = sweep_blocks_per_cu(pr);
+    const auto tc1a = t_now();
+    pr->nblocks = grid_for(ctx, pr, opt, per_cu, vitems, cut.items.size());
+    static const std::vector<uint32_t> no_woff;
+    const std::vector<uint32_t>* woff = &no_woff;
+    if (vitems) {
+        const uint32_t nw = pr->nblocks * WAVES;
+        const auto td0 = t_now();
+        const std::vector<double>& cost = item_costs(cut, g->h_indeg_nd, g->h_indeg_d, g->sl_nd, GI, pr->nwave);
+        const auto td0a = t_now();
+        std::vector<uint32_t>& owner = deal_items(cut, cost, nw, pr->nwave, opt);
+#ifdef SS_PR_WAVETIME
+        dump_wave_loads(cut, cost, owner, nw);
+#endif
+        const auto td1 = t_now();
+        if (trace) fprintf(stderr, "[pr trace]   deal: occupancy query %.2f ms, costs %.3f ms, owners %.3f ms\n", t_ms(tc1, tc1a), t_ms(td0, td0a), t_ms(td0a, td1));
+        woff = &place_items(cut, owner, nw);
+        if (trace) fprintf(stderr, "[pr trace]   deal: placement %.3f ms\n", t_ms(td1, t_now()));
+    }
+    const std::vector<WorkItem>& items = cut.items;
+
+    // the graph's build temporaries (ss_graph::late_free): its last kernels ran under the host work above
+    g->settle();
+    const auto tc2 = t_now();
+    SS_HIP(ctx, pr->partials.alloc(((size_t)std::max(pr->nblocks, ss::begin_blocks(pr)) + 8) * 2 * GW));   // block rows + 8 group rows
+    SS_HIP(ctx, pr->segpart.alloc((size_t)std::max(cut.nsegs, 1u) * GW));
+    SS_HIP(ctx, pr->rowticket.alloc(std::max(cut.nmulti, 1u)));
+    SS_HIP(ctx, hipMemsetAsync(pr->rowticket.p, 0, pr->rowticket.bytes(), st));
+    SS_HIP(ctx, pr->woff.alloc(std::max<size_t>(woff->size(), 8)));
+    if (!woff->empty()) SS_HIP(ctx, hipMemcpyAsync(pr->woff.p, woff->data(), woff->size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SS_HIP(ctx, pr->work.alloc(items.size()));
+    SS_HIP(ctx, hipMemcpyAsync(pr->work.p, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+    if (vitems)
+        hipLaunchKernelGGL(k_pr_item_ranges, dim3(ss::div_up(items.size(), TPB)), dim3(TPB), 0, st, pr->work.p, (uint32_t)items.size(), (const uint32_t*)g->in_ptr.p);
+    SS_HIP(ctx, pr->ctl.alloc(1));
+    SS_HIP(ctx, hipMemsetAsync(pr->ctl.p, 0, sizeof(PrCtl), st));
+    double h_x0[MAXK];
+    for (int k = 0; k < MAXK; k++) h_x0[k] = k < k_topics ? 1.0 / (double)n_topic[k] : 0.0;   // pagerank.go:104
+    SS_HIP(ctx, pr->x0.alloc(MAXK));
+    SS_HIP(ctx, hipMemcpyAsync(pr->x0.p, h_x0, sizeof(h_x0), hipMemcpyHostToDevice, st));
+    SS_HIP(ctx, hipStreamSynchronize(st));   // items / h_x0 are stack/host temporaries
+    if (trace) fprintf(stderr, "[pr trace] ss_pr_create: build_work %.2f ms (%zu items), edge ranges + deal %.2f ms, alloc + upload %.2f ms\n", t_ms(tc0, tc1), items.size(), t_ms(tc1, tc2), t_ms(tc2, t_now()));
+    if (trace) fprintf(stderr, "[pr trace] where the state lives: x %p  tab0 %p  tab1 %p  in_src %p  in_ptr %p  outdeg %p  work %p  woff %p\n", (void*)pr->x.p, (void*)pr->tab0.p,
+                       (void*)pr->tab1.p, (void*)g->in_src.p, (void*)g->in_ptr.p, (void*)g->outdeg.p, (void*)pr->work.p, (void*)pr->woff.p);
+
+    fill_params(pr, cut, opt, damping, eps, max_iter, k_topics);
+    if (trace) trace_plan(pr, items, *woff);
 #ifdef SS_PR_EXP_KINDMASK
-    p.kind_mask = getenv("SS_PR_KIND_MASK") ? (uint32_t)strtoul(getenv("SS_PR_KIND_MASK"), nullptr, 0) : 0xFFFFFFFFu;
+    pr->prm.kind_mask = getenv("SS_PR_KIND_MASK") ? (uint32_t)strtoul(getenv("SS_PR_KIND_MASK"), nullptr, 0) : 0xFFFFFFFFu;
     {
         size_t cnt[16] = {0};
         for (auto& it : items) cnt[it.kind & 15]++;
@@ -2471,25 +1897,7 @@ int32_t ss_pr_set_teleport(ss_pr* pr, const uint64_t* set_ptr, const uint32_t* s
 
 int32_t ss_pr_destroy(ss_pr* pr) {
 #ifdef SS_PR_WAVETIME
-    if (pr && pr->gw >= 8) {
-        (void)hipDeviceSynchronize();
-        const uint32_t nwv = std::min<uint32_t>(65536u, pr->nblocks * WAVES);
-        std::vector<unsigned long long> h((size_t)nwv * 2);
-        if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_pr_wt), h.size() * sizeof(unsigned long long)) == hipSuccess && nwv) {
-            unsigned long long t0 = ~0ull;
-            for (uint32_t w = 0; w < nwv; w++) t0 = std::min(t0, h[2 * w]);
-            std::vector<double> st(nwv), en(nwv);
-            for (uint32_t w = 0; w < nwv; w++) { st[w] = (double)(h[2 * w] - t0) / 100.0; en[w] = (double)(h[2 * w + 1] - t0) / 100.0; }
-            std::sort(st.begin(), st.end()); std::sort(en.begin(), en.end());
-            if (FILE* f = fopen("gpurun_out/pr_wt.csv", "w")) {
-                fprintf(f, "wave,start_us,end_us\n");
-                for (uint32_t w = 0; w < nwv; w++) fprintf(f, "%u,%.2f,%.2f\n", w, (double)(h[2 * w] - t0) / 100.0, (double)(h[2 * w + 1] - t0) / 100.0);
-                fclose(f);
-            }
-            fprintf(stderr, "[pr wavetime] %u waves: start us median %.1f max %.1f | out of items us min %.1f p10 %.1f median %.1f p90 %.1f p99 %.1f max %.1f\n", nwv,
-                    st[nwv / 2], st[nwv - 1], en[0], en[nwv / 10], en[nwv / 2], en[nwv * 9 / 10], en[(size_t)nwv * 99 / 100], en[nwv - 1]);
-        }
-    }
+    if (pr) dump_wave_times(pr);
 #endif
 
     if (!pr) return SS_ERR_INVALID;
@@ -2511,10 +1919,8 @@ int32_t ss_pr_begin(ss_pr* pr) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
     if (pr->need_finalize) return ctx->fail(SS_ERR_STATE, "ss_pr_begin: pending exchange/finalize");
-    const size_t n_el = (size_t)pr->g->n_local() * pr->gw;
-    const unsigned nb = std::max(1u, std::min(2048u, ss::div_up(n_el, TPB)));
     SS_HIP(ctx, hipMemsetAsync(&pr->ctl.p->ticket, 0, sizeof(uint32_t), ctx->stream));
-    SS_GW_DISPATCH(pr->gw, launch_begin, pr, ctx->stream, nb);
+    ss::pr_launch_begin(pr, ctx->stream, ss::begin_blocks(pr));
     SS_HIP(ctx, hipGetLastError());
     pr->begun = true;
     if (pr->g->world > 1) {
@@ -2537,7 +1943,7 @@ int32_t ss_pr_step(ss_pr* pr, int32_t n_steps) {
     if (pr->persist && !pr->prm.memb && !pr->prm.aff) {
         SS_GW_DISPATCH(pr->gw, launch_multi, pr, ctx->stream, (int)n_steps);   // the sweeps wait for each other inside the launch
     } else {
-        for (int i = 0; i < n_steps; i++) SS_GW_DISPATCH(pr->gw, launch_step, pr, ctx->stream);
+        for (int i = 0; i < n_steps; i++) ss::pr_launch_step(pr, ctx->stream);
     }
     SS_HIP(ctx, hipEventRecord(ctx->ev[0][1], ctx->stream));
     ctx->ev_valid[0] = true;
@@ -2556,7 +1962,7 @@ int32_t ss_pr_finalize(ss_pr* pr) {
     SS_HIP(ctx, hipSetDevice(ctx->device));
     if (pr->g->world == 1) return ctx->fail(SS_ERR_STATE, "ss_pr_finalize: world==1 folds the finalize into the sweep");
     if (!pr->need_finalize) return ctx->fail(SS_ERR_STATE, "ss_pr_finalize: nothing to finalize");
-    SS_GW_DISPATCH(pr->gw, launch_finalize, pr, ctx->stream, pr->finalize_is_begin ? 1 : 0);
+    ss::pr_launch_finalize(pr, ctx->stream, pr->finalize_is_begin ? 1 : 0);
     SS_HIP(ctx, hipGetLastError());
     pr->need_finalize = false;
     return SS_OK;
@@ -2585,11 +1991,11 @@ int32_t ss_pr_exchange(ss_pr* pr, int32_t allreduce) {
         return ctx->fail(SS_ERR_STATE, "ss_pr_exchange: the context's communicator (rank %d of %d) does not match the graph's shard (rank %d of %d)",
                          ctx->comm ? ctx->comm_rank : -1, ctx->comm ? ctx->comm_world : 0, g->rank, g->world);
     const size_t slice = (size_t)g->sl_nd * pr->gw;            // doubles per rank
-    if (!allreduce && ctx->opt("pr.wire_f32", 0) != 0) {       // opt-in: float32 on the wire (see k_wire_pack)
-        SS_HIP(ctx, wire_alloc(pr));
-        wire_pack(pr, ctx->stream);
-        SS_TRY(ss::comm_allgather(ctx, pr->wire_send.p, pr->wire_recv.p, wire_floats(pr) * sizeof(float)));
-        wire_unpack(pr, ctx->stream);
+    if (!allreduce && ctx->opt("pr.wire_f32", 0) != 0) {       // opt-in: float32 on the wire (pagerank_run.hip: k_wire_pack)
+        SS_HIP(ctx, ss::pr_wire_alloc(pr));
+        ss::pr_wire_pack(pr, ctx->stream);
+        SS_TRY(ss::comm_allgather(ctx, pr->wire_send.p, pr->wire_recv.p, ss::pr_wire_floats(pr) * sizeof(float)));
+        ss::pr_wire_unpack(pr, ctx->stream);
         return SS_OK;
     }
     if (!allreduce) return ss::comm_allgather(ctx, pr->send.p, pr->tab0.p, slice * sizeof(double));
@@ -2599,456 +2005,14 @@ int32_t ss_pr_exchange(ss_pr* pr, int32_t allreduce) {
     return ss::comm_allreduce_f64(ctx, pr->tab0.p, pr->tab0.p, slice * (size_t)g->world);
 }
 
-}  // extern "C"
-
-namespace {
-
-// ---- the sharded power iteration as ONE pipeline inside the library ---------------------------------
-// The K topic vectors are split into B topic blocks (separate states over the same shard); block b's exchange runs on the
-// context's second stream while block b+1 is finalised and swept on the first:
-//     compute:  [fin 0][sweep 0]      [fin 1][sweep 1]      [fin 0][sweep 0] ...
-//     comm:                 [exchange 0 ..........][exchange 1 ..........]
-// HIP events order the two streams; the host enqueues and looks at the device-side stop rule every BATCH sweeps.  Topics are
-// independent power iterations (pagerank.go:54-63), so a block's results are bit for bit those of running its topics alone.
-// The exchange is a functor: RCCL for one shard per process (ss_pagerank_run_sharded), device-to-device copies for the
-// shards of a single-process group (ss_pagerank_run_group: tests, and one process driving several shards on one device).
-struct ShardBlocks { std::vector<ss_pr*> blk; };
-
-template <typename Exchange>
-int32_t run_pipelined(ss_ctx* ctx, std::vector<ShardBlocks>& sh, int32_t max_iter, Exchange&& exchange, int32_t* iters_out,
-                      const std::vector<int>& blk_k0) {
-    const int B = (int)sh[0].blk.size(), S = (int)sh.size();
-    hipStream_t cs = ctx->stream, xs = ctx->comm_stream;
-    std::vector<hipEvent_t> ev_step(B), ev_xchg(B);
-    for (int b = 0; b < B; b++) {
-        SS_HIP(ctx, hipEventCreateWithFlags(&ev_step[b], hipEventDisableTiming));
-        SS_HIP(ctx, hipEventCreateWithFlags(&ev_xchg[b], hipEventDisableTiming));
-    }
-    auto cleanup = [&] {
-        if (!ss::device_wedged(ctx->device)) {                       // (after a timed-out collective neither stream will ever drain)
-            (void)hipStreamSynchronize(xs);
-            (void)hipStreamSynchronize(cs);
-        }
-        for (int b = 0; b < B; b++) { (void)hipEventDestroy(ev_step[b]); (void)hipEventDestroy(ev_xchg[b]); }
-    };
-    int32_t rc = SS_OK;
-    auto start_exchange = [&](int b) -> int32_t {
-        SS_HIP(ctx, hipEventRecord(ev_step[b], cs));
-        SS_HIP(ctx, hipStreamWaitEvent(xs, ev_step[b], 0));
-        SS_TRY(exchange(b, xs));
-        SS_HIP(ctx, hipEventRecord(ev_xchg[b], xs));
-        return SS_OK;
-    };
-    // prime: every block begun, its first exchange in flight
-    for (int b = 0; b < B && rc == SS_OK; b++) {
-        for (int s = 0; s < S; s++) {
-            ss_pr* pr = sh[s].blk[b];
-            const size_t n_el = (size_t)pr->g->n_local() * pr->gw;
-            const unsigned nb = std::max(1u, std::min(2048u, ss::div_up(n_el, TPB)));
-            SS_HIP(ctx, hipMemsetAsync(&pr->ctl.p->ticket, 0, sizeof(uint32_t), cs));
-            SS_GW_DISPATCH(pr->gw, launch_begin, pr, cs, nb);
-            pr->begun = true;
-        }
-        rc = start_exchange(b);
-    }
-    bool first = true;
-    const int BATCH = 8;
-    int32_t sweeps_done = 0;
-    for (;;) {
-        if (rc != SS_OK) break;
-        int todo = BATCH;
-        if (max_iter > 0) todo = std::min(BATCH, std::max(1, max_iter - sweeps_done));
-        for (int i = 0; i < todo && rc == SS_OK; i++) {
-            for (int b = 0; b < B && rc == SS_OK; b++) {
-                if (hipStreamWaitEvent(cs, ev_xchg[b], 0) != hipSuccess) { rc = ctx->fail(SS_ERR_HIP, "hipStreamWaitEvent"); break; }
-                for (int s = 0; s < S; s++) SS_GW_DISPATCH(sh[s].blk[b]->gw, launch_finalize, sh[s].blk[b], cs, first ? 1 : 0);
-                for (int s = 0; s < S; s++) SS_GW_DISPATCH(sh[s].blk[b]->gw, launch_step, sh[s].blk[b], cs);
-                rc = start_exchange(b);
-            }
-            first = false;
-            sweeps_done++;
-        }
-        if (rc != SS_OK) break;
-        if (hipGetLastError() != hipSuccess) { rc = ctx->fail(SS_ERR_HIP, "sharded sweep: launch failed"); break; }
-        // the stop rule lives on the device and is evaluated identically on every rank (same gathered sums, same order);
-        // what the host reads lags the in-flight sweep by one, and launches after convergence are no-ops on all ranks alike
-        int32_t n_active = 0;
-        for (int b = 0; b < B && rc == SS_OK; b++) {
-            ctx->pin_used = 0;
-            PrCtl* const hp = ctx->pin<PrCtl>();
-            if (hipMemcpyAsync(hp, sh[0].blk[b]->ctl.p, sizeof(PrCtl), hipMemcpyDeviceToHost, cs) != hipSuccess) { rc = ctx->fail(SS_ERR_HIP, "sharded sweep: status read failed"); break; }
-            if ((rc = ss::sync_bounded(ctx, cs, "sharded sweep (waiting for the exchange)")) != SS_OK) break;
-            n_active += hp->n_active;
-        }
-        if (n_active == 0) break;
-    }
-    // drain: apply the exchanges still in flight (no-ops after convergence)
-    for (int b = 0; b < B && rc == SS_OK; b++) {
-        if (hipStreamWaitEvent(cs, ev_xchg[b], 0) != hipSuccess) { rc = ctx->fail(SS_ERR_HIP, "hipStreamWaitEvent"); break; }
-        for (int s = 0; s < S; s++) {
-            SS_GW_DISPATCH(sh[s].blk[b]->gw, launch_finalize, sh[s].blk[b], cs, first ? 1 : 0);
-            sh[s].blk[b]->need_finalize = false;
-        }
-    }
-    if (rc == SS_OK && iters_out) {
-        for (int b = 0; b < B && rc == SS_OK; b++) {
-            ctx->pin_used = 0;
-            PrCtl* const hp = ctx->pin<PrCtl>();
-            if (hipMemcpyAsync(hp, sh[0].blk[b]->ctl.p, sizeof(PrCtl), hipMemcpyDeviceToHost, cs) != hipSuccess) { rc = ctx->fail(SS_ERR_HIP, "sharded sweep: status read failed"); break; }
-            if ((rc = ss::sync_bounded(ctx, cs, "sharded sweep (last exchange)")) != SS_OK) break;
-            for (int k = 0; k < sh[0].blk[b]->k; k++) iters_out[blk_k0[b] + k] = hp->iters[k];
-        }
-    }
-    cleanup();
-    return rc;
-}
-
-// topic blocks of a K-topic run: option "pr.topic_blocks" (default 2 above 8 topics: one block's exchange then hides behind
-// the other block's sweep — and both blocks still fill an 8-wide table; splitting 8 topics or fewer would pad every block to
-// the 8-wide kernel and double the bytes on the wire), never more blocks than topics
-int topic_blocks_for(ss_ctx* ctx, int k_topics) {
-    int B = (int)ctx->opt("pr.topic_blocks", k_topics > 8 ? 2 : 1);
-    return std::max(1, std::min(B, k_topics));
-}
-
-// ---- the two-vector form on a sharded graph (option "pr.affine"): a TWO-column exchange per iteration, whatever K is -------------
-// One K = 2 state per shard; per iteration: sweep (local rows) -> all-gather of the 2-wide contribution slices -> k_pr_finalize
-// (affine branch: r, s, the column teleports; identical on every rank) -> the topics' L1 changes over the local rows -> all-gather
-// of the ranks' K sums -> stop rule (k_aff_ctl adds them in rank order) -> write-out of the topics that have just stopped.
-struct AffShard {
-    ss::DevBuf<AffCtl> aff;
-    ss::DevBuf<double> x_alt, partials, loc, gath, out;
-    double n_zero = 0.0;
-};
-int32_t aff_attach(ss_pr* pr, AffShard& A, int32_t k_topics, const int32_t* n_topic, int world) {
-    ss_ctx* ctx = pr->g->ctx;
-    hipStream_t st = ctx->stream;
-    if (!pr->nwave || pr->gw != 2) return ctx->fail(SS_ERR_UNSUPPORTED, "pr.affine: needs the wave-item K = 2 sweep (pr.narrow_wave / pr.force_narrow at their defaults)");
-    const ss_graph* g = pr->g;
-    const size_t n_rows = (size_t)g->cnt_nd + g->cnt_d;
-    SS_HIP(ctx, A.aff.alloc(1));
-    SS_HIP(ctx, A.x_alt.alloc((size_t)g->n_local() * 2));
-    SS_HIP(ctx, A.partials.alloc((size_t)AFF_NB * AFF_MAXK));
-    SS_HIP(ctx, A.loc.alloc(AFF_MAXK));
-    SS_HIP(ctx, A.gath.alloc((size_t)world * AFF_MAXK));
-    SS_HIP(ctx, A.out.alloc(std::max<size_t>(1, (size_t)k_topics * n_rows)));
-    SS_HIP(ctx, hipMemsetAsync(A.loc.p, 0, A.loc.bytes(), st));
-    std::vector<AffCtl> h(1);
-    std::memset(h.data(), 0, sizeof(AffCtl));
-    for (int k = 0; k < k_topics; k++) { h[0].u[k] = 1.0 / (double)n_topic[k]; h[0].active[k] = 1; }   // pagerank.go:104
-    h[0].k_real = k_topics;
-    h[0].n_active = k_topics;
-    SS_HIP(ctx, hipMemcpyAsync(A.aff.p, h.data(), sizeof(AffCtl), hipMemcpyHostToDevice, st));
-    const double x0[MAXK] = {1.0, 0.0};
-    SS_HIP(ctx, hipMemcpyAsync(pr->x0.p, x0, sizeof(x0), hipMemcpyHostToDevice, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    pr->prm.aff = A.aff.p;
-    pr->prm.tele_col = pr->ctl.p->tele;
-    pr->prm.x_alt = A.x_alt.p;
-    A.n_zero = (double)((g->cnt_nd - pr->prm.pos_nd) + (g->cnt_d - pr->prm.pos_d));
-    return SS_OK;
-}
-template <typename Exchange, typename ExchangeSums>
-int32_t run_affine_sharded(ss_ctx* ctx, std::vector<ShardBlocks>& sh, std::vector<AffShard>& A, int world, double eps, int32_t max_iter, int32_t k_topics,
-                           Exchange&& exchange, ExchangeSums&& exchange_sums, int32_t* iters_out) {
-    const int S = (int)sh.size();
-    hipStream_t st = ctx->stream;
-    for (int s = 0; s < S; s++) {
-        ss_pr* pr = sh[s].blk[0];
-        const size_t n_el = (size_t)pr->g->n_local() * pr->gw;
-        const unsigned nb = std::max(1u, std::min(2048u, ss::div_up(n_el, TPB)));
-        SS_HIP(ctx, hipMemsetAsync(&pr->ctl.p->ticket, 0, sizeof(uint32_t), st));
-        launch_begin<2>(pr, st, nb);
-        pr->begun = true;
-    }
-    SS_TRY(exchange(0, st));
-    for (int s = 0; s < S; s++) launch_finalize<2>(sh[s].blk[0], st, 1);
-    int32_t n_active = k_topics, it = 0;
-    const int BATCH = 4;
-    // ONE collective per iteration (option "pr.affine_lag", default 1): the ranks' per-topic L1 sums of iteration i are written into the
-    // spare tail rows of the rank's contribution slice (graph.hpp: TAIL_SUM_ROWS) and travel with iteration i + 1's all-gather, so the
-    // stop decisions of iteration i are taken one exchange later — from the same numbers, added in the same rank order — and the ranks
-    // of a topic that stops are written from the vectors of the iteration it stopped in, which the alternating pair still holds.
-    // A second, 2 KB all-gather per iteration was pure latency on a ~0.25 ms iteration; it survives only as the flush
-    // after the last sweep of a max_iter run.  0: the round-4 protocol (sums in a collective of their own, decisions at once).
-    // (the spare rows hold 2 * TAIL_SUM_ROWS = 64 sums = SS_MAX_TOPICS; these two entry points take up to AFF_MAXK topics in this form, and
-    //  beyond 64 the sums keep their own collective)
-    const bool lag = ctx->opt("pr.affine_lag", 1) != 0 && k_topics <= (int32_t)(2 * TAIL_SUM_ROWS);
-    auto sums_row = [&](ss_pr* pr, double* base) { return base + ((size_t)pr->g->sl_nd - 2 - TAIL_SUM_ROWS) * 2; };
-    auto delta_and_local = [&](int s, double* loc) {
-        ss_pr* pr = sh[s].blk[0];
-        const ss_graph* g = pr->g;
-        const double2* const x_old = reinterpret_cast<const double2*>((it & 1) ? A[s].x_alt.p : pr->x.p);
-        const double2* const x_new = reinterpret_cast<const double2*>((it & 1) ? pr->x.p : A[s].x_alt.p);
-        hipLaunchKernelGGL(k_aff_delta, dim3(AFF_NB), dim3(TPB), 0, st, x_old, x_new, (const AffCtl*)A[s].aff.p, g->sl_nd, pr->prm.pos_nd, pr->prm.pos_d,
-                           A[s].partials.p);
-        hipLaunchKernelGGL(k_aff_local, dim3(1), dim3(AFF_MAXK), 0, st, (const AffCtl*)A[s].aff.p, (const PrCtl*)pr->ctl.p, (const double*)A[s].partials.p,
-                           AFF_NB, A[s].n_zero, loc);
-    };
-    auto ctl_and_emit = [&](int s, const double* sums, size_t stride, int emit_lag) {
-        ss_pr* pr = sh[s].blk[0];
-        const ss_graph* g = pr->g;
-        // (emit_lag: the vectors before the last sweep — iteration it - 1 — else the ones it has just written)
-        const bool odd = (it & 1) != 0;
-        const double2* const x_src = reinterpret_cast<const double2*>(emit_lag ? (odd ? A[s].x_alt.p : pr->x.p) : (odd ? pr->x.p : A[s].x_alt.p));
-        hipLaunchKernelGGL(k_aff_ctl, dim3(1), dim3(AFF_MAXK), 0, st, A[s].aff.p, pr->ctl.p, sums, (unsigned)world, 0.0, eps, max_iter, stride);
-        const unsigned nbe = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(4096, ss::div_up((uint64_t)g->cnt_nd + g->cnt_d, TPB)));
-        hipLaunchKernelGGL(k_aff_emit_local, dim3(nbe), dim3(TPB), 0, st, x_src, (const PrCtl*)pr->ctl.p, (const AffCtl*)A[s].aff.p, g->sl_nd, g->cnt_nd,
-                           g->cnt_d, pr->prm.pos_nd, pr->prm.pos_d, A[s].out.p, emit_lag);
-    };
-    while (n_active > 0) {
-        for (int b = 0; b < BATCH; b++) {
-            for (int s = 0; s < S; s++) launch_step<2>(sh[s].blk[0], st);
-            SS_TRY(exchange(0, st));
-            for (int s = 0; s < S; s++) launch_finalize<2>(sh[s].blk[0], st, 0);
-            if (lag) {
-                for (int s = 0; s < S; s++) {
-                    ss_pr* pr = sh[s].blk[0];
-                    // iteration it - 1: its sums have just arrived with this iteration's table (every rank's slice, rank order)
-                    if (it > 0) ctl_and_emit(s, sums_row(pr, pr->tab0.p), (size_t)pr->g->sl_nd * 2, 1);
-                    delta_and_local(s, sums_row(pr, pr->send.p));              // iteration it: into the slice the NEXT all-gather sends
-                }
-            } else {
-                for (int s = 0; s < S; s++) delta_and_local(s, A[s].loc.p);
-                SS_TRY(exchange_sums(st));
-                for (int s = 0; s < S; s++) ctl_and_emit(s, A[s].gath.p, (size_t)AFF_MAXK, 0);
-            }
-            it++;
-            if (max_iter > 0 && it >= max_iter) break;
-        }
-        SS_HIP(ctx, hipGetLastError());
-        ctx->pin_used = 0;
-        int32_t* const hn = ctx->pin<int32_t>();
-        SS_HIP(ctx, hipMemcpyAsync(hn, &A[0].aff.p->n_active, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        SS_TRY(ss::sync_bounded(ctx, st, "sharded two-vector sweep (waiting for the exchange)"));
-        n_active = *hn;
-        if (max_iter > 0 && it >= max_iter) break;
-    }
-    if (lag && max_iter > 0 && it >= max_iter && n_active > 0) {
-        // the last sweep's sums have no further all-gather to ride on: one small collective of their own, then the decisions (every
-        // topic still running stops here: it >= max_iter) and the ranks from the vectors that sweep has written
-        it--;                                                          // (the lambdas take the parity of the sweep they describe)
-        for (int s = 0; s < S; s++) {
-            ss_pr* pr = sh[s].blk[0];
-            hipLaunchKernelGGL(k_aff_local, dim3(1), dim3(AFF_MAXK), 0, st, (const AffCtl*)A[s].aff.p, (const PrCtl*)pr->ctl.p, (const double*)A[s].partials.p,
-                               AFF_NB, A[s].n_zero, A[s].loc.p);
-        }
-        SS_TRY(exchange_sums(st));
-        for (int s = 0; s < S; s++) ctl_and_emit(s, A[s].gath.p, (size_t)AFF_MAXK, 0);
-        it++;
-        SS_HIP(ctx, hipGetLastError());
-    }
-    for (int s = 0; s < S; s++) sh[s].blk[0]->need_finalize = false;
-    if (iters_out) {
-        std::vector<AffCtl> h(1);
-        SS_HIP(ctx, hipMemcpyAsync(h.data(), A[0].aff.p, sizeof(AffCtl), hipMemcpyDeviceToHost, st));
-        SS_TRY(ss::sync_bounded(ctx, st, "sharded two-vector sweep (status)"));
-        for (int k = 0; k < k_topics; k++) iters_out[k] = h[0].iters[k];
-    }
-    return SS_OK;
-}
-// the ids of a shard's rows in local order (what ss_pr_read_local returns beside the ranks)
-int32_t local_ids(ss_pr* pr, uint32_t* ids_out) {
-    const size_t n_rows = (size_t)pr->g->cnt_nd + pr->g->cnt_d;
-    std::vector<double> scratch(std::max<size_t>(1, n_rows * (size_t)pr->k));
-    return ss_pr_read_local(pr, ids_out, scratch.data());
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t ss_pagerank_run_sharded(ss_graph* g, double damping, double eps, int32_t max_iter, int32_t k_topics,
-                                const int32_t* n_topic, int32_t allreduce, uint32_t* ids_out, double* rank_out, int32_t* iters_out) {
-    if (!g) return SS_ERR_INVALID;
-    ss_ctx* ctx = g->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (g->world < 2) return ctx->fail(SS_ERR_STATE, "ss_pagerank_run_sharded: needs a sharded graph (world > 1); use ss_pagerank_run");
-    const bool affine = ctx->opt("pr.affine", 0) != 0 && !allreduce;      // the two-vector form: a 2-column exchange whatever K is
-    const int k_max = affine ? AFF_MAXK : MAXK;
-    if (k_topics < 1 || k_topics > k_max || !n_topic || !rank_out)
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_sharded: k_topics must be 1..%d, n_topic/rank_out not NULL", k_max);
-    if (!(eps >= 0.0) && max_iter <= 0 && !(eps != eps))
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_sharded: eps < 0 (never converges) needs max_iter > 0");
-    if (!ctx->comm || ctx->comm_world != g->world || ctx->comm_rank != g->rank)
-        return ctx->fail(SS_ERR_STATE, "ss_pagerank_run_sharded: the context's communicator (rank %d of %d) does not match the graph's shard (rank %d of %d)",
-                         ctx->comm ? ctx->comm_rank : -1, ctx->comm ? ctx->comm_world : 0, g->rank, g->world);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    const int B = affine ? 1 : topic_blocks_for(ctx, k_topics);
-    std::vector<ShardBlocks> sh(1);
-    std::vector<AffShard> aff(affine ? 1 : 0);
-    std::vector<int> k0(B + 1);
-    for (int b = 0; b <= B; b++) k0[b] = (int)((int64_t)k_topics * b / B);
-    int32_t rc = SS_OK;
-    const int32_t two[2] = {1, 1};
-    for (int b = 0; b < B && rc == SS_OK; b++) {
-        ss_pr* pr = nullptr;
-        rc = affine ? ss_pr_create(g, damping, -1.0, 0, 2, two, &pr) : ss_pr_create(g, damping, eps, max_iter, k0[b + 1] - k0[b], n_topic + k0[b], &pr);
-        if (rc == SS_OK) sh[0].blk.push_back(pr);
-    }
-    if (affine && rc == SS_OK)
-        for (int k = 0; k < k_topics && rc == SS_OK; k++)
-            if (n_topic[k] < 1) rc = ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_sharded: n_topic[%d] < 1", k);
-    if (affine && rc == SS_OK) rc = aff_attach(sh[0].blk[0], aff[0], k_topics, n_topic, g->world);
-    const bool wire_f32 = ctx->opt("pr.wire_f32", 0) != 0;
-    if (rc == SS_OK) {
-        auto exchange = [&](int b, hipStream_t xs) -> int32_t {
-            ss_pr* pr = sh[0].blk[b];
-            const size_t slice = (size_t)g->sl_nd * pr->gw;            // doubles per rank
-            if (!allreduce && wire_f32) {
-                SS_HIP(ctx, wire_alloc(pr));
-                wire_pack(pr, xs);
-                SS_TRY(ss::comm_allgather_on(ctx, pr->wire_send.p, pr->wire_recv.p, wire_floats(pr) * sizeof(float), xs));
-                wire_unpack(pr, xs);
-                return SS_OK;
-            }
-            if (!allreduce) return ss::comm_allgather_on(ctx, pr->send.p, pr->tab0.p, slice * sizeof(double), xs);
-            // north-star form: own slice inside a zeroed full-size table, tables summed
-            SS_HIP(ctx, hipMemsetAsync(pr->tab0.p, 0, pr->tab0.bytes(), xs));
-            SS_HIP(ctx, hipMemcpyAsync(pr->tab0.p + (size_t)g->rank * slice, pr->send.p, slice * sizeof(double), hipMemcpyDeviceToDevice, xs));
-            return ss::comm_allreduce_f64_on(ctx, pr->tab0.p, pr->tab0.p, slice * (size_t)g->world, xs);
-        };
-        if (affine) {
-            auto exchange_sums = [&](hipStream_t xs) -> int32_t {
-                return ss::comm_allgather_on(ctx, aff[0].loc.p, aff[0].gath.p, (size_t)AFF_MAXK * sizeof(double), xs);
-            };
-            rc = run_affine_sharded(ctx, sh, aff, g->world, eps, max_iter, k_topics, exchange, exchange_sums, iters_out);
-        } else {
-            rc = run_pipelined(ctx, sh, max_iter, exchange, iters_out, k0);
-        }
-    }
-    // this rank's rows: ids once, ranks block by block (topic-major: rank_out[k][rows])
-    const size_t n_rows = (size_t)g->cnt_nd + g->cnt_d;
-    if (affine) {
-        if (rc == SS_OK && ids_out) rc = local_ids(sh[0].blk[0], ids_out);
-        if (rc == SS_OK && n_rows) {
-            if (hipMemcpyAsync(rank_out, aff[0].out.p, (size_t)k_topics * n_rows * sizeof(double), hipMemcpyDefault, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                rc = ctx->fail(SS_ERR_HIP, "ss_pagerank_run_sharded: copy of the ranks failed");
-        }
-    } else
-    for (int b = 0; b < (int)sh[0].blk.size() && rc == SS_OK; b++)
-        rc = ss_pr_read_local(sh[0].blk[b], b == 0 ? ids_out : nullptr, rank_out + (size_t)k0[b] * n_rows);
-    for (ss_pr* pr : sh[0].blk) ss_pr_destroy(pr);
-    return rc;
-}
-
-int32_t ss_pagerank_run_group(ss_graph* const* shards, int32_t world, double damping, double eps, int32_t max_iter, int32_t k_topics,
-                              const int32_t* n_topic, double* rank_out, int32_t* iters_out) {
-    if (!shards || world < 2 || !shards[0]) return SS_ERR_INVALID;
-    ss_ctx* ctx = shards[0]->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    const bool affine = ctx->opt("pr.affine", 0) != 0;
-    const int k_max = affine ? AFF_MAXK : MAXK;
-    if (k_topics < 1 || k_topics > k_max || !n_topic || !rank_out)
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_group: k_topics must be 1..%d, n_topic/rank_out not NULL", k_max);
-    if (!(eps >= 0.0) && max_iter <= 0 && !(eps != eps))
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_group: eps < 0 (never converges) needs max_iter > 0");
-    for (int s = 0; s < world; s++)
-        if (!shards[s] || shards[s]->ctx != ctx || shards[s]->world != world || shards[s]->rank != s || shards[s]->n != shards[0]->n)
-            return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_group: shards[%d] is not shard %d of %d of the same graph on this context", s, s, world);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    const int B = affine ? 1 : topic_blocks_for(ctx, k_topics);
-    std::vector<ShardBlocks> sh(world);
-    std::vector<AffShard> aff(affine ? world : 0);
-    std::vector<int> k0(B + 1);
-    for (int b = 0; b <= B; b++) k0[b] = (int)((int64_t)k_topics * b / B);
-    int32_t rc = SS_OK;
-    const int32_t two[2] = {1, 1};
-    for (int k = 0; k < k_topics && affine && rc == SS_OK; k++)
-        if (n_topic[k] < 1) rc = ctx->fail(SS_ERR_INVALID, "ss_pagerank_run_group: n_topic[%d] < 1", k);
-    for (int s = 0; s < world && rc == SS_OK; s++)
-        for (int b = 0; b < B && rc == SS_OK; b++) {
-            ss_pr* pr = nullptr;
-            rc = affine ? ss_pr_create(shards[s], damping, -1.0, 0, 2, two, &pr)
-                        : ss_pr_create(shards[s], damping, eps, max_iter, k0[b + 1] - k0[b], n_topic + k0[b], &pr);
-            if (rc == SS_OK) sh[s].blk.push_back(pr);
-            if (rc == SS_OK && affine) rc = aff_attach(pr, aff[s], k_topics, n_topic, world);
-        }
-    if (rc == SS_OK) {
-        // the all-gather, by hand: every shard's slice into every shard's table, rank order
-        const bool wire_f32 = ctx->opt("pr.wire_f32", 0) != 0;
-        auto exchange = [&](int b, hipStream_t xs) -> int32_t {
-            if (wire_f32) {                                         // the float32 wire format, played by device-to-device copies
-                for (int src = 0; src < world; src++) {
-                    SS_HIP(ctx, wire_alloc(sh[src].blk[b]));
-                    wire_pack(sh[src].blk[b], xs);
-                }
-                for (int dst = 0; dst < world; dst++) {
-                    ss_pr* to = sh[dst].blk[b];
-                    for (int src = 0; src < world; src++) {
-                        ss_pr* from = sh[src].blk[b];
-                        SS_HIP(ctx, hipMemcpyAsync(to->wire_recv.p + (size_t)src * wire_floats(from), from->wire_send.p, wire_floats(from) * sizeof(float),
-                                                   hipMemcpyDeviceToDevice, xs));
-                    }
-                    wire_unpack(to, xs);
-                }
-                return SS_OK;
-            }
-            for (int dst = 0; dst < world; dst++)
-                for (int src = 0; src < world; src++) {
-                    ss_pr* from = sh[src].blk[b];
-                    ss_pr* to = sh[dst].blk[b];
-                    const size_t slice = (size_t)shards[src]->sl_nd * from->gw;
-                    SS_HIP(ctx, hipMemcpyAsync(to->tab0.p + (size_t)src * slice, from->send.p, slice * sizeof(double), hipMemcpyDeviceToDevice, xs));
-                }
-            return SS_OK;
-        };
-        if (affine) {
-            auto exchange_sums = [&](hipStream_t xs) -> int32_t {     // the K sums of every shard into every shard's table, rank order
-                for (int dst = 0; dst < world; dst++)
-                    for (int src = 0; src < world; src++)
-                        SS_HIP(ctx, hipMemcpyAsync(aff[dst].gath.p + (size_t)src * AFF_MAXK, aff[src].loc.p, (size_t)AFF_MAXK * sizeof(double),
-                                                   hipMemcpyDeviceToDevice, xs));
-                return SS_OK;
-            };
-            rc = run_affine_sharded(ctx, sh, aff, world, eps, max_iter, k_topics, exchange, exchange_sums, iters_out);
-        } else {
-            rc = run_pipelined(ctx, sh, max_iter, exchange, iters_out, k0);
-        }
-    }
-    // assemble [K][N] by original id
-    const uint64_t n = shards[0]->n;
-    for (int s = 0; s < world && rc == SS_OK && affine; s++) {
-        const size_t n_rows = (size_t)shards[s]->cnt_nd + shards[s]->cnt_d;
-        std::vector<uint32_t> ids(n_rows);
-        std::vector<double> part((size_t)k_topics * n_rows);
-        rc = local_ids(sh[s].blk[0], ids.data());
-        if (rc == SS_OK && n_rows) {
-            if (hipMemcpyAsync(part.data(), aff[s].out.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                rc = ctx->fail(SS_ERR_HIP, "ss_pagerank_run_group: copy of the ranks failed");
-        }
-        for (int k = 0; k < k_topics && rc == SS_OK; k++)
-            for (size_t i = 0; i < n_rows; i++) rank_out[(size_t)k * n + ids[i]] = part[(size_t)k * n_rows + i];
-    }
-    for (int s = 0; s < world && rc == SS_OK && !affine; s++) {
-        const size_t n_rows = (size_t)shards[s]->cnt_nd + shards[s]->cnt_d;
-        std::vector<uint32_t> ids(n_rows);
-        for (int b = 0; b < B && rc == SS_OK; b++) {
-            const int kb = k0[b + 1] - k0[b];
-            std::vector<double> part((size_t)kb * n_rows);
-            rc = ss_pr_read_local(sh[s].blk[b], ids.data(), part.data());
-            if (rc != SS_OK) break;
-            for (int k = 0; k < kb; k++)
-                for (size_t i = 0; i < n_rows; i++) rank_out[(size_t)(k0[b] + k) * n + ids[i]] = part[(size_t)k * n_rows + i];
-        }
-    }
-    for (auto& s : sh)
-        for (ss_pr* pr : s.blk) ss_pr_destroy(pr);
-    return rc;
-}
-
 int32_t ss_pr_status(ss_pr* pr, int32_t* iters_out, int32_t* n_active, int32_t* sweeps, double* last_delta_out,
                      double* last_total_out) {
     if (!pr) return SS_ERR_INVALID;
     ss_ctx* ctx = pr->g->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->pin_used = 0;
-    PrCtl* const hp = ctx->pin<PrCtl>();               // pinned: a read-back into pageable memory pins the page per call (ss_ctx::h_pin)
-    SS_HIP(ctx, hipMemcpyAsync(hp, pr->ctl.p, sizeof(PrCtl), hipMemcpyDeviceToHost, ctx->stream));
-    SS_TRY(ss::sync_bounded(ctx, ctx->stream, "ss_pr_status"));
+    const PrCtl* hp = nullptr;
+    SS_TRY(read_ctl(ctx, pr, ctx->stream, "ss_pr_status", &hp));
     const PrCtl h = *hp;
     if (h.stuck) return ctx->fail(SS_ERR_STATE, "ss_pr_status: the multi-sweep kernel gave up waiting between two sweeps (its grid of %u blocks was not resident: "
                                   "other kernels held the CUs for seconds); the state is void — set option pr.persistent = 0 and run again", pr->nblocks);
@@ -3140,111 +2104,6 @@ int32_t ss_pr_probe(ss_pr* pr, int32_t mode, int32_t n_reps, float* ms_out) {
     (void)hipEventDestroy(e1);
     SS_HIP(ctx, hipGetLastError());
     *ms_out = ms / (float)n_reps;
-    return SS_OK;
-}
-
-// ss_pagerank_run in the two-vector form (option "pr.affine" = 1; world 1, the reference's uniform teleport): every topic of the
-// reference's recurrence from TWO vectors (AffCtl).  One iteration = a copy of the stored vectors, one K = 2 sweep (k_pr_sweep_n<2>),
-// one streaming pass for the topics' L1 changes, the stop rule, and the write-out of the topics that have just stopped.
-static int32_t run_affine(ss_graph* g, double damping, double eps, int32_t max_iter, int32_t k_topics, const int32_t* n_topic,
-                          double* rank_out, int32_t* iters_out) {
-    ss_ctx* ctx = g->ctx;
-    hipStream_t st = ctx->stream;
-    if (k_topics > AFF_MAXK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pagerank_run (pr.affine): at most %d topics", AFF_MAXK);
-    for (int k = 0; k < k_topics; k++)
-        if (n_topic[k] < 1) return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run: n_topic[%d] < 1", k);
-    const int32_t two[2] = {1, 1};
-    ss_pr* pr = nullptr;
-    SS_TRY(ss_pr_create(g, damping, -1.0, 0, 2, two, &pr));
-    struct Guard { ss_pr* p; ~Guard() { ss_pr_destroy(p); } } guard{pr};
-    if (!pr->nwave || pr->gw != 2) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_pagerank_run (pr.affine): needs the wave-item K = 2 sweep (pr.narrow_wave / pr.force_narrow at their defaults)");
-    const uint32_t n_local = g->n_local();
-    ss::DevBuf<AffCtl> aff;
-    ss::DevBuf<double> x_prev, partials, d_out;
-    SS_HIP(ctx, aff.alloc(1));
-    SS_HIP(ctx, x_prev.alloc((size_t)n_local * 2));
-    SS_HIP(ctx, partials.alloc((size_t)AFF_NB * AFF_MAXK));
-    std::vector<AffCtl> h(1);
-    std::memset(h.data(), 0, sizeof(AffCtl));
-    for (int k = 0; k < k_topics; k++) { h[0].u[k] = 1.0 / (double)n_topic[k]; h[0].active[k] = 1; }   // pagerank.go:104
-    h[0].k_real = k_topics;
-    h[0].n_active = k_topics;
-    SS_HIP(ctx, hipMemcpyAsync(aff.p, h.data(), sizeof(AffCtl), hipMemcpyHostToDevice, st));
-    const double x0[MAXK] = {1.0, 0.0};                            // p = 1, q = 0: the start vector is u * 1
-    SS_HIP(ctx, hipMemcpyAsync(pr->x0.p, x0, sizeof(x0), hipMemcpyHostToDevice, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));                         // (h, x0: host temporaries)
-    pr->prm.aff = aff.p;
-    pr->prm.tele_col = pr->ctl.p->tele;
-    pr->prm.x_alt = x_prev.p;
-    // results: straight into the caller's array when it lives on the device
-    hipPointerAttribute_t at{};
-    const bool dev_out = hipPointerGetAttributes(&at, rank_out) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    double* out = rank_out;
-    if (!dev_out) {
-        SS_HIP(ctx, d_out.alloc((size_t)k_topics * g->n));
-        out = d_out.p;
-    }
-    SS_TRY(ss_pr_begin(pr));
-    const double n_zero = (double)((g->cnt_nd - pr->prm.pos_nd) + (g->cnt_d - pr->prm.pos_d));
-    int32_t n_active = k_topics, it = 0;
-    const int BATCH = 4;
-    while (n_active > 0) {
-        for (int b = 0; b < BATCH; b++) {
-            // sweep number `it` (from 0) reads x / x_alt (even / odd) and writes the other one
-            const double2* const x_old = reinterpret_cast<const double2*>((it & 1) ? x_prev.p : pr->x.p);
-            const double2* const x_new = reinterpret_cast<const double2*>((it & 1) ? pr->x.p : x_prev.p);
-            launch_step<2>(pr, st);
-            hipLaunchKernelGGL(k_aff_delta, dim3(AFF_NB), dim3(TPB), 0, st, x_old, x_new, (const AffCtl*)aff.p, g->sl_nd, pr->prm.pos_nd, pr->prm.pos_d, partials.p);
-            hipLaunchKernelGGL(k_aff_ctl, dim3(1), dim3(AFF_MAXK), 0, st, aff.p, pr->ctl.p, (const double*)partials.p, AFF_NB, n_zero, eps, max_iter, (size_t)AFF_MAXK);
-            hipLaunchKernelGGL(k_aff_emit, dim3((unsigned)std::min<uint64_t>(4096, ss::div_up(g->n, TPB))), dim3(TPB), 0, st, x_new, (const PrCtl*)pr->ctl.p,
-                               (const AffCtl*)aff.p, (const uint32_t*)g->new_id.p, g->n, g->sl_nd, pr->prm.pos_nd, pr->prm.pos_d, out);
-            it++;
-            if (max_iter > 0 && it >= max_iter) break;
-        }
-        SS_HIP(ctx, hipGetLastError());
-        SS_HIP(ctx, ss::fetch(ctx, st, &n_active, &aff.p->n_active, sizeof(int32_t)));
-        if (max_iter > 0 && it >= max_iter) break;                 // (the stop rule has closed every topic at max_iter)
-    }
-    SS_HIP(ctx, hipMemcpyAsync(h.data(), aff.p, sizeof(AffCtl), hipMemcpyDeviceToHost, st));
-    if (!dev_out) SS_HIP(ctx, hipMemcpyAsync(rank_out, d_out.p, (size_t)k_topics * g->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (iters_out)
-        for (int k = 0; k < k_topics; k++) iters_out[k] = h[0].iters[k];
-    return SS_OK;
-}
-
-int32_t ss_pagerank_run(ss_graph* g, double damping, double eps, int32_t max_iter, int32_t k_topics,
-                        const int32_t* n_topic, double* rank_out, int32_t* iters_out) {
-    if (!g) return SS_ERR_INVALID;
-    ss_ctx* ctx = g->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (g->world != 1) return ctx->fail(SS_ERR_STATE, "ss_pagerank_run: needs a (rank 0, world 1) graph");
-    if (k_topics < 1 || k_topics > SS_MAX_TOPICS || !n_topic || !rank_out)
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run: bad k_topics / NULL argument");
-    if (!(eps >= 0.0) && max_iter <= 0 && !(eps != eps))
-        return ctx->fail(SS_ERR_INVALID, "ss_pagerank_run: eps < 0 (never converges) needs max_iter > 0");
-    if (ctx->opt("pr.affine", 0) != 0) return run_affine(g, damping, eps, max_iter, k_topics, n_topic, rank_out, iters_out);
-    // topics are independent power iterations (pagerank.go:54-63): run them MAXK at a time
-    for (int k0 = 0; k0 < k_topics; k0 += MAXK) {
-        const int kk = std::min(MAXK, k_topics - k0);
-        ss_pr* pr = nullptr;
-        SS_TRY(ss_pr_create(g, damping, eps, max_iter, kk, n_topic + k0, &pr));
-        int32_t rc = ss_pr_begin(pr);
-        int32_t n_active = kk, sweeps = 0;
-        // the stop rule lives on the device; the host only looks every BATCH sweeps
-        // (launches after convergence are no-ops)
-        const int BATCH = 8;
-        while (rc == SS_OK && n_active > 0) {
-            int todo = BATCH;
-            if (max_iter > 0) todo = std::min(BATCH, std::max(1, max_iter - sweeps));
-            rc = ss_pr_step(pr, todo);
-            if (rc == SS_OK) rc = ss_pr_status(pr, iters_out ? iters_out + k0 : nullptr, &n_active, &sweeps, nullptr, nullptr);
-        }
-        if (rc == SS_OK) rc = ss_pr_read(pr, rank_out + (size_t)k0 * g->n);
-        ss_pr_destroy(pr);
-        if (rc != SS_OK) return rc;
-    }
     return SS_OK;
 }
 

@@ -1,0 +1,137 @@
+// pr_state.hpp — the PageRank state and everything of the PageRank path that crosses a translation unit: pagerank.hip (sweep kernels,
+// their launchers, ss_pr_create and the ss_pr_* stepping API) and pagerank_run.hip (the one-call drivers ss_pagerank_run*, the
+// two-vector kernels, float32 on the wire).  The work items and their constants (WorkItem, W_* / V_*, TPB, WAVES, CH, SEGW) come
+// from pr_plan.hpp, which has to stay free of device headers.  The kernel-side types live in an anonymous namespace, like
+// score_common.hpp's: every translation unit has its own copy of the device code.
+#pragma once
+#include "graph.hpp"
+#include "pr_plan.hpp"
+
+namespace {
+
+constexpr int MAXK = 16;
+
+struct PrCtl {
+    double S[MAXK];       // normaliser (`totalValue`) for the next sweep
+    double delta[MAXK];   // last L1 change
+    double csum[MAXK];    // last contribution sum (diagnostics)
+    double xz[MAXK];      // rank of EVERY row without in-edges (they all share one value per topic)
+    double xz_in[MAXK];   // topic-sensitive teleport only: that rank for the rows INSIDE the topic's teleport set (xz: outside)
+    double tele[MAXK];    // two-vector form only ("pr.affine"): the teleport of each COLUMN for the next sweep
+    int32_t active[MAXK];
+    int32_t iters[MAXK];
+    int32_t sweep;        // sweeps completed
+    int32_t n_active;
+    uint32_t ticket;      // last-group arrival counter
+    uint32_t stuck;       // k_pr_multi_n: a wait between two sweeps ran out of patience (the grid was not resident): the state is void
+    uint32_t gticket[8];  // last-block-of-a-group arrival counters
+};
+
+// The two-vector form of the reference's recurrence (option "pr.affine", opt-in; DESIGN K1b).  Every topic of pagerank.go:85-124 runs
+// the SAME linear map on the same graph and differs only in its start value u_k = 1/n_k (:104); with x = (p*u + q) / (r*u + s)
+// elementwise (p, q vectors over the nodes, r, s scalars) one iteration maps (p, q, r, s) to
+//     p' = M p + tau*r*1,  q' = M q + tau*s*1,  r' = W p + tau*N*r,  s' = W q + tau*N*s        (M: the inherited part, W: the sum of
+// the contributions, tau = 1 - d; iteration 1 adds the start vector: p += 1) — so TWO vectors carry every topic, whatever K is.
+// The state is kept scaled to r + s = 1.  Per-topic ranks, L1 changes and stop decisions are evaluated from (p, q, r) by streaming
+// kernels; a topic's ranks are written out in the iteration it stops.  Not the reference's float64 operation order: ranks agree
+// with the oracle to ~1e-13, iteration counts where the stop rule is not at a rounding tie.
+constexpr int AFF_MAXK = 256;
+constexpr unsigned AFF_NB = 512;  // blocks of k_aff_delta (their partial sums are added in a fixed order)
+struct AffCtl {
+    double u[AFF_MAXK];       // 1 / n_topic
+    double delta[AFF_MAXK];   // last L1 change of the topic
+    int32_t active[AFF_MAXK], iters[AFF_MAXK], just[AFF_MAXK];   // just: stopped in the iteration that has just been evaluated
+    double r_x, r_prev, r_next;      // r of the stored vectors, of the previous ones, of the next sweep's result
+    double s_x, s_prev, s_next;      // ... and s (the state is kept scaled to r + s = 1: s alone vanishes when d = 1)
+    double xz_prev[2];               // the edge-less rows' (p, q) before the last sweep
+    int32_t n_active, n_just, k_real, it;
+};
+
+struct PrParams {
+    const uint32_t* in_ptr;
+    const uint32_t* in_src;
+    const uint32_t* outdeg;
+    double* x;
+    const double* tab_rd[2];
+    double* tab_wr[2];
+    const WorkItem* work;
+    double* partials;     // [nblocks][2][GW]
+    double* segpart;      // [nsegs][GW]
+    uint32_t* rowticket;  // [n multi-segment rows]
+    PrCtl* ctl;
+    const double* x0;     // [GW] 1/n_topic
+    double d, teleport, eps, tele_n;
+    int32_t max_iter, k_topics, world;
+    uint32_t sl_nd, cnt_nd, sl_d, cnt_d, seg_edges, n_items;
+    uint32_t pos_nd, pos_d;   // rows WITH in-edges per class (they come first: rows are in-degree sorted)
+    // opt-in true topic-sensitive teleport (ss_pr_set_teleport; null = the reference's uniform teleport):
+    const uint32_t* memb;     // [n_local] bit k: the row's node is in topic k's teleport set
+    const double* tin;        // [MAXK] teleport of a member: (1-d) * N / |set_k|
+    const double* nz_in;      // [MAXK] rows without in-edges (this rank) inside topic k's set
+    uint32_t ts_mask;         // bit k: topic k has a teleport set (others keep the uniform teleport)
+    uint32_t zrow;            // index of the table's all-zero row (= nd_int): where the unused slots of a chunk gather from
+    const uint32_t* woff;     // k_pr_sweep: [waves][8]: wave w's items of class c are work[woff[8w+c] .. woff[8w+c+1])
+    uint32_t stagger_div;     // k_pr_sweep: blocks per arrival round (= CUs); 0 = every block walks the classes in the same order
+    uint32_t stagger_code;    // start classes of the rounds as base-6 digits (0 = round r starts at position r of the class order)
+    uint32_t class_order;     // k_pr_sweep: the order in which a wave walks its six work classes, 3 bits per position
+    uint32_t n_order;         // k_pr_sweep_n: the order of its four phases, 2 bits per position
+    double* x_alt;            // two-vector form: sweep s reads x (s even) / x_alt (s odd) and writes the other one; null otherwise
+    AffCtl* aff;              // two-vector form ("pr.affine"): its control block; null otherwise
+    const double* tele_col;   // ... and the per-column teleport (ctl->tele); null = the uniform p.teleport
+#ifdef SS_PR_EXP_KINDMASK
+    uint32_t kind_mask;       // experiment builds only: run just these work classes (bit = kind)
+#endif
+};
+
+}  // namespace
+
+struct ss_pr {
+    ss_graph* g = nullptr;
+    int gw = 1;            // lane-group width = padded topic count
+    ss::DevBuf<float> wire_send, wire_recv;   // option "pr.wire_f32": the contribution slice as float32 on the wire
+    bool nwave = false;    // K <= 2 on the wave-item kernel k_pr_sweep_n (gw = K; the work items are those of the 8-wide sweep)
+    int persist_mode = 1;  // 1: write-through hand-offs, 2: release / acquire fences around the wait
+    bool persist = false;  // ... with ss_pr_step's sweeps inside ONE launch (k_pr_multi_n): small graphs, whose sweep is mostly fixed cost
+    int k = 1;
+    PrParams prm{};
+    unsigned nblocks = 0;
+    ss::DevBuf<double> x, tab0, tab1, send, partials, segpart, x0;
+    ss::DevBuf<uint32_t> rowticket;
+    ss::DevBuf<uint32_t> memb;          // topic-sensitive teleport (optional)
+    ss::DevBuf<double> tin, nz_in;
+    ss::DevBuf<WorkItem> work;
+    ss::DevBuf<uint32_t> woff;          // k_pr_sweep: per-wave class offsets into work
+    ss::DevBuf<PrCtl> ctl;
+    bool begun = false;
+    bool need_finalize = false;   // world>1: a begin/step is waiting for its exchange + finalize
+    bool finalize_is_begin = false;
+};
+
+// (hidden: these cross translation units, not the library's boundary — the exported symbols stay those of include/spaghetti_rank.h)
+#pragma GCC visibility push(hidden)
+namespace ss {
+// pagerank.hip: launchers of its kernels; the kernel for the state's lane-group width (and teleport sets) is picked inside
+unsigned begin_blocks(const ss_pr* pr);                            // grid of k_pr_begin
+void pr_launch_begin(ss_pr* pr, hipStream_t st, unsigned nb);
+void pr_launch_step(ss_pr* pr, hipStream_t st);                    // one sweep
+void pr_launch_finalize(ss_pr* pr, hipStream_t st, int is_begin);  // world > 1: behind the exchange
+// pagerank_run.hip: float32 on the wire (option "pr.wire_f32")
+size_t pr_wire_floats(const ss_pr* pr);
+hipError_t pr_wire_alloc(ss_pr* pr);
+void pr_wire_pack(ss_pr* pr, hipStream_t st);
+void pr_wire_unpack(ss_pr* pr, hipStream_t st);
+}  // namespace ss
+#pragma GCC visibility pop
+
+namespace {
+// The state's control block, read back into the context's pinned scratch (a read-back into pageable memory pins the page per call:
+// ss_ctx::h_pin); waits for `st`, bounded where a collective may be in flight.  `what` names the wait in the error.
+inline int32_t read_ctl(ss_ctx* ctx, const ss_pr* pr, hipStream_t st, const char* what, const PrCtl** out) {
+    ctx->pin_used = 0;
+    PrCtl* const hp = ctx->pin<PrCtl>();
+    if (hipMemcpyAsync(hp, pr->ctl.p, sizeof(PrCtl), hipMemcpyDeviceToHost, st) != hipSuccess) return ctx->fail(SS_ERR_HIP, "%s: status read failed", what);
+    SS_TRY(ss::sync_bounded(ctx, st, what));
+    *out = hp;
+    return SS_OK;
+}
+}  // namespace

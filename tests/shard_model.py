@@ -127,7 +127,7 @@ class NumpyShardState:
 
 
 # ------------------------------------------------------------------------------------------------
-# CPU model of ONE shard of the TWO-VECTOR form on doc-range shards (library option "pr.affine", csrc/pagerank.hip
+# CPU model of ONE shard of the TWO-VECTOR form on doc-range shards (library option "pr.affine", csrc/pagerank_run.hip
 # run_affine_sharded): every topic's ranks are (p*u_k + q) / (r*u_k + s) with u_k = 1/n_k; the shards exchange the 2-wide
 # contribution slices and, per iteration, their K local L1 sums.  Same layout as NumpyShardState (k = 2, start vector (1, 0)).
 

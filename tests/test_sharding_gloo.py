@@ -108,7 +108,7 @@ def test_pipelined_topic_blocks_gloo_match_oracle(tmp_path, world):
     np.testing.assert_allclose(got["rank"], ref, rtol=1e-12)
 
 
-# ---- the two-vector form on doc-range shards (library option "pr.affine", csrc/pagerank.hip run_affine_sharded) ---------------------
+# ---- the two-vector form on doc-range shards (library option "pr.affine", csrc/pagerank_run.hip run_affine_sharded) ---------------------
 def _worker_affine(rank, world, port, n, e, n_topic, eps, max_iter, out_path, lag=True):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)

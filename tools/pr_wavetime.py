@@ -4,6 +4,8 @@ import os, sys
 import numpy as np, torch
 sys.path.insert(0, '.')
 from spaghettisearch_amd import engine, synth
+# where the variant build writes its two dumps (the library reads the same variable; default: the working directory)
+DUMP_DIR = os.environ.setdefault("SS_PR_WAVETIME_DIR", ".")
 dev = torch.device('cuda', 0)
 ctx = engine.Context(0)
 for kv in os.environ.get("OPTS", "").split(","):
@@ -15,8 +17,8 @@ pr = engine.PageRankState(g, 0.75, -1.0, synth.topic_sizes(n, kt), max_iter=0)
 pr.begin(); pr.step(5)
 pr.step(20); ctx.synchronize(); print("sweep ms", ctx.last_kernel_ms(0) / 20)
 pr.close(); g.close(); ctx.close()
-wt = np.loadtxt("gpurun_out/pr_wt.csv", delimiter=",", skiprows=1)
-ld = np.loadtxt("gpurun_out/pr_load.csv", delimiter=",", skiprows=1)
+wt = np.loadtxt(os.path.join(DUMP_DIR, "pr_wt.csv"), delimiter=",", skiprows=1)
+ld = np.loadtxt(os.path.join(DUMP_DIR, "pr_load.csv"), delimiter=",", skiprows=1)
 end = wt[:, 2]; load = ld[:, 1]
 print("waves", len(end), "end us: min %.0f mean %.0f max %.0f" % (end.min(), end.mean(), end.max()))
 print("modelled load: min %.1f mean %.1f max %.1f" % (load.min(), load.mean(), load.max()))
