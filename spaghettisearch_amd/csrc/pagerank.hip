@@ -16,6 +16,9 @@
 //   table [nd_int+1][GW]  contributions w_p of ALL non-dangling nodes, read by
 //                         random gather; written for the next sweep; the last row is
 //                         all zero (where the unused slots of a turn gather from)
+//                         ("pr.share_zero_rows", k_pr_sweep without teleport sets: the rows without in-edges are not
+//                          in the table — one shared row per distinct out-degree stands behind the zero row, and the
+//                          state's own copy of in_src names it: SharedRows in pr_plan.hpp)
 //                         (world==1: ping-pong pair; world>1: own slice -> `send`,
 //                          ss_pr_exchange all-gathers it into `table`)
 // One kernel per sweep (k_pr_sweep for K >= 3, k_pr_step for K <= 2 on large graphs).
@@ -767,6 +770,17 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
     c.act = ctl->active[c.t] != 0;
     c.x0 = sweep == 0 ? p.x0[c.t] : 0.0;      // Q4: iteration 1 accumulates onto 1/n
 
+    // The shared rows of the next sweep's table (p.share): what V_ZERO would store for a row of that out-degree, once per degree.
+    // Written by the grid's first threads in front of their items and added to nothing, so no partial sum changes its order.
+    if constexpr (!TS) {
+        if (p.n_shared) {
+            const double xz_out = c.act ? zero_row_rank(p, sweep, c.S, p.x0[c.t]) : ctl->xz[c.t];
+            const uint32_t nel = p.n_shared * (uint32_t)GW;        // (element i belongs to topic i % GW = c.t: TPB is a multiple of GW)
+            for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < nel; i += gridDim.x * TPB)
+                c.Tw[(size_t)(p.zrow + 1) * GW + i] = p.d * xz_out / (double)p.sh_deg[i / GW];   // pagerank.go:136
+        }
+    }
+
     // This wave's items: work[off[k] .. off[k+1]) for class k.  The host dealt the items to the waves so that every wave
     // gets the same number of turns (ss_pr_create); one loop per class, so that the register allocator sees each
     // pipeline on its own instead of the union of all of them.
@@ -807,6 +821,8 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
         const WorkItem w = p.work[item];
         // V_ZERO: non-dangling rows without in-edges: their rank is the shared value xz, only the next contribution
         // d*xz/outdeg has to be written (dangling ones need nothing at all); 16 rows per lane group and item at most
+        // (p.share: the table has no such rows — the contributions are only added up, in the same order)
+        const bool store = TS || !p.share;
         const bool ts = TS && p.memb && ((p.ts_mask >> c.t) & 1u);
         const double xz_out = c.act ? (ts ? zero_row_rank_ts(p, sweep, c.S, p.x0[c.t], 0.0) : zero_row_rank(p, sweep, c.S, p.x0[c.t])) : ctl->xz[c.t];
         const double xz_inn = ts ? (c.act ? zero_row_rank_ts(p, sweep, c.S, p.x0[c.t], p.tin[c.t]) : ctl->xz_in[c.t]) : xz_out;
@@ -823,7 +839,7 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
                 const uint32_t lrow = w.row + rr;
                 const double xz = ts && ((p.memb[lrow] >> c.t) & 1u) ? xz_inn : xz_out;
                 const double cc = p.d * xz / (double)od[i];                      // pagerank.go:136
-                NT_STORE(cc, &c.Tw[(size_t)lrow * GW + c.t]);
+                if (store) NT_STORE(cc, &c.Tw[(size_t)lrow * GW + c.t]);
                 c.csum += cc;                                                     // pagerank.go:137
             }
         }
@@ -1253,6 +1269,31 @@ __global__ void k_pr_item_ranges(WorkItem* __restrict__ work, uint32_t n_items, 
     work[i] = w;
 }
 
+// "pr.share_zero_rows": the state's copy of the in-edge stream.  A source without in-edges (>= pos_nd) becomes the shared row of its
+// out-degree (sh_deg is rising: a bisection), flag bits kept; every other word is copied.  One streaming pass at create time.
+__global__ __launch_bounds__(TPB) void k_pr_remap_src(const uint32_t* __restrict__ in_src, uint32_t* __restrict__ out, size_t n_edges, uint32_t pos_nd,
+                                                      uint32_t cnt_nd, const uint32_t* __restrict__ outdeg, const uint32_t* __restrict__ sh_deg,
+                                                      uint32_t n_shared, uint32_t zrow) {
+    for (size_t e = (size_t)blockIdx.x * TPB + threadIdx.x; e < n_edges; e += (size_t)gridDim.x * TPB) {
+        uint32_t w = NT_LOAD(&in_src[e]);
+        const uint32_t s = w & SRC_MASK;
+        if (s >= pos_nd) {
+            uint32_t row = zrow;                              // (a source outside the map — there is none — would add an exact 0.0)
+            if (s < cnt_nd && n_shared) {
+                const uint32_t od = outdeg[s];
+                uint32_t lo = 0, hi = n_shared;               // first j with sh_deg[j] >= od
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (sh_deg[mid] < od) lo = mid + 1; else hi = mid;
+                }
+                if (lo < n_shared && sh_deg[lo] == od) row = zrow + 1 + lo;
+            }
+            w = (w & ~SRC_MASK) | row;
+        }
+        NT_STORE(w, &out[e]);
+    }
+}
+
 // x0 = 1/n, first contributions and their sum (pagerank.go:103-106 + first :136-137)
 template <int GW>
 __global__ __launch_bounds__(TPB) void k_pr_begin(PrParams p) {
@@ -1261,6 +1302,9 @@ __global__ __launch_bounds__(TPB) void k_pr_begin(PrParams p) {
     const double x0 = p.x0[t];
     double* __restrict__ Tw = p.tab_wr[1];   // the table sweep 0 reads (tab_rd[0]) — see pr_make_params
     double csum = 0.0;
+    // (p.share: the first table's shared rows, as k_pr_sweep writes them for the later ones)
+    for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < p.n_shared * (uint32_t)GW; i += gridDim.x * TPB)
+        Tw[(size_t)(p.zrow + 1) * GW + i] = p.d * x0 / (double)p.sh_deg[i / GW];
     const size_t n_el = ((size_t)p.sl_nd + p.sl_d) * GW;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n_el; i += (size_t)gridDim.x * TPB) {
         const uint32_t lrow = (uint32_t)(i / GW);
@@ -1269,7 +1313,7 @@ __global__ __launch_bounds__(TPB) void k_pr_begin(PrParams p) {
         if (lrow < p.sl_nd) {
             double c = 0.0;
             if (real) c = p.d * x0 / (double)p.outdeg[lrow];
-            if (p.world == 1 || lrow + 2 < p.sl_nd) Tw[i] = c;   // world>1: last two rows are the tail
+            if ((p.world == 1 || lrow + 2 < p.sl_nd) && lrow < p.tab_rows) Tw[i] = c;   // world>1: last two rows are the tail
             csum += c;
         }
     }
@@ -1639,6 +1683,7 @@ void fill_params(ss_pr* pr, const Cut& cut, const PlanOptions& opt, double dampi
     p.pos_nd = cut.pos_nd;
     p.pos_d = cut.pos_d;
     p.zrow = (uint32_t)g->nd_int;
+    p.tab_rows = g->sl_nd;
     p.woff = pr->woff.p;
     p.stagger_div = opt.stagger != 0 ? (uint32_t)std::max(g->ctx->cu_count, 1) : 0u;
     p.stagger_code = opt.stagger >= 10 ? (uint32_t)(opt.stagger - 10) : 0u;
@@ -1662,6 +1707,43 @@ void trace_plan(const ss_pr* pr, const std::vector<WorkItem>& work, const std::v
             (unsigned long long)fnv1a(work.data(), work.size() * sizeof(WorkItem)), work.size(),
             (unsigned long long)fnv1a(woff.data(), woff.size() * sizeof(uint32_t)),
             (unsigned long long)fnv1a(su, sizeof(su), fnv1a(sd, sizeof(sd))), pr->nblocks);
+}
+
+// The contribution table(s) of a state, zeroed: `rows` rows including the all-zero row k_pr_sweep's unused slots gather from (never
+// written: the exchange and the sweeps stop in front of it).
+int32_t alloc_tables(ss_pr* pr, hipStream_t st, size_t rows) {
+    const ss_graph* g = pr->g;
+    ss_ctx* ctx = g->ctx;
+    const size_t GW = (size_t)pr->gw;
+    SS_HIP(ctx, pr->tab0.alloc(rows * GW));
+    SS_HIP(ctx, hipMemsetAsync(pr->tab0.p, 0, std::max<size_t>(pr->tab0.bytes(), 8), st));
+    if (g->world == 1) {
+        SS_HIP(ctx, pr->tab1.alloc(rows * GW));
+        SS_HIP(ctx, hipMemsetAsync(pr->tab1.p, 0, std::max<size_t>(pr->tab1.bytes(), 8), st));
+    } else {
+        SS_HIP(ctx, pr->send.alloc((size_t)g->sl_nd * GW));
+        SS_HIP(ctx, hipMemsetAsync(pr->send.p, 0, std::max<size_t>(pr->send.bytes(), 8), st));
+    }
+    return SS_OK;
+}
+// A state with shared rows back to the full table and the graph's own index stream (before ss_pr_begin: nothing is in the tables yet).
+int32_t unshare_rows(ss_pr* pr, hipStream_t st) {
+    if (!pr->prm.share) return SS_OK;
+    const ss_graph* g = pr->g;
+    SS_HIP(g->ctx, hipStreamSynchronize(st));
+    SS_TRY(alloc_tables(pr, st, (size_t)g->nd_int + 1));
+    pr->src_shared.release();
+    pr->sh_deg.release();
+    PrParams& p = pr->prm;
+    p.tab_rd[0] = pr->tab0.p; p.tab_wr[0] = pr->tab1.p;
+    p.tab_rd[1] = pr->tab1.p; p.tab_wr[1] = pr->tab0.p;
+    p.in_src = g->in_src.p;
+    p.sh_deg = nullptr;
+    p.n_shared = 0;
+    p.share = 0;
+    p.zrow = (uint32_t)g->nd_int;
+    p.tab_rows = g->sl_nd;
+    return SS_OK;
 }
 
 #ifdef SS_PR_WAVETIME
@@ -1742,16 +1824,11 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     // the large tables first: the device zeroes them (gigabytes at config 4) while the host builds and deals the work items below
     SS_HIP(ctx, pr->x.alloc_streaming(n_local * GW));
-    // + the all-zero row k_pr_sweep's unused slots gather from (never written: the exchange and the sweeps stop at nd_int)
-    SS_HIP(ctx, pr->tab0.alloc(((size_t)g->nd_int + 1) * GW));
-    SS_HIP(ctx, hipMemsetAsync(pr->tab0.p, 0, std::max<size_t>(pr->tab0.bytes(), 8), st));
-    if (g->world == 1) {
-        SS_HIP(ctx, pr->tab1.alloc(((size_t)g->nd_int + 1) * GW));
-        SS_HIP(ctx, hipMemsetAsync(pr->tab1.p, 0, std::max<size_t>(pr->tab1.bytes(), 8), st));
-    } else {
-        SS_HIP(ctx, pr->send.alloc((size_t)g->sl_nd * GW));
-        SS_HIP(ctx, hipMemsetAsync(pr->send.p, 0, std::max<size_t>(pr->send.bytes(), 8), st));
-    }
+    // Shared rows for the edge-less sources (option "pr.share_zero_rows", default on): a state on k_pr_sweep<GW, false> — one rank, not
+    // the two-vector form; teleport sets arrive later and take the state back to the full table (unshare_rows).  The table's size is
+    // then known only behind the plan (the out-degrees of the rows without in-edges come back from the device under the deal).
+    bool share = GW >= 8 && g->world == 1 && ctx->opt("pr.affine", 0) == 0 && ctx->opt("pr.share_zero_rows", 1) != 0;
+    if (!share) SS_TRY(alloc_tables(pr, st, (size_t)g->nd_int + 1));
 
     // the plan (pr_plan.hpp): rows cut into items, the grid, and for the wave-item kernels the items dealt to the grid's waves — the
     // items' turn counts come from the sorted in-degrees the graph keeps on the host, their edge ranges are filled in on the device
@@ -1759,6 +1836,18 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     const auto tc0 = t_now();
     const PlanOptions opt = plan_options(ctx, pr, n_local);
     Cut cut = cut_items(g->h_indeg_nd, g->h_indeg_d, g->sl_nd, GI, pr->nwave, opt);
+    // (share: the tail's out-degrees travel to pinned host memory while the items are dealt; no tail, nothing to share)
+    const uint32_t n_tail = g->cnt_nd - cut.pos_nd;
+    struct PinGuard { ss_ctx* c; void* p = nullptr; size_t cap = 0; ~PinGuard() { c->pin_free(p, cap); } } tail_od{ctx};
+    if (share && n_tail == 0) {
+        share = false;
+        SS_TRY(alloc_tables(pr, st, (size_t)g->nd_int + 1));
+    }
+    if (share) {
+        tail_od.p = ctx->pin_alloc((size_t)n_tail * sizeof(uint32_t), &tail_od.cap);
+        if (!tail_od.p) return ctx->fail(SS_ERR_OOM, "ss_pr_create: no pinned host memory for %u out-degrees", n_tail);
+        SS_HIP(ctx, hipMemcpyAsync(tail_od.p, g->outdeg.p + cut.pos_nd, (size_t)n_tail * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     const auto tc1 = t_now();
     const int per_cu = sweep_blocks_per_cu(pr);
     const auto tc1a = t_now();
@@ -1784,6 +1873,23 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     // the graph's build temporaries (ss_graph::late_free): its last kernels ran under the host work above
     g->settle();
     const auto tc2 = t_now();
+    SharedRows sh;
+    if (share) {
+        SS_HIP(ctx, hipStreamSynchronize(st));
+        const auto ts0 = t_now();
+        sh = plan_shared_rows(static_cast<const uint32_t*>(tail_od.p), n_tail, cut.pos_nd);
+        const auto ts1 = t_now();
+        SS_TRY(alloc_tables(pr, st, (size_t)sh.table_rows));
+        SS_HIP(ctx, pr->sh_deg.alloc(sh.deg.size()));
+        SS_HIP(ctx, hipMemcpyAsync(pr->sh_deg.p, sh.deg.data(), sh.deg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        SS_HIP(ctx, pr->src_shared.alloc(g->e_local));
+        if (g->e_local)
+            hipLaunchKernelGGL(k_pr_remap_src, dim3((unsigned)std::min<uint64_t>(ss::div_up(g->e_local, TPB), (uint64_t)ctx->cu_count * 16)), dim3(TPB), 0, st,
+                               (const uint32_t*)g->in_src.p, pr->src_shared.p, (size_t)g->e_local, cut.pos_nd, g->cnt_nd, (const uint32_t*)g->outdeg.p,
+                               (const uint32_t*)pr->sh_deg.p, (uint32_t)sh.deg.size(), sh.zrow);
+        if (trace) fprintf(stderr, "[pr trace]   shared rows: %u rows without in-edges -> %zu shared rows (host %.3f ms), table %llu rows\n", n_tail, sh.deg.size(),
+                           t_ms(ts0, ts1), (unsigned long long)sh.table_rows);
+    }
     SS_HIP(ctx, pr->partials.alloc(((size_t)std::max(pr->nblocks, ss::begin_blocks(pr)) + 8) * 2 * GW));   // block rows + 8 group rows
     SS_HIP(ctx, pr->segpart.alloc((size_t)std::max(cut.nsegs, 1u) * GW));
     SS_HIP(ctx, pr->rowticket.alloc(std::max(cut.nmulti, 1u)));
@@ -1806,6 +1912,15 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
                        (void*)pr->tab1.p, (void*)g->in_src.p, (void*)g->in_ptr.p, (void*)g->outdeg.p, (void*)pr->work.p, (void*)pr->woff.p);
 
     fill_params(pr, cut, opt, damping, eps, max_iter, k_topics);
+    if (share) {
+        PrParams& p = pr->prm;
+        p.in_src = pr->src_shared.p;
+        p.sh_deg = pr->sh_deg.p;
+        p.n_shared = (uint32_t)sh.deg.size();
+        p.share = 1;
+        p.zrow = sh.zrow;
+        p.tab_rows = cut.pos_nd;
+    }
     if (trace) trace_plan(pr, items, *woff);
 #ifdef SS_PR_EXP_KINDMASK
     pr->prm.kind_mask = getenv("SS_PR_KIND_MASK") ? (uint32_t)strtoul(getenv("SS_PR_KIND_MASK"), nullptr, 0) : 0xFFFFFFFFu;
@@ -1835,6 +1950,7 @@ int32_t ss_pr_set_teleport(ss_pr* pr, const uint64_t* set_ptr, const uint32_t* s
     }
     const ss_graph* g = pr->g;
     const int K = pr->k;
+    SS_TRY(unshare_rows(pr, st));                    // the teleport-set kernels keep a table row per row
     std::vector<uint64_t> h_ptr(K + 1);
     SS_HIP(ctx, ss::copy_in(ctx->stream, h_ptr.data(), set_ptr, (K + 1) * sizeof(uint64_t)));
     if (h_ptr[0] != 0) return ctx->fail(SS_ERR_INVALID, "ss_pr_set_teleport: set_ptr[0] != 0");
@@ -2083,7 +2199,13 @@ int32_t ss_pr_probe(ss_pr* pr, int32_t mode, int32_t n_reps, float* ms_out) {
     SS_HIP(ctx, hipEventCreate(&e0));
     SS_HIP(ctx, hipEventCreate(&e1));
     hipStream_t st = ctx->stream;
-    const double* T = pr->tab0.p;
+    // (the probe walks the GRAPH's index stream over a table of nd_int rows; a state with shared rows has a shorter one: a scratch table)
+    ss::DevBuf<double> full;
+    if (pr->prm.share) {
+        SS_HIP(ctx, full.alloc(((size_t)g->nd_int + 1) * pr->gw));
+        SS_HIP(ctx, hipMemsetAsync(full.p, 0, full.bytes(), ctx->stream));
+    }
+    const double* T = pr->prm.share ? full.p : pr->tab0.p;
     for (int r = 0; r < n_reps + 1; r++) {
         if (r == 1) SS_HIP(ctx, hipEventRecord(e0, st));          // first launch = warm-up
 #define SS_PROBE_LAUNCH(GWV, POLV) hipLaunchKernelGGL((k_pr_probe<GWV, POLV>), dim3(nb), dim3(TPB), 0, st, T, (const uint32_t*)g->in_src.p, (size_t)g->e_local, (uint32_t)g->nd_int, mode, sink.p, hot)

@@ -396,4 +396,41 @@ inline uint32_t pack_n_order(int64_t code) {
     return seen == 0xFu ? packed : (0u | 1u << 2 | 2u << 4 | 3u << 6);
 }
 
+// ---- shared table rows of the edge-less sources ("pr.share_zero_rows") ----------------------------------------------------------
+// A non-dangling row without in-edges holds the one rank all such rows share, so its contribution d * xz / outdeg depends on its
+// out-degree alone: the sweep's table keeps ONE row per distinct out-degree among them instead of one per row.  Layout of such a
+// table: rows [0, pos_nd) as ever (the rows with in-edges), the all-zero row at pos_nd, the shared rows behind it in rising degree.
+struct SharedRows {
+    std::vector<uint32_t> deg;      // the distinct out-degrees, rising: shared row j belongs to deg[j]
+    uint32_t zrow = 0;              // the all-zero row (= pos_nd)
+    uint32_t base = 0;              // first shared row (= pos_nd + 1)
+    uint64_t table_rows = 0;        // rows of one table buffer: pos_nd + 1 + deg.size()
+    // the table row of a source with out-degree `od`; the zero row for a degree that is not in the map
+    uint32_t row_of(uint32_t od) const {
+        const auto it = std::lower_bound(deg.begin(), deg.end(), od);
+        return it != deg.end() && *it == od ? base + (uint32_t)(it - deg.begin()) : zrow;
+    }
+};
+// `od`: the out-degrees of the n non-dangling rows without in-edges (table rows pos_nd .. pos_nd + n).  Any number of distinct
+// values: flags per value while the largest stays near n, a sort otherwise.
+inline SharedRows plan_shared_rows(const uint32_t* od, size_t n, uint32_t pos_nd) {
+    SharedRows sh;
+    uint32_t hi = 0;
+    for (size_t i = 0; i < n; i++) hi = std::max(hi, od[i]);
+    if (n && (uint64_t)hi <= 4 * (uint64_t)n + 65536) {
+        std::vector<unsigned char> seen((size_t)hi + 1, 0);
+        for (size_t i = 0; i < n; i++) seen[od[i]] = 1;
+        for (size_t v = 0; v <= hi; v++)
+            if (seen[v]) sh.deg.push_back((uint32_t)v);
+    } else if (n) {
+        sh.deg.assign(od, od + n);
+        std::sort(sh.deg.begin(), sh.deg.end());
+        sh.deg.erase(std::unique(sh.deg.begin(), sh.deg.end()), sh.deg.end());
+    }
+    sh.zrow = pos_nd;
+    sh.base = pos_nd + 1;
+    sh.table_rows = (uint64_t)pos_nd + 1 + sh.deg.size();
+    return sh;
+}
+
 }  // namespace

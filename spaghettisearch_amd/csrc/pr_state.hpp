@@ -78,6 +78,11 @@ struct PrParams {
     double* x_alt;            // two-vector form: sweep s reads x (s even) / x_alt (s odd) and writes the other one; null otherwise
     AffCtl* aff;              // two-vector form ("pr.affine"): its control block; null otherwise
     const double* tele_col;   // ... and the per-column teleport (ctl->tele); null = the uniform p.teleport
+    // shared rows of the edge-less sources (option "pr.share_zero_rows", k_pr_sweep<GW, false> only; pr_plan.hpp: SharedRows)
+    const uint32_t* sh_deg;   // [n_shared] the distinct out-degrees of the non-dangling rows without in-edges, rising
+    uint32_t n_shared;        // shared rows: table rows zrow + 1 .. zrow + n_shared
+    uint32_t share;           // 1: the table ends at pos_nd (+ zero row + shared rows) and in_src is the state's remapped copy
+    uint32_t tab_rows;        // rows of the table that belong to a local row of their own (share: pos_nd, otherwise sl_nd)
 #ifdef SS_PR_EXP_KINDMASK
     uint32_t kind_mask;       // experiment builds only: run just these work classes (bit = kind)
 #endif
@@ -101,6 +106,8 @@ struct ss_pr {
     ss::DevBuf<double> tin, nz_in;
     ss::DevBuf<WorkItem> work;
     ss::DevBuf<uint32_t> woff;          // k_pr_sweep: per-wave class offsets into work
+    ss::DevBuf<uint32_t> src_shared;    // "pr.share_zero_rows": the state's copy of in_src, sources without in-edges -> their shared row
+    ss::DevBuf<uint32_t> sh_deg;        // ... and the shared rows' out-degrees
     ss::DevBuf<PrCtl> ctl;
     bool begun = false;
     bool need_finalize = false;   // world>1: a begin/step is waiting for its exchange + finalize
