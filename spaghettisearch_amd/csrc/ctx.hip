@@ -319,7 +319,6 @@ static const char* const k_option_names[] = {
     "score.trace",          // 1: ss_score_topk prints the host phases of a call (copies in, plan, staging, launches) to stderr
     "pr.probe_hot",         // ss_pr_probe policies 3/4: rows below this index use the default cache policy
     "pr.topic_blocks",      // ss_pagerank_run_sharded: split K into this many topic blocks whose exchanges overlap the next block's sweep
-    "tfidf.fused",          // 0: weight + count pass, then a scatter over the weighted postings (round 3); default 1: count pass over the doc ids, weights multiplied inside the scatter
     "tfidf.blocks",         // workgroups of the bucketed magnitude pass (default 4096)
     "tfidf.bucket_shift",   // log2 docs per bucket (default 13, 14 beyond 33M docs)
     "tfidf.head_min_run",   // head lists (summed bucket-major in place): average postings per bucket run, 0 = off (default 64)
@@ -338,8 +337,6 @@ static const char* const k_option_names[] = {
                             //    (tests, A/B: a 1024-query tail batch is slower that way, 0.14 against 0.09 ms); 0: never.  Bit-identical hits (DESIGN K4c)
     "score.small_max_batch",// "score.small" = 2: longest call (queries) that may take k_score_small (default 64)
     "score.small_batch",    // 1 (with "score.small" = 2): longer calls with device outputs send their small queries to k_score_small too, on an internal stream, rows staged (default 0)
-    "score.debug_floor",    // EXPERIMENT, only in a library built with -DSS_EXP_FLOOR (tools/floor_exp.py; no effect in the product): 1 = every host-output call records its
-                            //    queries' k-th best FinalRank, and the next call of as many queries starts its filters from them (wrong hits if the batch changes)
     "score.small_cap",
     "score.pipeline",       // 0: every scoring kernel on the context's stream.  n >= 1: device-output batches that are all k_score_wave run k_wave_prep and
                             //    k_score_wave on one of n internal streams taken in turn (default 2, as include/spaghetti_rank.h says; at most 3) and

@@ -311,13 +311,8 @@ __device__ __forceinline__ void block_reduce_and_publish(const PrParams& p, doub
 
 // Streaming data (ranks, indices, next contributions) is touched once per sweep: mark it
 // non-temporal so that it does not push the randomly gathered table out of L2.
-#ifndef SS_PR_NO_NT
 #define NT_LOAD(p) __builtin_nontemporal_load(p)
 #define NT_STORE(v, p) __builtin_nontemporal_store(v, p)
-#else
-#define NT_LOAD(p) (*(p))
-#define NT_STORE(v, p) (*(p) = (v))
-#endif
 
 // ---- gather ------------------------------------------------------------------
 // T[row][t] addressed as table base (wave-uniform, scalar registers) + 32-bit byte offset: the contribution table of a rank
@@ -391,9 +386,6 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
 
     for (uint32_t item = blockIdx.x; item < p.n_items; item += gridDim.x) {
         const WorkItem w = p.work[item];
-#ifdef SS_PR_EXP_KINDMASK
-        if (!((p.kind_mask >> w.kind) & 1u)) continue;
-#endif
         if (w.kind == W_SEG) {
             // one block per segment of a long row
             const uint32_t lrow = w.row;
@@ -482,7 +474,7 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
 //   V_QUAD           one row per lane group, all rows of the item `nch` turns long (rows are in-degree sorted)
 //   V_DEG<R>         R rows of exactly D <= 16/R in-edges per lane group and turn, at fixed slots
 // Measured on the 10M/50M R-MAT, K=16 (MI355X): 1.41 ms per sweep for the block-per-item / flag-driven kernel this
-// replaces; every class alone was latency-bound (0.60 + 0.53 + 0.57 + 0.16 ms, tools/pr_kmask.sh).
+// replaces; every class alone was latency-bound (0.60 + 0.53 + 0.57 + 0.16 ms).
 
 // TS: the state holds teleport sets (ss_pr_set_teleport).  A kernel of its own, so that the reference's path carries no
 // membership loads (a load under a branch in finish_row makes the compiler drain the loads in flight: s_waitcnt vmcnt(0)).
@@ -740,11 +732,6 @@ __device__ __forceinline__ void deg_rows(SweepCtx<GW, TS>& c, const WorkItem* __
     }
 }
 
-#ifdef SS_PR_EXP_KINDMASK
-#define SS_PR_CLASS_ON(c) ((p.kind_mask >> (8 + (c))) & 1u)
-#else
-#define SS_PR_CLASS_ON(c) true
-#endif
 #ifndef SS_PR_MINW
 #define SS_PR_MINW 1
 #endif
@@ -810,13 +797,12 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
         c.slot = ln / GW;
     }
     switch (cls) {
-    case 0: if (SS_PR_CLASS_ON(0)) long_rows<GW>(c, p.work, off[0], off[1], lane); break;
-    case 1: if (SS_PR_CLASS_ON(1)) quad_rows<GW>(c, p.work, off[1], off[2]); break;
-    case 2: if (SS_PR_CLASS_ON(2)) deg_rows<GW, 2>(c, p.work, off[2], off[3]); break;
-    case 3: if (SS_PR_CLASS_ON(3)) deg_rows<GW, 4>(c, p.work, off[3], off[4]); break;
-    case 4: if (SS_PR_CLASS_ON(4)) deg_rows<GW, 8>(c, p.work, off[4], off[5]); break;
+    case 0: long_rows<GW>(c, p.work, off[0], off[1], lane); break;
+    case 1: quad_rows<GW>(c, p.work, off[1], off[2]); break;
+    case 2: deg_rows<GW, 2>(c, p.work, off[2], off[3]); break;
+    case 3: deg_rows<GW, 4>(c, p.work, off[3], off[4]); break;
+    case 4: deg_rows<GW, 8>(c, p.work, off[4], off[5]); break;
     default:
-    if (SS_PR_CLASS_ON(5))
     for (uint32_t item = off[5]; item < off[6]; item++) {
         const WorkItem w = p.work[item];
         // V_ZERO: non-dangling rows without in-edges: their rank is the shared value xz, only the next contribution
@@ -1004,7 +990,6 @@ __device__ __forceinline__ void sweep_n_body(const PrParams& p, const int sweep,
     switch ((p.n_order >> (2 * s4)) & 3u) {
     case 0: {
         // ---- V_SEG / V_ROWW: the wave strides the row's (piece's) edges, four gathers per lane in flight
-        if (SS_PR_CLASS_ON(0))
         for (uint32_t it = off[0]; it < off[1]; it++) {
             const WorkItem w = p.work[it];
             const uint32_t lrow = w.row;
@@ -1081,7 +1066,6 @@ __device__ __forceinline__ void sweep_n_body(const PrParams& p, const int sweep,
         // ---- V_QUAD: one row per 8-lane group; the rows of an item are all nch 16-edge turns long
         {
             const int gl = lane & 7, grp = lane >> 3;
-            if (SS_PR_CLASS_ON(1))
             for (uint32_t it = off[1]; it < off[2]; it++) {
                 const WorkItem w = p.work[it];
                 const uint32_t nq = (w.count + 7) / 8;
@@ -1130,7 +1114,6 @@ __device__ __forceinline__ void sweep_n_body(const PrParams& p, const int sweep,
     } break;
     case 2: {
         // ---- V_DEG (all three classes): rows of exactly D <= 8 in-edges, their edges contiguous from item.beg: one lane per row
-        if (SS_PR_CLASS_ON(2))
         for (uint32_t it = off[2]; it < off[5]; it++) {
             const WorkItem w = p.work[it];
             if (w.nseg <= 2) deg_lane_rows<KW, TS, 2, PS>(c, w, lane);          // (wave-uniform: most rows of a power-law graph)
@@ -1141,7 +1124,6 @@ __device__ __forceinline__ void sweep_n_body(const PrParams& p, const int sweep,
     } break;
     default: {
         // ---- V_ZERO: non-dangling rows without in-edges: their rank is the shared value, only the next contribution is written
-        if (SS_PR_CLASS_ON(5))
         for (uint32_t it = off[5]; it < off[6]; it++) {
             const WorkItem w = p.work[it];
             for (uint32_t r0 = 0; r0 < w.count; r0 += 64) {
@@ -1823,7 +1805,7 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     auto t_now = [] { return std::chrono::steady_clock::now(); };
     auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     // the large tables first: the device zeroes them (gigabytes at config 4) while the host builds and deals the work items below
-    SS_HIP(ctx, pr->x.alloc_streaming(n_local * GW));
+    SS_HIP(ctx, pr->x.alloc(n_local * GW));
     // Shared rows for the edge-less sources (option "pr.share_zero_rows", default on): a state on k_pr_sweep<GW, false> — one rank, not
     // the two-vector form; teleport sets arrive later and take the state back to the full table (unshare_rows).  The table's size is
     // then known only behind the plan (the out-degrees of the rows without in-edges come back from the device under the deal).
@@ -1922,15 +1904,6 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
         p.tab_rows = cut.pos_nd;
     }
     if (trace) trace_plan(pr, items, *woff);
-#ifdef SS_PR_EXP_KINDMASK
-    pr->prm.kind_mask = getenv("SS_PR_KIND_MASK") ? (uint32_t)strtoul(getenv("SS_PR_KIND_MASK"), nullptr, 0) : 0xFFFFFFFFu;
-    {
-        size_t cnt[16] = {0};
-        for (auto& it : items) cnt[it.kind & 15]++;
-        fprintf(stderr, "[pr] items: seg %zu wave %zu group %zu zero %zu | vseg %zu vroww %zu vquad %zu vdeg %zu vzero %zu; blocks %u\n", cnt[0], cnt[1], cnt[2], cnt[3],
-                cnt[8], cnt[9], cnt[10], cnt[11], cnt[12], pr->nblocks);
-    }
-#endif
     g->users++;
     *out = guard.release();
     return SS_OK;

@@ -83,9 +83,6 @@ struct PrParams {
     uint32_t n_shared;        // shared rows: table rows zrow + 1 .. zrow + n_shared
     uint32_t share;           // 1: the table ends at pos_nd (+ zero row + shared rows) and in_src is the state's remapped copy
     uint32_t tab_rows;        // rows of the table that belong to a local row of their own (share: pos_nd, otherwise sl_nd)
-#ifdef SS_PR_EXP_KINDMASK
-    uint32_t kind_mask;       // experiment builds only: run just these work classes (bit = kind)
-#endif
 };
 
 }  // namespace

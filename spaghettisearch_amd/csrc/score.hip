@@ -429,11 +429,7 @@ __device__ __forceinline__ void merge_query(const ScoreParams& p, const uint32_t
     DIAG_NOWX(t_g0);
     __syncthreads();
     if (FLAT) {
-#ifdef SSM_EXP_NOGATHER        // (timing experiments only: wrong results)
-        const uint32_t n = min(p.qc_cnt[q], 1u);
-#else
         const uint32_t n = p.qc_cnt[q];
-#endif
         DIAG_ADD(18, n);
         DIAG_ADD(17, 1);
         const size_t base = (size_t)p.slice_base[q] * k;
@@ -507,14 +503,8 @@ __device__ __forceinline__ void merge_query(const ScoreParams& p, const uint32_t
         }
         __syncthreads();
     }
-#ifdef SSM_EXP_NOSORT           // (timing experiments only: wrong results)
-    __syncthreads();
-    if (tid == 0) sc32[0] = min(sc32[0], (uint32_t)k);
-    __syncthreads();
-#else
     if (FLAT) topk_compact_net(tk, k);
     else topk_compact(tk, k);
-#endif
     const uint32_t n_out = sc32[0];
 
     // explain: TitleRank/BodyRank of the winners, re-derived from the posting lists
@@ -529,11 +519,7 @@ __device__ __forceinline__ void merge_query(const ScoreParams& p, const uint32_t
         // k_score_wave's queries have their combined lists: ONE search per (winner, term) finds the doc's body and title posting
         // side by side, and it runs through the skip index (4 bytes per 64 postings: cache-resident) and then inside one 512-byte
         // block, instead of two interpolation searches over the whole lists (the merge's searches were 58 of its 98 us)
-#ifdef SSM_EXP_NOEXPLAIN
-        for (uint32_t task = tid; task < 0 * nd; task += NT) {
-#else
         for (uint32_t task = tid; task < n_out * nd; task += NT) {
-#endif
             const uint32_t i = task / nd, l = task % nd;
             const uint64_t p0 = tm_p0[l], p1 = tm_p1[l];
             if (p1 == p0) continue;
@@ -719,12 +705,6 @@ __global__ __launch_bounds__(TPB, (TPB / 256) * SS_WGS_PER_CU) void k_score_slic
             if (floor_l > 0.0f) atomicMax(thr0_bits, __float_as_uint(floor_l));
         }
     }
-#ifdef SS_EXP_FLOOR      // variant build only (tools/floor_exp.py): a per-query floor handed in by the host
-    if (tid == 0 && p.q_floor && !exact_all && !Q.mask) {
-        const float f = p.q_floor[q];
-        if (f > 0.0f) atomicMax(thr0_bits, __float_as_uint(f));
-    }
-#endif
     __syncthreads();
     DIAG_NOW(t_s1);
     DIAG_ADD(6, t_s1 - t_k0);

@@ -35,7 +35,7 @@ struct CallArgs {
 // the options a call reads, each looked up once per call, in one place (a look-up builds a std::string key)
 constexpr int64_t OPT_UNSET = INT64_MIN;    // options whose default is computed from the batch
 struct ScoreOptions {
-    bool trace, timed, grade_slices, wave, pipeline_slices, separate_merge, debug_floor;
+    bool trace, timed, grade_slices, wave, pipeline_slices, separate_merge;
     int64_t pipeline, slice_target, wave_slice_target, wave_big_pct, wave_big_x100, wave_small_x100, wave_max_terms, wave_min_list,
         wave_share_pct, small, small_cap, small_batch, small_max_batch;
 };
@@ -62,9 +62,6 @@ ScoreOptions read_options(const ss_ctx* ctx) {
     o.small_cap = ctx->opt("score.small_cap", ss::score_small_cap());
     o.small_batch = ctx->opt("score.small_batch", 0);
     o.small_max_batch = ctx->opt("score.small_max_batch", 64);
-#ifdef SS_EXP_FLOOR
-    o.debug_floor = ctx->opt("score.debug_floor", 0) != 0;
-#endif
     return o;
 }
 
@@ -141,7 +138,7 @@ struct StagedBatch {
     int turn = 0;
     size_t plan_bytes = 0, res_rows = 0, res_bytes = 0;
     uint64_t set_stride = 0;
-    bool use_floor = false, one_copy = false;
+    bool one_copy = false;
     ScoreParams p{};
     ConstraintParams cp{};
 };
@@ -730,8 +727,8 @@ struct PlanWriter {
 };
 
 // THE list of the plan's sections: order, source, size, and whether the kernels see it.  Returns where k_score_small's table goes.
-unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const float* floor,
-                             ScoreParams& p, ConstraintParams& cp) {
+unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, ScoreParams& p,
+                             ConstraintParams& cp) {
     const size_t n_q = (size_t)in.n_q;
     const bool ph = pl.any_phrase;
     w.add(p.q_off, pl.qoff.data(), n_q + 1);
@@ -755,7 +752,6 @@ unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const Constra
     w.add(p.q_mask, in.mask.data(), in.any_mask ? n_q : 0, in.any_mask);
     w.add(cp.sets, cons.sets.data(), cons.sets.size());
     w.add(cp.terms, cons.terms.data(), cons.terms.size());
-    w.add(p.q_floor, floor, floor ? n_q : 0, floor != nullptr);
     return small_tab;
 }
 
@@ -898,15 +894,13 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
 
 // one pinned staging buffer (one H2D copy: enqueue), the workspaces, the kernel parameters
 int32_t stage_plan(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const Route& r,
-                   const ScoreOptions& opt, StagedBatch& sb, Stamps& t) {
-    sb.use_floor = opt.debug_floor && s->dbg_floor.size() == (size_t)in.n_q;     // (never in the product build: SS_EXP_FLOOR)
-    const float* const floor = sb.use_floor ? s->dbg_floor.data() : nullptr;
+                   StagedBatch& sb, Stamps& t) {
     PlanWriter measure;
-    plan_sections(measure, in, cons, pl, floor, sb.p, sb.cp);
+    plan_sections(measure, in, cons, pl, sb.p, sb.cp);
     sb.plan_bytes = measure.o;
     SS_TRY(acquire_turn(s, sb.plan_bytes, cons.sets.size(), sb));
     PlanWriter w{s->h_plan[sb.turn], s->d_plan2[sb.turn].p, 0};
-    unsigned char* tab = plan_sections(w, in, cons, pl, floor, sb.p, sb.cp);
+    unsigned char* tab = plan_sections(w, in, cons, pl, sb.p, sb.cp);
     // k_score_small's table: the 1024-slot queries first, then the larger ones (launch_score_small)
     for (const std::vector<SmallEnt>* v : {&pl.small_a, &pl.small_b})
         for (const SmallEnt& en : *v) {
@@ -1027,20 +1021,7 @@ int32_t enqueue(ss_scorer* s, const BatchInputs& in, const ConstraintPlan& cons,
 }
 
 // ---- 7. host outputs -------------------------------------------------------------------------------------------------------
-// experiment only: the next call of the same batch starts from these thresholds
-void capture_floor(ss_scorer* s, const CallArgs& a, const ScoreOptions& opt) {
-    if (!opt.debug_floor) return;                // (never in the product build: SS_EXP_FLOOR)
-    s->dbg_floor.assign((size_t)a.n_q, 0.0f);
-    for (int q = 0; q < a.n_q; q++)
-        if (a.n_hits_out[q] == a.k) {
-            const double f = a.hits_out[(size_t)q * a.k + (a.k - 1)].final;
-            float ff = (float)f;
-            if ((double)ff > f) ff = std::nextafterf(ff, -INFINITY);
-            if (ff > 0.0f && f == f) s->dbg_floor[q] = ff;
-        }
-}
-
-int32_t read_back(ss_scorer* s, const CallArgs& a, const ScoreOptions& opt, const StagedBatch& sb) {
+int32_t read_back(ss_scorer* s, const CallArgs& a, const StagedBatch& sb) {
     ss_ctx* ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const size_t n_q = (size_t)a.n_q;
@@ -1050,7 +1031,6 @@ int32_t read_back(ss_scorer* s, const CallArgs& a, const ScoreOptions& opt, cons
         SS_HIP(ctx, hipStreamSynchronize(st));
         std::memcpy(a.hits_out, hp1, sb.res_rows * sizeof(ss_hit));
         std::memcpy(a.n_hits_out, hp1 + sb.res_rows * sizeof(ss_hit), n_q * sizeof(int32_t));
-        capture_floor(s, a, opt);
         return SS_OK;
     }
     SS_HIP(ctx, hipMemcpyAsync(a.hits_out, s->d_hits.p, sb.res_rows * sizeof(ss_hit), hipMemcpyDefault, st));
@@ -1063,12 +1043,10 @@ int32_t read_back(ss_scorer* s, const CallArgs& a, const ScoreOptions& opt, cons
         SS_HIP(ctx, hipMemcpyAsync(hn, s->d_nhits.p, nh_bytes, hipMemcpyDeviceToHost, st));
         SS_HIP(ctx, hipStreamSynchronize(st));
         std::memcpy(a.n_hits_out, hn, nh_bytes);
-        capture_floor(s, a, opt);
         return SS_OK;
     }
     SS_HIP(ctx, hipMemcpyAsync(a.n_hits_out, s->d_nhits.p, nh_bytes, hipMemcpyDefault, st));
     SS_HIP(ctx, hipStreamSynchronize(st));
-    capture_floor(s, a, opt);
     return SS_OK;
 }
 
@@ -1098,7 +1076,7 @@ int32_t score_impl_inner(ss_scorer* s, const CallArgs& a) {
     t.planned = Clock::now();
     Route route = choose_route(plan, in.dev_out, opt);
     StagedBatch sb;
-    SS_TRY(stage_plan(s, a, in, cons, plan, route, opt, sb, t));
+    SS_TRY(stage_plan(s, a, in, cons, plan, route, sb, t));
     SS_TRY(enqueue(s, in, cons, plan, opt, route, sb, t));
     if (opt.trace) {
         auto us = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -1107,7 +1085,7 @@ int32_t score_impl_inner(ss_scorer* s, const CallArgs& a) {
                 us(t.uploaded, Clock::now()), route.pipe ? " (k_score_wave on the wave stream)" : "");
     }
     if (in.dev_out) return SS_OK;                // ordered on the ctx stream; ss_synchronize (or the stream's owner) waits
-    return read_back(s, a, opt, sb);
+    return read_back(s, a, sb);
 }
 
 // no C++ exception may cross the C ABI: host allocation failures come back as SS_ERR_OOM

@@ -534,9 +534,6 @@ template <int S_, int C_>
 __device__ __forceinline__ uint32_t block_add(uint32_t* sk, const WList& w, uint32_t dv, uint32_t b_lo, uint32_t span, int lane,
                                               u32x2 (&rec)[WDEPTH][WCW]) {
     ring_wait<(WCW - 1 - C_) + (WDEPTH - 1) * WCW>(rec[S_][C_]);
-#ifdef SSW_EXP_SKIPADD      // timing experiment only (wrong results): loads and waits, no filter work
-    return (rec[S_][C_].x == 0x12345678u) ? 0u : 4u * (uint32_t)WSK;
-#endif
     const uint32_t d = rl(dv, C_);
     const float cf = __uint_as_float(rl(__float_as_uint(w.coef_b), (int)(d & 15u)));      // one coefficient per list: title impacts are stored pre-scaled (k_merge_lists)
     const uint32_t doc = rec[S_][C_].x & 0x7FFFFFFFu;
@@ -825,9 +822,6 @@ __global__ __launch_bounds__(64, SSW_MINW) void k_score_wave(ScoreParams p, cons
     w.coef_b = coef_raw_b * C.fx_scale * (1.0f + 0x1p-20f);
     w.coef_t = coef_raw_t * C.fx_scale * (1.0f + 0x1p-20f);
     float thr0_f = __uint_as_float(wave_max(__float_as_uint(floor_l)));
-#ifdef SS_EXP_FLOOR      // variant build only (tools/floor_exp.py)
-    if (p.q_floor) thr0_f = fmaxf(thr0_f, p.q_floor[q]);
-#endif
     const uint64_t thr0_key = thr0_f > 0.0f ? fkey((double)thr0_f) : 0ull;
     C.tk = TopK{cd_key, cd_doc, &sc32[0], &sc64[0], reinterpret_cast<float*>(&sc32[2]), thr0_key, thr0_f > 0.0f ? thr0_f : -INFINITY, (uint32_t)WCB};
     if (lane == 0 && thr0_f > 0.0f) { sc64[0] = thr0_key; *reinterpret_cast<float*>(&sc32[2]) = thr0_f; }
@@ -963,9 +957,7 @@ __global__ __launch_bounds__(64, SSW_MINW) void k_score_wave(ScoreParams p, cons
                 PH_MARK(3, -);
                 const uint4 hv = *reinterpret_cast<const uint4*>(ghdr[ev_row]);
                 const uint32_t b_lo = rfl(hv.x), span = rfl(hv.y), n_blk = rfl(hv.w);
-#ifndef SSW_EXP_NOFLUSH
                 if (pend_n) wave_flush(lane, pend_n);
-#endif
                 pend_n = 0;
                 r0 = ev_row;                            // EV_FLUSH: the row has not been touched: it runs again
                 if (ev == EV_OVERFLOW) { slow_window(w, lane, ev_row, n_blk, b_lo, span, false); r0 = ev_row + 1; }
@@ -987,9 +979,7 @@ __global__ __launch_bounds__(64, SSW_MINW) void k_score_wave(ScoreParams p, cons
     WDIAG_ADD(7, pend_n);
     DIAG_NOW(t_ff0);
     PH_MARK(4, -);
-#if !defined(SSW_EXP_NOFINAL) && !defined(SSW_EXP_NOFLUSH)      // (timing experiments only: wrong results)
     if (pend_n) wave_flush(lane, pend_n);
-#endif
     DIAG_NOW(t_w2);
     PH_MARK(4, +); PH_MARK(5, -);
     WDIAG_ADD(20, t_w2 - t_ff0);

@@ -76,7 +76,6 @@ struct ss_scorer {
     // for the GPU, so the next call plans (and fills the other buffer) while this one's copy and kernels run
     unsigned char* h_plan[TURNS] = {};
     size_t h_plan_cap[TURNS] = {};
-    std::vector<float> dbg_floor;    // experiment "score.debug_floor": the k-th best FinalRank of every query of the last host-output call, rounded down
     unsigned char* h_res = nullptr;  // pinned landing block of small host results (one device-to-host copy for hits + counts)
     static constexpr size_t H_RES_BYTES = 128 << 10;
     hipEvent_t plan_ev[TURNS] = {}; // recorded after the H2D copy of the buffer (on the context's second stream)

@@ -144,11 +144,11 @@ __global__ __launch_bounds__(TPB) void k_weight(const uint64_t* __restrict__ ter
 // One float64 atomic per posting into a random 8-byte word of mag2 costs a memory-side read-modify-write each
 // (26 G/s on this part: 24.8 ms for the 641M-posting body table).  Instead the postings are partitioned once by
 // doc range ("bucket" = 2^shift consecutive docs) and every bucket is summed in LDS:
-//   k_weight_count   w = tf*idf in place; every block owns a contiguous range of postings and leaves its bucket histogram
-//                    as one column of a [bucket][block] count matrix
+//   k_weight_count   the count pass (doc ids only): every block owns a contiguous range of postings and leaves its bucket
+//                    histogram as one column of a [bucket][block] count matrix
 //   k_bucket_rowscan + k_bucket_offsets   exclusive scans: inside a bucket over the blocks, then over the buckets
 //   k_scatter        {doc, float32(w*w)} of every posting to its bucket's region (block claims a run per bucket,
-//                    LDS ticket per posting)
+//                    LDS ticket per posting); k_scatter<true> also computes w = tf*idf and writes it back in place
 //   k_bucket_sum     one workgroup per bucket: float64 LDS accumulators, sqrt, write mag
 // float32 squares summed in float64 are exact, so the order inside a bucket does not matter (same as the atomics).
 constexpr int NB_MAX = 4096;                 // most buckets (LDS histogram of a block)
@@ -273,31 +273,18 @@ __device__ __forceinline__ uint32_t head_first(const HeadArgs& h, uint32_t nh, u
     return lo;
 }
 
-// Pass 1.  Block b owns the contiguous postings [b*per, (b+1)*per) (per is a multiple of the chunk sizes of both passes):
-// WEIGHT: w = tf*idf in place; the block's bucket histogram is kept in LDS over its whole range and written ONCE, as column
-// b of the [bucket][block] count matrix — no global atomics (the first version added every block's counts of every touched
+// Pass 1: the count pass.  Block b owns the contiguous postings [b*per, (b+1)*per) (per is a multiple of the chunk sizes of both
+// passes) and reads their doc ids only: the block's bucket histogram is kept in LDS over its whole range and written ONCE, as
+// column b of the [bucket][block] count matrix — no global atomics (the first version added every block's counts of every touched
 // bucket to global counters and claimed its output runs the same way: ~150M returning atomics on ~1200 words, most of
 // the 9 ms the two passes took).
-constexpr int WIN = CH + 2;                   // term window of a chunk: a chunk of CH postings spans at most CH + 1 non-empty terms
-template <bool WEIGHT>
-__global__ __launch_bounds__(TPB) void k_weight_count(const uint64_t* __restrict__ term_ptr, uint64_t n_terms,
-                                                      const uint32_t* __restrict__ post_doc, float* __restrict__ post_w,
-                                                      const float* __restrict__ idf, uint64_t n_post, uint64_t per, int shift, uint32_t nb,
+// The kernel only counts: until round 4 it also multiplied w = tf*idf in place, which k_scatter<true> now does on its way through
+// the postings.  It keeps its name because the benchmark tells the TF-IDF kernels by their names.
+__global__ __launch_bounds__(TPB) void k_weight_count(const uint32_t* __restrict__ post_doc, uint64_t n_post, uint64_t per, int shift, uint32_t nb,
                                                       uint32_t nblk, uint32_t* __restrict__ mat, HeadArgs head) {
     __shared__ uint32_t s_hist[NB_MAX];
-    __shared__ uint32_t s_tp[WEIGHT ? WIN : 1];   // term_ptr[t0 + k] - base, clamped to [0, 2^32-1]: where the chunk's terms start
-    __shared__ uint64_t s_t0;
-    __shared__ uint32_t s_need;
     for (uint32_t b = threadIdx.x; b < nb; b += TPB) s_hist[b] = 0;
     const uint64_t r0 = (uint64_t)blockIdx.x * per, r1 = min(n_post, r0 + per);
-    if (WEIGHT && threadIdx.x == 0) {
-        uint64_t lo = 0, hi = n_terms;                                // largest t with term_ptr[t] <= r0 (once per block)
-        while (hi - lo > 1) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (term_ptr[mid] <= r0) lo = mid; else hi = mid;
-        }
-        s_t0 = lo;
-    }
     const uint32_t nh = head.n ? *head.n : 0u;
     uint32_t hcur = nh ? head_first(head, nh, r0) : 0u;
     __syncthreads();
@@ -306,50 +293,12 @@ __global__ __launch_bounds__(TPB) void k_weight_count(const uint64_t* __restrict
         const uint32_t n_here = (uint32_t)min((uint64_t)CH, r1 - base);
         if (nh) {
             head_skip(head, nh, hcur, base, hk);
-            if (hk.a_lo <= base && hk.a_hi >= base + n_here) {            // the whole chunk belongs to a head list: nothing to do here
-                if (WEIGHT) {
-                    __syncthreads();
-                    if (threadIdx.x == 0) s_t0 = head.term[hcur];         // where the next chunk's terms start
-                    __syncthreads();
-                }
-                continue;
-            }
+            if (hk.a_lo <= base && hk.a_hi >= base + n_here) continue;      // the whole chunk belongs to a head list: nothing to do here
         }
-        // every thread takes PER_THREAD CONSECUTIVE postings (vector loads), so it finds the term of its first posting
-        // once and walks from there; the chunk's term starts are staged in LDS relative to `base`
+        // every thread takes PER_THREAD CONSECUTIVE postings (vector loads)
         const uint32_t x0 = threadIdx.x * PER_THREAD;
-        uint32_t k = 0;
-        uint64_t t0 = 0;
-        if (WEIGHT) {
-            t0 = s_t0;                                                // term of posting `base` or an earlier one
-            if (threadIdx.x == 0) s_need = 0;
-            __syncthreads();
-            // coarse probe: how far do the chunk's terms reach?  thread q looks at term t0 + 1 + 16 q
-            {
-                const uint64_t t = t0 + 1 + (uint64_t)threadIdx.x * 16;
-                const uint64_t v = t <= n_terms ? term_ptr[t] : ~0ull;
-                if (v < base + n_here) atomicMax(&s_need, threadIdx.x + 1);
-            }
-            __syncthreads();
-            const uint32_t need = min((uint32_t)WIN, s_need * 16 + 18);   // window entries that can matter
-            for (uint32_t q = threadIdx.x; q < need; q += TPB) {
-                const uint64_t t = t0 + q;
-                const uint64_t v = t <= n_terms ? term_ptr[t] : ~0ull;
-                s_tp[q] = v <= base ? 0u : (v - base > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(v - base));
-            }
-            __syncthreads();
-            // largest k with s_tp[k] <= x0 (s_tp[0] = 0); a window that ends before the chunk does (runs of empty terms) is
-            // finished from global memory below
-            uint32_t lo = 0, hi = need;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_tp[mid] <= x0) lo = mid; else hi = mid;
-            }
-            k = lo;
-        }
         if (x0 < n_here) {
             uint32_t doc[PER_THREAD];
-            float w[PER_THREAD];
             const uint64_t i0 = base + x0;
             const bool full = x0 + PER_THREAD <= n_here;
             if (full) {
@@ -357,58 +306,18 @@ __global__ __launch_bounds__(TPB) void k_weight_count(const uint64_t* __restrict
                 for (int v4 = 0; v4 < PER_THREAD / 4; v4++) {
                     const uint4 d = *reinterpret_cast<const uint4*>(&post_doc[i0 + v4 * 4]);
                     doc[v4 * 4] = d.x; doc[v4 * 4 + 1] = d.y; doc[v4 * 4 + 2] = d.z; doc[v4 * 4 + 3] = d.w;
-                    if (WEIGHT) {
-                        const float4 f = *reinterpret_cast<const float4*>(&post_w[i0 + v4 * 4]);
-                        w[v4 * 4] = f.x; w[v4 * 4 + 1] = f.y; w[v4 * 4 + 2] = f.z; w[v4 * 4 + 3] = f.w;
-                    }
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < PER_THREAD; j++) {
                     const bool ok = x0 + j < n_here;
                     doc[j] = ok ? post_doc[i0 + j] : 0u;
-                    if (WEIGHT) w[j] = ok ? post_w[i0 + j] : 0.f;
                 }
-            }
-            if (WEIGHT) {
-                const uint32_t need = min((uint32_t)WIN, s_need * 16 + 18);
-                uint64_t t = t0 + k;
-#pragma unroll
-                for (int j = 0; j < PER_THREAD; j++) {
-                    const uint32_t x = x0 + j;
-                    if (x >= n_here) continue;
-                    if (nh && hk.hit(i0 + j)) continue;                  // head posting: weighted by k_bucket_sum (w[j] goes back as it came)
-                    while (k + 1 < need && s_tp[k + 1] <= x) k++;
-                    t = t0 + k;
-                    if (k + 1 >= need) {                              // past the staged window: rare (long runs of empty terms)
-                        uint64_t lo = t, hi = n_terms;
-                        const uint64_t i = i0 + j;
-                        if (term_ptr[hi] <= i) lo = hi;
-                        while (hi - lo > 1) {
-                            const uint64_t mid = (lo + hi) >> 1;
-                            if (term_ptr[mid] <= i) lo = mid; else hi = mid;
-                        }
-                        t = lo;
-                    }
-                    w[j] = w[j] * idf[t];                             // term_weighting.go:42
-                }
-                if (full) {
-#pragma unroll
-                    for (int v4 = 0; v4 < PER_THREAD / 4; v4++)
-                        *reinterpret_cast<float4*>(&post_w[i0 + v4 * 4]) = make_float4(w[v4 * 4], w[v4 * 4 + 1], w[v4 * 4 + 2], w[v4 * 4 + 3]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < PER_THREAD; j++)
-                        if (x0 + j < n_here) post_w[i0 + j] = w[j];
-                }
-                // the thread holding the chunk's last posting knows where the next chunk's terms start
-                if (x0 + PER_THREAD >= n_here) s_t0 = t;
             }
 #pragma unroll
             for (int j = 0; j < PER_THREAD; j++)
                 if (x0 + j < n_here && !(nh && hk.hit(i0 + j))) atomicAdd(&s_hist[doc[j] >> shift], 1u);
         }
-        if (WEIGHT) __syncthreads();                                  // s_t0 / s_tp are rewritten by the next chunk
     }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nb; b += TPB) mat[(size_t)b * nblk + blockIdx.x] = s_hist[b];
@@ -497,11 +406,7 @@ inline size_t scatter_lds_bytes(uint32_t nbt) { return (size_t)SC_CH * 8 + (size
 // bytes; the count pass in front of this kernel now reads doc ids only).  A thread takes SC_PT CONSECUTIVE postings, finds the
 // term of its first one in the chunk's term window (term starts relative to the chunk and their idf, staged in the LDS that holds
 // the sorted records later in the chunk) and walks on from there.
-#ifdef SS_SC_NO_NT
-#define SC_NT_LOAD(p) (*(p))
-#else
 #define SC_NT_LOAD(p) __builtin_nontemporal_load(p)
-#endif
 #ifdef SS_SC_PHASES
 // variant build (tools/build_variant.sh scph -DSS_SC_PHASES): cycles wave 0 of every block spends in each phase of a chunk, summed over
 // the grid and printed by the build (s_memtime; the kernel's time is unchanged within 1 %)
@@ -644,11 +549,6 @@ __global__ __launch_bounds__(SC_TPB, SS_SC_MINW) void k_scatter(const uint32_t* 
             loads(base + SC_CH);
             continue;
         }
-#if defined(SS_EXP_SC) && SS_EXP_SC == 3      // timing experiments only (wrong results): loads alone
-        if (doc[0] == 0x12345678u) out[0] = make_uint2(0u, __float_as_uint(w[0]));
-        loads(base + SC_CH);
-        continue;
-#endif
         if (WEIGHT) {
             // (0) the chunk's term window, then w = tf * idf (term_weighting.go:42) for this thread's postings, written back in place
             const uint32_t n_here = (uint32_t)min((uint64_t)SC_CH, r1 - base);
@@ -729,15 +629,11 @@ __global__ __launch_bounds__(SC_TPB, SS_SC_MINW) void k_scatter(const uint32_t* 
 #pragma unroll
                     for (int v4 = 0; v4 < SC_PT / 4; v4++)
                     {
-#ifdef SS_SC_W_PLAIN_STORE
-                        *reinterpret_cast<float4*>(&post_w[i0 + v4 * 4]) = make_float4(w[v4 * 4], w[v4 * 4 + 1], w[v4 * 4 + 2], w[v4 * 4 + 3]);
-#else
                         // (streamed out, never read again here: non-temporal, so that the weights do not push the half-written lines of
                         //  the block's bucket runs out of the L2)
                         typedef float f4s_t __attribute__((ext_vector_type(4)));
                         f4s_t wv; wv.x = w[v4 * 4]; wv.y = w[v4 * 4 + 1]; wv.z = w[v4 * 4 + 2]; wv.w = w[v4 * 4 + 3];
                         __builtin_nontemporal_store(wv, reinterpret_cast<f4s_t*>(&post_w[i0 + v4 * 4]));
-#endif
                     }
                 } else if (any) {
 #pragma unroll
@@ -829,10 +725,6 @@ __global__ __launch_bounds__(SC_TPB, SS_SC_MINW) void k_scatter(const uint32_t* 
         }
         __syncthreads();
         SC_PH(4);
-#if defined(SS_EXP_SC) && SS_EXP_SC == 2      // ... loads, count and scan
-        loads(base + SC_CH);
-        continue;
-#endif
         // (3) records to their staging positions
 #pragma unroll
         for (int j = 0; j < SC_PT; j++) {
@@ -849,14 +741,6 @@ __global__ __launch_bounds__(SC_TPB, SS_SC_MINW) void k_scatter(const uint32_t* 
         // (4) out, in staging order: consecutive lanes write consecutive records of a bucket's run
         // (the staged records end where the last bucket's run ends; head postings were never staged)
         const uint32_t n_staged = s_nstaged;
-#if defined(SS_EXP_SC) && SS_EXP_SC == 1      // ... everything but the stores
-        if (n_staged == 0x12345678u) out[0] = L_rec[0];
-        continue;
-#endif
-#if defined(SS_EXP_SC) && SS_EXP_SC == 4      // ... the stores as one coalesced stream (what perfectly joined bucket runs would cost)
-        for (uint32_t pos = threadIdx.x; pos < n_staged; pos += SC_TPB) out[base + pos] = L_rec[pos];
-        continue;
-#endif
         for (uint32_t pos = threadIdx.x; pos < n_staged; pos += SC_TPB) {
             const uint2 r = L_rec[pos];
             const uint32_t b = r.x >> shift;
@@ -1091,13 +975,9 @@ void bucket_pass_launch(ss_index* idx, hipStream_t st, BucketPass& bp, bool weig
                            (const uint64_t*)bp.h_hs.p, (const uint64_t*)bp.h_he.p, bp.shift, bp.nb, bp.h_bounds.p);
         head = HeadArgs{bp.h_n.p, bp.h_term.p, bp.h_hs.p, bp.h_he.p, bp.h_bounds.p};
     }
-    // the count pass reads doc ids only; the weights are multiplied by k_scatter<true> on its way through the postings (option
-    // "tfidf.fused" = 0: the round-3 order — weight + count, then a scatter that reads the weighted postings again)
-    const bool fused = weight && idx->ctx->opt("tfidf.fused", 1) != 0;
-    if (weight && !fused) hipLaunchKernelGGL(k_weight_count<true>, dim3(bp.nblk), dim3(TPB), 0, st, idx->term_ptr.p, T, idx->post_doc.p, idx->post_w.p,
-                                             idf, P, bp.per, bp.shift, bp.nb, bp.nblk, bp.mat.p, head);
-    else hipLaunchKernelGGL(k_weight_count<false>, dim3(bp.nblk), dim3(TPB), 0, st, idx->term_ptr.p, T, idx->post_doc.p, idx->post_w.p,
-                            idf, P, bp.per, bp.shift, bp.nb, bp.nblk, bp.mat.p, head);
+    // the count pass reads doc ids only; the weights are multiplied by k_scatter<true> on its way through the postings
+    hipLaunchKernelGGL(k_weight_count, dim3(bp.nblk), dim3(TPB), 0, st, (const uint32_t*)idx->post_doc.p, P, bp.per, bp.shift, bp.nb, bp.nblk,
+                       bp.mat.p, head);
     hipLaunchKernelGGL(k_bucket_rowscan, dim3(bp.nb), dim3(64), 0, st, bp.mat.p, bp.nblk, bp.cnt.p);
     hipLaunchKernelGGL(k_bucket_offsets, dim3(1), dim3(1024), 0, st, bp.cnt.p, bp.nb, bp.off.p, bp.cur.p);
     // (the owner threads' cursor registers are sized by the buckets per thread: 2 up to 1024 buckets, 4 up to 2048, 8 beyond)
@@ -1105,7 +985,7 @@ void bucket_pass_launch(ss_index* idx, hipStream_t st, BucketPass& bp, bool weig
     hipLaunchKernelGGL((k_scatter<W, B>), dim3(bp.nblk), dim3(SC_TPB), scatter_lds_bytes(bp.nbt), st, (const uint32_t*)idx->post_doc.p, idx->post_w.p, P, \
                        bp.per, bp.shift, bp.nb, bp.nblk, bp.bpt, bp.nbt, (const uint32_t*)bp.mat.p, (const uint32_t*)bp.off.p, bp.packed.p, head,   \
                        (const uint64_t*)idx->term_ptr.p, T, idf)
-    if (fused) {
+    if (weight) {
         if (bp.bpt <= 2) SS_SCATTER_LAUNCH(true, 2); else if (bp.bpt <= 4) SS_SCATTER_LAUNCH(true, 4); else SS_SCATTER_LAUNCH(true, SC_BPT_MAX);
     } else {
         if (bp.bpt <= 2) SS_SCATTER_LAUNCH(false, 2); else if (bp.bpt <= 4) SS_SCATTER_LAUNCH(false, 4); else SS_SCATTER_LAUNCH(false, SC_BPT_MAX);

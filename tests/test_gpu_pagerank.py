@@ -305,6 +305,14 @@ def test_option_names_are_checked(ss_ctx):
     ss_ctx.set_option("pr.force_narrow", None)
 
 
+@pytest.mark.parametrize("name, value", [("score.debug_floor", 1), ("tfidf.fused", 0)])
+def test_removed_experiment_options_are_unknown(ss_ctx, name, value):
+    # the threshold-floor experiment and the two-pass TF-IDF order left the library: their option names are refused like any unknown one
+    from spaghettisearch_amd import SpaghettiError
+    with pytest.raises(SpaghettiError):
+        ss_ctx.set_option(name, value)
+
+
 def test_bad_input_is_rejected(ss_ctx):
     from spaghettisearch_amd import SpaghettiError, engine
     ptr = np.array([0, 1, 2], dtype=np.uint64)
