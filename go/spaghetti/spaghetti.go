@@ -387,6 +387,34 @@ func (ix *Index) SetWeighted(mag []float64) {
 	check(ix.ctx, C.ss_index_set_weighted(ix.h, f64p(mag)), "ss_index_set_weighted")
 }
 
+// BuildDocView builds the doc-major view of the table as it stands (ss_index_build_doc_view): which terms a doc holds, with their
+// current weights.  A snapshot: TfIdfBuild, ApplyDelta and Resize free it.  8 bytes per posting + 8 per doc of device memory.
+func (ix *Index) BuildDocView() {
+	check(ix.ctx, C.ss_index_build_doc_view(ix.h), "ss_index_build_doc_view")
+}
+func (ix *Index) DropDocView() {
+	check(ix.ctx, C.ss_index_drop_doc_view(ix.h), "ss_index_drop_doc_view")
+}
+
+// DocTopTerms returns the m heaviest terms of every doc (weight descending, then term id; NaN last) and their weights:
+// what the reference keeps per page as Words_mapping cut by sortMap (retrieval/util.go:116-149).  Needs BuildDocView.
+func (ix *Index) DocTopTerms(docs []uint32, m int) ([][]uint32, [][]float32) {
+	if len(docs) == 0 {
+		return nil, nil
+	}
+	terms := make([]uint32, len(docs)*m)
+	w := make([]float32, len(docs)*m)
+	n := make([]int32, len(docs))
+	check(ix.ctx, C.ss_index_doc_top_terms(ix.h, C.uint64_t(len(docs)), u32p(docs), C.int32_t(m), u32p(terms), f32p(w), i32p(n)),
+		"ss_index_doc_top_terms")
+	outT, outW := make([][]uint32, len(docs)), make([][]float32, len(docs))
+	for i := range docs {
+		outT[i] = terms[i*m : i*m+int(n[i])]
+		outW[i] = w[i*m : i*m+int(n[i])]
+	}
+	return outT, outW
+}
+
 func (c *Ctx) NewScorer(title, body *Index) *Scorer {
 	var h *C.ss_scorer
 	check(c, C.ss_scorer_create(c.h, title.h, body.h, &h), "ss_scorer_create")
@@ -414,6 +442,31 @@ func (s *Scorer) ScoreTopKMasked(qPtr, qTerms, pPtr, pTerms []uint32, queryLen [
 	rc := C.ss_score_topk_masked(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), u32p(pPtr), u32p(pTerms), i32p(queryLen),
 		f64p(topicProbs), i32p(maskID), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
 	if err := statusErr(s.ctx, rc, "ss_score_topk_masked"); err != nil {
+		return nil, err
+	}
+	out := make([][]Hit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Hit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*k+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
+// SimilarTopK answers "similar pages": row q = the top k of the query made of seed doc q's m heaviest body terms, without the seed
+// itself (ss_similar_topk).  maskID as in ScoreTopKMasked (nil = none).  The body table needs its doc view (Index.BuildDocView).
+func (s *Scorer) SimilarTopK(seeds []uint32, m int, topicProbs []float64, maskID []int32, k int) ([][]Hit, error) {
+	nq := len(seeds)
+	if nq == 0 {
+		return nil, nil
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	rc := C.ss_similar_topk(s.h, C.int32_t(nq), u32p(seeds), C.int32_t(m), f64p(topicProbs), i32p(maskID), C.int32_t(k),
+		(*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	if err := statusErr(s.ctx, rc, "ss_similar_topk"); err != nil {
 		return nil, err
 	}
 	out := make([][]Hit, nq)

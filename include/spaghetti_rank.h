@@ -36,7 +36,8 @@ extern "C" {
  * internal wave streams and ss_last_kernel_ms(1) is the device time of the last scoring call's kernels on the stream that
  * carries its merge.  A binding checks ss_abi_version() == SS_ABI_VERSION at load.
  * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists);
- * ss_score_topk_constrained (required and excluded query terms). */
+ * ss_score_topk_constrained (required and excluded query terms); ss_index_build_doc_view / _drop_doc_view / _read_doc_view,
+ * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages"). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -309,6 +310,32 @@ int32_t ss_index_read(ss_index* idx, uint64_t* term_ptr_out /*[n_terms+1]*/, uin
 /* the positional postings as they stand (each nullable): pos_ptr_out [n_post+1], pos_out [pos_ptr[n_post]] */
 int32_t ss_index_read_positions(ss_index* idx, uint64_t* pos_ptr_out, float* pos_out);
 
+/* Doc-major view of a table: which terms does doc d hold?  (The tables are term-major; the reference keeps a page's words on the Go
+ * side, Words_mapping, cut to the five heaviest by sortMap, retrieval/util.go:116-149, and walks a page's old words to delete
+ * its postings, indexer.go:494-531.)  The view holds doc_ptr u64[n_docs+1] | doc_term u32[n_post] | doc_w f32[n_post]: row d =
+ * doc_term / doc_w [doc_ptr[d] .. doc_ptr[d+1]) lists the terms that have a posting of d in ASCENDING TERM ID, each with the
+ * posting's weight as it stands when the view is built (tf before ss_tfidf_build, tf*idf after).  It is a snapshot and a pure
+ * function of the table: two builds give identical bytes.  Resident size 8 bytes per posting + 8 per doc; the build needs about
+ * as much again for its temporaries, which are freed before the call returns.  Building where a view exists replaces it: the old
+ * view is freed FIRST (so that the peak does not grow by another 8 bytes per posting), and a build that fails (SS_ERR_OOM,
+ * SS_ERR_HIP) leaves the table WITHOUT a view, not with the old one.
+ * Every call that changes postings or weights frees the view: ss_tfidf_build, ss_index_apply_delta(_pos), ss_index_resize (and
+ * ss_index_destroy); ss_index_set_weighted and ss_index_set_doc_freq change neither and leave it.  Without a view
+ * ss_index_drop_doc_view, ss_index_read_doc_view, ss_index_doc_top_terms and ss_similar_topk return SS_ERR_STATE.
+ * A table of 2^32 postings or more is SS_ERR_UNSUPPORTED (the build indexes postings with 32 bits).  The calls wait for their
+ * work: the view is complete, and host outputs are there, when they return. */
+int32_t ss_index_build_doc_view(ss_index* idx);
+int32_t ss_index_drop_doc_view(ss_index* idx);
+/* the view as it stands: doc_ptr_out [n_docs+1], doc_term_out [n_post], doc_w_out [n_post], each nullable, host or device */
+int32_t ss_index_read_doc_view(ss_index* idx, uint64_t* doc_ptr_out, uint32_t* doc_term_out, float* doc_w_out);
+/* The heaviest terms of docs[0 .. n): row i of terms_out [n][m] / w_out [n][m] (nullable) holds the first n_out[i] = min(m, row
+ * length) entries of docs[i]'s view row in the order: weight descending as float32 VALUES (-0.0 and +0.0 are equal), then
+ * ascending term id; NaN weights last, among themselves by term id.  Selection and copying only: the weights are the stored
+ * bits.  Entries past n_out[i] are left untouched.  1 <= m <= SS_MAX_QUERY_TERMS and every doc id < n_docs, else SS_ERR_INVALID
+ * before anything is enqueued; a doc may appear more than once.  Pointers host or device. */
+int32_t ss_index_doc_top_terms(ss_index* idx, uint64_t n, const uint32_t* docs /*[n]*/, int32_t m,
+                               uint32_t* terms_out /*[n][m]*/, float* w_out /*[n][m] nullable*/, int32_t* n_out /*[n]*/);
+
 /* ---- scoring: retrieval/main_retrieve.go:50-103, get_metadata.go:31-69 -- */
 int32_t ss_scorer_create(ss_ctx* ctx, ss_index* title, ss_index* body, ss_scorer** out);
 int32_t ss_scorer_destroy(ss_scorer* s);
@@ -401,6 +428,20 @@ int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_p
                                   const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
                                   const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
                                   int32_t k, ss_hit* hits_out, int32_t* n_hits_out);
+
+/* Similar pages: the heaviest body terms of a page as a new query.  No reference counterpart (the reference ships the material:
+ * every Rank_combined carries the page's five heaviest words).  Query q = the ss_index_doc_top_terms row of seeds[q] (a doc id)
+ * in the BODY table's view with this m, in that order; query_len = its term count.  R = the row ss_score_topk_masked returns for
+ * that query with k + 1, topic_probs[q] and mask_id[q] (mask_id NULL: ss_score_topk).  Output row q = R without the hit whose doc
+ * is seeds[q] if it is there, cut to k: n_hits = min(k, |R| - [seed in R]); a seed without body postings gives an empty row.
+ * 1 <= k <= SS_MAX_TOPK - 1 (beyond: SS_ERR_UNSUPPORTED; k < 1 is SS_ERR_INVALID as in ss_score_topk), 1 <= m <=
+ * SS_MAX_QUERY_TERMS, the body view must exist (SS_ERR_STATE), a seed >= n_docs or a bad mask_id is SS_ERR_INVALID: every check
+ * comes before anything is enqueued and leaves the outputs untouched.  seeds / topic_probs / mask_id are read on the host like the
+ * query arrays.  The call waits once, for the seeds' terms (the slice plan is made on the CPU); outputs as ss_score_topk: with
+ * device outputs it returns once the rest is enqueued on the ctx stream.  There is no similar form of ss_score_topk_submit / _collect. */
+int32_t ss_similar_topk(ss_scorer* s, int32_t n_q, const uint32_t* seeds /*[n_q] doc ids*/, int32_t m,
+                        const double* topic_probs, const int32_t* mask_id /*NULL = none*/, int32_t k,
+                        ss_hit* hits_out, int32_t* n_hits_out);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SS_LIB_PATH") or os.path.join(_HERE, "libspaghetti_ra
 SS_OK = 0
 SS_MAX_TOPK = 1024
 SS_MAX_TOPICS = 64
+SS_MAX_QUERY_TERMS = 64
 SS_UNKNOWN_TERM = 0xFFFFFFFF
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
@@ -92,6 +93,10 @@ PROTOTYPES = {
     "ss_index_set_doc_freq": (_i32, [_vp, _vp]),
     "ss_index_set_weighted": (_i32, [_vp, _vp]),
     "ss_index_set_positions": (_i32, [_vp, _vp, _vp]),
+    "ss_index_build_doc_view": (_i32, [_vp]),
+    "ss_index_drop_doc_view": (_i32, [_vp]),
+    "ss_index_read_doc_view": (_i32, [_vp, _vp, _vp, _vp]),
+    "ss_index_doc_top_terms": (_i32, [_vp, _u64, _vp, _i32, _vp, _vp, _vp]),
     "ss_scorer_create": (_i32, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "ss_scorer_destroy": (_i32, [_vp]),
     "ss_scorer_set_prior": (_i32, [_vp, _i32, _vp]),
@@ -102,6 +107,7 @@ PROTOTYPES = {
     "ss_scorer_set_doc_masks": (_i32, [_vp, _i32, _vp]),
     "ss_score_topk_masked": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ss_score_topk_constrained": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ss_similar_topk": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

@@ -142,6 +142,14 @@ inline hipError_t copy_in(hipStream_t st, void* dst, const void* src, size_t byt
     std::memcpy(dst, src, bytes);
     return hipSuccess;
 }
+// An OUTPUT array of the ABI lives in device memory: the kernels may write it directly and the call need not wait.  Everything else
+// (plain, pinned or managed host memory) gets a device block and a copy.  One test for every entry point.
+inline bool on_device(const void* ptr) {
+    hipPointerAttribute_t a{};
+    const bool d = hipPointerGetAttributes(&a, ptr) == hipSuccess && a.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                 // plain host memory is reported as an error: not one
+    return d;
+}
 }  // namespace ss
 
 #define SS_HIP(ctx, expr)                                                                  \

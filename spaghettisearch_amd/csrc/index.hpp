@@ -23,4 +23,21 @@ struct ss_index {
     std::vector<uint64_t> h_term_ptr;  // host copy for query planning
     bool weighted = false;
     int users = 0;                 // scorers holding this index
+    // doc-major view (doc_view.hip, optional): doc_ptr u64[n_docs+1] | doc_term u32[P] | doc_w f32[P], row d = the terms of doc d in
+    // ascending term id with post_w as it stood at the build.  A snapshot: whatever changes postings or weights drops it.
+    ss::DevBuf<uint64_t> dv_ptr;
+    ss::DevBuf<uint32_t> dv_term;
+    ss::DevBuf<float> dv_w;
+    bool has_doc_view = false;
+    void drop_doc_view() {
+        dv_ptr.release();
+        dv_term.release();
+        dv_w.release();
+        has_doc_view = false;
+    }
 };
+
+namespace ss {
+// doc_view.hip: k_doc_top_terms over `n` doc ids in device memory (each < n_docs: checked by the caller); needs the view
+void launch_doc_top_terms(const ss_index* idx, const uint32_t* d_docs, uint64_t n, int32_t m, uint32_t* d_terms, float* d_w, int32_t* d_n, hipStream_t st);
+}  // namespace ss

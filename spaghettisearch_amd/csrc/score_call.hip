@@ -30,6 +30,7 @@ struct CallArgs {
     int32_t* n_hits_out;
     const int32_t* mask_id;
     const QueryConstraints* cons;
+    TurnRows* turn_rows;                        // ss::score_into_turn: the rows go to the plan turn's own block (hits_out / n_hits_out unused)
 };
 
 // the options a call reads, each looked up once per call, in one place (a look-up builds a std::string key)
@@ -151,7 +152,7 @@ struct Stamps { Clock::time_point begin, fetched, planned, staged, uploaded; }; 
 int32_t fetch_filter_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
     ss_ctx* ctx = s->ctx;
     const int32_t n_q = a.n_q;
-    if (n_q < 0 || !a.q_ptr || !a.hits_out || !a.n_hits_out) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: NULL argument or n_q < 0");
+    if (n_q < 0 || !a.q_ptr || (!a.turn_rows && (!a.hits_out || !a.n_hits_out))) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: NULL argument or n_q < 0");
     if (a.k < 1) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: k < 1");
     if (a.k > SS_MAX_TOPK) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_score_topk: k %d > SS_MAX_TOPK %d", a.k, SS_MAX_TOPK);
     if (a.topic_probs && s->k_topics == 0) return ctx->fail(SS_ERR_STATE, "ss_score_topk: topic_probs given but no prior set (ss_scorer_set_prior)");
@@ -231,11 +232,7 @@ int32_t fetch_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
 
 // results straight into the caller's buffers when both live in device memory (then the call does not wait either)
 bool outputs_on_device(const CallArgs& a) {
-    hipPointerAttribute_t a1{}, a2{};
-    const bool d1 = hipPointerGetAttributes(&a1, a.hits_out) == hipSuccess && a1.type == hipMemoryTypeDevice;
-    const bool d2 = hipPointerGetAttributes(&a2, a.n_hits_out) == hipSuccess && a2.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();                 // plain host memory is reported as an error: not one
-    return d1 && d2;
+    return ss::on_device(a.hits_out) && ss::on_device(a.n_hits_out);
 }
 
 // ---- 2. query operators ----------------------------------------------------------------------------------------------------
@@ -757,7 +754,7 @@ unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const Constra
 
 // Takes the next turn of per-batch buffers and waits until the batch that last used it is done with them; the pinned buffer,
 // the device copy and the allowed sets are grown to this batch's size.
-int32_t acquire_turn(ss_scorer* s, size_t plan_bytes, size_t n_csets, StagedBatch& sb) {
+int32_t acquire_turn(ss_scorer* s, size_t plan_bytes, size_t n_csets, TurnRows* turn_rows, StagedBatch& sb) {
     ss_ctx* ctx = s->ctx;
     const int pb = sb.turn = s->plan_turn;
     s->plan_turn = (s->plan_turn + 1) % ss_scorer::TURNS;
@@ -781,6 +778,13 @@ int32_t acquire_turn(ss_scorer* s, size_t plan_bytes, size_t n_csets, StagedBatc
         s->batch_ev_pending[pb] = false;
     }
     SS_HIP(ctx, ensure(s->d_plan2[pb], plan_bytes));
+    if (turn_rows) {                             // ss_similar_topk's k + 1 rows: this turn's block, free since the wait above like the sets below
+        SS_HIP(ctx, ensure(s->d_turn_hits[pb], turn_rows->rows));
+        SS_HIP(ctx, ensure(s->d_turn_n[pb], turn_rows->n_q));
+        turn_rows->hits = s->d_turn_hits[pb].p;
+        turn_rows->n_hits = s->d_turn_n[pb].p;
+        turn_rows->turn = pb;
+    }
     // the call's allowed sets: this turn's buffer, free since the wait above (the batch that last read it is done); exactly the size
     // needed (1.25 MB per set at 10M docs), not grown by half like the other workspaces
     sb.set_stride = std::max<uint64_t>(4, ((s->n_docs + 31) / 32 + 3) & ~(uint64_t)3);
@@ -877,8 +881,8 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
     p.small_stride = (uint32_t)pl.small_stride;
     p.small_stage = r.small_staged ? s->d_small_stage[pb].p : nullptr;
     p.small_stage_n = r.small_staged ? s->d_small_stage_n[pb].p : nullptr;
-    p.hits = in.dev_out ? a.hits_out : s->d_hits.p;
-    p.n_hits = in.dev_out ? a.n_hits_out : sb.one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + sb.res_rows) : s->d_nhits.p;
+    p.hits = a.turn_rows ? a.turn_rows->hits : in.dev_out ? a.hits_out : s->d_hits.p;
+    p.n_hits = a.turn_rows ? a.turn_rows->n_hits : in.dev_out ? a.n_hits_out : sb.one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + sb.res_rows) : s->d_nhits.p;
     p.masks = n_csets ? s->d_sets[pb].p : in.any_mask ? s->masks.p : nullptr;
     p.mask_words = n_csets ? sb.set_stride : s->mask_words;
     if (n_csets) {
@@ -898,7 +902,7 @@ int32_t stage_plan(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const
     PlanWriter measure;
     plan_sections(measure, in, cons, pl, sb.p, sb.cp);
     sb.plan_bytes = measure.o;
-    SS_TRY(acquire_turn(s, sb.plan_bytes, cons.sets.size(), sb));
+    SS_TRY(acquire_turn(s, sb.plan_bytes, cons.sets.size(), a.turn_rows, sb));
     PlanWriter w{s->h_plan[sb.turn], s->d_plan2[sb.turn].p, 0};
     unsigned char* tab = plan_sections(w, in, cons, pl, sb.p, sb.cp);
     // k_score_small's table: the 1024-slot queries first, then the larger ones (launch_score_small)
@@ -1071,7 +1075,7 @@ int32_t score_impl_inner(ss_scorer* s, const CallArgs& a) {
     t.fetched = Clock::now();
     // (the options and the outputs' whereabouts here, not at the top: "score.trace" has always counted them with the plan)
     const ScoreOptions opt = read_options(ctx);
-    in.dev_out = outputs_on_device(a);
+    in.dev_out = a.turn_rows || outputs_on_device(a);
     if (const int32_t rc = plan_batch(in, view, opt, plan, err)) return ctx->fail(rc, "%s", err.msg);
     t.planned = Clock::now();
     Route route = choose_route(plan, in.dev_out, opt);
@@ -1101,6 +1105,14 @@ int32_t score_impl(ss_scorer* s, const CallArgs& a) {
 }
 
 }  // namespace
+
+// ss_similar_topk (similar.hip): ss_score_topk_masked without phrases, the rows left in the plan turn's own device block
+int32_t ss::score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
+                            const int32_t* mask_id, int32_t k, TurnRows* out) {
+    out->rows = (size_t)n_q * (size_t)k;
+    out->n_q = (size_t)n_q;
+    return score_impl(s, CallArgs{n_q, q_ptr, q_terms, nullptr, nullptr, nullptr, topic_probs, k, nullptr, nullptr, mask_id, nullptr, out});
+}
 
 extern "C" {
 

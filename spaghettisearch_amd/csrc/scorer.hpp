@@ -39,6 +39,21 @@ uint32_t constraint_blocks(uint64_t n_words);
 void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st);
 }  // namespace ss
 
+// Where a scoring call left its rows when they stay inside the scorer (ss::score_into_turn): the block of the plan turn the call took.
+// The block is that turn's until the turn comes round again, i.e. until the scorer has waited for the turn's batch_ev: whoever reads it
+// on the context's stream records batch_ev[turn] again behind the reader.
+struct TurnRows {
+    size_t rows = 0, n_q = 0;                   // in: hits and counts to make room for
+    ss_hit* hits = nullptr;                     // out: [n_q][k]
+    int32_t* n_hits = nullptr;                  // out: [n_q]
+    int turn = -1;                              // out: -1 if the call took no turn (it failed before staging)
+};
+namespace ss {
+// score_call.hip
+int32_t score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
+                        const int32_t* mask_id, int32_t k, TurnRows* out);
+}  // namespace ss
+
 struct ss_scorer {
     ss_ctx* ctx = nullptr;
     ss_index* title = nullptr;
@@ -93,6 +108,14 @@ struct ss_scorer {
     ss::DevBuf<int32_t> d_small_stage_n[TURNS];
     ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
     hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
+    ss::DevBuf<ss_hit> d_turn_hits[TURNS];           // ss_similar_topk: the batch's k + 1 rows, read by k_drop_seed on the caller's stream
+    ss::DevBuf<int32_t> d_turn_n[TURNS];
+    // ss_similar_topk's seeds, their terms and term counts: written and read on the context's stream only (grow-only), the terms
+    // brought to the host through a pinned block
+    ss::DevBuf<uint32_t> d_sim_seeds, d_sim_terms;
+    ss::DevBuf<int32_t> d_sim_cnt;
+    unsigned char* h_sim = nullptr;
+    size_t h_sim_cap = 0;
     hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
@@ -126,6 +149,7 @@ struct ss_scorer {
         for (int i = 0; i < TURNS; i++) {
             if (h_plan[i]) (void)hipHostFree(h_plan[i]);
             if (i == 0 && h_res) (void)hipHostFree(h_res);
+            if (i == 0 && h_sim) (void)hipHostFree(h_sim);
             if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);
             if (batch_ev[i]) (void)hipEventDestroy(batch_ev[i]);
             if (wave_ev[i]) (void)hipEventDestroy(wave_ev[i]);

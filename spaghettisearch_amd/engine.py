@@ -416,6 +416,42 @@ class InvertedIndex:
         check(self.ctx.lib.ss_index_read(self.h, _ptr(tp), _ptr(pd), _ptr(pw)), self.ctx.h)
         return tp, pd, pw
 
+    def build_doc_view(self) -> None:
+        """ss_index_build_doc_view: the doc-major view of the table as it stands (row d = the terms of doc d, ascending term id, with
+        their current weights).  A snapshot: tfidf_build, apply_delta and resize free it."""
+        check(self.ctx.lib.ss_index_build_doc_view(self.h), self.ctx.h)
+
+    def drop_doc_view(self) -> None:
+        check(self.ctx.lib.ss_index_drop_doc_view(self.h), self.ctx.h)
+
+    def read_doc_view(self):
+        """-> (doc_ptr uint64[n_docs+1], doc_term uint32[P], doc_w float32[P]) of the view."""
+        dp = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        check(self.ctx.lib.ss_index_read_doc_view(self.h, _ptr(dp), None, None), self.ctx.h)
+        dt = np.zeros(int(dp[-1]), dtype=np.uint32)
+        dw = np.zeros(int(dp[-1]), dtype=np.float32)
+        check(self.ctx.lib.ss_index_read_doc_view(self.h, None, _ptr(dt), _ptr(dw)), self.ctx.h)
+        return dp, dt, dw
+
+    def doc_top_terms(self, docs, m: int, want_w: bool = True, out=None):
+        """ss_index_doc_top_terms: the m heaviest terms of every doc of `docs` (weight descending, then term id; NaN last)
+        -> (terms uint32[n][m], w float32[n][m] | None, n_out int32[n]); entries past n_out[i] keep what the arrays held (zeros here).
+        out = (terms, w | None, n_out): caller's arrays (numpy, or torch int32 / float32 / int32 device tensors)."""
+        docs = _as(docs, "uint32")
+        n = int(docs.shape[0])
+        if out is not None:
+            terms, w, n_out = _as(out[0], "uint32"), _as(out[1], "float32"), _as(out[2], "int32")
+            count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+            if count(terms) < n * m or (w is not None and count(w) < n * m) or count(n_out) < n:
+                raise ValueError("output buffers too small")
+        else:
+            terms = np.zeros((n, m), dtype=np.uint32)
+            w = np.zeros((n, m), dtype=np.float32) if want_w else None
+            n_out = np.zeros(n, dtype=np.int32)
+        self.ctx.ready(docs, terms, w, n_out)
+        check(self.ctx.lib.ss_index_doc_top_terms(self.h, n, _ptr(docs), int(m), _ptr(terms), _ptr(w), _ptr(n_out)), self.ctx.h)
+        return terms, w, n_out
+
     def set_doc_freq(self, df) -> None:
         """ss_index_set_doc_freq: whole-corpus document frequencies when this table is one doc-range shard
         (uint64[n_terms]; None = local list lengths).  Call before tfidf_build."""
@@ -588,6 +624,27 @@ class Scorer:
         n_hits = np.zeros(n_q, dtype=np.int32)
         check(self.ctx.lib.ss_score_topk(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), k,
                                          hits.ctypes.data, _ptr(n_hits)), self.ctx.h)
+        return hits, n_hits
+
+    def similar_topk(self, seeds, k: int, m: int = 5, topic_probs=None, mask_id=None, out=None):
+        """ss_similar_topk: row q = the top k of the query made of seed doc q's m heaviest body terms, without the seed itself
+        (the body table needs its doc view: InvertedIndex.build_doc_view).  mask_id: allow-lists as in score_topk_masked.
+        out: device outputs as in score_topk."""
+        seeds = _as(seeds, "uint32")
+        topic_probs = _as(topic_probs, "float64")
+        mask_id = _as(mask_id, "int32")
+        n_q = int(seeds.shape[0])
+        self.ctx.ready(seeds, topic_probs, mask_id)
+        if out is not None:
+            hits, n_hits = out
+            if hits.numel() * hits.element_size() < n_q * k * HIT_DTYPE.itemsize or n_hits.numel() < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            hits, n_hits = np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32)
+        check(self.ctx.lib.ss_similar_topk(self.h, n_q, _ptr(seeds), int(m), _ptr(topic_probs), _ptr(mask_id), k, _ptr(hits), _ptr(n_hits)),
+              self.ctx.h)
+        if out is not None and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return hits, n_hits
 
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):

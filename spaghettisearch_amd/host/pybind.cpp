@@ -126,6 +126,14 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("queries"), py::arg("masks"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetDocMasks", &retrieval::DeviceIndex::SetDocMasks, py::arg("sets"))
         .def("SetQueryOperators", &retrieval::DeviceIndex::SetQueryOperators, py::arg("on"))
+        .def("SetSimilarPages", &retrieval::DeviceIndex::SetSimilarPages, py::arg("on"))
+        .def("DocTopTerms", &retrieval::DeviceIndex::DocTopTerms, py::arg("docHash"), py::arg("m") = 5)
+        .def("SimilarPages", [](retrieval::DeviceIndex& di, const std::string& docHash, int k, int m) { return di.SimilarPages(docHash, k, m); },
+             py::arg("docHash"), py::arg("k") = 50, py::arg("m") = 5)
+        .def("SimilarPages", [](retrieval::DeviceIndex& di, const std::string& docHash, const std::string& mask, int k, int m) {
+            return di.SimilarPages(docHash, mask, k, m);
+        }, py::arg("docHash"), py::arg("mask"), py::arg("k") = 50, py::arg("m") = 5)
+        .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;
             auto f = as_dbs(forw), i = as_dbs(inv);

@@ -236,6 +236,8 @@ public:
     std::map<std::string, std::vector<std::string>> mask_sets;
     std::map<std::string, int32_t> mask_index;      // name -> the scorer's mask id
     bool query_operators = false;                   // SetQueryOperators: "+word" / "-word" in RetrieveBatch's query strings
+    bool similar_pages = false;                     // SetSimilarPages: the body table keeps its doc-major view (8 B per posting + 8 B per doc)
+    bool doc_view_built = false;                    // the body table holds a view that this object built and nothing has freed since
 
     ~DeviceIndex() {
         if (scorer) ss_scorer_destroy(scorer);
@@ -318,7 +320,7 @@ public:
         if (scorer) { ss_scorer_destroy(scorer); scorer = nullptr; }
         if (title) { ss_index_destroy(title); title = nullptr; }
         if (body) { ss_index_destroy(body); body = nullptr; }
-        mags_resident = flat_stale = false;
+        mags_resident = flat_stale = doc_view_built = false;
         const size_t n = flat.doc_names.size(), T = flat.term_names.size();
         check(ss_index_create(default_ctx(), n, T, flat.title.term_ptr.data(), flat.title.post_doc.data(), flat.title.post_w.data(), &title), "ss_index_create(title)");
         check(ss_index_create(default_ctx(), n, T, flat.body.term_ptr.data(), flat.body.post_doc.data(), flat.body.post_w.data(), &body), "ss_index_create(body)");
@@ -331,7 +333,56 @@ public:
         const size_t K = categories.size();
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();
+        build_doc_view();
     }
+
+    // Similar pages (no reference counterpart; default off: nothing is built and memory is as it was).  On, the body table's
+    // doc-major view (ss_index_build_doc_view) is built now and again after every upload / ApplyDelta that re-creates the scorer
+    // (a delta frees the view with the postings it was made from); off, the view is freed.
+    void SetSimilarPages(bool on) {
+        similar_pages = on;
+        if (on) build_doc_view();
+        else if (body && doc_view_built) { doc_view_built = false; spaghetti::check(ss_index_drop_doc_view(body), "ss_index_drop_doc_view(body)"); }
+    }
+    void build_doc_view() {
+        if (!similar_pages || !body) return;
+        doc_view_built = false;                                 // (a failing build leaves the table without a view)
+        spaghetti::check(ss_index_build_doc_view(body), "ss_index_build_doc_view(body)");
+        doc_view_built = true;
+    }
+    bool HasDocView() const { return doc_view_built; }
+    // the m heaviest body words of a page (word hashes; weight descending, then dense term id), empty for an unknown hash
+    std::vector<std::string> DocTopTerms(const std::string& docHash, int m = 5) {
+        using namespace spaghetti;
+        auto it = docs.id.find(docHash);
+        if (it == docs.id.end()) return {};
+        std::vector<uint32_t> t((size_t)std::max(m, 1));
+        int32_t n = 0;
+        check(ss_index_doc_top_terms(body, 1, &it->second, m, t.data(), nullptr, &n), "ss_index_doc_top_terms");
+        std::vector<std::string> out;
+        for (int32_t i = 0; i < n; i++) out.push_back(terms.name[t[i]]);
+        return out;
+    }
+    // "Similar pages" of a result card: the page's m heaviest body words as a new query (ss_similar_topk), the page itself left
+    // out; the same Rank_combined rows Retrieve returns.  mask: a set of SetDocMasks, "" = the whole index.  An unknown hash
+    // gives an empty result.  Needs SetSimilarPages(true).
+    std::vector<Rank_combined> SimilarPages(const std::string& docHash, const std::string& mask, int k = 50, int m = 5) {
+        using namespace spaghetti;
+        if (!similar_pages) throw std::runtime_error("SimilarPages: switched off (SetSimilarPages)");
+        int32_t mask_id = -1;
+        if (!mask.empty()) {
+            auto mi = mask_index.find(mask);
+            if (mi == mask_index.end()) throw std::runtime_error("SimilarPages: no doc mask named '" + mask + "' (SetDocMasks)");
+            mask_id = mi->second;
+        }
+        auto it = docs.id.find(docHash);
+        if (it == docs.id.end()) return {};
+        std::vector<ss_hit> hits((size_t)std::max(k, 1));
+        std::vector<int32_t> n_hits(1);
+        check(ss_similar_topk(scorer, 1, &it->second, m, nullptr, mask.empty() ? nullptr : &mask_id, k, hits.data(), n_hits.data()), "ss_similar_topk");
+        return to_ranks(1, k, hits, n_hits)[0];
+    }
+    std::vector<Rank_combined> SimilarPages(const std::string& docHash, int k = 50, int m = 5) { return SimilarPages(docHash, std::string(), k, m); }
 
     // Replace the named allow-lists: name -> doc hashes (hashes the index does not hold are ignored).
     void SetDocMasks(const std::map<std::string, std::vector<std::string>>& sets) {
@@ -430,6 +481,7 @@ public:
                 if (ss_scorer_create(spaghetti::default_ctx(), di.title, di.body, &di.scorer) != SS_OK) { di.scorer = nullptr; return; }
                 if (K > 0 && K <= SS_MAX_TOPICS && di.flat.prior.size() == K * nd) (void)ss_scorer_set_prior(di.scorer, (int32_t)K, di.flat.prior.data());
                 try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
+                try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
             }
         } scorer_guard{*this};
         bool resized = false;
@@ -441,6 +493,7 @@ public:
             terms.name.resize(t_before);
         };
         if (scorer) { ss_scorer_destroy(scorer); scorer = nullptr; }      // scorers on a table go before its delta
+        doc_view_built = false;                                           // resize / the delta free the view; every way out builds it again
         try {
             if (n != n_before || T != t_before) {
                 check(ss_index_resize(title, n, T), "ss_index_resize(title)");
@@ -546,6 +599,7 @@ public:
         check(ss_scorer_create(default_ctx(), title, body, &scorer), "ss_scorer_create");
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();                                                 // the new scorer, the ids as they stand now
+        build_doc_view();                                                 // (the deltas freed it)
     }
 
     // forw[3] was rewritten (UpdateTopicSensitivePagerank / ResidentPagerank::Run): refresh the scorer's PageRank table.
