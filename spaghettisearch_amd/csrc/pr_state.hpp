@@ -1,11 +1,19 @@
-// pr_state.hpp — the PageRank state and everything of the PageRank path that crosses a translation unit: pagerank.hip (sweep kernels,
-// their launchers, ss_pr_create and the ss_pr_* stepping API) and pagerank_run.hip (the one-call drivers ss_pagerank_run*, the
-// two-vector kernels, float32 on the wire).  The work items and their constants (WorkItem, W_* / V_*, TPB, WAVES, CH, SEGW) come
-// from pr_plan.hpp, which has to stay free of device headers.  The kernel-side types live in an anonymous namespace, like
+// pr_state.hpp — the PageRank state and everything of the PageRank path that crosses a translation unit: pagerank.hip (the small
+// kernels, the choice of the sweep kernel, ss_pr_create and the ss_pr_* stepping API), the sweep-kernel families pr_sweep.hip,
+// pr_sweep_n.hip and pr_step.hip (each behind one launcher and one occupancy query, below) and pagerank_run.hip (the one-call drivers
+// ss_pagerank_run*, the two-vector kernels, float32 on the wire).  The device helpers the kernels share are in pr_device.hpp.  The
+// work items and their constants (WorkItem, W_* / V_*, TPB, WAVES, CH, SEGW) come from pr_plan.hpp, which has to stay free of
+// device headers.  The kernel-side types live in an anonymous namespace, like
 // score_common.hpp's: every translation unit has its own copy of the device code.
 #pragma once
 #include "graph.hpp"
 #include "pr_plan.hpp"
+
+#ifdef SS_PR_WAVETIME
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#endif
 
 namespace {
 
@@ -87,8 +95,16 @@ struct PrParams {
 
 }  // namespace
 
+// the sweep-kernel families: which one a state runs is decided once, in ss_pr_create (pagerank.hip: pick_kernel)
+enum PrKernel : int {
+    PR_STEP = 0,           // k_pr_step: block items, K <= 2 by option only
+    PR_SWEEP = 1,          // k_pr_sweep: wave items, lane groups of 8 / 16 topics
+    PR_SWEEP_N = 2,        // k_pr_sweep_n (and its persistent form k_pr_multi_n): wave items, K <= 2 unpadded
+};
+
 struct ss_pr {
     ss_graph* g = nullptr;
+    PrKernel kernel = PR_SWEEP;
     int gw = 1;            // lane-group width = padded topic count
     ss::DevBuf<float> wire_send, wire_recv;   // option "pr.wire_f32": the contribution slice as float32 on the wire
     bool nwave = false;    // K <= 2 on the wave-item kernel k_pr_sweep_n (gw = K; the work items are those of the 8-wide sweep)
@@ -117,8 +133,22 @@ namespace ss {
 // pagerank.hip: launchers of its kernels; the kernel for the state's lane-group width (and teleport sets) is picked inside
 unsigned begin_blocks(const ss_pr* pr);                            // grid of k_pr_begin
 void pr_launch_begin(ss_pr* pr, hipStream_t st, unsigned nb);
-void pr_launch_step(ss_pr* pr, hipStream_t st);                    // one sweep
+void pr_launch_step(ss_pr* pr, hipStream_t st);                    // one sweep: the one place that switches on pr->kernel
 void pr_launch_finalize(ss_pr* pr, hipStream_t st, int is_begin);  // world > 1: behind the exchange
+// The sweep-kernel families, one file each: a launcher of one sweep over pr->nblocks blocks, which picks the instantiation for the
+// state's width, teleport sets and mode itself, and the blocks per CU the runtime admits of the family's kernel of width gw
+// (unclamped; pagerank.hip asks once per kernel and process and keeps the answer)
+void pr_sweep_launch(ss_pr* pr, hipStream_t st);                   // pr_sweep.hip: k_pr_sweep<8|16, TS>
+int pr_sweep_occupancy(int gw);
+void pr_sweep_n_launch(ss_pr* pr, hipStream_t st);                 // pr_sweep_n.hip: k_pr_sweep_n<1|2, TS>
+int pr_sweep_n_occupancy(int gw);
+void pr_multi_n_launch(ss_pr* pr, hipStream_t st, int n_steps);    // ... and k_pr_multi_n<1|2, 1|2>: n_steps sweeps in one launch
+int pr_multi_n_occupancy(int gw);
+void pr_step_launch(ss_pr* pr, hipStream_t st);                    // pr_step.hip: k_pr_step<1|2>
+int pr_step_occupancy(int gw);
+#ifdef SS_PR_WAVETIME
+void pr_dump_wave_times(const ss_pr* pr);                          // pr_sweep.hip (variant build): called by ss_pr_destroy
+#endif
 // pagerank_run.hip: float32 on the wire (option "pr.wire_f32")
 size_t pr_wire_floats(const ss_pr* pr);
 hipError_t pr_wire_alloc(ss_pr* pr);
@@ -128,6 +158,13 @@ void pr_wire_unpack(ss_pr* pr, hipStream_t st);
 #pragma GCC visibility pop
 
 namespace {
+#ifdef SS_PR_WAVETIME
+// the variant build's two dumps go to the directory the environment names in SS_PR_WAVETIME_DIR (default: the working directory)
+inline FILE* open_dump(const char* name) {
+    const char* dir = getenv("SS_PR_WAVETIME_DIR");
+    return fopen((std::string(dir && *dir ? dir : ".") + "/" + name).c_str(), "w");
+}
+#endif
 // The state's control block, read back into the context's pinned scratch (a read-back into pageable memory pins the page per call:
 // ss_ctx::h_pin); waits for `st`, bounded where a collective may be in flight.  `what` names the wait in the error.
 inline int32_t read_ctl(ss_ctx* ctx, const ss_pr* pr, hipStream_t st, const char* what, const PrCtl** out) {

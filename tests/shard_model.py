@@ -1,7 +1,7 @@
 """CPU model of ONE shard of the doc-range-sharded PageRank (test infrastructure).
 
 It follows the same layout and exchange protocol as the HIP library
-(spaghettisearch_amd/csrc/graph.hip + pagerank.hip): nodes ordered
+(spaghettisearch_amd/csrc/graph.hip, pagerank.hip, pr_device.hpp): nodes ordered
 [non-dangling | dangling], in-degree descending inside a class, dealt round-robin
 to the ranks; every rank's all-gather piece = its non-dangling contribution rows +
 two tail rows (contribution sum, L1 delta).  Used by the gloo world_size-2 test to

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from spaghettisearch_amd import synth
+from tests.pr_graphs import NARROW_VARIANTS, csr, skewed_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +28,6 @@ def run_both(ss_ctx, oracle, n, out_ptr, out_dst, n_topic, eps, max_iter=0, d=D)
         g.close()
     ref, ref_iters = oracle.pagerank(n, out_ptr, out_dst, d, eps, n_topic, max_iter=max_iter)
     return rank, iters, ref, ref_iters
-
-
-def csr(n, edges):
-    edges = sorted(edges)
-    ptr = np.zeros(n + 1, dtype=np.uint64)
-    for s, _ in edges:
-        ptr[s + 1] += 1
-    return np.cumsum(ptr).astype(np.uint64), np.array([d for _, d in edges], dtype=np.uint32)
 
 
 def test_kat_graph(ss_ctx, oracle):
@@ -186,7 +179,7 @@ def test_two_vector_form_on_hard_graphs(ss_ctx, oracle):
         rank, iters, ref, ref_iters = run_both(ss_ctx, oracle, 1, ptr, dst, [1], 1e-12)
         assert iters.tolist() == ref_iters.tolist()
         np.testing.assert_allclose(rank, ref, rtol=1e-14)
-        n, ptr, dst = _skewed_graph()
+        n, ptr, dst = skewed_graph()
         rank, iters, ref, ref_iters = run_both(ss_ctx, oracle, n, ptr, dst, synth.topic_sizes(n, 16), 1e-10)
         assert iters.tolist() == ref_iters.tolist()
         np.testing.assert_allclose(rank, ref, rtol=1e-12)
@@ -226,21 +219,10 @@ def test_edge_cases(ss_ctx, oracle):
 # path, V_ROWW, V_QUAD, V_DEG by lane, V_ZERO); "pr.narrow_wave" = 0: the choice before it (small graphs: k_pr_sweep<8> with padded
 # topics); "pr.force_narrow" = 1: the block-item kernel k_pr_step<1/2> (W_SEG, W_WAVE, W_GROUP, W_ZERO).  Every one of them meets
 # the oracle directly.
-NARROW_VARIANTS = {"wave_items": {}, "padded_8_wide": {"pr__narrow_wave": 0}, "block_items": {"pr__force_narrow": 1}}
-def _skewed_graph():
-    rng = np.random.default_rng(3)
-    n = 70000
-    edges = {(int(s), 0) for s in range(1, 60001)}                      # hub: 60k in-edges = many W_SEG segments
-    edges |= {(int(s), 1) for s in rng.choice(n, 3000, replace=False)}  # several segments at K=1 (128*64 edges each)
-    edges |= {(int(s), 2) for s in rng.choice(n, 300, replace=False)}
-    edges |= {(int(a), int(b)) for a, b in rng.integers(0, n, size=(50000, 2))}
-    return (n,) + csr(n, list(edges))
-
-
 @pytest.mark.parametrize("variant", list(NARROW_VARIANTS))
 @pytest.mark.parametrize("k_topics", [1, 2])
 def test_narrow_kernel_skewed_rows(ss_ctx, oracle, k_topics, variant):
-    n, ptr, dst = _skewed_graph()
+    n, ptr, dst = skewed_graph()
     n_topic = [n, 7][:k_topics]
     with ss_ctx.options(**NARROW_VARIANTS[variant]):
         rank, iters, ref, ref_iters = run_both(ss_ctx, oracle, n, ptr, dst, n_topic, 1e-10)

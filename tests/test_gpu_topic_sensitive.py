@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from spaghettisearch_amd import engine, sharding, synth
+from tests.pr_graphs import NARROW_VARIANTS, skewed_graph
 
 pytestmark = pytest.mark.gpu
 D = 0.75
@@ -28,7 +29,7 @@ def run_ts(ctx, n, ptr, dst, n_topic, sets, eps, max_iter=0):
     return x, s["iters"]
 
 
-@pytest.mark.parametrize("k_topics", [1, 3, 16])
+@pytest.mark.parametrize("k_topics", [1, 2, 3, 16])
 def test_teleport_sets_match_oracle(ss_ctx, oracle, k_topics):
     n, e = 30000, 150000
     ptr, dst = synth.rmat_graph(n, e, seed=31 + k_topics)
@@ -48,6 +49,48 @@ def test_teleport_sets_match_oracle(ss_ctx, oracle, k_topics):
     # the set's members hold visibly more rank than under the uniform teleport
     base, _ = oracle.pagerank(n, ptr, dst, D, 1e-10, n_topic[:1])
     assert x[0][sets[0].astype(np.int64)].mean() > 3 * base[0][sets[0].astype(np.int64)].mean()
+
+
+_SKEWED = {}
+
+
+def _skewed_with_sets():
+    """The skewed graph of test_gpu_pagerank.py (a 60 000-edge hub cut into pieces, mid rows, many short rows, edge-less rows,
+    dangling nodes) and two teleport sets: one holds the hub and edge-less rows (dangling ones among them), one holds neither."""
+    if not _SKEWED:
+        n, ptr, dst = skewed_graph()
+        indeg = np.bincount(dst.astype(np.int64), minlength=n)
+        outdeg = np.diff(ptr.astype(np.int64))
+        edgeless = np.flatnonzero(indeg == 0)
+        assert (outdeg[edgeless] > 0).any() and (outdeg[edgeless] == 0).any() and indeg[0] >= 60000
+        rng = np.random.default_rng(17)
+        fed = np.flatnonzero(indeg > 0)[1:]                                # rows with in-edges, without the hub (node 0)
+        with_hub = np.concatenate([[0], rng.choice(edgeless[outdeg[edgeless] > 0], 40, replace=False),
+                                   rng.choice(edgeless[outdeg[edgeless] == 0], 10, replace=False), rng.choice(fed, 50, replace=False)])
+        _SKEWED.update(graph=(n, ptr, dst), refs={},
+                       sets={"hub_and_edgeless": with_hub.astype(np.uint32), "neither": rng.choice(fed, 100, replace=False).astype(np.uint32)})
+    return _SKEWED
+
+
+@pytest.mark.parametrize("variant", list(NARROW_VARIANTS))
+@pytest.mark.parametrize("k_topics", [1, 2])
+def test_teleport_sets_on_every_narrow_kernel(ss_ctx, oracle, k_topics, variant):
+    """Teleport sets under each kernel K <= 2 can run on: k_pr_sweep_n<K, true> (default), k_pr_sweep<8, true> (padded) and
+    k_pr_step<K> with membership bits (block items), on a graph that has every work class of all three."""
+    sk = _skewed_with_sets()
+    n, ptr, dst = sk["graph"]
+    n_topic = [n, 7][:k_topics]
+    runs = [["hub_and_edgeless"], ["neither"]] if k_topics == 1 else [["hub_and_edgeless", "neither"]]
+    for names in runs:
+        with ss_ctx.options(**NARROW_VARIANTS[variant]):
+            x, iters = run_ts(ss_ctx, n, ptr, dst, n_topic, [sk["sets"][s] for s in names], 1e-10)
+        for k, name in enumerate(names):
+            key = (name, int(n_topic[k]))
+            if key not in sk["refs"]:
+                sk["refs"][key] = oracle.pagerank_topic_ts(n, ptr, dst, D, 1e-10, int(n_topic[k]), sk["sets"][name])
+            ref, rit = sk["refs"][key]
+            assert int(iters[k]) == rit, (k, name)
+            np.testing.assert_allclose(x[k], ref, rtol=1e-12, atol=1e-300)
 
 
 def test_default_path_is_untouched_and_clearable(ss_ctx, oracle):
