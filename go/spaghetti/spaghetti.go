@@ -480,6 +480,39 @@ func (s *Scorer) SimilarTopK(seeds []uint32, m int, topicProbs []float64, maskID
 	return out, nil
 }
 
+// RelatedTerm is one refinement word of RelatedTerms: a dense term id and the float64 sum of its weights over the feedback pages.
+type RelatedTerm struct {
+	Term  uint32
+	Score float64
+}
+
+// RelatedTerms answers "which words do this query's best pages have in common that the user did not type?" (ss_related_terms): row q
+// = up to m terms among the mDoc heaviest body terms of the query's kFb best pages, their weights summed per term in rank order, the
+// query's own terms left out; score descending, then term id.  queryLen / topicProbs / maskID as in ScoreTopKMasked (nil = none).
+// The body table needs its doc view (Index.BuildDocView).
+func (s *Scorer) RelatedTerms(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32, kFb, mDoc, m int) ([][]RelatedTerm, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	terms := make([]uint32, nq*m)
+	score := make([]float64, nq*m)
+	nOut := make([]int32, nq)
+	rc := C.ss_related_terms(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), i32p(maskID),
+		C.int32_t(kFb), C.int32_t(mDoc), C.int32_t(m), u32p(terms), f64p(score), i32p(nOut))
+	if err := statusErr(s.ctx, rc, "ss_related_terms"); err != nil {
+		return nil, err
+	}
+	out := make([][]RelatedTerm, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]RelatedTerm, nOut[q])
+		for i := range out[q] {
+			out[q][i] = RelatedTerm{terms[q*m+i], score[q*m+i]}
+		}
+	}
+	return out, nil
+}
+
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every
 // result contains it, title or body), excPtr/excTerms its excluded ones ("-word": no result does); nil pointers = none.  The
 // constraint terms only filter; put a required word in qTerms too for it to be scored.

@@ -37,7 +37,8 @@ extern "C" {
  * carries its merge.  A binding checks ss_abi_version() == SS_ABI_VERSION at load.
  * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists);
  * ss_score_topk_constrained (required and excluded query terms); ss_index_build_doc_view / _drop_doc_view / _read_doc_view,
- * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages"). */
+ * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages");
+ * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -321,7 +322,7 @@ int32_t ss_index_read_positions(ss_index* idx, uint64_t* pos_ptr_out, float* pos
  * SS_ERR_HIP) leaves the table WITHOUT a view, not with the old one.
  * Every call that changes postings or weights frees the view: ss_tfidf_build, ss_index_apply_delta(_pos), ss_index_resize (and
  * ss_index_destroy); ss_index_set_weighted and ss_index_set_doc_freq change neither and leave it.  Without a view
- * ss_index_drop_doc_view, ss_index_read_doc_view, ss_index_doc_top_terms and ss_similar_topk return SS_ERR_STATE.
+ * ss_index_drop_doc_view, ss_index_read_doc_view, ss_index_doc_top_terms, ss_similar_topk and ss_related_terms return SS_ERR_STATE.
  * A table of 2^32 postings or more is SS_ERR_UNSUPPORTED (the build indexes postings with 32 bits).  The calls wait for their
  * work: the view is complete, and host outputs are there, when they return. */
 int32_t ss_index_build_doc_view(ss_index* idx);
@@ -442,6 +443,34 @@ int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_p
 int32_t ss_similar_topk(ss_scorer* s, int32_t n_q, const uint32_t* seeds /*[n_q] doc ids*/, int32_t m,
                         const double* topic_probs, const int32_t* mask_id /*NULL = none*/, int32_t k,
                         ss_hit* hits_out, int32_t* n_hits_out);
+
+/* Related terms: which words do a query's best pages have in common that the user did not type?  No reference counterpart (the
+ * reference ships the material per page, Words_mapping, retrieval/util.go:116-149; it never aggregates over a result list).  The
+ * pseudo-relevance-feedback step behind "related searches" / "refine by" and the input of an expanded re-query.  Defined bit for bit:
+ *   Hits.       R = the row ss_score_topk_masked returns for query q with k = k_fb, this query_len, topic_probs[q] and mask_id[q]
+ *               (mask_id NULL: the ss_score_topk row).  There are no phrases.
+ *   Per hit.    For hit j of R in rank order, T_j = the ss_index_doc_top_terms row of doc R[j].doc in the BODY table's view with
+ *               m_doc: term ids and the stored float32 weights.  A hit without body postings contributes nothing.
+ *   Candidates. Every term of some T_j whose id is not among q_terms[q_ptr[q] .. q_ptr[q+1]).
+ *   Score.      score(t) = the float64 sum of (double)w_j(t) over the hits j with t in T_j, added in ASCENDING j, starting from 0.0.
+ *               The order is part of the definition: stored weights can lie more than 29 binary orders apart, and then the last
+ *               bit depends on it.  (A sum of -0.0 weights alone is +0.0: 0.0 + -0.0.)
+ *   Output.     Row q of terms_out [n_q][m] / score_out [n_q][m] (nullable) holds the first n_out[q] = min(m, #candidates)
+ *               candidates ordered by score descending as float64 VALUES (-0.0 and +0.0 are equal), then ascending term id; NaN
+ *               scores last, among themselves by term id — the convention of ss_index_doc_top_terms, one width up.  score_out
+ *               holds the sums' bits.  Entries past n_out[q] are left untouched.
+ *   Empty rows. A query without hits gives an empty row; so does a query whose hits hold only query terms.
+ * 1 <= k_fb <= SS_MAX_FEEDBACK_DOCS, 1 <= m_doc <= SS_MAX_QUERY_TERMS, 1 <= m <= SS_MAX_QUERY_TERMS, a bad mask_id: SS_ERR_INVALID;
+ * no body view, or topic_probs without a prior: SS_ERR_STATE; a bad q_ptr as in ss_score_topk.  Every check comes before anything
+ * is enqueued and leaves the outputs untouched.
+ * The query arrays are read on the host like every scoring call's.  Outputs host or device memory: when terms_out, n_out and
+ * score_out (if given) are all device memory the call only enqueues on the ctx stream and, unlike ss_similar_topk, NEVER waits —
+ * hits, their docs' terms, the sums and the selection all stay on the device.  There is no _submit / _collect form. */
+#define SS_MAX_FEEDBACK_DOCS 64
+int32_t ss_related_terms(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                         const int32_t* query_len, const double* topic_probs, const int32_t* mask_id /*NULL = none*/,
+                         int32_t k_fb, int32_t m_doc, int32_t m,
+                         uint32_t* terms_out /*[n_q][m]*/, double* score_out /*[n_q][m] nullable*/, int32_t* n_out /*[n_q]*/);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

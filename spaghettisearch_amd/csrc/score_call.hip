@@ -1106,12 +1106,13 @@ int32_t score_impl(ss_scorer* s, const CallArgs& a) {
 
 }  // namespace
 
-// ss_similar_topk (similar.hip): ss_score_topk_masked without phrases, the rows left in the plan turn's own device block
+// ss_similar_topk (similar.hip), ss_related_terms (related.hip): ss_score_topk_masked without phrases, the rows left in the plan
+// turn's own device block
 int32_t ss::score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
-                            const int32_t* mask_id, int32_t k, TurnRows* out) {
+                            const int32_t* mask_id, int32_t k, TurnRows* out, const int32_t* query_len) {
     out->rows = (size_t)n_q * (size_t)k;
     out->n_q = (size_t)n_q;
-    return score_impl(s, CallArgs{n_q, q_ptr, q_terms, nullptr, nullptr, nullptr, topic_probs, k, nullptr, nullptr, mask_id, nullptr, out});
+    return score_impl(s, CallArgs{n_q, q_ptr, q_terms, nullptr, nullptr, query_len, topic_probs, k, nullptr, nullptr, mask_id, nullptr, out});
 }
 
 extern "C" {

@@ -49,9 +49,9 @@ struct TurnRows {
     int turn = -1;                              // out: -1 if the call took no turn (it failed before staging)
 };
 namespace ss {
-// score_call.hip
+// score_call.hip (query_len: as ss_score_topk's, NULL = term count)
 int32_t score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
-                        const int32_t* mask_id, int32_t k, TurnRows* out);
+                        const int32_t* mask_id, int32_t k, TurnRows* out, const int32_t* query_len = nullptr);
 }  // namespace ss
 
 struct ss_scorer {
@@ -108,7 +108,7 @@ struct ss_scorer {
     ss::DevBuf<int32_t> d_small_stage_n[TURNS];
     ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
     hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
-    ss::DevBuf<ss_hit> d_turn_hits[TURNS];           // ss_similar_topk: the batch's k + 1 rows, read by k_drop_seed on the caller's stream
+    ss::DevBuf<ss_hit> d_turn_hits[TURNS];           // ss_similar_topk / ss_related_terms: the batch's rows, read by k_drop_seed / k_hit_docs on the caller's stream
     ss::DevBuf<int32_t> d_turn_n[TURNS];
     // ss_similar_topk's seeds, their terms and term counts: written and read on the context's stream only (grow-only), the terms
     // brought to the host through a pinned block
@@ -116,6 +116,15 @@ struct ss_scorer {
     ss::DevBuf<int32_t> d_sim_cnt;
     unsigned char* h_sim = nullptr;
     size_t h_sim_cap = 0;
+    // ss_related_terms (related.hip): the hits' docs, their heaviest terms (ids, weights, counts), the queries' own terms and the
+    // device blocks of host outputs: written and read on the context's stream only (grow-only).  The queries' own terms go up through a
+    // pinned block per turn, rewritten only after the wait for batch_ev[turn]: the call never waits for its own copy.
+    ss::DevBuf<uint32_t> d_rel_docs, d_rel_terms, d_rel_q, d_rel_out_terms;
+    ss::DevBuf<float> d_rel_w;
+    ss::DevBuf<int32_t> d_rel_cnt;
+    ss::DevBuf<double> d_rel_out_score;
+    uint32_t* h_rel[TURNS] = {};
+    size_t h_rel_cap[TURNS] = {};
     hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
@@ -148,6 +157,7 @@ struct ss_scorer {
         }
         for (int i = 0; i < TURNS; i++) {
             if (h_plan[i]) (void)hipHostFree(h_plan[i]);
+            if (h_rel[i]) (void)hipHostFree(h_rel[i]);
             if (i == 0 && h_res) (void)hipHostFree(h_res);
             if (i == 0 && h_sim) (void)hipHostFree(h_sim);
             if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);

@@ -647,6 +647,35 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return hits, n_hits
 
+    def related_terms(self, q_ptr, q_terms, m: int = 10, k_fb: int = 10, m_doc: int = 5, query_len=None, topic_probs=None, mask_id=None,
+                      out=None):
+        """ss_related_terms: the m heaviest words the k_fb best pages of every query have in common — each page's m_doc heaviest body
+        terms, their weights summed per term in rank order — without the query's own terms (the body table needs its doc view).
+        -> (terms uint32[n_q][m], score float64[n_q][m], n_out int32[n_q]); entries past n_out[q] keep what the arrays held (zeros here).
+        out = (terms, score | None, n_out): caller's arrays (numpy, or torch int32 / float64 / int32 device tensors); with device
+        tensors the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        mask_id = _as(mask_id, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        if out is not None:
+            terms, score, n_out = _as(out[0], "uint32"), _as(out[1], "float64"), _as(out[2], "int32")
+            count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+            if count(terms) < n_q * m or (score is not None and count(score) < n_q * m) or count(n_out) < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            terms = np.zeros((n_q, m), dtype=np.uint32)
+            score = np.zeros((n_q, m), dtype=np.float64)
+            n_out = np.zeros(n_q, dtype=np.int32)
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, mask_id, terms, score, n_out)
+        check(self.ctx.lib.ss_related_terms(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), _ptr(mask_id),
+                                            int(k_fb), int(m_doc), int(m), _ptr(terms), _ptr(score), _ptr(n_out)), self.ctx.h)
+        if out is not None and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return terms, score, n_out
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""

@@ -133,6 +133,7 @@ PYBIND11_MODULE(_host, m) {
         .def("SimilarPages", [](retrieval::DeviceIndex& di, const std::string& docHash, const std::string& mask, int k, int m) {
             return di.SimilarPages(docHash, mask, k, m);
         }, py::arg("docHash"), py::arg("mask"), py::arg("k") = 50, py::arg("m") = 5)
+        .def("RelatedTerms", &retrieval::DeviceIndex::RelatedTerms, py::arg("query"), py::arg("m") = 10, py::arg("k_fb") = 10, py::arg("m_doc") = 5)
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;

@@ -359,9 +359,7 @@ public:
         std::vector<uint32_t> t((size_t)std::max(m, 1));
         int32_t n = 0;
         check(ss_index_doc_top_terms(body, 1, &it->second, m, t.data(), nullptr, &n), "ss_index_doc_top_terms");
-        std::vector<std::string> out;
-        for (int32_t i = 0; i < n; i++) out.push_back(terms.name[t[i]]);
-        return out;
+        return term_hashes(t.data(), n);
     }
     // "Similar pages" of a result card: the page's m heaviest body words as a new query (ss_similar_topk), the page itself left
     // out; the same Rank_combined rows Retrieve returns.  mask: a set of SetDocMasks, "" = the whole index.  An unknown hash
@@ -383,6 +381,26 @@ public:
         return to_ranks(1, k, hits, n_hits)[0];
     }
     std::vector<Rank_combined> SimilarPages(const std::string& docHash, int k = 50, int m = 5) { return SimilarPages(docHash, std::string(), k, m); }
+    // "Related searches" of a result list: the m words (hashes, best first) that the k_fb best pages of `query` have in common
+    // among their m_doc heaviest body words and that the user did not type (ss_related_terms).  The query is tokenised as Retrieve
+    // does; quoted phrases and '+' / '-' operators are not interpreted (the phrase words leave the query, operator tokens are plain
+    // words).  Needs SetSimilarPages(true): the body view must exist.
+    std::vector<std::string> RelatedTerms(const std::string& query, int m = 10, int k_fb = 10, int m_doc = 5) {
+        using namespace spaghetti;
+        if (!similar_pages) throw std::runtime_error("RelatedTerms: switched off (SetSimilarPages)");
+        const Tokenised t = tokenise({query}, nullptr, false);
+        std::vector<uint32_t> ids((size_t)std::max(m, 1));
+        int32_t n = 0;
+        check(ss_related_terms(scorer, 1, t.q_ptr.data(), t.q_terms.data(), nullptr, nullptr, nullptr, k_fb, m_doc, m, ids.data(), nullptr, &n),
+              "ss_related_terms");
+        return term_hashes(ids.data(), n);
+    }
+    // dense term ids -> word hashes (DocTopTerms, RelatedTerms)
+    std::vector<std::string> term_hashes(const uint32_t* ids, int32_t n) const {
+        std::vector<std::string> out;
+        for (int32_t i = 0; i < n; i++) out.push_back(terms.name[ids[i]]);
+        return out;
+    }
 
     // Replace the named allow-lists: name -> doc hashes (hashes the index does not hold are ignored).
     void SetDocMasks(const std::map<std::string, std::vector<std::string>>& sets) {
