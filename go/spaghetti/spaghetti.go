@@ -513,6 +513,63 @@ func (s *Scorer) RelatedTerms(qPtr, qTerms []uint32, queryLen []int32, topicProb
 	return out, nil
 }
 
+// TermMatch says how one query token matched one hit (ss_term_match): the stored weights of the (term, doc) postings, which of them
+// exist, and the earliest body position >= 0 (HasPos false: no positional postings, no body posting, or no such position).
+type TermMatch struct {
+	TitleW  float32
+	BodyW   float32
+	InTitle bool
+	InBody  bool
+	HasPos  bool
+	BodyPos float32
+}
+
+// ExplainHits answers "which of the query's tokens matched each result, and where?" (ss_explain_hits) for rows any scoring call
+// returned: out[q][j][i] describes hits[q][j] and token i of query q (qTerms[qPtr[q]+i]; duplicates get equal entries).  Only the
+// hits' Doc is read.  Unknown terms and doc ids the index does not hold match nothing.
+func (s *Scorer) ExplainHits(qPtr, qTerms []uint32, hits [][]Hit) ([][][]TermMatch, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 || len(hits) != nq {
+		return nil, nil
+	}
+	k, stride := 1, 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > k {
+			k = len(hits[q])
+		}
+		if n := int(qPtr[q+1] - qPtr[q]); n > stride {
+			stride = n
+		}
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nHits[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			raw[q*k+j].doc = C.uint32_t(h.Doc)
+		}
+	}
+	m := make([]C.ss_term_match, nq*k*stride)
+	rc := C.ss_explain_hits(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])),
+		i32p(nHits), C.int32_t(stride), (*C.ss_term_match)(unsafe.Pointer(&m[0])))
+	if err := statusErr(s.ctx, rc, "ss_explain_hits"); err != nil {
+		return nil, err
+	}
+	out := make([][][]TermMatch, nq)
+	for q := 0; q < nq; q++ {
+		nt := int(qPtr[q+1] - qPtr[q])
+		out[q] = make([][]TermMatch, len(hits[q]))
+		for j := range out[q] {
+			out[q][j] = make([]TermMatch, nt)
+			for i := 0; i < nt; i++ {
+				e := m[(q*k+j)*stride+i]
+				out[q][j][i] = TermMatch{float32(e.title_w), float32(e.body_w), e.flags&1 != 0, e.flags&2 != 0, e.flags&4 != 0, float32(e.body_pos)}
+			}
+		}
+	}
+	return out, nil
+}
+
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every
 // result contains it, title or body), excPtr/excTerms its excluded ones ("-word": no result does); nil pointers = none.  The
 // constraint terms only filter; put a required word in qTerms too for it to be scored.

@@ -38,7 +38,8 @@ extern "C" {
  * Added under 4, nothing changed: ss_scorer_set_doc_masks and ss_score_topk_masked (per-query doc allow-lists);
  * ss_score_topk_constrained (required and excluded query terms); ss_index_build_doc_view / _drop_doc_view / _read_doc_view,
  * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages");
- * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits). */
+ * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits);
+ * ss_term_match and ss_explain_hits (which query tokens matched each result row, and where). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -471,6 +472,45 @@ int32_t ss_related_terms(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const
                          const int32_t* query_len, const double* topic_probs, const int32_t* mask_id /*NULL = none*/,
                          int32_t k_fb, int32_t m_doc, int32_t m,
                          uint32_t* terms_out /*[n_q][m]*/, double* score_out /*[n_q][m] nullable*/, int32_t* n_out /*[n_q]*/);
+
+/* Explain hits: which of the query's tokens matched each result row, with what stored weight, and where in the body.  The reference
+ * cannot say (queries are a pure OR; to find a word it parses the cached HTML of every candidate, retrieval/get_metadata.go:79-209).
+ * What a result card needs for bold matched words, a "Missing: word" line, a snippet anchored at the first occurrence and a
+ * "why is this ranked here" view.  Defined bit for bit:
+ *   Entries.    Entry (q, j, i) = out[(q * k + j) * t_stride + i] describes hit j of query q, hits[q * k + j], and the query's i-th
+ *               TOKEN, q_terms[q_ptr[q] + i].  Token order is kept; duplicate tokens get identical entries.
+ *   Written.    Only entries with j < n_hits[q] and i < q_ptr[q+1] - q_ptr[q] are written; all others are left untouched (the
+ *               convention of ss_index_doc_top_terms and ss_related_terms).
+ *   Read.       Of a hit only .doc is read, and n_hits[q].  The rows may come from any scoring call (ss_score_topk, _phrase, _masked,
+ *               _constrained, ss_similar_topk, ss_merge_hits with local ids) or be made up by the caller.
+ *   Flags.      Bit 0 is set iff the title table has a posting of the term for the doc, at any weight, zero included
+ *               (ss_score_topk_constrained's "contains"); bit 1 the same for the body table.  title_w / body_w are the posting's
+ *               stored float32 BITS (a -0.0 or a NaN comes back as it is): the flag, not the value, says "absent".
+ *   Nothing.    A term id >= n_terms (SS_UNKNOWN_TERM included) has no postings, nor has a doc id >= n_docs: the entry is all zero.
+ *               Defined, not an error; no hit, whatever it holds, makes the kernel read outside the tables.
+ *   body_pos.   Bit 2 is set iff the body table has positional postings (ss_index_set_positions), the body posting exists and its
+ *               position list holds at least one value v with v >= 0 (NaN compares false; so does -100, the marker of anchor / meta
+ *               text, parser/parser.go:195-207).  body_pos is then the smallest such v as a float32 VALUE; a smallest value of zero
+ *               comes back as +0.0 whichever zeros the list holds.  Lists need not be sorted.  An empty list, or one of negative or
+ *               NaN values only, leaves bit 2 clear and body_pos +0.0.  Title positions are not reported.
+ * Checks, all before anything is enqueued and with `out` untouched: NULL handle or out (or hits / n_hits with n_q > 0), n_q < 0,
+ * k < 1, t_stride < 1, a bad q_ptr as in ss_score_topk, a query of more than t_stride tokens: SS_ERR_INVALID; k > SS_MAX_TOPK,
+ * t_stride > SS_MAX_QUERY_TERMS or n_q * k * t_stride >= 2^31: SS_ERR_UNSUPPORTED; n_hits[q] outside [0, k]: SS_ERR_INVALID when
+ * n_hits is host memory, clamped by the kernel when it is device memory.  n_q == 0 is SS_OK and does nothing.
+ * q_ptr / q_terms are read on the host like every query array.  hits / n_hits / out may each be host or device memory: when all three
+ * are device memory the call only enqueues on the ctx stream and NEVER waits, so it can sit right behind an ss_score_topk whose
+ * outputs are device buffers; otherwise it stages through blocks the scorer owns and returns when out is written.
+ * It reads the tables as they stand (scorers are destroyed before an index update and re-created after, as ever), is serialised on
+ * the ctx like the other scoring calls, and has no _submit / _collect form. */
+typedef struct ss_term_match {
+    float    title_w;   /* stored weight bits of the title posting of (term, doc); +0.0 bits if there is none */
+    float    body_w;    /* the same for the body table */
+    uint32_t flags;     /* bit 0: a title posting exists; bit 1: a body posting exists; bit 2: body_pos is valid */
+    float    body_pos;  /* see above; +0.0 bits when bit 2 is clear */
+} ss_term_match;        /* 16 bytes */
+int32_t ss_explain_hits(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                        int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
+                        int32_t t_stride, ss_term_match* out /*[n_q][k][t_stride]*/);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

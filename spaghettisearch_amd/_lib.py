@@ -34,6 +34,10 @@ class SsHit(C.Structure):
                 ("pagerank", C.c_double), ("final", C.c_double)]
 
 
+class SsTermMatch(C.Structure):
+    _fields_ = [("title_w", C.c_float), ("body_w", C.c_float), ("flags", C.c_uint32), ("body_pos", C.c_float)]
+
+
 class SsGraphInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("n_nondangling", C.c_uint64),
                 ("n_rows_local", C.c_uint64), ("n_edges_local", C.c_uint64), ("max_indeg", C.c_uint32),
@@ -110,6 +114,7 @@ PROTOTYPES = {
     "ss_score_topk_constrained": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ss_similar_topk": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_related_terms": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ss_explain_hits": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

@@ -125,6 +125,19 @@ struct ss_scorer {
     ss::DevBuf<double> d_rel_out_score;
     uint32_t* h_rel[TURNS] = {};
     size_t h_rel_cap[TURNS] = {};
+    // ss_explain_hits (explain.hip): the call takes no plan turn (it scores nothing), so it has turns of its own.  Per turn: the pinned
+    // block the queries' table goes up through, its device copy, and an event behind the kernel that read them (waited for before the
+    // block is rewritten: the call never waits for its own copy).  d_exp_hits / _n / _out: device blocks of HOST arrays (grow-only; a
+    // call that uses one waits before it returns).
+    uint32_t* h_exp[TURNS] = {};
+    size_t h_exp_cap[TURNS] = {};
+    ss::DevBuf<uint32_t> d_exp_q[TURNS];
+    hipEvent_t exp_ev[TURNS] = {};
+    bool exp_ev_pending[TURNS] = {};
+    int exp_turn = 0;
+    ss::DevBuf<ss_hit> d_exp_hits;
+    ss::DevBuf<int32_t> d_exp_n;
+    ss::DevBuf<ss_term_match> d_exp_out;
     hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
@@ -158,6 +171,8 @@ struct ss_scorer {
         for (int i = 0; i < TURNS; i++) {
             if (h_plan[i]) (void)hipHostFree(h_plan[i]);
             if (h_rel[i]) (void)hipHostFree(h_rel[i]);
+            if (h_exp[i]) (void)hipHostFree(h_exp[i]);
+            if (exp_ev[i]) (void)hipEventDestroy(exp_ev[i]);
             if (i == 0 && h_res) (void)hipHostFree(h_res);
             if (i == 0 && h_sim) (void)hipHostFree(h_sim);
             if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);

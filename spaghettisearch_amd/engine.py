@@ -12,10 +12,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import SsGraphInfo, SsHit, check
+from ._lib import SsGraphInfo, SsHit, SsTermMatch, check
 
 HIT_DTYPE = np.dtype([("doc", "<u4"), ("_pad", "<u4"), ("title", "<f8"), ("body", "<f8"),
                       ("pagerank", "<f8"), ("final", "<f8")])
+
+TERM_MATCH_DTYPE = np.dtype([("title_w", "<f4"), ("body_w", "<f4"), ("flags", "<u4"), ("body_pos", "<f4")])   # ss_term_match
 
 _NP2T = {"uint64": "int64", "uint32": "int32"}
 
@@ -676,6 +678,44 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return terms, score, n_out
 
+    def explain_hits(self, q_ptr, q_terms, hits, n_hits, t_stride: Optional[int] = None, out=None, k: Optional[int] = None):
+        """ss_explain_hits: per (hit, query token) the stored title / body weight of the (term, doc) posting, whether it exists, and
+        the earliest body position >= 0 -> TERM_MATCH_DTYPE [n_q][k][t_stride].  hits [n_q][k] / n_hits [n_q]: the rows of any scoring
+        call (numpy HIT_DTYPE, or the torch uint8 / int32 device tensors score_topk's `out` takes); k defaults to what hits holds per
+        query.  t_stride
+        defaults to the longest query of the batch.  Entries behind a query's last hit or last token keep what the array held (zeros
+        here).  out: the caller's array (numpy TERM_MATCH_DTYPE, or a torch uint8 device tensor of n_q * k * t_stride * 16 bytes,
+        returned as it is); with device hits, n_hits and out the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        n_hits = _as(n_hits, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        self.ctx.ready(q_ptr)
+        lens = np.diff(q_ptr.cpu().numpy().astype(np.int64) if _is_torch(q_ptr) else q_ptr.astype(np.int64))
+        if t_stride is None:
+            t_stride = max(1, int(lens.max())) if n_q > 0 else 1
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if not _is_torch(hits):
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        else:
+            hits = hits.contiguous()
+        if k is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k) * HIT_DTYPE.itemsize or (n_hits.numel() if _is_torch(n_hits) else n_hits.size) < n_q:
+            raise ValueError("hits / n_hits too small")
+        if out is None:
+            out = np.zeros((n_q, k, int(t_stride)), dtype=TERM_MATCH_DTYPE)
+        elif nbytes(out) < n_q * k * int(t_stride) * TERM_MATCH_DTYPE.itemsize:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(q_terms, hits, n_hits, out)
+        check(self.ctx.lib.ss_explain_hits(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), int(k), _ptr(hits), _ptr(n_hits), int(t_stride),
+                                           _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return out
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""
@@ -705,4 +745,5 @@ class Scorer:
             self.h = None
 
 
-__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "SsHit", "pack_doc_masks"]
+__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "SsHit", "SsTermMatch",
+           "pack_doc_masks"]

@@ -35,6 +35,14 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("TitleRank", &retrieval::Rank_combined::TitleRank)
         .def_readonly("BodyRank", &retrieval::Rank_combined::BodyRank);
 
+    py::class_<retrieval::ResultExplanation>(m, "ResultExplanation")
+        .def_readonly("TitleWords", &retrieval::ResultExplanation::TitleWords)
+        .def_readonly("BodyWords", &retrieval::ResultExplanation::BodyWords)
+        .def_readonly("MissingWords", &retrieval::ResultExplanation::MissingWords)
+        .def_property_readonly("FirstPosition", [](const retrieval::ResultExplanation& e) -> py::object {
+            return e.HasPosition ? py::object(py::float_(e.FirstPosition)) : py::object(py::none());
+        });
+
     auto as_dbs = [](std::vector<db::MemDB*>& v) {
         std::vector<db::DB*> out;
         for (auto* p : v) out.push_back(p);
@@ -134,6 +142,7 @@ PYBIND11_MODULE(_host, m) {
             return di.SimilarPages(docHash, mask, k, m);
         }, py::arg("docHash"), py::arg("mask"), py::arg("k") = 50, py::arg("m") = 5)
         .def("RelatedTerms", &retrieval::DeviceIndex::RelatedTerms, py::arg("query"), py::arg("m") = 10, py::arg("k_fb") = 10, py::arg("m_doc") = 5)
+        .def("ExplainResults", &retrieval::DeviceIndex::ExplainResults, py::arg("query"), py::arg("results"))
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;

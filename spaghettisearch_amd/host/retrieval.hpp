@@ -30,6 +30,15 @@ struct Rank_combined {          // util.go:25-36 (decoration fields are left to 
     double TitleRank = 0, BodyRank = 0;   // diagnostics: the cosine-normalised parts
 };
 
+// Why a row is in a result (DeviceIndex::ExplainResults; no reference counterpart): the query's words, as md5-hex hashes in token
+// order and each once, that the page holds in its title, in its body, and not at all; and the body position of the earliest matched
+// word (the smallest position >= 0 over the query's words; none for a table without positions or a page matched in the title only).
+struct ResultExplanation {
+    std::vector<std::string> TitleWords, BodyWords, MissingWords;
+    bool HasPosition = false;
+    double FirstPosition = 0;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -394,6 +403,59 @@ public:
         check(ss_related_terms(scorer, 1, t.q_ptr.data(), t.q_terms.data(), nullptr, nullptr, nullptr, k_fb, m_doc, m, ids.data(), nullptr, &n),
               "ss_related_terms");
         return term_hashes(ids.data(), n);
+    }
+    // Per row of `results` — the Rank_combined rows Retrieve / RetrieveBatch returned for `query` — which of the query's words matched
+    // where (ss_explain_hits).  The query is tokenised as Retrieve does; the words of quoted phrases count as tokens, behind the
+    // others.  With SetQueryOperators(true) the string is read as RetrieveBatch reads it: '-' tokens leave the query, '+' tokens are
+    // plain words.  A row whose DocHash the index does not hold lacks every word.  Changes nothing unless called.
+    std::vector<ResultExplanation> ExplainResults(const std::string& query, const std::vector<Rank_combined>& results) {
+        using namespace spaghetti;
+        std::string text = query_operators ? parseQueryOperators(query, laundry).query : query;
+        const std::vector<std::string> phrases = getPhrase(text);      // main_retrieve.go:17-36, as tokenise()
+        for (auto& ph : phrases) {
+            const size_t pos = text.find("\"" + ph + "\"");
+            if (pos != std::string::npos) text.erase(pos, ph.size() + 2);
+        }
+        std::string joined;
+        for (auto& ph : phrases) joined += ph + " ";
+        std::vector<std::string> words = laundry(text);
+        for (auto& w : laundry(joined)) words.push_back(w);
+        std::vector<std::string> hashed;
+        for (auto& w : words) hashed.push_back(md5::hex(w));
+        std::vector<ResultExplanation> out(results.size());
+        if (results.empty()) return out;
+        auto add_once = [](std::vector<std::string>& v, const std::string& x) {
+            if (std::find(v.begin(), v.end(), x) == v.end()) v.push_back(x);
+        };
+        const size_t k = results.size(), T = hashed.size();
+        if (T == 0) return out;
+        if (k > (size_t)SS_MAX_TOPK || T > (size_t)SS_MAX_QUERY_TERMS) throw std::runtime_error("ExplainResults: too many rows or query words");
+        std::vector<uint32_t> q_ptr{0, (uint32_t)T}, q_terms;
+        for (auto& h : hashed) {
+            auto it = terms.id.find(h);
+            q_terms.push_back(it == terms.id.end() ? SS_UNKNOWN_TERM : it->second);
+        }
+        std::vector<ss_hit> hits(k);
+        for (size_t j = 0; j < k; j++) {
+            auto it = docs.id.find(results[j].DocHash);
+            hits[j] = ss_hit{};
+            hits[j].doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;      // no such doc: no postings
+        }
+        const int32_t n_hits = (int32_t)k;
+        std::vector<ss_term_match> m(k * T);
+        check(ss_explain_hits(scorer, 1, q_ptr.data(), q_terms.data(), (int32_t)k, hits.data(), &n_hits, (int32_t)T, m.data()), "ss_explain_hits");
+        for (size_t j = 0; j < k; j++)
+            for (size_t i = 0; i < T; i++) {
+                const ss_term_match& e = m[j * T + i];
+                if (e.flags & 1u) add_once(out[j].TitleWords, hashed[i]);
+                if (e.flags & 2u) add_once(out[j].BodyWords, hashed[i]);
+                if (!(e.flags & 3u)) add_once(out[j].MissingWords, hashed[i]);
+                if ((e.flags & 4u) && (!out[j].HasPosition || (double)e.body_pos < out[j].FirstPosition)) {
+                    out[j].HasPosition = true;
+                    out[j].FirstPosition = (double)e.body_pos;
+                }
+            }
+        return out;
     }
     // dense term ids -> word hashes (DocTopTerms, RelatedTerms)
     std::vector<std::string> term_hashes(const uint32_t* ids, int32_t n) const {
