@@ -54,16 +54,21 @@ def pagerank(n_nodes, out_ptr, out_dst, d, eps, n_topic, max_iter=0):
     return np.stack(ranks), np.asarray(iters, dtype=np.int32)
 
 
-def tfidf(term_ptr, post_doc, post_tf, total_docs, n_docs):
+def tfidf(term_ptr, post_doc, post_tf, total_docs, n_docs, idf=None):
     """ranking/term_weighting.go:29-50 + :72 (sqrt).  np.log2 stands in for Go's
-    math.Log2 (may differ in the last float64 bit before narrowing to float32)."""
+    math.Log2 (may differ in the last float64 bit before narrowing to float32);
+    idf (float32 per term), when given, replaces it: weights and magnitudes of this
+    restatement can then be compared with oracle.c bit for bit."""
     term_ptr = np.asarray(term_ptr, dtype=np.int64)
-    df = np.diff(term_ptr).astype(np.float64)
-    with np.errstate(divide="ignore"):
-        idf = np.log2(np.float64(total_docs) / df).astype(np.float32)       # :37
+    if idf is None:
+        df = np.diff(term_ptr).astype(np.float64)
+        with np.errstate(divide="ignore"):
+            idf = np.log2(np.float64(total_docs) / df).astype(np.float32)   # :37
+    idf = np.asarray(idf, dtype=np.float32)
     per_post_idf = np.repeat(idf, np.diff(term_ptr))
-    w = (np.asarray(post_tf, dtype=np.float32) * per_post_idf).astype(np.float32)   # :42
-    sq = (w * w).astype(np.float32).astype(np.float64)                      # :44
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        w = (np.asarray(post_tf, dtype=np.float32) * per_post_idf).astype(np.float32)   # :42
+        sq = (w * w).astype(np.float32).astype(np.float64)                  # :44
     mag2 = np.bincount(np.asarray(post_doc, dtype=np.int64), weights=sq, minlength=n_docs)
     return w, np.sqrt(mag2), idf
 

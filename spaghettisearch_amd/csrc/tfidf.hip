@@ -1142,7 +1142,8 @@ int32_t ss_index_refresh_magnitudes(ss_index* idx, double* mag_out) {
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t P = idx->n_post, N = idx->n_docs;
-    int shift = 13;
+    int shift = 13;                                                   // the same partition as ss_tfidf_build: option, clamp, switch to 14
+    shift = (int)std::max<int64_t>(10, std::min<int64_t>(14, ctx->opt("tfidf.bucket_shift", shift)));
     if ((N >> shift) >= (uint64_t)NB_MAX) shift = 14;
     const uint64_t nb64 = ss::div_up(std::max<uint64_t>(N, 1), (uint64_t)1 << shift);
     const uint64_t min_p = (uint64_t)ctx->opt("tfidf.bucket_min", (int64_t)1 << 22);     // tests, A/B (as in ss_tfidf_build)
