@@ -216,6 +216,58 @@ struct DevBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// Pinned host block that frees itself, grow-only: a block too small is replaced by one of twice the size asked for.  What it held is
+// not kept, and whoever grows it must know that no copy still reads it.  After a failure it is empty ({nullptr, 0}).
+struct PinBuf {
+    unsigned char* p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes) {                  // exactly `bytes`
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    hipError_t ensure(size_t bytes) { return cap >= bytes ? hipSuccess : alloc(bytes * 2); }
+    template <typename T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A hipEventDisableTiming event, created when it is first recorded, and whether a record of it has not been waited for yet.
+// record() is the whole "last reader" handshake of a buffer that comes round again: the event behind the reader and the mark that
+// makes the next owner wait.
+struct Event {
+    hipEvent_t h = nullptr;
+    bool pending = false;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    hipError_t record(hipStream_t st) {
+        hipError_t e = h ? hipSuccess : hipEventCreateWithFlags(&h, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(h, st);
+        if (e == hipSuccess) pending = true;
+        return e;
+    }
+    hipError_t wait() {                               // the host waits for the last record, if nobody has yet
+        if (!pending) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(h);
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+    // `waiter` continues behind what `behind` holds so far
+    hipError_t wait_behind(hipStream_t behind, hipStream_t waiter) {
+        const hipError_t e = record(behind);
+        return e == hipSuccess ? hipStreamWaitEvent(waiter, h, 0) : e;
+    }
+};
+
 inline unsigned div_up(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 
 // comm.hip: collectives on the context's stream (enqueue only); SS_ERR_STATE without a communicator

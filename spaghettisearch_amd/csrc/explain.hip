@@ -140,12 +140,10 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
     hipStream_t st = ctx->stream;
     const size_t nq = (size_t)n_q;
     std::vector<uint32_t> h_ptr(nq + 1);
-    SS_HIP(ctx, ss::copy_in(st, h_ptr.data(), q_ptr, (nq + 1) * sizeof(uint32_t)));
-    for (size_t q = 0; q < nq; q++) {
-        if (h_ptr[q + 1] < h_ptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: q_ptr not non-decreasing");
+    SS_TRY(fetch_ptr_array(ctx, "ss_explain_hits", "q", q_ptr, nq, h_ptr.data()));
+    for (size_t q = 0; q < nq; q++)
         if (h_ptr[q + 1] - h_ptr[q] > (uint32_t)t_stride)
             return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: query %zu has %u tokens, t_stride = %d", q, h_ptr[q + 1] - h_ptr[q], t_stride);
-    }
     const size_t tok0 = h_ptr[0], n_tok = h_ptr[nq] - tok0;
     if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: q_terms is NULL");
     const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits), dev_o = ss::on_device(out);
@@ -156,31 +154,21 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
             if (h_n[q] < 0 || h_n[q] > k) return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: n_hits[%zu] = %d outside 0 .. k = %d", q, h_n[q], k);
     }
     // ---- the queries' table in the pinned block of the next explain turn: ptr [n_q + 1] (from 0) | tokens
-    const int turn = s->exp_turn;
-    if (!s->exp_ev[turn]) SS_HIP(ctx, hipEventCreateWithFlags(&s->exp_ev[turn], hipEventDisableTiming));
-    if (s->exp_ev_pending[turn]) {
-        SS_HIP(ctx, hipEventSynchronize(s->exp_ev[turn]));            // the call TURNS calls ago has read this turn's blocks
-        s->exp_ev_pending[turn] = false;
-    }
+    ExplainTurn& turn = s->exp[s->exp_turn];
+    SS_HIP(ctx, turn.ev.wait());                          // the call TURNS calls ago has read this turn's blocks
     const size_t q_words = nq + 1 + n_tok;
-    if (s->h_exp_cap[turn] < q_words * sizeof(uint32_t)) {
-        if (s->h_exp[turn]) (void)hipHostFree(s->h_exp[turn]);
-        s->h_exp[turn] = nullptr;
-        s->h_exp_cap[turn] = 0;
-        SS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_exp[turn]), q_words * sizeof(uint32_t) * 2, hipHostMallocDefault));
-        s->h_exp_cap[turn] = q_words * sizeof(uint32_t) * 2;
-    }
-    uint32_t* const hq = s->h_exp[turn];
+    SS_HIP(ctx, turn.h_q.ensure(q_words * sizeof(uint32_t)));
+    uint32_t* const hq = turn.h_q.as<uint32_t>();
     for (size_t q = 0; q <= nq; q++) hq[q] = h_ptr[q] - (uint32_t)tok0;
     SS_HIP(ctx, ss::copy_in(st, hq + nq + 1, q_terms ? q_terms + tok0 : nullptr, n_tok * sizeof(uint32_t)));
-    SS_HIP(ctx, ensure(s->d_exp_q[turn], q_words));
+    SS_HIP(ctx, ensure(turn.d_q, q_words));
     const size_t n_rows = nq * (size_t)k, n_ent = n_rows * (size_t)t_stride;
     if (!dev_h) SS_HIP(ctx, ensure(s->d_exp_hits, n_rows));
     if (!dev_n) SS_HIP(ctx, ensure(s->d_exp_n, nq));
     if (!dev_o) SS_HIP(ctx, ensure(s->d_exp_out, n_ent));
-    s->exp_turn = (turn + 1) % ss_scorer::TURNS;
+    s->exp_turn = (s->exp_turn + 1) % ss_scorer::TURNS;
     // ---- the pipeline
-    SS_HIP(ctx, hipMemcpyAsync(s->d_exp_q[turn].p, hq, q_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SS_HIP(ctx, hipMemcpyAsync(turn.d_q.p, hq, q_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     // (host rows and counts: the caller's array and h_n outlive their copies, a call with any host array waits before it returns)
     if (!dev_h) SS_HIP(ctx, hipMemcpyAsync(s->d_exp_hits.p, hits, n_rows * sizeof(ss_hit), hipMemcpyHostToDevice, st));
     if (!dev_n) SS_HIP(ctx, hipMemcpyAsync(s->d_exp_n.p, h_n.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -190,8 +178,8 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
     p.b_pos_ptr = s->body->pos_ptr.p;
     p.b_pos = s->body->pos.p;
     p.n_docs = s->n_docs;
-    p.q_ptr = s->d_exp_q[turn].p;
-    p.q_terms = s->d_exp_q[turn].p + nq + 1;
+    p.q_ptr = turn.d_q.p;
+    p.q_terms = turn.d_q.p + nq + 1;
     p.hits = dev_h ? hits : s->d_exp_hits.p;
     p.n_hits = dev_n ? n_hits : s->d_exp_n.p;
     p.out = dev_o ? out : s->d_exp_out.p;
@@ -199,8 +187,7 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
     p.blocks_per_q = ss::div_up((uint64_t)k * (uint64_t)t_stride, EX_TPB);
     hipLaunchKernelGGL(k_explain_hits, dim3(p.n_q * p.blocks_per_q), dim3(EX_TPB), 0, st, p);   // (< 2^31 / 256 * 2 blocks)
     SS_HIP(ctx, hipGetLastError());
-    SS_HIP(ctx, hipEventRecord(s->exp_ev[turn], st));     // the turn's pinned block and its device copy are read until here
-    s->exp_ev_pending[turn] = true;
+    SS_HIP(ctx, turn.ev.record(st));                      // the turn's pinned block and its device copy are read until here
     if (dev_h && dev_n && dev_o) return SS_OK;            // ordered on the ctx stream; nothing comes back, nothing is waited for
     // ---- staged: wait; a host `out` gets exactly the entries the kernel wrote.  (Device n_hits with a host out: the counts come back
     // too, clamped as the kernel clamps them.)

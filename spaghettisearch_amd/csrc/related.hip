@@ -11,10 +11,10 @@
 //   k_related_terms            one workgroup per query: the entries (term, w, e = j * m_doc + i) sorted by (term, e) in LDS, every
 //                              term's weights summed in float64 in ascending e (= ascending rank j, from 0.0), then m rounds of a
 //                              workgroup-wide maximum over (ordered score, ~term) strictly below the previous winner; writes
-//                              terms_out, score_out and n_out and is the turn's last reader, so batch_ev[turn] is recorded again
+//                              terms_out, score_out and n_out and is the turn's last reader, so the turn's batch_ev is recorded again
 //                              behind it
 // Everything runs on the context's stream and nothing comes back to the host: with device outputs the call never waits.  The
-// queries' own terms go up through a pinned block of the turn (rewritten only after the wait for batch_ev[turn]).
+// queries' own terms go up through a pinned block of the turn (rewritten only after the wait for the turn's batch_ev).
 #include "scorer.hpp"
 
 #include <algorithm>
@@ -211,9 +211,7 @@ int32_t related_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
     hipStream_t st = ctx->stream;
     const size_t nq = (size_t)n_q;
     std::vector<uint32_t> h_ptr(nq + 1);
-    SS_HIP(ctx, ss::copy_in(st, h_ptr.data(), q_ptr, (nq + 1) * sizeof(uint32_t)));
-    for (size_t q = 0; q < nq; q++)
-        if (h_ptr[q + 1] < h_ptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_related_terms: q_ptr not non-decreasing");
+    SS_TRY(fetch_ptr_array(ctx, "ss_related_terms", "q", q_ptr, nq, h_ptr.data()));
     const size_t n_tok = h_ptr[nq];
     if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "ss_related_terms: q_terms is NULL");
     std::vector<uint32_t> h_terms(n_tok);
@@ -225,20 +223,14 @@ int32_t related_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
         return ctx->fail(rc, "ss_related_terms: scoring the queries at k_fb failed: %s", why.c_str());
     }
     if (tr.turn < 0) return ctx->fail(SS_ERR_STATE, "ss_related_terms: internal: the scoring call took no turn");
-    // From here on the turn is taken: whatever happens, batch_ev[turn] stays recorded behind the scoring kernels (enqueue did that),
+    // From here on the turn is taken: whatever happens, the turn's batch_ev stays recorded behind the scoring kernels (enqueue did that),
     // and is recorded again behind k_related_terms, the last reader of the turn's rows and of the turn's pinned block.
     // ---- the queries' own terms, each once (the scoring call has accepted them: at most SS_MAX_QUERY_TERMS distinct per query)
     // pinned block of the turn and its device copy: ptr [n_q + 1] | terms
-    const int turn = tr.turn;
+    Turn& turn = s->turn[tr.turn];
     const size_t q_words = nq + 1 + n_tok;
-    if (s->h_rel_cap[turn] < q_words * sizeof(uint32_t)) {
-        if (s->h_rel[turn]) (void)hipHostFree(s->h_rel[turn]);
-        s->h_rel[turn] = nullptr;
-        s->h_rel_cap[turn] = 0;
-        SS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_rel[turn]), q_words * sizeof(uint32_t) * 2, hipHostMallocDefault));
-        s->h_rel_cap[turn] = q_words * sizeof(uint32_t) * 2;
-    }
-    uint32_t* const hq = s->h_rel[turn];
+    SS_HIP(ctx, turn.h_rel.ensure(q_words * sizeof(uint32_t)));
+    uint32_t* const hq = turn.h_rel.as<uint32_t>();
     uint32_t* const hq_terms = hq + nq + 1;
     uint32_t n_own = 0;
     for (size_t q = 0; q < nq; q++) {
@@ -280,8 +272,7 @@ int32_t related_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
                            (const uint32_t*)s->d_rel_terms.p, (const float*)s->d_rel_w.p, (const int32_t*)s->d_rel_cnt.p, d_qptr, d_qt,
                            (uint32_t)k_fb, (uint32_t)m_doc, (uint32_t)m, np, o_terms, o_score, o_n);
     SS_HIP(ctx, hipGetLastError());
-    SS_HIP(ctx, hipEventRecord(s->batch_ev[turn], st));   // the turn's rows and pinned block are read until here
-    s->batch_ev_pending[turn] = true;
+    SS_HIP(ctx, turn.batch_ev.record(st));                // the turn's rows and pinned block are read until here
     if (dev_t && dev_n && (!score_out || dev_s)) return SS_OK;   // ordered on the ctx stream; nothing comes back, nothing is waited for
     // ---- host outputs
     const bool host_rows = !dev_t || (score_out && !dev_s);

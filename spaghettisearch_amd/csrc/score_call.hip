@@ -177,10 +177,8 @@ int32_t fetch_filter_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
     in.exc_ptr.assign(n_q + 1, 0);
     auto load = [&](const uint32_t* ptr, const uint32_t* terms, std::vector<uint32_t>& hp, std::vector<uint32_t>& ht, const char* what) -> int32_t {
         if (!ptr) return SS_OK;
-        SS_HIP(ctx, ss::copy_in(ctx->stream, hp.data(), ptr, (n_q + 1) * sizeof(uint32_t)));
+        SS_TRY(fetch_ptr_array(ctx, "ss_score_topk_constrained", what, ptr, (size_t)n_q, hp.data()));
         if (hp[0] != 0) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr[0] is %u, not 0", what, hp[0]);
-        for (int q = 0; q < n_q; q++)
-            if (hp[q + 1] < hp[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_ptr not non-decreasing", what);
         ht.resize(hp[n_q]);
         if (hp[n_q] && !terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_constrained: %s_terms is NULL", what);
         if (hp[n_q]) SS_HIP(ctx, ss::copy_in(ctx->stream, ht.data(), terms, ht.size() * sizeof(uint32_t)));
@@ -195,10 +193,8 @@ int32_t fetch_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
     ss_ctx* ctx = s->ctx;
     const int32_t n_q = a.n_q;
     in.qptr.resize(n_q + 1);
-    SS_HIP(ctx, ss::copy_in(ctx->stream, in.qptr.data(), a.q_ptr, (n_q + 1) * sizeof(uint32_t)));
+    SS_TRY(fetch_ptr_array(ctx, "ss_score_topk", "q", a.q_ptr, (size_t)n_q, in.qptr.data()));
     const uint32_t n_tok = in.n_tok = in.qptr[n_q];
-    for (int q = 0; q < n_q; q++)
-        if (in.qptr[q + 1] < in.qptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: q_ptr not non-decreasing");
     if (n_tok && !a.q_terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk: q_terms is NULL");
     in.terms.resize(n_tok);
     if (n_tok) SS_HIP(ctx, ss::copy_in(ctx->stream, in.terms.data(), a.q_terms, n_tok * sizeof(uint32_t)));
@@ -208,9 +204,7 @@ int32_t fetch_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
     if (a.p_ptr) {
         if (!s->title->pos_ptr.p || !s->body->pos_ptr.p)
             return ctx->fail(SS_ERR_STATE, "ss_score_topk_phrase: positional postings not loaded (ss_index_set_positions on both tables)");
-        SS_HIP(ctx, ss::copy_in(ctx->stream, in.pptr.data(), a.p_ptr, (n_q + 1) * sizeof(uint32_t)));
-        for (int q = 0; q < n_q; q++)
-            if (in.pptr[q + 1] < in.pptr[q]) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_ptr not non-decreasing");
+        SS_TRY(fetch_ptr_array(ctx, "ss_score_topk_phrase", "p", a.p_ptr, (size_t)n_q, in.pptr.data()));
         in.pterms.resize(in.pptr[n_q]);
         if (in.pptr[n_q]) {
             if (!a.p_terms) return ctx->fail(SS_ERR_INVALID, "ss_score_topk_phrase: p_terms is NULL");
@@ -758,41 +752,27 @@ int32_t acquire_turn(ss_scorer* s, size_t plan_bytes, size_t n_csets, TurnRows* 
     ss_ctx* ctx = s->ctx;
     const int pb = sb.turn = s->plan_turn;
     s->plan_turn = (s->plan_turn + 1) % ss_scorer::TURNS;
-    if (!s->plan_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->plan_ev[pb], hipEventDisableTiming));
-    if (s->plan_ev_pending[pb]) {                // the copy that last read this buffer (two calls ago) must be over
-        SS_HIP(ctx, hipEventSynchronize(s->plan_ev[pb]));
-        s->plan_ev_pending[pb] = false;
-    }
-    if (s->h_plan_cap[pb] < plan_bytes) {
-        if (s->h_plan[pb]) (void)hipHostFree(s->h_plan[pb]);
-        s->h_plan[pb] = nullptr;
-        s->h_plan_cap[pb] = 0;
-        SS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_plan[pb]), plan_bytes * 2, hipHostMallocDefault));
-        s->h_plan_cap[pb] = plan_bytes * 2;
-    }
-    if (!s->batch_ev[pb]) SS_HIP(ctx, hipEventCreateWithFlags(&s->batch_ev[pb], hipEventDisableTiming));
+    Turn& t = s->turn[pb];
+    SS_HIP(ctx, t.h_plan.ensure(plan_bytes));
     // the batch two calls ago used this turn's device buffers (plan, prep, candidates) and may still be running — in pipelined mode its
     // merge certainly may: the host runs at most two batches ahead, and waits here BEFORE any of those buffers is grown or rewritten
-    if (s->batch_ev_pending[pb]) {
-        SS_HIP(ctx, hipEventSynchronize(s->batch_ev[pb]));
-        s->batch_ev_pending[pb] = false;
-    }
-    SS_HIP(ctx, ensure(s->d_plan2[pb], plan_bytes));
+    SS_HIP(ctx, t.batch_ev.wait());
+    SS_HIP(ctx, ensure(t.d_plan, plan_bytes));
     if (turn_rows) {                             // ss_similar_topk's k + 1 rows: this turn's block, free since the wait above like the sets below
-        SS_HIP(ctx, ensure(s->d_turn_hits[pb], turn_rows->rows));
-        SS_HIP(ctx, ensure(s->d_turn_n[pb], turn_rows->n_q));
-        turn_rows->hits = s->d_turn_hits[pb].p;
-        turn_rows->n_hits = s->d_turn_n[pb].p;
+        SS_HIP(ctx, ensure(t.d_hits, turn_rows->rows));
+        SS_HIP(ctx, ensure(t.d_n, turn_rows->n_q));
+        turn_rows->hits = t.d_hits.p;
+        turn_rows->n_hits = t.d_n.p;
         turn_rows->turn = pb;
     }
     // the call's allowed sets: this turn's buffer, free since the wait above (the batch that last read it is done); exactly the size
     // needed (1.25 MB per set at 10M docs), not grown by half like the other workspaces
     sb.set_stride = std::max<uint64_t>(4, ((s->n_docs + 31) / 32 + 3) & ~(uint64_t)3);
-    if (n_csets && s->d_sets[pb].n < n_csets * sb.set_stride) {
-        const hipError_t e = s->d_sets[pb].alloc(n_csets * sb.set_stride);
+    if (n_csets && t.d_sets.n < n_csets * sb.set_stride) {
+        const hipError_t e = t.d_sets.alloc(n_csets * sb.set_stride);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            s->d_sets[pb].release();
+            t.d_sets.release();
             return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "ss_score_topk_constrained: no device memory for %zu allowed sets of %llu bytes",
                              n_csets, (unsigned long long)(sb.set_stride * sizeof(uint32_t)));
         }
@@ -803,34 +783,34 @@ int32_t acquire_turn(ss_scorer* s, size_t plan_bytes, size_t n_csets, TurnRows* 
 // the turn's device workspaces, grown to this batch's size (grow-only: no hipMalloc / hipFree on the steady-state query path)
 int32_t grow_workspaces(ss_scorer* s, const BatchInputs& in, const BatchPlan& pl, const Route& r, StagedBatch& sb) {
     ss_ctx* ctx = s->ctx;
-    const int pb = sb.turn;
+    Turn& t = s->turn[sb.turn];
     const size_t n_q = (size_t)in.n_q, k = (size_t)in.k;
     hipStream_t st = ctx->stream;
     if (pl.any_phrase) {
         for (int x = 0; x < 4; x++) {
-            SS_HIP(ctx, ensure(s->d_x[pb][x], (size_t)pl.xoff[n_q]));
-            SS_HIP(ctx, ensure(s->d_xw[pb][x], (size_t)pl.xoff[n_q]));
+            SS_HIP(ctx, ensure(t.d_x[x], (size_t)pl.xoff[n_q]));
+            SS_HIP(ctx, ensure(t.d_xw[x], (size_t)pl.xoff[n_q]));
         }
-        SS_HIP(ctx, ensure(s->d_xcnt[pb], n_q * 4));
-        SS_HIP(ctx, ensure(s->d_pcnt[pb], std::max<size_t>(pl.parts.size(), 1) * 2));
+        SS_HIP(ctx, ensure(t.d_xcnt, n_q * 4));
+        SS_HIP(ctx, ensure(t.d_pcnt, std::max<size_t>(pl.parts.size(), 1) * 2));
     }
-    SS_HIP(ctx, ensure(s->d_so_key2[pb], pl.n_slices * k));
-    SS_HIP(ctx, ensure(s->d_so_doc2[pb], pl.n_slices * k));
-    SS_HIP(ctx, ensure(s->d_so_cnt2[pb], pl.n_slices));
+    SS_HIP(ctx, ensure(t.d_so_key, pl.n_slices * k));
+    SS_HIP(ctx, ensure(t.d_so_doc, pl.n_slices * k));
+    SS_HIP(ctx, ensure(t.d_so_cnt, pl.n_slices));
     if (r.small_staged) {
-        SS_HIP(ctx, ensure(s->d_small_stage[pb], pl.n_small * k));
-        SS_HIP(ctx, ensure(s->d_small_stage_n[pb], pl.n_small));
+        SS_HIP(ctx, ensure(t.d_small_stage, pl.n_small * k));
+        SS_HIP(ctx, ensure(t.d_small_stage_n, pl.n_small));
     }
     if (r.fused && s->qticket_zeroed < n_q) {
         SS_HIP(ctx, ensure(s->d_qticket, n_q));
         SS_HIP(ctx, hipMemsetAsync(s->d_qticket.p, 0, n_q * sizeof(uint32_t), st));
         s->qticket_zeroed = n_q;
     }
-    if (!pl.mergeq.empty() && s->qcnt_zeroed2[pb] < n_q) {    // k_merge_flat hands every counter back at zero
-        SS_HIP(ctx, ensure(s->d_qcnt2[pb], n_q));
-        SS_HIP(ctx, hipMemsetAsync(s->d_qcnt2[pb].p, 0, s->d_qcnt2[pb].bytes(), st));
+    if (!pl.mergeq.empty() && t.qcnt_zeroed < n_q) {    // k_merge_flat hands every counter back at zero
+        SS_HIP(ctx, ensure(t.d_qcnt, n_q));
+        SS_HIP(ctx, hipMemsetAsync(t.d_qcnt.p, 0, t.d_qcnt.bytes(), st));
         SS_HIP(ctx, hipStreamSynchronize(st));                        // (first use or growth only) k_score_wave may run on another stream
-        s->qcnt_zeroed2[pb] = s->d_qcnt2[pb].n;
+        t.qcnt_zeroed = t.d_qcnt.n;
     }
     // Small results that go back to the host (a lone query, a handful): hits and counts in ONE device block, one copy into the context's
     // pinned scratch, two host memcpys — a second device-to-host copy costs a lone query ~8 us of its ~0.12 ms (round 5)
@@ -839,21 +819,20 @@ int32_t grow_workspaces(ss_scorer* s, const BatchInputs& in, const BatchPlan& pl
     // (up to 128 KB — 32 queries at k = 100 —: beyond that the extra host copy costs more than the second transfer; a 4 MB batch through
     //  a pinned block measured 0.79 against 0.655 ms in round 4)
     sb.one_copy = !in.dev_out && sb.res_bytes <= ss_scorer::H_RES_BYTES;
-    if (sb.one_copy && !s->h_res && hipHostMalloc(reinterpret_cast<void**>(&s->h_res), ss_scorer::H_RES_BYTES, hipHostMallocDefault) != hipSuccess) {
+    if (sb.one_copy && !s->h_res.p && s->h_res.alloc(ss_scorer::H_RES_BYTES) != hipSuccess) {
         (void)hipGetLastError();
-        s->h_res = nullptr;
         sb.one_copy = false;
     }
     SS_HIP(ctx, ensure(s->d_hits, sb.res_rows + (sb.one_copy ? (n_q * sizeof(int32_t) + sizeof(ss_hit) - 1) / sizeof(ss_hit) : 0)));
     SS_HIP(ctx, ensure(s->d_nhits, n_q));
-    if (pl.n_fast_slices) SS_HIP(ctx, ensure(s->d_wprep2[pb], ss::score_wave_prep_bytes((unsigned)pl.n_fast_slices)));
+    if (pl.n_fast_slices) SS_HIP(ctx, ensure(t.d_wprep, ss::score_wave_prep_bytes((unsigned)pl.n_fast_slices)));
     return SS_OK;
 }
 
 // everything of the kernel parameters that is not a section of the plan: the index, this turn's workspaces, the outputs
 void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const Route& r,
                  StagedBatch& sb) {
-    const int pb = sb.turn;
+    const Turn& t = s->turn[sb.turn];
     const size_t n_csets = cons.sets.size();
     ScoreParams& p = sb.p;
     p.t_ptr = s->title->term_ptr.p; p.t_rec = s->t_rec.p; p.t_w = s->title->post_w.p; p.t_mag = s->title->mag.p; p.t_kth = s->t_kth.p;
@@ -863,9 +842,9 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
     p.t_pos_ptr = s->title->pos_ptr.p; p.t_pos = s->title->pos.p;
     p.b_pos_ptr = s->body->pos_ptr.p; p.b_pos = s->body->pos.p;
     if (pl.any_phrase) {
-        for (int x = 0; x < 4; x++) { p.x_rec[x] = s->d_x[pb][x].p; p.x_w[x] = s->d_xw[pb][x].p; }
-        p.x_cnt = s->d_xcnt[pb].p;
-        p.ph_pcnt = s->d_pcnt[pb].p;
+        for (int x = 0; x < 4; x++) { p.x_rec[x] = t.d_x[x].p; p.x_w[x] = t.d_xw[x].p; }
+        p.x_cnt = t.d_xcnt.p;
+        p.ph_pcnt = t.d_pcnt.p;
     }
     p.prior = in.K ? s->prior.p : nullptr;
     p.k_topics = in.K;
@@ -874,22 +853,22 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
     p.cb_flat = pl.cb_flat;
     p.kth_j = pl.kth_j;
     p.exact_all = pl.exact_all ? 1 : 0;
-    p.so_key = s->d_so_key2[pb].p; p.so_doc = s->d_so_doc2[pb].p; p.so_cnt = s->d_so_cnt2[pb].p;
+    p.so_key = t.d_so_key.p; p.so_doc = t.d_so_doc.p; p.so_cnt = t.d_so_cnt.p;
     p.q_ticket = r.fused ? s->d_qticket.p : nullptr;
-    p.qc_cnt = s->d_qcnt2[pb].p;
+    p.qc_cnt = t.d_qcnt.p;
     p.small_q = nullptr;
     p.small_stride = (uint32_t)pl.small_stride;
-    p.small_stage = r.small_staged ? s->d_small_stage[pb].p : nullptr;
-    p.small_stage_n = r.small_staged ? s->d_small_stage_n[pb].p : nullptr;
+    p.small_stage = r.small_staged ? t.d_small_stage.p : nullptr;
+    p.small_stage_n = r.small_staged ? t.d_small_stage_n.p : nullptr;
     p.hits = a.turn_rows ? a.turn_rows->hits : in.dev_out ? a.hits_out : s->d_hits.p;
     p.n_hits = a.turn_rows ? a.turn_rows->n_hits : in.dev_out ? a.n_hits_out : sb.one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + sb.res_rows) : s->d_nhits.p;
-    p.masks = n_csets ? s->d_sets[pb].p : in.any_mask ? s->masks.p : nullptr;
+    p.masks = n_csets ? t.d_sets.p : in.any_mask ? s->masks.p : nullptr;
     p.mask_words = n_csets ? sb.set_stride : s->mask_words;
     if (n_csets) {
         ConstraintParams& cp = sb.cp;
         cp.t_doc = s->title->post_doc.p; cp.b_doc = s->body->post_doc.p;
         cp.reg_masks = s->masks.p; cp.reg_words = s->mask_words;
-        cp.out = s->d_sets[pb].p;
+        cp.out = t.d_sets.p;
         cp.stride = sb.set_stride;
         cp.n_words = (s->n_docs + 31) / 32;
         cp.n_blocks = ss::constraint_blocks(sb.set_stride);
@@ -903,7 +882,7 @@ int32_t stage_plan(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const
     plan_sections(measure, in, cons, pl, sb.p, sb.cp);
     sb.plan_bytes = measure.o;
     SS_TRY(acquire_turn(s, sb.plan_bytes, cons.sets.size(), a.turn_rows, sb));
-    PlanWriter w{s->h_plan[sb.turn], s->d_plan2[sb.turn].p, 0};
+    PlanWriter w{s->turn[sb.turn].h_plan.p, s->turn[sb.turn].d_plan.p, 0};
     unsigned char* tab = plan_sections(w, in, cons, pl, sb.p, sb.cp);
     // k_score_small's table: the 1024-slot queries first, then the larger ones (launch_score_small)
     for (const std::vector<SmallEnt>* v : {&pl.small_a, &pl.small_b})
@@ -919,18 +898,10 @@ int32_t stage_plan(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const
 }
 
 // ---- 6. upload and launches ------------------------------------------------------------------------------------------------
-// `waiter` continues behind what `behind` holds so far
-hipError_t wait_behind(hipEvent_t& ev, hipStream_t behind, hipStream_t waiter) {
-    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ev, behind);
-    if (e == hipSuccess) e = hipStreamWaitEvent(waiter, ev, 0);
-    return e;
-}
-
 // The plan's upload.  *prep_done: k_wave_prep went out with it.
 int32_t upload_plan(ss_scorer* s, const BatchInputs& in, const BatchPlan& pl, const Route& r, const StagedBatch& sb, bool* prep_done) {
     ss_ctx* ctx = s->ctx;
-    const int pb = sb.turn;
+    const Turn& t = s->turn[sb.turn];
     // The upload goes out on the context's SECOND stream as soon as the plan is staged — beside the kernels of the previous
     // batch, which read the other device buffer.  (On the one stream the copy sat
     // between two batches: 39 us per batch in the kernel trace with the counter memset, 6 % of the wall time at config 3.)
@@ -938,16 +909,16 @@ int32_t upload_plan(ss_scorer* s, const BatchInputs& in, const BatchPlan& pl, co
     if (!in.dev_out) {
         // results go back to the host: the call waits for them anyway, and a second wait in the middle would only add to a lone
         // query's latency (0.15 ms, of which 0.08 are kernels): copy, kernels and read-back follow each other on the one stream
-        SS_HIP(ctx, hipMemcpyAsync(s->d_plan2[pb].p, s->h_plan[pb], sb.plan_bytes, hipMemcpyHostToDevice, ctx->stream));
+        SS_HIP(ctx, hipMemcpyAsync(t.d_plan.p, t.h_plan.p, sb.plan_bytes, hipMemcpyHostToDevice, ctx->stream));
         return SS_OK;
     }
-    SS_HIP(ctx, hipMemcpyAsync(s->d_plan2[pb].p, s->h_plan[pb], sb.plan_bytes, hipMemcpyHostToDevice, ctx->comm_stream));
+    SS_HIP(ctx, hipMemcpyAsync(t.d_plan.p, t.h_plan.p, sb.plan_bytes, hipMemcpyHostToDevice, ctx->comm_stream));
     // k_wave_prep reads the plan and the index, nothing of an earlier batch.  Unpipelined it follows the copy on the second
     // stream and so runs beside the previous batch's kernels (12 us of kernel and one launch gap per batch off the caller's
     // stream); pipelined it is enqueued on the wave stream in front of its k_score_wave (it finds no room beside the previous
     // batch's k_score_wave anyway: 3 x 168 VGPRs per SIMD).
     if (pl.n_fast_slices && !r.pipe) {
-        ss::launch_wave_prep(&sb.p, (unsigned)pl.n_fast_slices, s->d_wprep2[pb].p, ctx->comm_stream);
+        ss::launch_wave_prep(&sb.p, (unsigned)pl.n_fast_slices, t.d_wprep.p, ctx->comm_stream);
         *prep_done = true;
     }
     // ... and the HOST waits for the second stream (~30 us; it has 0.4 ms to spare per batch): the kernels then go out with no
@@ -980,7 +951,7 @@ int32_t bind_streams(ss_scorer* s, const ScoreOptions& opt, Route& r) {
 int32_t enqueue(ss_scorer* s, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const ScoreOptions& opt, Route& r,
                 const StagedBatch& sb, Stamps& t) {
     ss_ctx* ctx = s->ctx;
-    const int pb = sb.turn;
+    Turn& turn = s->turn[sb.turn];
     const ScoreParams& p = sb.p;
     const size_t n_csets = cons.sets.size();
     const unsigned n_fast = (unsigned)pl.n_fast_slices;
@@ -991,7 +962,7 @@ int32_t enqueue(ss_scorer* s, const BatchInputs& in, const ConstraintPlan& cons,
     SS_TRY(bind_streams(s, opt, r));
     if (n_csets) {                               // the allowed sets, in front of the kernels that read them (never k_score_wave)
         ss::launch_constraint_masks(&sb.cp, (uint32_t)n_csets, r.sst);
-        if (pl.n_small && r.small_st != r.sst) SS_HIP(ctx, wait_behind(s->set_ev[pb], r.sst, r.small_st));
+        if (pl.n_small && r.small_st != r.sst) SS_HIP(ctx, turn.set_ev.wait_behind(r.sst, r.small_st));
     }
     if (pl.n_small) {                  // writes its queries' hits itself: the caller's stream, like every kernel that does — or stages them
         const int32_t rc_s = ss::launch_score_small(&p, (unsigned)pl.n_small_a, (unsigned)pl.n_small_b, r.small_st);
@@ -1000,26 +971,25 @@ int32_t enqueue(ss_scorer* s, const BatchInputs& in, const ConstraintPlan& cons,
     // the phrase matches, in front of the kernel that merges them in (k_score_slices)
     if (pl.any_phrase) ss::launch_phrase(&p, (unsigned)pl.parts.size(), (unsigned)in.n_q, r.sst);
     if (n_fast) {
-        if (!prep_done) ss::launch_wave_prep(&p, n_fast, s->d_wprep2[pb].p, r.wst);
-        ss::launch_score_wave(&p, n_fast, s->d_wprep2[pb].p, r.wst);
+        if (!prep_done) ss::launch_wave_prep(&p, n_fast, turn.d_wprep.p, r.wst);
+        ss::launch_score_wave(&p, n_fast, turn.d_wprep.p, r.wst);
     }
     if (pl.n_slices > n_fast)
         SS_HIP(ctx, ss::launch_score_slices(&p, n_fast, (unsigned)(pl.n_slices - n_fast), in.any_mask, &s->lds_attr, &s->lds_attr_masked, r.sst));
     // the merge, on the caller's stream, behind this batch's k_score_slices
-    if (r.pipe_s) SS_HIP(ctx, wait_behind(s->wave_ev[pb], r.wst, r.st));
-    if (r.pipe_split || r.small_side) SS_HIP(ctx, wait_behind(s->slice_ev[pb], r.sst, r.st));
-    if (r.small_alone) SS_HIP(ctx, wait_behind(s->wave_ev[pb], r.wst, r.st));
+    if (r.pipe_s) SS_HIP(ctx, turn.wave_ev.wait_behind(r.wst, r.st));
+    if (r.pipe_split || r.small_side) SS_HIP(ctx, turn.slice_ev.wait_behind(r.sst, r.st));
+    if (r.small_alone) SS_HIP(ctx, turn.wave_ev.wait_behind(r.wst, r.st));
     if (r.small_staged) ss::launch_small_copy(&p, (unsigned)pl.n_small, r.st);
     if (!r.fused && pl.n_slices > n_fast) ss::launch_merge_topk(&p, (unsigned)in.n_q, r.st);
     // the merge, on the caller's stream, behind this batch's k_score_wave
-    if (r.pipe) SS_HIP(ctx, wait_behind(s->wave_ev[pb], r.wst, r.st));
+    if (r.pipe) SS_HIP(ctx, turn.wave_ev.wait_behind(r.wst, r.st));
     if (!pl.mergeq.empty()) ss::launch_merge_flat(&p, (unsigned)pl.mergeq.size(), r.st);
     if (opt.timed) {                             // (pipelined: from the end of the previous batch's merge to the end of this one's)
         SS_HIP(ctx, hipEventRecord(ctx->ev[1][1], r.st));
         ctx->ev_valid[1] = true;
     }
-    SS_HIP(ctx, hipEventRecord(s->batch_ev[pb], r.st));
-    s->batch_ev_pending[pb] = true;
+    SS_HIP(ctx, turn.batch_ev.record(r.st));       // until here the batch reads the turn's buffers; a later reader of its rows records again
     SS_HIP(ctx, hipGetLastError());
     return SS_OK;
 }
@@ -1030,7 +1000,7 @@ int32_t read_back(ss_scorer* s, const CallArgs& a, const StagedBatch& sb) {
     hipStream_t st = ctx->stream;
     const size_t n_q = (size_t)a.n_q;
     if (sb.one_copy) {
-        unsigned char* const hp1 = s->h_res;
+        unsigned char* const hp1 = s->h_res.p;
         SS_HIP(ctx, hipMemcpyAsync(hp1, s->d_hits.p, sb.res_bytes, hipMemcpyDeviceToHost, st));
         SS_HIP(ctx, hipStreamSynchronize(st));
         std::memcpy(a.hits_out, hp1, sb.res_rows * sizeof(ss_hit));
@@ -1162,7 +1132,6 @@ int32_t ss_score_topk_submit(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
     const size_t rows = (size_t)n_q * (size_t)k;
     if (a->hits.n < rows) SS_HIP(ctx, a->hits.alloc(rows + rows / 4));
     if (a->n_hits.n < (size_t)n_q) SS_HIP(ctx, a->n_hits.alloc((size_t)n_q + 64));
-    if (!a->ev) SS_HIP(ctx, hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
     a->pin_mode = ctx->opt("score.collect_pinned", 0) != 0;
     if (a->pin_mode) {
         const size_t bytes = rows * sizeof(ss_hit) + (size_t)n_q * sizeof(int32_t);
@@ -1187,7 +1156,7 @@ int32_t ss_score_topk_submit(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
         // between two merges that the wave kernel stretches (period 0.48 ms instead of 0.345), on a stream of its own it shared a
         // hardware queue with a wave stream (0.59).  At collect time the batch is finished, the copy takes its 85 us and blocks
         // nothing: the host spends 0.13 ms in submit and 0.09 in collect per batch, under the 0.345 ms the device needs.]
-        SS_HIP(ctx, hipEventRecord(a->ev, ctx->stream));
+        SS_HIP(ctx, a->ev.record(ctx->stream));
     }
     a->n_q = n_q;
     a->k = k;
@@ -1220,7 +1189,7 @@ int32_t ss_score_topk_collect(ss_scorer* s, uint64_t ticket, ss_hit* hits_out, i
         a->collecting = true;                   // (a second collect of the same ticket from another thread is refused, not raced)
         trace = ctx->opt("score.trace", 0) != 0;
         pin_mode = a->pin_mode;
-        n_q = a->n_q; k = a->k; ev = a->ev; out_stream = s->out_stream;
+        n_q = a->n_q; k = a->k; ev = a->ev.h; out_stream = s->out_stream;
         d_hits = a->hits.p; d_n = a->n_hits.p; pin = a->pin; pin_n = a->pin_n;
     }
     // (the wait and the copies run outside the context's lock: another thread may submit the next batch meanwhile; the slot itself

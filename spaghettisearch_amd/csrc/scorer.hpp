@@ -41,7 +41,7 @@ void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st
 
 // Where a scoring call left its rows when they stay inside the scorer (ss::score_into_turn): the block of the plan turn the call took.
 // The block is that turn's until the turn comes round again, i.e. until the scorer has waited for the turn's batch_ev: whoever reads it
-// on the context's stream records batch_ev[turn] again behind the reader.
+// on the context's stream records the turn's batch_ev again behind the reader.
 struct TurnRows {
     size_t rows = 0, n_q = 0;                   // in: hits and counts to make room for
     ss_hit* hits = nullptr;                     // out: [n_q][k]
@@ -53,6 +53,40 @@ namespace ss {
 int32_t score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
                         const int32_t* mask_id, int32_t k, TurnRows* out, const int32_t* query_len = nullptr);
 }  // namespace ss
+
+// Everything one plan turn owns.  A scoring call takes the next turn (acquire_turn) and waits for batch_ev there, i.e. for the batch
+// that used the turn TURNS calls ago, before any of these buffers is grown or rewritten.
+struct Turn {
+    // pinned staging for the plan, double-buffered: a call that returns results in device memory does not wait
+    // for the GPU, so the next call plans (and fills the other buffer) while this one's copy and kernels run
+    ss::PinBuf h_plan;
+    ss::DevBuf<unsigned char> d_plan, d_wprep; // the plan on the device, one buffer per turn: batch i+1's upload runs beside batch i's kernels
+    ss::DevBuf<Rec> d_x[4];                    // phrase result lists: scoring records (one set per turn: batches overlap)
+    ss::DevBuf<float> d_xw[4];                 // ... and their float32 weight sums
+    ss::DevBuf<uint32_t> d_xcnt, d_pcnt;
+    ss::DevBuf<uint64_t> d_so_key;             // the slices' candidates, one set per turn ("score.pipeline": batch i's merge reads its set while batch i+1 fills the other)
+    ss::DevBuf<uint32_t> d_so_doc, d_so_cnt, d_qcnt;
+    size_t qcnt_zeroed = 0;                    // counters known to be zero (k_merge_flat leaves its query's counter at zero)
+    ss::DevBuf<ss_hit> d_small_stage;          // k_score_small's rows of a pipelined batch (k_small_copy moves them on the caller's stream)
+    ss::DevBuf<int32_t> d_small_stage_n;
+    ss::DevBuf<uint32_t> d_sets;               // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
+    ss::DevBuf<ss_hit> d_hits;                 // ss_similar_topk / ss_related_terms: the batch's rows, read by k_drop_seed / k_hit_docs on the caller's stream
+    ss::DevBuf<int32_t> d_n;
+    ss::PinBuf h_rel;                          // ss_related_terms: the queries' own terms go up through it (see d_rel_q below)
+    ss::Event batch_ev;                        // recorded behind the kernels of the batch that read this turn's buffers, and again behind whoever reads the turn's rows last
+    ss::Event wave_ev;                         // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
+    ss::Event slice_ev;                        // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
+    ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
+};
+
+// ss_explain_hits (explain.hip): the call takes no plan turn (it scores nothing), so it has turns of its own.  Per turn: the pinned
+// block the queries' table goes up through, its device copy, and an event behind the kernel that read them (waited for before the
+// block is rewritten: the call never waits for its own copy).
+struct ExplainTurn {
+    ss::PinBuf h_q;
+    ss::DevBuf<uint32_t> d_q;
+    ss::Event ev;
+};
 
 struct ss_scorer {
     ss_ctx* ctx = nullptr;
@@ -86,61 +120,31 @@ struct ss_scorer {
 #endif
     static constexpr int TURNS = SS_TURNS;
     unsigned wave_turn = 0;                    // which wave stream the next pipelined batch takes
-    ss::DevBuf<unsigned char> d_plan2[TURNS], d_wprep2[TURNS];   // the plan on the device, one buffer per turn: batch i+1's upload runs beside batch i's kernels
-    // pinned staging for the plan, double-buffered: a call that returns results in device memory does not wait
-    // for the GPU, so the next call plans (and fills the other buffer) while this one's copy and kernels run
-    unsigned char* h_plan[TURNS] = {};
-    size_t h_plan_cap[TURNS] = {};
-    unsigned char* h_res = nullptr;  // pinned landing block of small host results (one device-to-host copy for hits + counts)
-    static constexpr size_t H_RES_BYTES = 128 << 10;
-    hipEvent_t plan_ev[TURNS] = {}; // recorded after the H2D copy of the buffer (on the context's second stream)
-    hipEvent_t batch_ev[TURNS] = {};// recorded behind the kernels of the batch that read device buffer [turn]
-    bool batch_ev_pending[TURNS] = {};
-    size_t qcnt_zeroed2[TURNS] = {};           // counters known to be zero (k_merge_flat leaves its query's counter at zero)
-    bool plan_ev_pending[TURNS] = {};
+    Turn turn[TURNS];
     int plan_turn = 0;
-    ss::DevBuf<Rec> d_x[TURNS][4];              // phrase result lists: scoring records (one set per turn: batches overlap)
-    ss::DevBuf<float> d_xw[TURNS][4];           // ... and their float32 weight sums
-    ss::DevBuf<uint32_t> d_xcnt[TURNS], d_pcnt[TURNS];
-    ss::DevBuf<uint64_t> d_so_key2[TURNS];           // the slices' candidates, one set per turn ("score.pipeline": batch i's merge reads its set while batch i+1 fills the other)
-    ss::DevBuf<uint32_t> d_so_doc2[TURNS], d_so_cnt2[TURNS], d_qticket, d_qcnt2[TURNS];
-    ss::DevBuf<ss_hit> d_small_stage[TURNS];         // k_score_small's rows of a pipelined batch (k_small_copy moves them on the caller's stream)
-    ss::DevBuf<int32_t> d_small_stage_n[TURNS];
-    ss::DevBuf<uint32_t> d_sets[TURNS];              // ss_score_topk_constrained: the batch's allowed sets [n_sets][stride], built by k_constraint_masks
-    hipEvent_t set_ev[TURNS] = {};                   // ... behind k_constraint_masks, when k_score_small runs on another stream
-    ss::DevBuf<ss_hit> d_turn_hits[TURNS];           // ss_similar_topk / ss_related_terms: the batch's rows, read by k_drop_seed / k_hit_docs on the caller's stream
-    ss::DevBuf<int32_t> d_turn_n[TURNS];
+    ss::PinBuf h_res;                // pinned landing block of small host results (one device-to-host copy for hits + counts)
+    static constexpr size_t H_RES_BYTES = 128 << 10;
+    ss::DevBuf<uint32_t> d_qticket;
+    size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
     // ss_similar_topk's seeds, their terms and term counts: written and read on the context's stream only (grow-only), the terms
     // brought to the host through a pinned block
     ss::DevBuf<uint32_t> d_sim_seeds, d_sim_terms;
     ss::DevBuf<int32_t> d_sim_cnt;
-    unsigned char* h_sim = nullptr;
-    size_t h_sim_cap = 0;
+    ss::PinBuf h_sim;
     // ss_related_terms (related.hip): the hits' docs, their heaviest terms (ids, weights, counts), the queries' own terms and the
     // device blocks of host outputs: written and read on the context's stream only (grow-only).  The queries' own terms go up through a
-    // pinned block per turn, rewritten only after the wait for batch_ev[turn]: the call never waits for its own copy.
+    // pinned block per turn (Turn::h_rel), rewritten only after the wait for the turn's batch_ev: the call never waits for its own copy.
     ss::DevBuf<uint32_t> d_rel_docs, d_rel_terms, d_rel_q, d_rel_out_terms;
     ss::DevBuf<float> d_rel_w;
     ss::DevBuf<int32_t> d_rel_cnt;
     ss::DevBuf<double> d_rel_out_score;
-    uint32_t* h_rel[TURNS] = {};
-    size_t h_rel_cap[TURNS] = {};
-    // ss_explain_hits (explain.hip): the call takes no plan turn (it scores nothing), so it has turns of its own.  Per turn: the pinned
-    // block the queries' table goes up through, its device copy, and an event behind the kernel that read them (waited for before the
-    // block is rewritten: the call never waits for its own copy).  d_exp_hits / _n / _out: device blocks of HOST arrays (grow-only; a
-    // call that uses one waits before it returns).
-    uint32_t* h_exp[TURNS] = {};
-    size_t h_exp_cap[TURNS] = {};
-    ss::DevBuf<uint32_t> d_exp_q[TURNS];
-    hipEvent_t exp_ev[TURNS] = {};
-    bool exp_ev_pending[TURNS] = {};
+    // ss_explain_hits: its own turns; d_exp_hits / _n / _out: device blocks of HOST arrays (grow-only; a call that uses one waits
+    // before it returns).
+    ExplainTurn exp[TURNS];
     int exp_turn = 0;
     ss::DevBuf<ss_hit> d_exp_hits;
     ss::DevBuf<int32_t> d_exp_n;
     ss::DevBuf<ss_term_match> d_exp_out;
-    hipEvent_t wave_ev[TURNS] = {};  // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
-    hipEvent_t slice_ev[TURNS] = {}; // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
-    size_t qticket_zeroed = 0;         // tickets known to be zero (every fused call leaves them so)
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
@@ -148,7 +152,7 @@ struct ss_scorer {
     struct AsyncSlot {
         ss::DevBuf<ss_hit> hits;
         ss::DevBuf<int32_t> n_hits;
-        hipEvent_t ev = nullptr;             // behind the batch's kernels on the caller's stream
+        ss::Event ev;                        // behind the batch's kernels on the caller's stream
         void* pin = nullptr;                 // "score.collect_pinned": the copy-out lands here first
         size_t pin_cap = 0;
         bool pin_mode = false;
@@ -161,25 +165,12 @@ struct ss_scorer {
     uint64_t next_ticket = 1;
     hipStream_t out_stream = nullptr;        // collect's copies
     ss::DevBuf<int32_t> d_nhits;
+    // What the members cannot do themselves.  (ss_scorer_destroy has set the device and drained the context's streams before this runs.)
     ~ss_scorer() {
         if (out_stream) { (void)hipStreamSynchronize(out_stream); (void)hipStreamDestroy(out_stream); }
         for (auto& a : aslot) {
-            if (a.ev) (void)hipEventDestroy(a.ev);
             if (a.pin) ctx->pin_free(a.pin, a.pin_cap);
             if (a.pin_n) ctx->pin_free(a.pin_n, a.pin_n_cap);
-        }
-        for (int i = 0; i < TURNS; i++) {
-            if (h_plan[i]) (void)hipHostFree(h_plan[i]);
-            if (h_rel[i]) (void)hipHostFree(h_rel[i]);
-            if (h_exp[i]) (void)hipHostFree(h_exp[i]);
-            if (exp_ev[i]) (void)hipEventDestroy(exp_ev[i]);
-            if (i == 0 && h_res) (void)hipHostFree(h_res);
-            if (i == 0 && h_sim) (void)hipHostFree(h_sim);
-            if (plan_ev[i]) (void)hipEventDestroy(plan_ev[i]);
-            if (batch_ev[i]) (void)hipEventDestroy(batch_ev[i]);
-            if (wave_ev[i]) (void)hipEventDestroy(wave_ev[i]);
-            if (slice_ev[i]) (void)hipEventDestroy(slice_ev[i]);
-            if (set_ev[i]) (void)hipEventDestroy(set_ev[i]);
         }
     }
 };
@@ -190,6 +181,16 @@ inline hipError_t ensure(ss::DevBuf<T>& b, size_t n) {
     return b.alloc(n + n / 2 + 16);
 }
 inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// A pointer array of the ABI (`name`_ptr: n + 1 offsets, host or device memory) copied to `dst` and checked to be non-decreasing;
+// `entry`: the entry point the caller sees in the error.  What else a site demands of its array (a first offset of 0, a bound on
+// every step) it checks itself.
+inline int32_t fetch_ptr_array(ss_ctx* ctx, const char* entry, const char* name, const uint32_t* src, size_t n, uint32_t* dst) {
+    SS_HIP(ctx, ss::copy_in(ctx->stream, dst, src, (n + 1) * sizeof(uint32_t)));
+    for (size_t q = 0; q < n; q++)
+        if (dst[q + 1] < dst[q]) return ctx->fail(SS_ERR_INVALID, "%s: %s_ptr not non-decreasing", entry, name);
+    return SS_OK;
+}
 
 // the constraint arrays of ss_score_topk_constrained (NULL pointers: none)
 struct QueryConstraints { const uint32_t *req_ptr, *req_terms, *exc_ptr, *exc_terms; };

@@ -9,7 +9,7 @@
 //                              block of the plan turn the call took
 //   k_drop_seed                on the context's stream: an ordered copy of every row that skips the seed, cut to k; writes hits_out
 //                              and n_hits_out (zero rows behind the last hit, as the scoring kernels leave them) and is the turn's
-//                              last reader, so batch_ev[turn] is recorded again behind it
+//                              last reader, so the turn's batch_ev is recorded again behind it
 #include "scorer.hpp"
 
 namespace {
@@ -80,26 +80,21 @@ int32_t similar_impl(ss_scorer* s, int32_t n_q, const uint32_t* seeds, int32_t m
     // pinned block: terms [n_q][m] | counts [n_q] | seeds [n_q]
     const size_t cnt_off = align16(n_terms_max * sizeof(uint32_t)), seed_off = align16(cnt_off + nq * sizeof(int32_t));
     const size_t h_bytes = seed_off + nq * sizeof(uint32_t);
-    if (s->h_sim_cap < h_bytes) {
-        if (s->h_sim) (void)hipHostFree(s->h_sim);
-        s->h_sim = nullptr;
-        s->h_sim_cap = 0;
-        SS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&s->h_sim), h_bytes * 2, hipHostMallocDefault));
-        s->h_sim_cap = h_bytes * 2;
-    }
+    SS_HIP(ctx, s->h_sim.ensure(h_bytes));
+    unsigned char* const h_sim = s->h_sim.p;
     SS_HIP(ctx, ensure(s->d_sim_seeds, nq));
     SS_HIP(ctx, ensure(s->d_sim_terms, n_terms_max));
     SS_HIP(ctx, ensure(s->d_sim_cnt, nq));
     // (the seeds go up through the pinned block: an asynchronous copy; the wait for the terms below covers it)
-    std::memcpy(s->h_sim + seed_off, h_seeds.data(), nq * sizeof(uint32_t));
-    SS_HIP(ctx, hipMemcpyAsync(s->d_sim_seeds.p, s->h_sim + seed_off, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::memcpy(h_sim + seed_off, h_seeds.data(), nq * sizeof(uint32_t));
+    SS_HIP(ctx, hipMemcpyAsync(s->d_sim_seeds.p, h_sim + seed_off, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     ss::launch_doc_top_terms(s->body, s->d_sim_seeds.p, (uint64_t)nq, m, s->d_sim_terms.p, nullptr, s->d_sim_cnt.p, st);
     SS_HIP(ctx, hipGetLastError());
-    SS_HIP(ctx, hipMemcpyAsync(s->h_sim, s->d_sim_terms.p, n_terms_max * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipMemcpyAsync(s->h_sim + cnt_off, s->d_sim_cnt.p, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(ctx, hipMemcpyAsync(h_sim, s->d_sim_terms.p, n_terms_max * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(ctx, hipMemcpyAsync(h_sim + cnt_off, s->d_sim_cnt.p, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     SS_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t* const h_terms = reinterpret_cast<const uint32_t*>(s->h_sim);
-    const int32_t* const h_cnt = reinterpret_cast<const int32_t*>(s->h_sim + cnt_off);
+    const uint32_t* const h_terms = reinterpret_cast<const uint32_t*>(h_sim);
+    const int32_t* const h_cnt = reinterpret_cast<const int32_t*>(h_sim + cnt_off);
     std::vector<uint32_t> q_ptr(nq + 1, 0), q_terms;
     q_terms.reserve(n_terms_max);
     for (size_t q = 0; q < nq; q++) {
@@ -124,8 +119,7 @@ int32_t similar_impl(ss_scorer* s, int32_t n_q, const uint32_t* seeds, int32_t m
     hipLaunchKernelGGL(k_drop_seed, dim3(ss::div_up(nq, DS_WAVES)), dim3(DS_WAVES * 64), 0, st, (const ss_hit*)tr.hits, (const int32_t*)tr.n_hits,
                        (const uint32_t*)s->d_sim_seeds.p, n_q, k, d_hits, d_n);
     SS_HIP(ctx, hipGetLastError());
-    SS_HIP(ctx, hipEventRecord(s->batch_ev[tr.turn], st));    // the turn's rows are read until here
-    s->batch_ev_pending[tr.turn] = true;
+    SS_HIP(ctx, s->turn[tr.turn].batch_ev.record(st));        // the turn's rows are read until here
     if (dev_out) return SS_OK;                          // ordered on the ctx stream, as ss_score_topk's device outputs
     SS_HIP(ctx, hipMemcpyAsync(hits_out, d_hits, nq * (size_t)k * sizeof(ss_hit), hipMemcpyDefault, st));
     SS_HIP(ctx, hipMemcpyAsync(n_hits_out, d_n, nq * sizeof(int32_t), hipMemcpyDefault, st));

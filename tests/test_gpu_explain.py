@@ -141,6 +141,38 @@ def test_rows_of_score_topk_equal_the_model(ss_ctx, world, scorer, k, t_stride):
     assert got.tobytes() == model(world, q_ptr, q_terms, hits, clamped, t_stride).tobytes()
 
 
+def test_turn_blocks_regrown_under_queued_calls(ss_ctx, world, scorer):
+    """Seven device-only calls back to back, more than twice the scorer's three turns, nothing waited for in between.  The batches
+    hold 3, 40, 7, 64, 1, 64 and 5 queries (windows of the world's seven queries taken round and round), so the calls of 64 meet their
+    turn's pinned block and device copy too small and replace them while the two calls before them are still queued.  Every output
+    then equals the host-output call on the same window, byte for byte."""
+    import torch
+    sc, ti, bi = scorer
+    lib = ss_ctx.lib
+    k, t_stride = 10, world["longest"]
+    seven = [world["q_terms"][world["q_ptr"][q]:world["q_ptr"][q + 1]].tolist() for q in range(7)]
+    q_ptr, q_terms = queries([seven[i % 7] for i in range(64)])
+    hits, n_hits = sc.score_topk(q_ptr, q_terms, k)
+    calls = []
+    for n, first in zip((3, 40, 7, 64, 1, 64, 5), (0, 11, 50, 0, 33, 0, 20)):
+        qp = (q_ptr[first:first + n + 1] - q_ptr[first]).astype(np.uint32)
+        qt = np.ascontiguousarray(q_terms[q_ptr[first]:q_ptr[first + n]])
+        h, nh = np.ascontiguousarray(hits[first:first + n]), np.ascontiguousarray(n_hits[first:first + n])
+        calls.append({"n": n, "qp": qp, "qt": qt, "h": h, "nh": nh,
+                      "d_h": torch.from_numpy(h.view(np.uint8).reshape(-1)).cuda(), "d_nh": torch.from_numpy(nh).cuda(),
+                      "d_out": torch.full((n * k * t_stride * 16,), FILL, dtype=torch.uint8, device="cuda")})
+    torch.cuda.synchronize()
+    for c in calls:
+        rc = lib.ss_explain_hits(sc.h, c["n"], c["qp"].ctypes.data, c["qt"].ctypes.data, k, c["d_h"].data_ptr(), c["d_nh"].data_ptr(),
+                                 t_stride, c["d_out"].data_ptr())
+        assert rc == 0
+    ss_ctx.synchronize()
+    assert any(int(c["nh"].sum()) > 0 for c in calls)
+    for i, c in enumerate(calls):
+        want = explain(sc, c["qp"], c["qt"], c["h"], c["nh"], t_stride)
+        assert c["d_out"].cpu().numpy().tobytes() == want.tobytes(), i
+
+
 def edge_tables():
     """700 docs, 4 terms.  body: term 0 no postings, term 1 one posting (doc 5), term 2 every even doc from 10 to 608 (300 postings:
     more than three times the wave width, the widest granule of the kernel), term 3 every doc.  title: term 2 every third doc."""

@@ -284,6 +284,41 @@ def test_device_outputs(ss_ctx, oracle, world, scorer):
     assert_same_hits(h2, n2, r2, rn2)
 
 
+def test_turn_blocks_regrown_under_queued_calls(ss_ctx, oracle, world, scorer):
+    """Seven device-only calls back to back, more than twice the scorer's three turns, nothing waited for in between.  The batches
+    hold 3, 40, 7, 64, 1, 64 and 5 of the world's queries, so the calls of 64 meet their turn's pinned blocks (the plan's, the queries'
+    own terms') and device buffers too small and replace them while the two calls before them are still queued.  Every output then
+    equals the host-output call on the same queries, byte for byte, and a plain score_topk afterwards still equals the oracle."""
+    import torch
+    sc, ti, bi = scorer
+    lib = ss_ctx.lib
+    q_ptr, q_terms = world["q_ptr"], world["q_terms"]
+    k_fb, m_doc, m = 10, 5, 10
+    calls = []
+    for n, first in zip((3, 40, 7, 64, 1, 64, 5), (0, 11, 50, 0, 33, 0, 20)):
+        calls.append({"n": n, "qp": (q_ptr[first:first + n + 1] - q_ptr[first]).astype(np.uint32),
+                      "qt": np.ascontiguousarray(q_terms[q_ptr[first]:q_ptr[first + n]]),
+                      "terms": torch.zeros(n * m, dtype=torch.int32, device="cuda"),
+                      "score": torch.zeros(n * m, dtype=torch.float64, device="cuda"),
+                      "n_out": torch.zeros(n, dtype=torch.int32, device="cuda")})
+    torch.cuda.synchronize()
+    for c in calls:
+        rc = lib.ss_related_terms(sc.h, c["n"], c["qp"].ctypes.data, c["qt"].ctypes.data, None, None, None, k_fb, m_doc, m,
+                                  c["terms"].data_ptr(), c["score"].data_ptr(), c["n_out"].data_ptr())
+        assert rc == 0
+    ss_ctx.synchronize()
+    for c in calls:
+        n = c["n"]
+        got = (c["terms"].cpu().numpy().view(np.uint32).reshape(n, m), c["score"].cpu().numpy().reshape(n, m), c["n_out"].cpu().numpy())
+        same(got, sc.related_terms(c["qp"], c["qt"], m=m, k_fb=k_fb, m_doc=m_doc))
+    assert sum(int(c["n_out"].sum()) for c in calls) > 0
+    # afterwards plain score_topk on the same scorer still equals the oracle (its rows computed once for the two routings)
+    if "rows20" not in world["refs"]:
+        world["refs"]["rows20"] = oracle.score_topk_batch(N_DOCS, world["title"], world["body"], world["mt"], world["mb"], q_ptr, q_terms, 20)
+    h2, n2 = sc.score_topk(q_ptr, q_terms, 20)
+    assert_same_hits(h2, n2, *world["refs"]["rows20"])
+
+
 def test_refusals_leave_outputs_untouched(ss_ctx, oracle, world):
     sc, ti, bi = make_scorer(ss_ctx, N_DOCS, world["title"], world["body"], world["mt"], world["mb"])
     q_ptr, q_terms = world["q_ptr"][:5], world["q_terms"][:int(world["q_ptr"][4])]
