@@ -570,6 +570,95 @@ func (s *Scorer) ExplainHits(qPtr, qTerms []uint32, hits [][]Hit) ([][][]TermMat
 	return out, nil
 }
 
+// NoGroup in a group table: the doc is never collapsed with anything (SS_NO_GROUP).
+const NoGroup = uint32(C.SS_NO_GROUP)
+
+// SetDocGroups registers the doc -> group table for collapsed result pages: group[d] = the site of doc d (any 32-bit value),
+// NoGroup = never collapsed; one entry per doc of the scorer (nil clears).
+func (s *Scorer) SetDocGroups(group []uint32) {
+	check(s.ctx, C.ss_scorer_set_doc_groups(s.h, u32p(group)), "ss_scorer_set_doc_groups")
+}
+
+// CollapsedPage is one page of a query's results with at most g rows per group: Same[i] = rows of the whole window in the group of
+// Hits[i], the row itself included; Kept = rows the whole window keeps.
+type CollapsedPage struct {
+	Hits []Hit
+	Same []uint32
+	Kept int
+}
+
+func collapsedPages(nq, k int, raw []C.ss_hit, nHits []int32, same []uint32, kept []int32) []CollapsedPage {
+	out := make([]CollapsedPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q] = CollapsedPage{make([]Hit, n), append([]uint32(nil), same[q*k:q*k+n]...), int(kept[q])}
+		for i := 0; i < n; i++ {
+			r := raw[q*k+i]
+			out[q].Hits[i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out
+}
+
+// CollapseHits keeps at most g rows per group of every window hits[q], in the order given (ss_collapse_hits), and returns page
+// [first, first+k) of the kept rows.  The rows may come from any scoring call; needs SetDocGroups.
+func (s *Scorer) CollapseHits(hits [][]Hit, g, first, k int) ([]CollapsedPage, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	kIn := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > kIn {
+			kIn = len(hits[q])
+		}
+	}
+	in := make([]C.ss_hit, nq*kIn)
+	nIn := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			in[q*kIn+j] = C.ss_hit{doc: C.uint32_t(h.Doc), title: C.double(h.Title), body: C.double(h.Body), pagerank: C.double(h.PageRank),
+				final: C.double(h.Final)}
+		}
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, kept, same := make([]int32, nq), make([]int32, nq), make([]uint32, nq*kk)
+	rc := C.ss_collapse_hits(s.h, C.int32_t(nq), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), C.int32_t(g),
+		C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), u32p(same), i32p(kept))
+	if err := statusErr(s.ctx, rc, "ss_collapse_hits"); err != nil {
+		return nil, err
+	}
+	return collapsedPages(nq, kk, raw, nHits, same, kept), nil
+}
+
+// ScoreTopKCollapsed = ScoreTopKMasked without phrases at k = kWindow, then CollapseHits on its rows, in one library call: the window
+// never leaves the device (ss_score_topk_collapsed).  maskID nil = none.
+func (s *Scorer) ScoreTopKCollapsed(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32, kWindow, g, first,
+	k int) ([]CollapsedPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, kept, same := make([]int32, nq), make([]int32, nq), make([]uint32, nq*kk)
+	rc := C.ss_score_topk_collapsed(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), i32p(maskID),
+		C.int32_t(kWindow), C.int32_t(g), C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), u32p(same),
+		i32p(kept))
+	if err := statusErr(s.ctx, rc, "ss_score_topk_collapsed"); err != nil {
+		return nil, err
+	}
+	return collapsedPages(nq, kk, raw, nHits, same, kept), nil
+}
+
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every
 // result contains it, title or body), excPtr/excTerms its excluded ones ("-word": no result does); nil pointers = none.  The
 // constraint terms only filter; put a required word in qTerms too for it to be scored.

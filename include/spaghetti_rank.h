@@ -39,7 +39,8 @@ extern "C" {
  * ss_score_topk_constrained (required and excluded query terms); ss_index_build_doc_view / _drop_doc_view / _read_doc_view,
  * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages");
  * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits);
- * ss_term_match and ss_explain_hits (which query tokens matched each result row, and where). */
+ * ss_term_match and ss_explain_hits (which query tokens matched each result row, and where);
+ * SS_NO_GROUP, ss_scorer_set_doc_groups, ss_collapse_hits and ss_score_topk_collapsed (at most g rows per site, with paging). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -511,6 +512,57 @@ typedef struct ss_term_match {
 int32_t ss_explain_hits(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
                         int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
                         int32_t t_stride, ss_term_match* out /*[n_q][k][t_stride]*/);
+
+/* Collapse by group ("host crowding"): at most g rows of one site on a result page, a "more from this site" count, and pages that
+ * continue where the last one stopped.  The reference ranks pages, not sites (retrieval/main_retrieve.go:99-103 cuts the sorted list at 50).
+ * The doc -> group table: group[d] is any 32-bit value (a site number, a hash of the host name); SS_NO_GROUP = doc d is never
+ * collapsed with anything.  [n_docs] (the scorer's), host or device memory, copied; NULL clears.  Replaces the previous table after the
+ * scorer's outstanding work (pipelined batches, tickets) has finished with it.  The table lives as long as the scorer: after an index
+ * update (destroy scorers before, re-create after) register it again.  4 bytes per doc. */
+#define SS_NO_GROUP 0xFFFFFFFFu
+int32_t ss_scorer_set_doc_groups(ss_scorer* s, const uint32_t* group /*[n_docs], NULL clears*/);
+
+/* ss_collapse_hits: collapse given rows.  Defined bit for bit:
+ *   Window.     Row q's window is hits[q * k_in .. q * k_in + n_hits[q]), in the order given.  Nothing is re-sorted by score and only
+ *               .doc of a row is read to decide anything: the rows may come from any scoring call or be made up by the caller.
+ *   Group.      If doc < n_docs and group[doc] != SS_NO_GROUP the row's group is group[doc].  Otherwise the row is a group of its own:
+ *               two such rows are never in the same group, even with equal docs.  Defined, not an error; no doc id makes the kernel
+ *               read outside the table.
+ *   Kept.       Row j is kept iff fewer than g rows i < j of the window are in j's group (the walk "keep a hit unless its site
+ *               already has g").
+ *   Output.     With the kept rows in window order K_0 .. K_{n_kept-1}: hits_out[q * k + r] = the 40 bytes of K_{first + r} (_pad included) for
+ *               r < n_hits_out[q] = clamp(n_kept - first, 0, k) — page first / k of pages of k rows.  same_out[q * k + r]
+ *               (nullable) = the number of rows of the WHOLE window in that row's group, the row itself included (1 for a row of its
+ *               own): the number behind "3 more from this site".  n_kept_out[q] (nullable) = n_kept, so a pager knows how many pages
+ *               the window holds.  Entries past n_hits_out[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle (or hits / n_hits / hits_out / n_hits_out with
+ * n_q > 0), n_q < 0, k_in < 1, k < 1, g < 1, first < 0, hits_out overlapping hits as address ranges: SS_ERR_INVALID; k_in or k above
+ * SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no group table registered: SS_ERR_STATE; n_hits[q] outside [0, k_in]: SS_ERR_INVALID when n_hits is
+ * host memory, clamped by the kernel when it is device memory.  n_q == 0 is SS_OK and does nothing.
+ * Every pointer may be host or device memory: when all given pointers are device memory the call only enqueues on the ctx stream and
+ * NEVER waits, so it can sit right behind a scoring call whose outputs are device buffers (ss_score_topk_phrase, _constrained,
+ * ss_similar_topk: there is no collapsed form of those, chain this call) and in front of ss_explain_hits; otherwise it
+ * stages through blocks the scorer owns and returns when the outputs are written.  Serialised on the ctx like every scoring call; no
+ * _submit / _collect form. */
+int32_t ss_collapse_hits(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/,
+                         const int32_t* n_hits /*[n_q]*/, int32_t g, int32_t first, int32_t k,
+                         ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                         uint32_t* same_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
+
+/* Score and collapse in one call: row q = ss_collapse_hits applied to the row ss_score_topk_masked returns for query q with
+ * k = k_window, this query_len, topic_probs[q] and mask_id[q] (mask_id NULL: the ss_score_topk row).  The window never leaves the
+ * device: the scored rows stay inside the scorer and one kernel behind them writes the page.  With device outputs the call only
+ * enqueues and never waits.  The window is the first k_window rows of the ranking: n_kept_out[q] counts kept rows of the window, and a
+ * window that came back full (k_window rows) can mean the ranking, and the site's rows, continue past it — a caller who needs deeper
+ * pages asks with a larger window; beyond SS_MAX_TOPK rows paging is not exact.  The query arrays are read on the host like every
+ * scoring call's.  Checks as ss_collapse_hits (k_window for k_in) and as ss_score_topk_masked, plus topic_probs without a prior:
+ * SS_ERR_STATE; all before anything is enqueued.  There is no phrase or constrained form: those callers score into device buffers
+ * with their own call and chain ss_collapse_hits, which does not wait. */
+int32_t ss_score_topk_collapsed(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                                const int32_t* query_len, const double* topic_probs, const int32_t* mask_id /*NULL = none*/,
+                                int32_t k_window, int32_t g, int32_t first, int32_t k,
+                                ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                                uint32_t* same_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

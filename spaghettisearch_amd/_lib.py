@@ -17,6 +17,7 @@ SS_MAX_TOPICS = 64
 SS_MAX_QUERY_TERMS = 64
 SS_MAX_FEEDBACK_DOCS = 64
 SS_UNKNOWN_TERM = 0xFFFFFFFF
+SS_NO_GROUP = 0xFFFFFFFF
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -115,6 +116,9 @@ PROTOTYPES = {
     "ss_similar_topk": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_related_terms": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_explain_hits": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
+    "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

@@ -145,6 +145,13 @@ struct ss_scorer {
     ss::DevBuf<ss_hit> d_exp_hits;
     ss::DevBuf<int32_t> d_exp_n;
     ss::DevBuf<ss_term_match> d_exp_out;
+    // ss_scorer_set_doc_groups (collapse.hip): [n_docs] the group of every doc, SS_NO_GROUP = a group of its own.  ss_collapse_hits /
+    // ss_score_topk_collapsed: d_col_*: device blocks of HOST arrays (grow-only; a call that uses one waits before it returns).
+    ss::DevBuf<uint32_t> groups;
+    bool has_groups = false;
+    ss::DevBuf<ss_hit> d_col_hits, d_col_out;
+    ss::DevBuf<int32_t> d_col_n, d_col_nout, d_col_kept;
+    ss::DevBuf<uint32_t> d_col_same;
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.

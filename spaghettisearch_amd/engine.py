@@ -716,6 +716,77 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return out
 
+    def set_doc_groups(self, group) -> None:
+        """ss_scorer_set_doc_groups: register the doc -> group table (uint32 [n_docs], numpy or torch; SS_NO_GROUP = never collapsed),
+        or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
+        if group is None:
+            check(self.ctx.lib.ss_scorer_set_doc_groups(self.h, None), self.ctx.h)
+            return
+        group = _as(group, "uint32")
+        n = group.numel() if _is_torch(group) else group.size
+        if n != self.title.n_docs:
+            raise ValueError(f"group table holds {n} entries, the scorer has {self.title.n_docs} docs")
+        self.ctx.ready(group)
+        check(self.ctx.lib.ss_scorer_set_doc_groups(self.h, _ptr(group)), self.ctx.h)
+
+    def _collapse_out(self, n_q: int, k: int, out, want_same: bool, want_kept: bool):
+        """The four output arrays of the collapse calls: the caller's (hits, n_hits, same | None, n_kept | None) or fresh numpy ones."""
+        if out is None:
+            return (np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                    np.zeros((n_q, k), dtype=np.uint32) if want_same else None, np.zeros(n_q, dtype=np.int32) if want_kept else None)
+        hits, n_hits, same, n_kept = out
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        n_hits, same, n_kept = _as(n_hits, "int32"), _as(same, "uint32"), _as(n_kept, "int32")
+        if (nbytes(hits) < n_q * k * HIT_DTYPE.itemsize or nbytes(n_hits) < n_q * 4 or (same is not None and nbytes(same) < n_q * k * 4)
+                or (n_kept is not None and nbytes(n_kept) < n_q * 4)):
+            raise ValueError("output buffers too small")
+        return hits, n_hits, same, n_kept
+
+    def collapse_hits(self, hits, n_hits, g: int, k: int, first: int = 0, k_in: Optional[int] = None, out=None,
+                      want_same: bool = True, want_kept: bool = True):
+        """ss_collapse_hits: at most g rows per group of every window hits[q][: n_hits[q]], in window order, page [first, first + k)
+        of the kept rows -> (hits [n_q][k], n_hits [n_q], same [n_q][k] | None, n_kept [n_q] | None).  hits / n_hits: the rows of any
+        scoring call (numpy HIT_DTYPE, or the torch uint8 / int32 device tensors score_topk's `out` takes); k_in defaults to what hits
+        holds per query.  Entries behind a row's last hit keep what the arrays held (zeros here).  out = (hits, n_hits, same | None,
+        n_kept | None): the caller's arrays, returned as they are; with device arrays throughout the library only enqueues."""
+        n_hits = _as(n_hits, "int32")
+        n_q = int(n_hits.numel() if _is_torch(n_hits) else n_hits.size)
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k_in is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k_in = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k_in) * HIT_DTYPE.itemsize:
+            raise ValueError("hits too small")
+        o_hits, o_n, o_same, o_kept = self._collapse_out(n_q, int(k), out, want_same, want_kept)
+        self.ctx.ready(hits, n_hits, o_hits, o_n, o_same, o_kept)
+        check(self.ctx.lib.ss_collapse_hits(self.h, n_q, int(k_in), _ptr(hits), _ptr(n_hits), int(g), int(first), int(k), _ptr(o_hits),
+                                            _ptr(o_n), _ptr(o_same), _ptr(o_kept)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_same, o_kept
+
+    def score_topk_collapsed(self, q_ptr, q_terms, k_window: int, g: int, k: int, first: int = 0, query_len=None, topic_probs=None,
+                             mask_id=None, out=None, want_same: bool = True, want_kept: bool = True):
+        """ss_score_topk_collapsed: collapse_hits applied to the rows score_topk_masked gives at k = k_window, without the window
+        leaving the device -> (hits [n_q][k], n_hits [n_q], same | None, n_kept | None).  out as in collapse_hits: with device arrays
+        the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        mask_id = _as(mask_id, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        o_hits, o_n, o_same, o_kept = self._collapse_out(n_q, int(k), out, want_same, want_kept)
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, mask_id, o_hits, o_n, o_same, o_kept)
+        check(self.ctx.lib.ss_score_topk_collapsed(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs),
+                                                   _ptr(mask_id), int(k_window), int(g), int(first), int(k), _ptr(o_hits), _ptr(o_n),
+                                                   _ptr(o_same), _ptr(o_kept)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_same, o_kept
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""

@@ -43,6 +43,11 @@ PYBIND11_MODULE(_host, m) {
             return e.HasPosition ? py::object(py::float_(e.FirstPosition)) : py::object(py::none());
         });
 
+    py::class_<retrieval::CollapsedPage>(m, "CollapsedPage")
+        .def_readonly("Results", &retrieval::CollapsedPage::Results)
+        .def_readonly("Same", &retrieval::CollapsedPage::Same)
+        .def_readonly("Kept", &retrieval::CollapsedPage::Kept);
+
     auto as_dbs = [](std::vector<db::MemDB*>& v) {
         std::vector<db::DB*> out;
         for (auto* p : v) out.push_back(p);
@@ -133,6 +138,14 @@ PYBIND11_MODULE(_host, m) {
             return di.RetrieveBatch(queries, masks, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("masks"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetDocMasks", &retrieval::DeviceIndex::SetDocMasks, py::arg("sets"))
+        .def("SetDocGroups", &retrieval::DeviceIndex::SetDocGroups, py::arg("keys"))
+        .def("RetrieveBatchCollapsed", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, int g, int first,
+                                          int k, py::object topic_probs, bool live_topic_probs) {
+            if (topic_probs.is_none()) return di.RetrieveBatchCollapsed(queries, k_window, g, first, k, nullptr, live_topic_probs);
+            auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
+            return di.RetrieveBatchCollapsed(queries, k_window, g, first, k, &tp, live_topic_probs);
+        }, py::arg("queries"), py::arg("k_window"), py::arg("g"), py::arg("first") = 0, py::arg("k") = 50,
+           py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetQueryOperators", &retrieval::DeviceIndex::SetQueryOperators, py::arg("on"))
         .def("SetSimilarPages", &retrieval::DeviceIndex::SetSimilarPages, py::arg("on"))
         .def("DocTopTerms", &retrieval::DeviceIndex::DocTopTerms, py::arg("docHash"), py::arg("m") = 5)

@@ -39,6 +39,15 @@ struct ResultExplanation {
     double FirstPosition = 0;
 };
 
+// One page of a query's results with at most g rows per site (DeviceIndex::RetrieveBatchCollapsed; no reference counterpart).
+// Same[i]: how many rows of the query's window are on the site of Results[i], the row itself included ("Same[i] - 1 more from this
+// site"); Kept: how many rows the whole window keeps, i.e. how far paging can go.
+struct CollapsedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<uint32_t> Same;
+    int Kept = 0;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -247,6 +256,10 @@ public:
     bool query_operators = false;                   // SetQueryOperators: "+word" / "-word" in RetrieveBatch's query strings
     bool similar_pages = false;                     // SetSimilarPages: the body table keeps its doc-major view (8 B per posting + 8 B per doc)
     bool doc_view_built = false;                    // the body table holds a view that this object built and nothing has freed since
+    // Site keys for collapsed result pages (SetDocGroups): doc hash -> key string, kept by hash like the allow-lists and registered
+    // again on every scorer this index creates.  has_doc_groups: SetDocGroups was called (an empty map is a table of SS_NO_GROUP).
+    std::map<std::string, std::string> doc_group_keys;
+    bool has_doc_groups = false;
 
     ~DeviceIndex() {
         if (scorer) ss_scorer_destroy(scorer);
@@ -342,6 +355,7 @@ public:
         const size_t K = categories.size();
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();
+        register_groups();
         build_doc_view();
     }
 
@@ -490,6 +504,32 @@ public:
         check(ss_scorer_set_doc_masks(scorer, m, m ? words.data() : nullptr), "ss_scorer_set_doc_masks");
     }
 
+    // Site keys for collapsed pages: doc hash -> key string (the caller's: a host name, a registrable domain; this mirror holds no
+    // URLs — the reference's forw[1] does).  Equal strings are one site; docs not named are never collapsed (SS_NO_GROUP); hashes
+    // the index does not hold are ignored.
+    void SetDocGroups(const std::map<std::string, std::string>& keys) {
+        doc_group_keys = keys;
+        has_doc_groups = true;
+        register_groups();
+    }
+    // doc_group_keys -> the scorer's group table (ss_scorer_set_doc_groups): a key's number is its rank among the distinct keys
+    void register_groups() {
+        using namespace spaghetti;
+        if (!has_doc_groups || !scorer || !title) return;
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        std::map<std::string, uint32_t> number;
+        for (auto& kv : doc_group_keys) number.emplace(kv.second, 0u);
+        uint32_t next = 0;
+        for (auto& kv : number) kv.second = next++;
+        std::vector<uint32_t> group((size_t)n, SS_NO_GROUP);
+        for (auto& kv : doc_group_keys) {
+            auto it = docs.id.find(kv.first);
+            if (it != docs.id.end() && it->second < n) group[it->second] = number[kv.second];
+        }
+        check(ss_scorer_set_doc_groups(scorer, group.data()), "ss_scorer_set_doc_groups");
+    }
+
     // On-disk snapshot of the flattened tables with the md5-hex <-> dense-id maps: written once after
     // the offline rank update, read at every server start instead of decoding the JSON tables.
     void save_snapshot(const std::string& path) { sync_flat(); flat.save(path); }
@@ -561,6 +601,7 @@ public:
                 if (ss_scorer_create(spaghetti::default_ctx(), di.title, di.body, &di.scorer) != SS_OK) { di.scorer = nullptr; return; }
                 if (K > 0 && K <= SS_MAX_TOPICS && di.flat.prior.size() == K * nd) (void)ss_scorer_set_prior(di.scorer, (int32_t)K, di.flat.prior.data());
                 try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
+                try { di.register_groups(); } catch (...) {}                // (RetrieveBatchCollapsed then reports the missing table)
                 try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
             }
         } scorer_guard{*this};
@@ -679,6 +720,7 @@ public:
         check(ss_scorer_create(default_ctx(), title, body, &scorer), "ss_scorer_create");
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();                                                 // the new scorer, the ids as they stand now
+        register_groups();
         build_doc_view();                                                 // (the deltas freed it)
     }
 
@@ -908,6 +950,43 @@ public:
                                    t.probs.empty() ? nullptr : t.probs.data(), mask_id.data(), k, hits.data(), n_hits.data()),
               "ss_score_topk_masked");
         return to_ranks(t.nq, k, hits, n_hits);
+    }
+    // RetrieveBatch with at most g rows per site (SetDocGroups): page [first, first + k) of every query's ranking after the
+    // collapse, taken over the first k_window rows of the ranking (a window that comes back full can continue past its end: ask with
+    // a larger window for deeper pages; k_window <= SS_MAX_TOPK).  Queries without quoted phrases are scored and collapsed in one
+    // library call and only the pages come back (ss_score_topk_collapsed); a batch with a quoted phrase is scored by
+    // ss_score_topk_phrase and its rows go through ss_collapse_hits.  Query operators are not read here.
+    std::vector<CollapsedPage> RetrieveBatchCollapsed(const std::vector<std::string>& queries, int k_window, int g, int first = 0,
+                                                      int k = 50, const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                      bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (!has_doc_groups) throw std::runtime_error("RetrieveBatchCollapsed: no site keys (SetDocGroups)");
+        if (query_operators) throw std::runtime_error("RetrieveBatchCollapsed: query operators are not read here (SetQueryOperators(false))");
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
+        std::vector<ss_hit> page(nq * kk);
+        std::vector<int32_t> n_page(nq), n_kept(nq);
+        std::vector<uint32_t> same(nq * kk);
+        const double* probs = t.probs.empty() ? nullptr : t.probs.data();
+        if (t.p_terms.empty()) {
+            check(ss_score_topk_collapsed(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.q_len.data(), probs, nullptr, k_window, g, first, k,
+                                          page.data(), n_page.data(), same.data(), n_kept.data()), "ss_score_topk_collapsed");
+        } else {
+            std::vector<ss_hit> rows(nq * (size_t)std::max(k_window, 1));
+            std::vector<int32_t> n_rows(nq);
+            check(ss_score_topk_phrase(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(), probs,
+                                       k_window, rows.data(), n_rows.data()), "ss_score_topk_phrase");
+            check(ss_collapse_hits(scorer, t.nq, k_window, rows.data(), n_rows.data(), g, first, k, page.data(), n_page.data(), same.data(),
+                                   n_kept.data()), "ss_collapse_hits");
+        }
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<CollapsedPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Same.assign(same.begin() + q * kk, same.begin() + q * kk + n_page[q]);
+            out[q].Kept = n_kept[q];
+        }
+        return out;
     }
     // The same in two halves, for a caller that has the next batch ready while this one runs (RetrieveBatcher): BeginBatch tokenises
     // and enqueues (ss_score_topk_submit; up to SS_SCORE_INFLIGHT batches), FinishBatch waits for that batch and converts its rows.
