@@ -570,6 +570,56 @@ func (s *Scorer) ExplainHits(qPtr, qTerms []uint32, hits [][]Hit) ([][][]TermMat
 	return out, nil
 }
 
+// Passage is the best body window of one hit (ss_passage): Start and Last are the position values of its first and last occurrence,
+// Distinct the distinct query terms and Occurrences the occurrences inside it; bit i of TokenMask: the query's i-th token's term
+// occurs in it.  Occurrences == 0: the doc has no passage.
+type Passage struct {
+	Start       float32
+	Last        float32
+	Distinct    uint32
+	Occurrences uint32
+	TokenMask   uint64
+}
+
+// BestPassages answers "where should each result's snippet start?" (ss_best_passages) for rows any scoring call returned:
+// out[q][j] is the window of width body positions of hits[q][j] that holds most distinct terms of query q, then most occurrences,
+// then starts earliest.  Only the hits' Doc is read.  Unknown terms and doc ids the index does not hold have no occurrences.
+func (s *Scorer) BestPassages(qPtr, qTerms []uint32, hits [][]Hit, width int) ([][]Passage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 || len(hits) != nq {
+		return nil, nil
+	}
+	k := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > k {
+			k = len(hits[q])
+		}
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nHits[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			raw[q*k+j].doc = C.uint32_t(h.Doc)
+		}
+	}
+	m := make([]C.ss_passage, nq*k)
+	rc := C.ss_best_passages(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])),
+		i32p(nHits), C.int32_t(width), (*C.ss_passage)(unsafe.Pointer(&m[0])))
+	if err := statusErr(s.ctx, rc, "ss_best_passages"); err != nil {
+		return nil, err
+	}
+	out := make([][]Passage, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Passage, len(hits[q]))
+		for j := range out[q] {
+			e := m[q*k+j]
+			out[q][j] = Passage{float32(e.start), float32(e.last), uint32(e.n_distinct), uint32(e.n_occ), uint64(e.token_mask)}
+		}
+	}
+	return out, nil
+}
+
 // NoGroup in a group table: the doc is never collapsed with anything (SS_NO_GROUP).
 const NoGroup = uint32(C.SS_NO_GROUP)
 

@@ -40,6 +40,7 @@ extern "C" {
  * ss_index_doc_top_terms and ss_similar_topk (doc-major view of a table, a doc's heaviest terms, "similar pages");
  * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits);
  * ss_term_match and ss_explain_hits (which query tokens matched each result row, and where);
+ * ss_passage and ss_best_passages (per result row the body window that covers most of the query's terms);
  * SS_NO_GROUP, ss_scorer_set_doc_groups, ss_collapse_hits and ss_score_topk_collapsed (at most g rows per site, with paging). */
 #define SS_ABI_VERSION 4
 
@@ -512,6 +513,48 @@ typedef struct ss_term_match {
 int32_t ss_explain_hits(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
                         int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
                         int32_t t_stride, ss_term_match* out /*[n_q][k][t_stride]*/);
+
+/* Best passage per hit: the body window of `width` word positions that covers most of the query's terms: the anchor of a result
+ * card's snippet.  The reference's summary (retrieval/get_metadata.go:121-192) shows twenty words around the FIRST word that matches
+ * any query token, found by parsing the cached HTML; ss_explain_hits' body_pos gives that anchor.  This call reads the body table's
+ * positional postings (ss_index_set_positions; parser/parser.go:195-207: one float32 word index per occurrence, -100 for anchor and
+ * meta text) and returns the BEST place instead of the first.  The host slices the cached words at [start, start + width).
+ * Defined bit for bit.  Entry (q, j) = out[q * k + j] describes hit j of query q, doc d = hits[q * k + j].doc; of a hit only .doc
+ * is read, and n_hits[q].
+ *   Occurrences.  For each DISTINCT term id t among the query's tokens, each value v of the body position list of posting (t, d) with
+ *                 v >= 0 is one occurrence (v, t); NaN and negative values (the -100 marker) compare false and are none.  Equal
+ *                 values of a list count separately; lists need not be sorted.  There are no occurrences when the term id is
+ *                 >= n_terms (SS_UNKNOWN_TERM included), d >= n_docs, the posting is missing or the body table has no positions:
+ *                 defined, not an error; no hit, whatever it holds, makes the kernel read outside the tables.
+ *   Window.       For every occurrence value p, W(p) is the set of occurrences (v, t) with v >= p and
+ *                 (double)v < (double)p + (double)width, as that float64 expression evaluates (the window of p = +inf is empty).
+ *                 Both zeros are equal.
+ *   Best.         The window that maximises n_distinct (distinct term ids in it), then n_occ (occurrences in it), then has the smallest
+ *                 p as a float value.  start = that p, a zero as +0.0; last = the largest v in the window; token_mask bit i is set
+ *                 iff the term of the query's i-th token (token order as given) has an occurrence in the window: duplicate tokens
+ *                 get equal bits.  (n_occ is counted modulo 2^32.)
+ *   Written.      Every entry with j < n_hits[q] is written; a doc without occurrences, a query without tokens, or a best window
+ *                 that is empty gives 24 zero bytes.  All other entries are left untouched.
+ * Checks, all before anything is enqueued and with `out` untouched: NULL handle, out or q_ptr (or hits / n_hits with n_q > 0), n_q < 0,
+ * k < 1, width < 1, a bad q_ptr as in ss_score_topk, n_hits[q] outside [0, k] when n_hits is host memory (device memory: clamped by
+ * the kernel): SS_ERR_INVALID; k > SS_MAX_TOPK, width > 2^24, a query of more than SS_MAX_QUERY_TERMS tokens or n_q * k >= 2^31:
+ * SS_ERR_UNSUPPORTED.  n_q == 0 is SS_OK and does nothing.
+ * q_ptr / q_terms are read on the host like every query array.  hits / n_hits / out may each be host or device memory: when all three
+ * are device memory the call only enqueues on the ctx stream and NEVER waits, so it chains behind score -> collapse -> explain;
+ * otherwise it stages through blocks the scorer owns and returns when out is written.  Docs with more position values under the
+ * query's terms than option "passage.lds_events" (default 512, 1 .. 4096) are answered from global memory instead of the LDS:
+ * the same bytes, more slowly.  Serialised on the ctx like the other scoring calls; no _submit / _collect form; title positions
+ * are not read. */
+typedef struct ss_passage {
+    float    start;       /* position value of the window's first occurrence; +0.0 bits when n_occ == 0 */
+    float    last;        /* largest occurrence value inside the window; +0.0 bits when n_occ == 0 */
+    uint32_t n_distinct;  /* distinct query TERM ids with an occurrence in the window */
+    uint32_t n_occ;       /* occurrences in the window; 0 = the doc has no passage: all 24 bytes are zero */
+    uint64_t token_mask;  /* bit i: the query's i-th token's term occurs in the window */
+} ss_passage;             /* 24 bytes */
+int32_t ss_best_passages(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                         int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
+                         int32_t width, ss_passage* out /*[n_q][k]*/);
 
 /* Collapse by group ("host crowding"): at most g rows of one site on a result page, a "more from this site" count, and pages that
  * continue where the last one stopped.  The reference ranks pages, not sites (retrieval/main_retrieve.go:99-103 cuts the sorted list at 50).

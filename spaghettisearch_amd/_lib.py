@@ -39,6 +39,10 @@ class SsTermMatch(C.Structure):
     _fields_ = [("title_w", C.c_float), ("body_w", C.c_float), ("flags", C.c_uint32), ("body_pos", C.c_float)]
 
 
+class SsPassage(C.Structure):
+    _fields_ = [("start", C.c_float), ("last", C.c_float), ("n_distinct", C.c_uint32), ("n_occ", C.c_uint32), ("token_mask", C.c_uint64)]
+
+
 class SsGraphInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("n_nondangling", C.c_uint64),
                 ("n_rows_local", C.c_uint64), ("n_edges_local", C.c_uint64), ("max_indeg", C.c_uint32),
@@ -116,6 +120,7 @@ PROTOTYPES = {
     "ss_similar_topk": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_related_terms": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_explain_hits": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "ss_best_passages": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
     "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

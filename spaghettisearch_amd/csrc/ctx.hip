@@ -347,6 +347,8 @@ static const char* const k_option_names[] = {
     "score.exact_all",      // 1: switch the upper-bound filter off (every record takes the exact stage)
     "score.slice_target",   // postings per (query, slice) workgroup (default: from the batch)
     "score.separate_merge", // 1: the per-query merge runs as its own launch (k_merge_topk)
+    "passage.lds_events",   // k_best_passages: a (query, hit) with at most this many position values under the query's terms is answered from
+                            //    the LDS (sorted there), a longer one from global memory; the same bytes either way (default 512, 1 .. 4096; tests reach the long path)
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

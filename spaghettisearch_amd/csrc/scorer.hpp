@@ -88,6 +88,14 @@ struct ExplainTurn {
     ss::Event ev;
 };
 
+// ss_best_passages (passage.hip): turns of its own, as ss_explain_hits has.  The queries' table carries one more word per token (the
+// first token index of the token's term).
+struct PassageTurn {
+    ss::PinBuf h_q;
+    ss::DevBuf<uint32_t> d_q;
+    ss::Event ev;
+};
+
 struct ss_scorer {
     ss_ctx* ctx = nullptr;
     ss_index* title = nullptr;
@@ -145,6 +153,13 @@ struct ss_scorer {
     ss::DevBuf<ss_hit> d_exp_hits;
     ss::DevBuf<int32_t> d_exp_n;
     ss::DevBuf<ss_term_match> d_exp_out;
+    // ss_best_passages: its own turns; d_pas_hits / _n / _out: device blocks of HOST arrays (grow-only; a call that uses one waits
+    // before it returns).
+    PassageTurn pas[TURNS];
+    int pas_turn = 0;
+    ss::DevBuf<ss_hit> d_pas_hits;
+    ss::DevBuf<int32_t> d_pas_n;
+    ss::DevBuf<ss_passage> d_pas_out;
     // ss_scorer_set_doc_groups (collapse.hip): [n_docs] the group of every doc, SS_NO_GROUP = a group of its own.  ss_collapse_hits /
     // ss_score_topk_collapsed: d_col_*: device blocks of HOST arrays (grow-only; a call that uses one waits before it returns).
     ss::DevBuf<uint32_t> groups;

@@ -12,12 +12,14 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import SsGraphInfo, SsHit, SsTermMatch, check
+from ._lib import SsGraphInfo, SsHit, SsPassage, SsTermMatch, check
 
 HIT_DTYPE = np.dtype([("doc", "<u4"), ("_pad", "<u4"), ("title", "<f8"), ("body", "<f8"),
                       ("pagerank", "<f8"), ("final", "<f8")])
 
 TERM_MATCH_DTYPE = np.dtype([("title_w", "<f4"), ("body_w", "<f4"), ("flags", "<u4"), ("body_pos", "<f4")])   # ss_term_match
+
+PASSAGE_DTYPE = np.dtype([("start", "<f4"), ("last", "<f4"), ("n_distinct", "<u4"), ("n_occ", "<u4"), ("token_mask", "<u8")])   # ss_passage
 
 _NP2T = {"uint64": "int64", "uint32": "int32"}
 
@@ -716,6 +718,36 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return out
 
+    def best_passages(self, q_ptr, q_terms, hits, n_hits, width: int = 20, out=None, k: Optional[int] = None):
+        """ss_best_passages: per hit the window of `width` body positions that holds most distinct query terms, then most occurrences,
+        then starts earliest -> PASSAGE_DTYPE [n_q][k] (n_occ == 0: the doc has no passage).  hits [n_q][k] / n_hits [n_q]: the rows of
+        any scoring call (numpy HIT_DTYPE, or the torch uint8 / int32 device tensors score_topk's `out` takes); k defaults to what hits
+        holds per query.  Entries behind a query's last hit keep what the array held (zeros here).  out: the caller's array (numpy
+        PASSAGE_DTYPE, or a torch uint8 device tensor of n_q * k * 24 bytes, returned as it is); with device hits, n_hits and out the
+        library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        n_hits = _as(n_hits, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k) * HIT_DTYPE.itemsize or (n_hits.numel() if _is_torch(n_hits) else n_hits.size) < n_q:
+            raise ValueError("hits / n_hits too small")
+        if out is None:
+            out = np.zeros((n_q, k), dtype=PASSAGE_DTYPE)
+        elif nbytes(out) < n_q * k * PASSAGE_DTYPE.itemsize:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(q_ptr, q_terms, hits, n_hits, out)
+        check(self.ctx.lib.ss_best_passages(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), int(k), _ptr(hits), _ptr(n_hits), int(width),
+                                            _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return out
+
     def set_doc_groups(self, group) -> None:
         """ss_scorer_set_doc_groups: register the doc -> group table (uint32 [n_docs], numpy or torch; SS_NO_GROUP = never collapsed),
         or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
@@ -816,5 +848,5 @@ class Scorer:
             self.h = None
 
 
-__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "SsHit", "SsTermMatch",
+__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
            "pack_doc_masks"]

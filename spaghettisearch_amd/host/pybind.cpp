@@ -35,6 +35,13 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("TitleRank", &retrieval::Rank_combined::TitleRank)
         .def_readonly("BodyRank", &retrieval::Rank_combined::BodyRank);
 
+    py::class_<retrieval::ResultPassage>(m, "ResultPassage")
+        .def_readonly("HasPassage", &retrieval::ResultPassage::HasPassage)
+        .def_readonly("Start", &retrieval::ResultPassage::Start)
+        .def_readonly("Last", &retrieval::ResultPassage::Last)
+        .def_readonly("Words", &retrieval::ResultPassage::Words)
+        .def_readonly("Distinct", &retrieval::ResultPassage::Distinct)
+        .def_readonly("Occurrences", &retrieval::ResultPassage::Occurrences);
     py::class_<retrieval::ResultExplanation>(m, "ResultExplanation")
         .def_readonly("TitleWords", &retrieval::ResultExplanation::TitleWords)
         .def_readonly("BodyWords", &retrieval::ResultExplanation::BodyWords)
@@ -156,6 +163,7 @@ PYBIND11_MODULE(_host, m) {
         }, py::arg("docHash"), py::arg("mask"), py::arg("k") = 50, py::arg("m") = 5)
         .def("RelatedTerms", &retrieval::DeviceIndex::RelatedTerms, py::arg("query"), py::arg("m") = 10, py::arg("k_fb") = 10, py::arg("m_doc") = 5)
         .def("ExplainResults", &retrieval::DeviceIndex::ExplainResults, py::arg("query"), py::arg("results"))
+        .def("BestPassages", &retrieval::DeviceIndex::BestPassages, py::arg("query"), py::arg("results"), py::arg("width") = 20)
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;

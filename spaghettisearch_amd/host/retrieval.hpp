@@ -39,6 +39,18 @@ struct ResultExplanation {
     double FirstPosition = 0;
 };
 
+// Where a row's snippet should start (DeviceIndex::BestPassages; no reference counterpart, getSummary anchors at the first matched
+// word): the window of `width` body positions that holds most of the query's distinct words, then most occurrences, then starts
+// earliest.  Start / Last: the first and the last occurrence inside it (the caller cuts the cached words at [Start, Start + width));
+// Words: the query's words found in the window, as md5-hex hashes in token order and each once; Distinct / Occurrences: the counts.
+// HasPassage false (all else zero / empty): no positional postings, no such doc, or none of the words in the page's body text.
+struct ResultPassage {
+    bool HasPassage = false;
+    double Start = 0, Last = 0;
+    std::vector<std::string> Words;
+    uint32_t Distinct = 0, Occurrences = 0;
+};
+
 // One page of a query's results with at most g rows per site (DeviceIndex::RetrieveBatchCollapsed; no reference counterpart).
 // Same[i]: how many rows of the query's window are on the site of Results[i], the row itself included ("Same[i] - 1 more from this
 // site"); Kept: how many rows the whole window keeps, i.e. how far paging can go.
@@ -424,18 +436,7 @@ public:
     // plain words.  A row whose DocHash the index does not hold lacks every word.  Changes nothing unless called.
     std::vector<ResultExplanation> ExplainResults(const std::string& query, const std::vector<Rank_combined>& results) {
         using namespace spaghetti;
-        std::string text = query_operators ? parseQueryOperators(query, laundry).query : query;
-        const std::vector<std::string> phrases = getPhrase(text);      // main_retrieve.go:17-36, as tokenise()
-        for (auto& ph : phrases) {
-            const size_t pos = text.find("\"" + ph + "\"");
-            if (pos != std::string::npos) text.erase(pos, ph.size() + 2);
-        }
-        std::string joined;
-        for (auto& ph : phrases) joined += ph + " ";
-        std::vector<std::string> words = laundry(text);
-        for (auto& w : laundry(joined)) words.push_back(w);
-        std::vector<std::string> hashed;
-        for (auto& w : words) hashed.push_back(md5::hex(w));
+        const std::vector<std::string> hashed = query_word_hashes(query);
         std::vector<ResultExplanation> out(results.size());
         if (results.empty()) return out;
         auto add_once = [](std::vector<std::string>& v, const std::string& x) {
@@ -469,6 +470,62 @@ public:
                     out[j].FirstPosition = (double)e.body_pos;
                 }
             }
+        return out;
+    }
+    // The query's word hashes in token order, as ExplainResults and BestPassages read a query string: tokenised as Retrieve does; the
+    // words of quoted phrases count as tokens, behind the others.  With SetQueryOperators(true) the string is read as RetrieveBatch
+    // reads it: '-' tokens leave the query, '+' tokens are plain words.
+    std::vector<std::string> query_word_hashes(const std::string& query) const {
+        std::string text = query_operators ? parseQueryOperators(query, laundry).query : query;
+        const std::vector<std::string> phrases = getPhrase(text);      // main_retrieve.go:17-36, as tokenise()
+        for (auto& ph : phrases) {
+            const size_t pos = text.find("\"" + ph + "\"");
+            if (pos != std::string::npos) text.erase(pos, ph.size() + 2);
+        }
+        std::string joined;
+        for (auto& ph : phrases) joined += ph + " ";
+        std::vector<std::string> words = laundry(text);
+        for (auto& w : laundry(joined)) words.push_back(w);
+        std::vector<std::string> hashed;
+        for (auto& w : words) hashed.push_back(md5::hex(w));
+        return hashed;
+    }
+    // Per row of `results` — the Rank_combined rows Retrieve / RetrieveBatch returned for `query` — the best body window of `width`
+    // word positions (ss_best_passages).  The query is tokenised as ExplainResults does it.  A row whose DocHash the index does not
+    // hold has no passage.  Changes nothing unless called.
+    std::vector<ResultPassage> BestPassages(const std::string& query, const std::vector<Rank_combined>& results, int width = 20) {
+        using namespace spaghetti;
+        const std::vector<std::string> hashed = query_word_hashes(query);
+        std::vector<ResultPassage> out(results.size());
+        if (results.empty()) return out;
+        const size_t k = results.size(), T = hashed.size();
+        if (T == 0) return out;
+        if (k > (size_t)SS_MAX_TOPK || T > (size_t)SS_MAX_QUERY_TERMS) throw std::runtime_error("BestPassages: too many rows or query words");
+        std::vector<uint32_t> q_ptr{0, (uint32_t)T}, q_terms;
+        for (auto& h : hashed) {
+            auto it = terms.id.find(h);
+            q_terms.push_back(it == terms.id.end() ? SS_UNKNOWN_TERM : it->second);
+        }
+        std::vector<ss_hit> hits(k);
+        for (size_t j = 0; j < k; j++) {
+            auto it = docs.id.find(results[j].DocHash);
+            hits[j] = ss_hit{};
+            hits[j].doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;      // no such doc: no postings
+        }
+        const int32_t n_hits = (int32_t)k;
+        std::vector<ss_passage> m(k);
+        check(ss_best_passages(scorer, 1, q_ptr.data(), q_terms.data(), (int32_t)k, hits.data(), &n_hits, (int32_t)width, m.data()), "ss_best_passages");
+        for (size_t j = 0; j < k; j++) {
+            if (!m[j].n_occ) continue;
+            out[j].HasPassage = true;
+            out[j].Start = (double)m[j].start;
+            out[j].Last = (double)m[j].last;
+            out[j].Distinct = m[j].n_distinct;
+            out[j].Occurrences = m[j].n_occ;
+            for (size_t i = 0; i < T; i++)
+                if (((m[j].token_mask >> i) & 1u) && std::find(out[j].Words.begin(), out[j].Words.end(), hashed[i]) == out[j].Words.end())
+                    out[j].Words.push_back(hashed[i]);
+        }
         return out;
     }
     // dense term ids -> word hashes (DocTopTerms, RelatedTerms)
