@@ -856,3 +856,113 @@ func (c *Ctx) MergeHits(parts [][][]Hit, docBase []uint32, k int) [][]Hit {
 	}
 	return res
 }
+
+// Lexicon is the vocabulary on the device (ss_lexicon): the words of forw[0] keyed by dense term id.  It answers the reference's
+// /wordlist/{pre} route (cmd/server/server.go:54-85) a page at a time and suggests known words for a misspelt one.  Immutable apart
+// from the frequencies: after an index update that adds terms, Close it and make a new one.
+type Lexicon struct {
+	h     *C.ss_lexicon
+	ctx   *Ctx
+	words []string
+}
+
+func u8p(s []byte) *C.uint8_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint8_t)(unsafe.Pointer(&s[0]))
+}
+
+// flattenWords packs words into the (offsets, bytes) pair the library takes.
+func flattenWords(words []string) ([]uint32, []byte) {
+	ptr := make([]uint32, len(words)+1)
+	var data []byte
+	for i, w := range words {
+		data = append(data, w...)
+		ptr[i+1] = uint32(len(data))
+	}
+	return ptr, data
+}
+
+// NewLexicon uploads the words (word t = words[t], any bytes) with their popularity freq (nil = all 0; the retrieval shim passes
+// title list length + body list length).
+func (c *Ctx) NewLexicon(words []string, freq []uint32) *Lexicon {
+	ptr := make([]uint64, len(words)+1)
+	var data []byte
+	for i, w := range words {
+		data = append(data, w...)
+		ptr[i+1] = uint64(len(data))
+	}
+	lx := &Lexicon{ctx: c, words: words}
+	check(c, C.ss_lexicon_create(c.h, C.uint64_t(len(words)), u64p(ptr), u8p(data), u32p(freq), &lx.h), "ss_lexicon_create")
+	return lx
+}
+
+func (lx *Lexicon) Close() { C.ss_lexicon_destroy(lx.h) }
+
+// SetFreq replaces the popularity of every word (nil = all 0) without re-creating the lexicon.
+func (lx *Lexicon) SetFreq(freq []uint32) {
+	check(lx.ctx, C.ss_lexicon_set_freq(lx.h, u32p(freq)), "ss_lexicon_set_freq")
+}
+
+// Order returns the permutation that sorts the words as Go's string < does (equal words by term id).
+func (lx *Lexicon) Order() []uint32 {
+	var n, b C.uint64_t
+	check(lx.ctx, C.ss_lexicon_get_info(lx.h, &n, &b), "ss_lexicon_get_info")
+	out := make([]uint32, int(n))
+	check(lx.ctx, C.ss_lexicon_read_order(lx.h, u32p(out)), "ss_lexicon_read_order")
+	return out
+}
+
+// WordList is the route's answer, one page of it: the words that start with pre in sorted order, entries first .. first+k, and
+// the number of words with the prefix.
+func (lx *Lexicon) WordList(pre string, first int64, k int) ([]string, uint64, error) {
+	ptr, data := flattenWords([]string{pre})
+	terms := make([]uint32, k)
+	nOut := make([]int32, 1)
+	nMatch := make([]uint64, 1)
+	rc := C.ss_lexicon_prefix(lx.h, C.int32_t(1), u32p(ptr), u8p(data), C.int64_t(first), C.int32_t(k), u32p(terms), i32p(nOut), u64p(nMatch))
+	if err := statusErr(lx.ctx, rc, "ss_lexicon_prefix"); err != nil {
+		return nil, 0, err
+	}
+	out := make([]string, nOut[0])
+	for i := range out {
+		out[i] = lx.words[terms[i]]
+	}
+	return out, nMatch[0], nil
+}
+
+// Suggestion is one known word near a query word: its term id, the word, and the byte edit distance (optimal string alignment:
+// insert, delete, substitute, swap of two adjacent bytes).
+type Suggestion struct {
+	Term uint32
+	Word string
+	Dist int
+}
+
+// Suggest returns per query word up to m known words within maxDist edits whose freq is at least minFreq, ordered by distance,
+// then freq descending, then term id.  Distance 0 is included: the caller sees that a word is known.
+func (lx *Lexicon) Suggest(words []string, maxDist int, minFreq uint32, m int) ([][]Suggestion, error) {
+	nq := len(words)
+	if nq == 0 {
+		return nil, nil
+	}
+	ptr, data := flattenWords(words)
+	terms := make([]uint32, nq*m)
+	dist := make([]int32, nq*m)
+	nOut := make([]int32, nq)
+	rc := C.ss_lexicon_suggest(lx.h, C.int32_t(nq), u32p(ptr), u8p(data), C.int32_t(maxDist), C.uint32_t(minFreq), C.int32_t(m),
+		u32p(terms), i32p(dist), i32p(nOut))
+	if err := statusErr(lx.ctx, rc, "ss_lexicon_suggest"); err != nil {
+		return nil, err
+	}
+	out := make([][]Suggestion, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Suggestion, nOut[q])
+		for i := range out[q] {
+			t := terms[q*m+i]
+			out[q][i] = Suggestion{t, lx.words[t], int(dist[q*m+i])}
+		}
+	}
+	return out, nil
+}

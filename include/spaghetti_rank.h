@@ -41,7 +41,9 @@ extern "C" {
  * SS_MAX_FEEDBACK_DOCS and ss_related_terms (refinement words from a query's top hits);
  * ss_term_match and ss_explain_hits (which query tokens matched each result row, and where);
  * ss_passage and ss_best_passages (per result row the body window that covers most of the query's terms);
- * SS_NO_GROUP, ss_scorer_set_doc_groups, ss_collapse_hits and ss_score_topk_collapsed (at most g rows per site, with paging). */
+ * SS_NO_GROUP, ss_scorer_set_doc_groups, ss_collapse_hits and ss_score_topk_collapsed (at most g rows per site, with paging);
+ * SS_MAX_WORD_BYTES, SS_MAX_EDIT_DIST, SS_MAX_SUGGEST, ss_lexicon, ss_lexicon_create / _set_freq / _get_info / _read_order / _destroy,
+ * ss_lexicon_prefix and ss_lexicon_suggest (the words of the vocabulary on the device: word list by prefix, spelling suggestions). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -606,6 +608,65 @@ int32_t ss_score_topk_collapsed(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
                                 int32_t k_window, int32_t g, int32_t first, int32_t k,
                                 ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
                                 uint32_t* same_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
+
+/* ---- term lexicon: cmd/server/server.go:54-85 (/wordlist/{pre}), database/database.go:414-454 (IterateInv) -------------
+ * The words of forw[0] keyed by dense term id, resident on the device.  The reference answers /wordlist/{pre} by walking every key
+ * of inv[0] and inv[1], fetching each word from forw[0] and testing strings.HasPrefix: a scan of the whole vocabulary per request,
+ * sorted afterwards (sort.StringSlice, server.go:83).  A lexicon answers the same question from a sorted order built once, one page
+ * at a time, and adds what the reference lacks: the known words within a small edit distance of a query word ("did you mean").
+ * Defined bit for bit:
+ *   Lexicon.   Word t is bytes[word_ptr[t] .. word_ptr[t+1]): any bytes, any length, zero included; embedded NULs are data; duplicate
+ *              words with different ids are allowed.  word_ptr must start at 0 and never decrease (SS_ERR_INVALID); 2^32 bytes or
+ *              more, or 2^32 terms or more, is SS_ERR_UNSUPPORTED.  Inputs host or device memory, copied.  The lexicon is immutable
+ *              apart from freq: after an index update that adds terms the caller destroys it and creates it again, as with scorers.
+ *              freq[t] is whatever popularity the caller wants (the host mirror passes title list length + body list length,
+ *              saturated at 2^32 - 1); NULL = all 0.
+ *   Order.     The sort order is the permutation of 0 .. n_terms-1 that sorts the words as arrays of UNSIGNED bytes,
+ *              lexicographically, a proper prefix first (Go's string <, what sort.StringSlice produces); equal words by ascending
+ *              term id.  Built once at create, a pure function of the input; ss_lexicon_read_order returns it (host or device).
+ *   Prefix.    Row q's matches are the terms whose word starts with prefix q = p_bytes[p_ptr[q] .. p_ptr[q+1]) (the empty prefix
+ *              matches every term).  n_match_out[q] (nullable) = the number of matches; terms_out[q * k + r] = match number
+ *              first + r in sort order for r < n_out[q] = clamp(n_match - first, 0, k).  Entries past n_out[q] are left untouched.
+ *              The reference ships the whole sorted list; the paging is ours.
+ *   Distance.  d(a, b) = the optimal-string-alignment distance over BYTES (not code points): unit-cost insert, delete, substitute
+ *              and swap of two ADJACENT bytes.  D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1,
+ *              D[i-1][j-1] + (a[i-1] != b[j-1]), and, if i, j >= 2 and a[i-1] == b[j-2] and a[i-2] == b[j-1], D[i-2][j-2] + 1).
+ *              d("ab", "ba") = 1; d("ca", "abc") = 3 (not 2: this is not the unrestricted Damerau distance).
+ *   Suggest.   The candidates of row q (query word w_bytes[w_ptr[q] .. w_ptr[q+1])) are the terms t with len(word t) <=
+ *              SS_MAX_WORD_BYTES, freq[t] >= min_freq and d(query word, word t) <= max_dist; distance 0 is included, so the caller
+ *              sees that a word is known.  A query word longer than SS_MAX_WORD_BYTES has no candidates: defined, not an error.
+ *              Row q of terms_out [n_q][m] / dist_out [n_q][m] (nullable) holds the first n_out[q] = min(m, #candidates) candidates
+ *              ordered by distance ascending, then freq descending, then term id ascending.  Entries past n_out[q] are left
+ *              untouched.  The row does not depend on the order in which workgroups finish: there are no atomics.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle or NULL required output (terms_out, n_out) or
+ * pointer array, n_q < 0, a p_ptr / w_ptr that decreases (as q_ptr in ss_score_topk), k < 1, m < 1, first < 0, max_dist < 0:
+ * SS_ERR_INVALID; k > SS_MAX_TOPK, m > SS_MAX_SUGGEST, max_dist > SS_MAX_EDIT_DIST: SS_ERR_UNSUPPORTED.  n_q == 0 is SS_OK and does
+ * nothing; every call on a lexicon of 0 terms is SS_OK: the rows come back empty and n_out is written as 0.
+ * Query bytes and pointers are read on the host like every query array.  Outputs may each be host or device memory: when all given
+ * outputs are device memory the call only enqueues on the ctx stream and NEVER waits (the queries go up through turns of pinned
+ * blocks the lexicon owns); otherwise it stages through blocks the lexicon owns and returns when the outputs are written.
+ * ss_lexicon_suggest compares every query word with every word of the length groups len - max_dist .. len + max_dist, one workgroup
+ * per (query word, chunk of option "lexicon.chunk_terms" words, default 4096, 1 .. 2^20); its temporaries are sized by m * chunks,
+ * never by the number of candidates.  Calls are serialised on the ctx like the scoring calls; there is no _submit / _collect form. */
+#define SS_MAX_WORD_BYTES 64   /* longest word that can be a suggestion candidate or a suggest query */
+#define SS_MAX_EDIT_DIST  3
+#define SS_MAX_SUGGEST    64
+typedef struct ss_lexicon ss_lexicon;
+
+int32_t ss_lexicon_create(ss_ctx* ctx, uint64_t n_terms, const uint64_t* word_ptr /*[n_terms+1]*/, const uint8_t* bytes,
+                          const uint32_t* freq /*[n_terms], NULL = all 0*/, ss_lexicon** out);
+int32_t ss_lexicon_set_freq(ss_lexicon* lx, const uint32_t* freq /*[n_terms], NULL = all 0*/);
+int32_t ss_lexicon_get_info(const ss_lexicon* lx, uint64_t* n_terms, uint64_t* n_bytes);
+int32_t ss_lexicon_read_order(ss_lexicon* lx, uint32_t* order_out /*[n_terms]*/);
+int32_t ss_lexicon_destroy(ss_lexicon* lx);
+
+int32_t ss_lexicon_prefix(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr /*[n_q+1]*/, const uint8_t* p_bytes,
+                          int64_t first, int32_t k, uint32_t* terms_out /*[n_q][k]*/, int32_t* n_out /*[n_q]*/,
+                          uint64_t* n_match_out /*[n_q] nullable*/);
+
+int32_t ss_lexicon_suggest(ss_lexicon* lx, int32_t n_q, const uint32_t* w_ptr /*[n_q+1]*/, const uint8_t* w_bytes,
+                           int32_t max_dist, uint32_t min_freq, int32_t m,
+                           uint32_t* terms_out /*[n_q][m]*/, int32_t* dist_out /*[n_q][m] nullable*/, int32_t* n_out /*[n_q]*/);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

@@ -18,6 +18,9 @@ SS_MAX_QUERY_TERMS = 64
 SS_MAX_FEEDBACK_DOCS = 64
 SS_UNKNOWN_TERM = 0xFFFFFFFF
 SS_NO_GROUP = 0xFFFFFFFF
+SS_MAX_WORD_BYTES = 64
+SS_MAX_EDIT_DIST = 3
+SS_MAX_SUGGEST = 64
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -124,6 +127,13 @@ PROTOTYPES = {
     "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
     "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_lexicon_create": (_i32, [_vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "ss_lexicon_set_freq": (_i32, [_vp, _vp]),
+    "ss_lexicon_get_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "ss_lexicon_read_order": (_i32, [_vp, _vp]),
+    "ss_lexicon_destroy": (_i32, [_vp]),
+    "ss_lexicon_prefix": (_i32, [_vp, _i32, _vp, _vp, C.c_int64, _i32, _vp, _vp, _vp]),
+    "ss_lexicon_suggest": (_i32, [_vp, _i32, _vp, _vp, _i32, C.c_uint32, _i32, _vp, _vp, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

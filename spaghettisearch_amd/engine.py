@@ -850,3 +850,114 @@ class Scorer:
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
            "pack_doc_masks"]
+
+
+def _flatten_words(words, ptr_dtype: str):
+    """A sequence of words (bytes, or str encoded as UTF-8) -> (ptr [n + 1], bytes uint8); a (ptr, bytes) pair of arrays (numpy or
+    torch: int64 / int32 ptr, uint8 bytes) passes through."""
+    if isinstance(words, tuple) and len(words) == 2 and not isinstance(words[0], (bytes, str)):
+        return _as(words[0], ptr_dtype), _as(words[1], "uint8")
+    raw = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+    ptr = np.zeros(len(raw) + 1, dtype=np.dtype(ptr_dtype))
+    if raw:
+        total = np.cumsum([len(w) for w in raw], dtype=np.uint64)
+        if ptr_dtype == "uint32" and int(total[-1]) >= 1 << 32:
+            raise ValueError("2^32 bytes of words or more in one call")
+        ptr[1:] = total
+    return ptr, np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
+
+
+class Lexicon:
+    """ss_lexicon: the vocabulary's words on the device, keyed by term id: the word list by prefix and spelling suggestions.
+    words: a sequence of bytes / str (word t = words[t]) or a (word_ptr uint64 [n + 1], bytes uint8) pair; freq uint32 [n] or None
+    (all 0).  Immutable apart from freq: after an index update that adds terms, close it and make a new one."""
+
+    def __init__(self, ctx: Context, words, freq=None):
+        self.ctx = ctx
+        ptr, data = _flatten_words(words, "uint64")
+        self.n_terms = int(ptr.shape[0]) - 1
+        freq = _as(freq, "uint32")
+        if freq is not None and (freq.numel() if _is_torch(freq) else freq.size) != self.n_terms:
+            raise ValueError("freq must hold one value per word")
+        ctx.ready(ptr, data, freq)
+        h = C.c_void_p()
+        check(ctx.lib.ss_lexicon_create(ctx.h, self.n_terms, _ptr(ptr), _ptr(data), _ptr(freq), C.byref(h)), ctx.h)
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            check(self.ctx.lib.ss_lexicon_destroy(self.h), self.ctx.h)
+            self.h = None
+
+    def info(self):
+        """-> (n_terms, n_bytes)"""
+        n, b = C.c_uint64(), C.c_uint64()
+        check(self.ctx.lib.ss_lexicon_get_info(self.h, C.byref(n), C.byref(b)), self.ctx.h)
+        return n.value, b.value
+
+    def set_freq(self, freq) -> None:
+        """ss_lexicon_set_freq: replace the popularity of every word (uint32 [n_terms], numpy or torch; None = all 0)."""
+        freq = _as(freq, "uint32")
+        if freq is not None and (freq.numel() if _is_torch(freq) else freq.size) != self.n_terms:
+            raise ValueError("freq must hold one value per word")
+        self.ctx.ready(freq)
+        check(self.ctx.lib.ss_lexicon_set_freq(self.h, _ptr(freq)), self.ctx.h)
+
+    def order(self, out=None):
+        """ss_lexicon_read_order: the permutation that sorts the words (unsigned bytes, a proper prefix first, equal words by id)."""
+        if out is None:
+            out = np.zeros(self.n_terms, dtype=np.uint32)
+        else:
+            out = _as(out, "uint32")
+            if (out.numel() if _is_torch(out) else out.size) < self.n_terms:
+                raise ValueError("output buffer too small")
+        self.ctx.ready(out)
+        check(self.ctx.lib.ss_lexicon_read_order(self.h, _ptr(out)), self.ctx.h)
+        return out
+
+    def prefix(self, prefixes, k: int, first: int = 0, out=None):
+        """ss_lexicon_prefix: per prefix the page [first, first + k) of the terms whose word starts with it, in sort order
+        -> (terms uint32 [n_q][k], n_out int32 [n_q], n_match uint64 [n_q]); entries past n_out[q] keep what the array held (zeros
+        here).  out = (terms, n_out, n_match | None): the caller's arrays (numpy, or torch int32 / int32 / int64 device tensors); with
+        device tensors the library only enqueues."""
+        p_ptr, p_bytes = _flatten_words(prefixes, "uint32")
+        n_q = int(p_ptr.shape[0]) - 1
+        count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+        if out is not None:
+            terms, n_out, n_match = _as(out[0], "uint32"), _as(out[1], "int32"), _as(out[2], "uint64")
+            if count(terms) < n_q * k or count(n_out) < n_q or (n_match is not None and count(n_match) < n_q):
+                raise ValueError("output buffers too small")
+        else:
+            terms = np.zeros((n_q, max(int(k), 0)), dtype=np.uint32)
+            n_out = np.zeros(n_q, dtype=np.int32)
+            n_match = np.zeros(n_q, dtype=np.uint64)
+        self.ctx.ready(p_ptr, p_bytes, terms, n_out, n_match)
+        check(self.ctx.lib.ss_lexicon_prefix(self.h, n_q, _ptr(p_ptr), _ptr(p_bytes), int(first), int(k), _ptr(terms), _ptr(n_out),
+                                             _ptr(n_match)), self.ctx.h)
+        if out is not None and _is_torch(terms) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return terms, n_out, n_match
+
+    def suggest(self, words, max_dist: int = 2, m: int = 10, min_freq: int = 1, out=None):
+        """ss_lexicon_suggest: per query word the m known words within max_dist edits (optimal string alignment over bytes: insert,
+        delete, substitute, swap of adjacent bytes) whose freq is at least min_freq, ordered by distance, then freq descending, then
+        term id -> (terms uint32 [n_q][m], dist int32 [n_q][m], n_out int32 [n_q]); entries past n_out[q] keep what the arrays held
+        (zeros here).  out = (terms, dist | None, n_out): the caller's arrays (numpy, or torch int32 device tensors); with device
+        tensors the library only enqueues."""
+        w_ptr, w_bytes = _flatten_words(words, "uint32")
+        n_q = int(w_ptr.shape[0]) - 1
+        count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+        if out is not None:
+            terms, dist, n_out = _as(out[0], "uint32"), _as(out[1], "int32"), _as(out[2], "int32")
+            if count(terms) < n_q * m or (dist is not None and count(dist) < n_q * m) or count(n_out) < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            terms = np.zeros((n_q, max(int(m), 0)), dtype=np.uint32)
+            dist = np.zeros((n_q, max(int(m), 0)), dtype=np.int32)
+            n_out = np.zeros(n_q, dtype=np.int32)
+        self.ctx.ready(w_ptr, w_bytes, terms, dist, n_out)
+        check(self.ctx.lib.ss_lexicon_suggest(self.h, n_q, _ptr(w_ptr), _ptr(w_bytes), int(max_dist), int(min_freq), int(m), _ptr(terms),
+                                              _ptr(dist), _ptr(n_out)), self.ctx.h)
+        if out is not None and _is_torch(terms) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return terms, dist, n_out

@@ -42,6 +42,11 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Words", &retrieval::ResultPassage::Words)
         .def_readonly("Distinct", &retrieval::ResultPassage::Distinct)
         .def_readonly("Occurrences", &retrieval::ResultPassage::Occurrences);
+    py::class_<retrieval::WordSuggestion>(m, "WordSuggestion")
+        .def_readonly("Token", &retrieval::WordSuggestion::Token)
+        .def_readonly("Words", &retrieval::WordSuggestion::Words)
+        .def_readonly("Distances", &retrieval::WordSuggestion::Distances)
+        .def_readonly("Freqs", &retrieval::WordSuggestion::Freqs);
     py::class_<retrieval::ResultExplanation>(m, "ResultExplanation")
         .def_readonly("TitleWords", &retrieval::ResultExplanation::TitleWords)
         .def_readonly("BodyWords", &retrieval::ResultExplanation::BodyWords)
@@ -165,6 +170,17 @@ PYBIND11_MODULE(_host, m) {
         .def("ExplainResults", &retrieval::DeviceIndex::ExplainResults, py::arg("query"), py::arg("results"))
         .def("BestPassages", &retrieval::DeviceIndex::BestPassages, py::arg("query"), py::arg("results"), py::arg("width") = 20)
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
+        .def("SetLexicon", [](retrieval::DeviceIndex& di, db::MemDB* forw0) {
+            db::Context ctx;
+            di.SetLexicon(ctx, forw0);
+        }, py::arg("forw0"))
+        .def("HasLexicon", &retrieval::DeviceIndex::HasLexicon)
+        .def("WordList", [](retrieval::DeviceIndex& di, const std::string& pre, int64_t first, int k) {
+            py::list out;
+            for (auto& w : di.WordList(pre, first, k)) out.append(py::bytes(w));       // words are bytes: not every prefix cut is UTF-8
+            return out;
+        }, py::arg("pre"), py::arg("first") = 0, py::arg("k") = 50)
+        .def("SuggestWords", &retrieval::DeviceIndex::SuggestWords, py::arg("query"), py::arg("max_dist") = 2, py::arg("m") = 5)
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;
             auto f = as_dbs(forw), i = as_dbs(inv);

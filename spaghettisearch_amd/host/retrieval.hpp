@@ -39,6 +39,15 @@ struct ResultExplanation {
     double FirstPosition = 0;
 };
 
+// "Did you mean" for one query token the index does not know (DeviceIndex::SuggestWords; no reference counterpart): the known words
+// within the edit distance asked for, best first (distance, then frequency descending, then term id), as ss_lexicon_suggest orders them.
+struct WordSuggestion {
+    std::string Token;                       // the token as the tokeniser emits it
+    std::vector<std::string> Words;          // suggested words of the vocabulary
+    std::vector<int> Distances;              // byte edit distance of each (optimal string alignment)
+    std::vector<uint32_t> Freqs;             // title + body list length of each, as the lexicon holds it
+};
+
 // Where a row's snippet should start (DeviceIndex::BestPassages; no reference counterpart, getSummary anchors at the first matched
 // word): the window of `width` body positions that holds most of the query's distinct words, then most occurrences, then starts
 // earliest.  Start / Last: the first and the last occurrence inside it (the caller cuts the cached words at [Start, Start + width));
@@ -272,8 +281,15 @@ public:
     // again on every scorer this index creates.  has_doc_groups: SetDocGroups was called (an empty map is a table of SS_NO_GROUP).
     std::map<std::string, std::string> doc_group_keys;
     bool has_doc_groups = false;
+    // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
+    // = title + body list length per term.  upload() drops it (the term ids are new): call SetLexicon again after load().
+    ss_lexicon* lexicon = nullptr;
+    std::vector<std::string> lex_words;
+    std::vector<uint32_t> lex_freq;
+    std::vector<bool> lex_known;                    // forw[0] held the term's hash when its word was read
 
     ~DeviceIndex() {
+        if (lexicon) ss_lexicon_destroy(lexicon);
         if (scorer) ss_scorer_destroy(scorer);
         if (title) ss_index_destroy(title);
         if (body) ss_index_destroy(body);
@@ -354,6 +370,7 @@ public:
         if (scorer) { ss_scorer_destroy(scorer); scorer = nullptr; }
         if (title) { ss_index_destroy(title); title = nullptr; }
         if (body) { ss_index_destroy(body); body = nullptr; }
+        drop_lexicon();
         mags_resident = flat_stale = doc_view_built = false;
         const size_t n = flat.doc_names.size(), T = flat.term_names.size();
         check(ss_index_create(default_ctx(), n, T, flat.title.term_ptr.data(), flat.title.post_doc.data(), flat.title.post_w.data(), &title), "ss_index_create(title)");
@@ -476,6 +493,12 @@ public:
     // words of quoted phrases count as tokens, behind the others.  With SetQueryOperators(true) the string is read as RetrieveBatch
     // reads it: '-' tokens leave the query, '+' tokens are plain words.
     std::vector<std::string> query_word_hashes(const std::string& query) const {
+        std::vector<std::string> hashed;
+        for (auto& w : query_words(query)) hashed.push_back(md5::hex(w));
+        return hashed;
+    }
+    // ... and the words themselves, before hashing (SuggestWords)
+    std::vector<std::string> query_words(const std::string& query) const {
         std::string text = query_operators ? parseQueryOperators(query, laundry).query : query;
         const std::vector<std::string> phrases = getPhrase(text);      // main_retrieve.go:17-36, as tokenise()
         for (auto& ph : phrases) {
@@ -486,9 +509,110 @@ public:
         for (auto& ph : phrases) joined += ph + " ";
         std::vector<std::string> words = laundry(text);
         for (auto& w : laundry(joined)) words.push_back(w);
-        std::vector<std::string> hashed;
-        for (auto& w : words) hashed.push_back(md5::hex(w));
-        return hashed;
+        return words;
+    }
+    // Term lexicon (ss_lexicon; the reference's /wordlist/{pre}, cmd/server/server.go:54-85, and "did you mean").  forw0 = forw[0],
+    // wordHash -> word: read for every resident term id; a term whose hash is missing there gets the empty word and freq 0.  freq =
+    // title list length + body list length, saturated at 2^32 - 1.  Changes nothing unless called.
+    void SetLexicon(db::Context& ctx, db::DB* forw0) {
+        if (!title || !body) throw std::runtime_error("SetLexicon: the index is not loaded");
+        lex_words.assign(terms.name.size(), std::string());
+        lex_known.assign(terms.name.size(), false);
+        for (size_t t = 0; t < terms.name.size(); t++)
+            if (forw0->Has(ctx, terms.name[t])) { lex_words[t] = forw0->Get(ctx, terms.name[t]); lex_known[t] = true; }
+        build_lexicon(lex_known);
+    }
+    bool HasLexicon() const { return lexicon != nullptr; }
+    void drop_lexicon() {
+        if (lexicon) { ss_lexicon_destroy(lexicon); lexicon = nullptr; }
+        lex_words.clear();
+        lex_freq.clear();
+        lex_known.clear();
+    }
+    // title + body list length of every term as the resident tables stand; 0 for a term forw[0] does not know
+    void read_lex_freq(const std::vector<bool>& known) {
+        using namespace spaghetti;
+        const size_t T = terms.name.size();
+        std::vector<uint64_t> tp(T + 1), bp(T + 1);
+        check(ss_index_read(title, tp.data(), nullptr, nullptr), "ss_index_read(title)");
+        check(ss_index_read(body, bp.data(), nullptr, nullptr), "ss_index_read(body)");
+        lex_freq.assign(T, 0u);
+        for (size_t t = 0; t < T; t++) {
+            const uint64_t f = (tp[t + 1] - tp[t]) + (bp[t + 1] - bp[t]);
+            lex_freq[t] = !known[t] ? 0u : f > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)f;
+        }
+    }
+    void build_lexicon(const std::vector<bool>& known) {
+        using namespace spaghetti;
+        if (lexicon) { ss_lexicon_destroy(lexicon); lexicon = nullptr; }
+        read_lex_freq(known);
+        std::vector<uint64_t> ptr(lex_words.size() + 1, 0);
+        std::string bytes;
+        for (size_t t = 0; t < lex_words.size(); t++) {
+            bytes += lex_words[t];
+            ptr[t + 1] = bytes.size();
+        }
+        check(ss_lexicon_create(default_ctx(), lex_words.size(), ptr.data(), reinterpret_cast<const uint8_t*>(bytes.data()), lex_freq.data(), &lexicon),
+              "ss_lexicon_create");
+    }
+    // after a delta: new term ids -> the lexicon is made again (their words from forw[0]); otherwise only the frequencies follow
+    void refresh_lexicon(db::Context& ctx, db::DB* forw0, size_t t_before) {
+        if (!lexicon) return;
+        if (terms.name.size() != t_before) {
+            lex_words.resize(terms.name.size());
+            lex_known.resize(terms.name.size(), false);
+            for (size_t t = t_before; t < terms.name.size(); t++)
+                if (forw0->Has(ctx, terms.name[t])) { lex_words[t] = forw0->Get(ctx, terms.name[t]); lex_known[t] = true; }
+            build_lexicon(lex_known);
+        } else {
+            read_lex_freq(lex_known);
+            spaghetti::check(ss_lexicon_set_freq(lexicon, lex_freq.data()), "ss_lexicon_set_freq");
+        }
+    }
+    // The route's answer, one page of it: the words that start with `pre`, sorted as the reference sorts them (bytes, a proper prefix
+    // first), entries first .. first + k.  Terms without a word in forw[0] hold the empty word and are listed under the empty prefix only.
+    std::vector<std::string> WordList(const std::string& pre, int64_t first = 0, int k = 50) {
+        using namespace spaghetti;
+        if (!lexicon) throw std::runtime_error("WordList: no lexicon (SetLexicon)");
+        const uint32_t p_ptr[2] = {0u, (uint32_t)pre.size()};
+        std::vector<uint32_t> ids((size_t)std::max(k, 1));
+        int32_t n = 0;
+        check(ss_lexicon_prefix(lexicon, 1, p_ptr, reinterpret_cast<const uint8_t*>(pre.data()), first, k, ids.data(), &n, nullptr), "ss_lexicon_prefix");
+        std::vector<std::string> out;
+        for (int32_t i = 0; i < n; i++) out.push_back(lex_words[ids[i]]);
+        return out;
+    }
+    // Per token of `query` that the index does not know (SS_UNKNOWN_TERM in Retrieve), the m known words within max_dist byte edits
+    // whose frequency is at least 1; nothing for known tokens.  The query is tokenised as ExplainResults does it.
+    std::vector<WordSuggestion> SuggestWords(const std::string& query, int max_dist = 2, int m = 5) {
+        using namespace spaghetti;
+        if (!lexicon) throw std::runtime_error("SuggestWords: no lexicon (SetLexicon)");
+        std::vector<WordSuggestion> out;
+        std::vector<uint32_t> w_ptr{0};
+        std::string bytes;
+        for (auto& w : query_words(query)) {
+            if (terms.id.find(md5::hex(w)) != terms.id.end()) continue;
+            bool seen = false;
+            for (auto& o : out) seen = seen || o.Token == w;
+            if (seen) continue;
+            out.push_back(WordSuggestion{w, {}, {}, {}});
+            bytes += w;
+            w_ptr.push_back((uint32_t)bytes.size());
+        }
+        if (out.empty()) return out;
+        const size_t nq = out.size(), mm = (size_t)std::max(m, 1);
+        std::vector<uint32_t> ids(nq * mm);
+        std::vector<int32_t> dist(nq * mm), n(nq);
+        check(ss_lexicon_suggest(lexicon, (int32_t)nq, w_ptr.data(), reinterpret_cast<const uint8_t*>(bytes.data()), max_dist, 1u, m, ids.data(),
+                                 dist.data(), n.data()), "ss_lexicon_suggest");
+        for (size_t q = 0; q < nq; q++)
+            for (int32_t r = 0; r < n[q]; r++) {
+                const uint32_t t = ids[q * mm + r];
+                out[q].Words.push_back(lex_words[t]);
+                out[q].Distances.push_back(dist[q * mm + r]);
+                out[q].Freqs.push_back(lex_freq[t]);
+            }
+        return out;
     }
     // Per row of `results` — the Rank_combined rows Retrieve / RetrieveBatch returned for `query` — the best body window of `width`
     // word positions (ss_best_passages).  The query is tokenised as ExplainResults does it.  A row whose DocHash the index does not
@@ -779,6 +903,7 @@ public:
         register_masks();                                                 // the new scorer, the ids as they stand now
         register_groups();
         build_doc_view();                                                 // (the deltas freed it)
+        refresh_lexicon(ctx, forw[0], t_before);                          // new term ids: a new lexicon; otherwise the frequencies only
     }
 
     // forw[3] was rewritten (UpdateTopicSensitivePagerank / ResidentPagerank::Run): refresh the scorer's PageRank table.
