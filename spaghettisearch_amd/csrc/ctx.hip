@@ -310,6 +310,8 @@ static const char* const k_option_names[] = {
     "pr.item_turns",        // turns per V_DEG work item of k_pr_sweep (V_QUAD: twice that); default 4 up to 4M local rows, 8 beyond
     "graph.late_free",      // 0: ss_graph_create waits for its last kernels and frees its temporaries before it returns (default 1: they are freed
                             //    at the graph's next use, the caller's host work overlaps the row permutation)
+    "graph.readback_runs",  // in-degree runs per class that ss_graph_create's one packed read-back holds (default and most: 8192, at least 1); a class with
+                            //    more runs costs a second copy.  Tests set it small to reach that copy; the layout is the same bytes for every value
     "pr.trace",             // 1: ss_graph_create / ss_pr_create print their phase times to stderr
     "score.collect_pinned", // ss_score_topk_collect: 1 = device -> pinned block on the copy engine, then a host memcpy (measured slower: 0.50 against 0.41 ms
                             //    per batch with three in flight); default 0 = hipMemcpy straight into the caller's memory

@@ -518,7 +518,8 @@ int32_t build(ss_graph* g, const uint64_t* out_ptr_in, const uint32_t* out_dst_i
     // each class land in a pinned block (a graph has a few thousand distinct in-degrees; more than RLE_SPEC costs a second copy).
     // [The counts, then the runs, then the offsets each had a wait of their own: six round trips of 25-40 us, a third of config 2's
     //  0.9 ms here.]
-    constexpr uint32_t RLE_SPEC = 8192;
+    // (option "graph.readback_runs": fewer runs in the block, so that tests reach the second copy with a handful of distinct in-degrees)
+    const uint32_t RLE_SPEC = (uint32_t)std::min<int64_t>(std::max<int64_t>(ctx->opt("graph.readback_runs", 8192), 1), 8192);
     const uint32_t cnt[2] = {g->cnt_nd, g->cnt_d};
     const uint64_t id0[2] = {id0_nd, id0_d};
     ss_graph::SortedDegrees* dst[2] = {&g->h_indeg_nd, &g->h_indeg_d};

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from spaghettisearch_amd import synth
-from tests.pr_graphs import NARROW_VARIANTS, csr, skewed_graph
+from tests.pr_graphs import NARROW_VARIANTS, chunk_corner_graph, csr, skewed_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -106,23 +106,10 @@ def test_skewed_rows_block_per_segment(ss_ctx, oracle):
 @pytest.mark.parametrize("k_topics", [1, 16])
 def test_graph_build_chunk_rows(ss_ctx, oracle, k_topics):
     # ss_graph_create finds the row of every edge slot per 2048-slot chunk (k_chunk_first_rows + LDS marks + running maximum,
-    # a bisection where a chunk holds a long stretch of empty rows).  A graph built to hit the corners: rows that start exactly
-    # on chunk boundaries, rows spanning several chunks, > 8192 edge-less rows inside one chunk in BOTH directions (dangling
-    # sources in id order; non-dangling pages nobody links to, which sort to the end of their class), an edge count that is a
-    # multiple of the chunk, and the last row ending at the last slot.
-    n = 120000
-    edges = []
-    hubs = list(range(100000, 100008))
-    for s in range(3):                                             # three sources with exactly 2048 children: rows on chunk boundaries
-        edges += [(s, 50000 + j) for j in range(2048)]
-    edges += [(3, 20000 + j) for j in range(5000)]                 # a row over several chunks
-    # sources 4 .. 29999 have no out-edges (dangling, a 26k-row empty stretch in the out-edge CSR)
-    edges += [(s, hubs[s % 8]) for s in range(30000, 60000)]       # 30k non-dangling pages with no in-edges of their own (50000.. get some)
-    edges += [(s, s + 1) for s in range(110000, 110100)]
-    fill = (-len(edges)) % 2048
-    edges += [(n - 1, 70000 + j) for j in range(fill)]             # the last row ends at the last slot of the last chunk
-    assert len(edges) % 2048 == 0 and len(set(edges)) == len(edges)
-    ptr, dst = csr(n, edges)
+    # a bisection where a chunk holds a long stretch of empty rows).  A graph built to hit the corners (tests/pr_graphs.py
+    # chunk_corner_graph; on shards: tests/test_gpu_graph_paths.py)
+    n, ptr, dst = chunk_corner_graph()
+    assert n == 120000 and len(dst) % 2048 == 0
     n_topic = synth.topic_sizes(n, k_topics)
     rank, iters, ref, ref_iters = run_both(ss_ctx, oracle, n, ptr, dst, n_topic, 1e-10)
     assert iters.tolist() == ref_iters.tolist()
