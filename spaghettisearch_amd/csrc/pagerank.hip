@@ -440,6 +440,8 @@ void fill_params(ss_pr* pr, const Cut& cut, const PlanOptions& opt, double dampi
     p.partials = pr->partials.p;
     p.segpart = pr->segpart.p;
     p.rowticket = pr->rowticket.p;
+    p.hubsum = pr->hubsum.p;
+    p.nmulti = cut.nmulti;
     p.ctl = pr->ctl.p;
     p.x0 = pr->x0.p;
     p.d = damping;
@@ -641,6 +643,8 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     SS_HIP(ctx, pr->partials.alloc(((size_t)std::max(pr->nblocks, ss::begin_blocks(pr)) + 8) * 2 * GW));   // block rows + 8 group rows
     SS_HIP(ctx, pr->segpart.alloc((size_t)std::max(cut.nsegs, 1u) * GW));
     SS_HIP(ctx, pr->rowticket.alloc(std::max(cut.nmulti, 1u)));
+    SS_HIP(ctx, pr->hubsum.alloc((size_t)std::max(cut.nmulti, 1u) * 2 * GW));
+    SS_HIP(ctx, hipMemsetAsync(pr->hubsum.p, 0, pr->hubsum.bytes(), st));
     SS_HIP(ctx, hipMemsetAsync(pr->rowticket.p, 0, pr->rowticket.bytes(), st));
     SS_HIP(ctx, pr->woff.alloc(std::max<size_t>(woff->size(), 8)));
     if (!woff->empty()) SS_HIP(ctx, hipMemcpyAsync(pr->woff.p, woff->data(), woff->size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));

@@ -240,6 +240,28 @@ __device__ __forceinline__ void block_reduce_and_publish(const PrParams& p, doub
         for (unsigned gq = 0; gq < ng; gq++)
             v += __hip_atomic_load(&gpart[(size_t)gq * NCOL + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         tot[threadIdx.x / GW][threadIdx.x % GW] = v;
+    } else if (!is_begin && p.nmulti) {
+        // the rows that were cut into pieces (PrParams::hubsum): the other threads add their terms meanwhile, in row order
+        const unsigned hp = threadIdx.x / NCOL - 1;                   // 0 .. NPART - 2
+        double acc = 0.0;
+        for (unsigned h0 = hp; h0 < p.nmulti; h0 += 16 * (NPART - 1)) {
+            double v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const unsigned h = h0 + u * (NPART - 1);
+                v[u] = __hip_atomic_load(&p.hubsum[(size_t)(h < p.nmulti ? h : h0) * NCOL + col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (h0 + u * (NPART - 1) < p.nmulti) acc += v[u];
+        }
+        colsum[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (!is_begin && p.nmulti && threadIdx.x < NCOL) {
+        double v = tot[threadIdx.x / GW][threadIdx.x % GW];
+        for (int q = 1; q < NPART; q++) v += colsum[q * NCOL + threadIdx.x];
+        tot[threadIdx.x / GW][threadIdx.x % GW] = v;
     }
     __syncthreads();
     // rows without in-edges: all equal, so their L1 change is count * |new - old| (not streamed, see zero_row_rank)

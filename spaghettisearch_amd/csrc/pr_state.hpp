@@ -66,6 +66,8 @@ struct PrParams {
     double* partials;     // [nblocks][2][GW]
     double* segpart;      // [nsegs][GW]
     uint32_t* rowticket;  // [n multi-segment rows]
+    double* hubsum;       // [n multi-segment rows][2][GW]: the L1 change and the next contribution of each such row, added in row order behind the blocks' sums
+    uint32_t nmulti;      // multi-segment rows
     PrCtl* ctl;
     const double* x0;     // [GW] 1/n_topic
     double d, teleport, eps, tele_n;
@@ -113,7 +115,7 @@ struct ss_pr {
     int k = 1;
     PrParams prm{};
     unsigned nblocks = 0;
-    ss::DevBuf<double> x, tab0, tab1, send, partials, segpart, x0;
+    ss::DevBuf<double> x, tab0, tab1, send, partials, segpart, hubsum, x0;
     ss::DevBuf<uint32_t> rowticket;
     ss::DevBuf<uint32_t> memb;          // topic-sensitive teleport (optional)
     ss::DevBuf<double> tin, nz_in;

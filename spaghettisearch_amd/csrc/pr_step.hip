@@ -44,7 +44,8 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
 
     double dsum = 0.0, csum = 0.0;
 
-    auto finish = [&](uint32_t lrow, double y) __attribute__((always_inline)) {
+    // hub: a row of several segments, finished by whichever block arrives last — its terms go to the row's own slot (PrParams::hubsum)
+    auto finish = [&](uint32_t lrow, double y, double* hub) __attribute__((always_inline)) {
         const double xo = NT_LOAD(&p.x[(size_t)lrow * GW + t]);
         const uint32_t od = lrow < p.sl_nd ? NT_LOAD(&p.outdeg[lrow]) : 1u;
         y += x0;
@@ -52,14 +53,19 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
         double xn = (y + teleport_of(p, lrow, t)) / S;  // pagerank.go:117
         if (act) {
             NT_STORE(xn, &p.x[xi]);
-            dsum += fabs(xn - xo);                      // pagerank.go:118
+            if (!hub) dsum += fabs(xn - xo);            // pagerank.go:118
         } else {
             xn = xo;                                    // converged topic: frozen
         }
+        double c = 0.0;
         if (lrow < p.sl_nd) {                           // non-dangling row: next sweep's contribution
-            const double c = p.d * xn / (double)od;     // pagerank.go:136
+            c = p.d * xn / (double)od;                  // pagerank.go:136
             NT_STORE(c, &Tw[xi]);
-            csum += c;                                  // pagerank.go:137
+            if (!hub) csum += c;                        // pagerank.go:137
+        }
+        if (hub) {
+            __hip_atomic_store(&hub[t], fabs(xn - xo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&hub[GW + t], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
 
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
                 for (int q = 1; q < WAVES; q++) y += rowred[q][t];
             }
             if (w.nseg == 1) {
-                if (threadIdx.x < GW) finish(lrow, y);
+                if (threadIdx.x < GW) finish(lrow, y, nullptr);
             } else {
                 // several blocks share this row: publish the segment partial; the last
                 // arriver adds the partials in segment order and finishes the row
@@ -102,7 +108,7 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
                     double ys = 0.0;
                     for (uint32_t q = 0; q < w.nseg; q++)
                         ys += __hip_atomic_load(&p.segpart[(size_t)(w.sbase + q) * GW + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    finish(lrow, ys);
+                    finish(lrow, ys, p.hubsum + (size_t)w.tix * 2 * GW);
                 }
             }
         } else if (w.kind == W_WAVE) {
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
                 const size_t beg = p.in_ptr[lrow], end = p.in_ptr[lrow + 1];
                 double acc = gather_sum<GW>(T, p.in_src, beg, end, slot, NSLOT, t);
                 acc = wave_sum_topic<GW>(acc);
-                if (slot == 0) finish(lrow, acc);
+                if (slot == 0) finish(lrow, acc, nullptr);
             }
         } else if (w.kind == W_GROUP) {
             // one lane group (GW lanes) per row; rows are degree-sorted so trip counts match inside a wave
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(TPB) void k_pr_step(PrParams p) {
                 const size_t beg = p.in_ptr[lrow], end = p.in_ptr[lrow + 1];
                 double acc = 0.0;
                 for (size_t e = beg; e < end; e++) acc += T[(size_t)(p.in_src[e] & SRC_MASK) * GW + t];
-                finish(lrow, acc);
+                finish(lrow, acc, nullptr);
             }
         } else {
             // non-dangling rows without in-edges: their rank is the shared value xz, only the next

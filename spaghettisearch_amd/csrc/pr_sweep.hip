@@ -64,8 +64,11 @@ __device__ __forceinline__ void gather_turn(const double* __restrict__ T, const 
     }
 }
 
+// hub: the row was cut into pieces and is finished by whichever wave handed its piece in last, a different one from run to run — its
+// two terms go to the row's own slot (PrParams::hubsum, added in row order by block_reduce_and_publish), not into this wave's sums,
+// whose order of addition must not depend on who arrives when
 template <int GW, bool TS>
-__device__ __forceinline__ void finish_row(SweepCtx<GW, TS>& c, uint32_t lrow, double y, double xo, uint32_t od) {
+__device__ __forceinline__ void finish_row(SweepCtx<GW, TS>& c, uint32_t lrow, double y, double xo, uint32_t od, double* hub = nullptr) {
     const PrParams& p = c.p;
     y += c.x0;
     const size_t xi = (size_t)lrow * GW + c.t;
@@ -74,14 +77,19 @@ __device__ __forceinline__ void finish_row(SweepCtx<GW, TS>& c, uint32_t lrow, d
     double xn = (y + tele) / c.S;                             // pagerank.go:117
     if (c.act) {
         NT_STORE(xn, &p.x[xi]);
-        c.dsum += fabs(xn - xo);                              // pagerank.go:118
+        if (!hub) c.dsum += fabs(xn - xo);                    // pagerank.go:118
     } else {
         xn = xo;                                              // converged topic: frozen
     }
+    double cc = 0.0;
     if (lrow < p.sl_nd) {                                     // non-dangling row: next sweep's contribution
-        const double cc = p.d * xn / (double)od;              // pagerank.go:136
+        cc = p.d * xn / (double)od;                           // pagerank.go:136
         NT_STORE(cc, &c.Tw[xi]);
-        c.csum += cc;                                         // pagerank.go:137
+        if (!hub) c.csum += cc;                               // pagerank.go:137
+    }
+    if (hub) {
+        __hip_atomic_store(&hub[c.t], fabs(xn - xo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&hub[GW + c.t], cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -141,7 +149,7 @@ __device__ __forceinline__ void long_rows(SweepCtx<GW, TS>& c, const WorkItem* _
                     double ys = 0.0;
                     for (uint32_t q = 0; q < cur.nseg; q++)
                         ys += __hip_atomic_load(&p.segpart[(size_t)(cur.sbase + q) * GW + c.t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    finish_row<GW>(c, lrow, ys, xo, od);
+                    finish_row<GW>(c, lrow, ys, xo, od, p.hubsum + (size_t)cur.tix * 2 * GW);
                 }
             }
         }

@@ -59,8 +59,10 @@ struct NCtx {
 };
 // XS: also the row's RANK is stored write-through — the rows that are cut into pieces (V_SEG) are finished by whichever wave hands its
 // piece in last, a different wave (and CU) from sweep to sweep, so inside k_pr_multi_n their ranks are handed from CU to CU like the table
+// hub: a row cut into pieces, finished by whichever wave arrives last — its terms go to the row's own slot (PrParams::hubsum), not
+// into this lane's sums (see k_pr_sweep's finish_row)
 template <int KW, bool TS, int PS = 0, bool XS = false>
-__device__ __forceinline__ void finish_n(NCtx<KW, TS>& c, uint32_t lrow, const NVec<KW>& y, const NVec<KW>& xo, uint32_t od) {
+__device__ __forceinline__ void finish_n(NCtx<KW, TS>& c, uint32_t lrow, const NVec<KW>& y, const NVec<KW>& xo, uint32_t od, double* hub = nullptr) {
     const PrParams& p = c.p;
 #pragma unroll
     for (int k = 0; k < KW; k++) {
@@ -72,14 +74,19 @@ __device__ __forceinline__ void finish_n(NCtx<KW, TS>& c, uint32_t lrow, const N
         if (c.act[k]) {
             if constexpr (XS) __hip_atomic_store(&c.xw[xi], xn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else NT_STORE(xn, &c.xw[xi]);
-            c.dsum[k] += fabs(xn - xo.v[k]);                      // pagerank.go:118
+            if (!hub) c.dsum[k] += fabs(xn - xo.v[k]);            // pagerank.go:118
         } else {
             xn = xo.v[k];                                         // converged topic: frozen
         }
+        double cc = 0.0;
         if (lrow < p.sl_nd) {                                     // non-dangling row: next sweep's contribution
-            const double cc = p.d * xn / (double)od;              // pagerank.go:136
+            cc = p.d * xn / (double)od;                           // pagerank.go:136
             tab_store<PS>(cc, &c.Tw[xi]);
-            c.csum[k] += cc;                                      // pagerank.go:137
+            if (!hub) c.csum[k] += cc;                            // pagerank.go:137
+        }
+        if (hub) {
+            __hip_atomic_store(&hub[k], fabs(xn - xo.v[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&hub[KW + k], cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -213,9 +220,9 @@ __device__ __forceinline__ void sweep_n_body(const PrParams& p, const int sweep,
                             NVec<KW> xs;
     #pragma unroll
                             for (int k = 0; k < KW; k++) xs.v[k] = __hip_atomic_load(&c.xr[(size_t)lrow * KW + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            finish_n<KW, TS, PS, true>(c, lrow, ys, xs, od);
+                            finish_n<KW, TS, PS, true>(c, lrow, ys, xs, od, p.hubsum + (size_t)w.tix * 2 * KW);
                         } else {
-                            finish_n<KW, TS, PS>(c, lrow, ys, xo, od);
+                            finish_n<KW, TS, PS>(c, lrow, ys, xo, od, p.hubsum + (size_t)w.tix * 2 * KW);
                         }
                     }
                 }

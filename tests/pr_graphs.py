@@ -99,6 +99,91 @@ def multi_edge_graph():
     return n, ptr, dst[order].astype(np.uint32)
 
 
+# ---- one graph with rows of every sweep-kernel row class, on both sides of every threshold, dangling or not ---------------------
+# (tests/test_pr_class_graph_cpu.py proves with the planner harness that it reaches what it claims; tests/test_gpu_pr_classes.py runs it)
+SEGW, T_MULTI = 2048, 4096
+# thresholds of the wave-item kernels from both sides: T_DEG (8 | 9), the chunks-per-row steps up to the last one below T_QUAD of
+# k_pr_sweep (128) and of k_pr_sweep_n (256), T_MULTI, and hubs whose last piece is one edge (2 SEGW + 1 = T_MULTI + 1, 3 SEGW + 1)
+# or full (3 SEGW).  (1 .. 8 come with the exact-degree runs below.)
+CLASS_WAVE_DEGREES = [9, 16, 17, 32, 33, 112, 113, 128, 129, 240, 241, 256, 257, T_MULTI, T_MULTI + 1, 2 * SEGW + 1, 3 * SEGW, 3 * SEGW + 1]
+# thresholds of k_pr_step at gw 1 and 2 (NSLOT = 64, 32): T_WAVE = 2 NSLOT, T_SEG = 32 NSLOT, one / two / four pieces of 128 NSLOT
+# edges.  (None is too large for the node count: the longest row, 3 * 8192 + 1 parents, is what sets it.)
+CLASS_STEP_DEGREES = sorted({v for s in (64, 32) for v in (2 * s - 1, 2 * s, 2 * s + 1, 32 * s - 1, 32 * s, 32 * s + 1, 128 * s, 128 * s + 1, 3 * 128 * s + 1)})
+CLASS_RUN_ROWS = {D: 2 * 256 + 1 + D for D in range(1, 9)}          # rows of exactly D in-edges: more than two items of 256, ragged tail
+# rows of one and of two 16-edge chunks: with the threshold rows 69 (9 .. 16) and 37 (17 .. 32) rows, more than max_groups * NSLOT
+# (64 / 32 at most) and no multiple of 4
+CLASS_NCH_FILL = {12: 67, 24: 35}
+CLASS_ZERO_ND, CLASS_ZERO_D = 20800, 40                              # rows without in-edges: non-dangling / dangling
+
+
+def class_degree_multiset():
+    """the in-degrees with in-edges that EACH class of class_boundary_graph() holds, falling"""
+    deg = CLASS_WAVE_DEGREES + CLASS_STEP_DEGREES
+    for D, rows in {**CLASS_RUN_ROWS, **CLASS_NCH_FILL}.items():
+        deg = deg + [D] * rows
+    return sorted(deg, reverse=True)
+
+
+@functools.lru_cache(maxsize=None)
+def class_boundary_graph(seed=17):
+    """About 30k nodes, unique edges, shuffled ids.  Both classes — non-dangling rows and dangling rows — hold class_degree_multiset();
+    CLASS_ZERO_ND non-dangling and CLASS_ZERO_D dangling rows have no in-edges.  A row's parents are distinct non-dangling nodes
+    (whoever has a child is one) drawn with weights that fall like a power of the node's position, so the out-degrees differ widely:
+    after two sweeps no two parents of a row need hold one contribution, and the rows without in-edges (a shared table row per
+    out-degree) have more than 64 distinct out-degrees.  Every non-dangling node gets a child: the longest row, drawn last, takes
+    those that have none by then."""
+    rng = np.random.default_rng(seed)
+    degs = class_degree_multiset()
+    n_nd, n_d = len(degs) + CLASS_ZERO_ND, len(degs) + CLASS_ZERO_D
+    n = n_nd + n_d
+    assert n_nd > degs[0]
+    w = rng.permutation((np.arange(n_nd) + 20.0) ** -0.9)
+    w /= w.sum()
+    cum = np.cumsum(w)
+    cum[-1] = 1.0
+    # rows: (child, in-degree); child ids 0 .. len(degs) - 1 are the non-dangling targets, n_nd .. the dangling ones; longest last
+    rows = sorted([(c, m) for c, m in enumerate(degs)] + [(n_nd + c, m) for c, m in enumerate(degs)], key=lambda r: r[1])
+    outdeg = np.zeros(n_nd, dtype=np.int64)
+    src, dst = [], []
+    for i, (child, m) in enumerate(rows):
+        if i == len(rows) - 1:                                       # the longest row: everyone still childless, the rest by weight
+            forced = np.flatnonzero(outdeg == 0)
+            p = w.copy()
+            p[forced] = 0.0
+            par = np.concatenate((forced, rng.choice(n_nd, m - len(forced), replace=False, p=p / p.sum())))
+        elif m > 48:
+            par = rng.choice(n_nd, m, replace=False, p=w)
+        else:
+            par = np.zeros(0, dtype=np.int64)
+            while len(par) < m:                                      # with replacement by weight, first appearances kept
+                c = np.concatenate((par, np.searchsorted(cum, rng.random(3 * m + 8), side="right")))
+                par = c[np.sort(np.unique(c, return_index=True)[1])]
+            par = par[:m]
+        outdeg[par] += 1
+        src.append(par)
+        dst.append(np.full(m, child, dtype=np.int64))
+    perm = rng.permutation(n)
+    src, dst = perm[np.concatenate(src)], perm[np.concatenate(dst)]
+    order = np.lexsort((dst, src))
+    ptr = np.zeros(n + 1, dtype=np.uint64)
+    ptr[1:] = np.cumsum(np.bincount(src, minlength=n))
+    return n, ptr, dst[order].astype(np.uint32)
+
+
+def class_degree_tables(n, ptr, dst):
+    """-> (nd, d, rows_nd, rows_d): the falling in-degrees of the non-dangling and of the dangling rows, as lists, and the original
+    ids in that order (class, in-degree descending, id ascending: the library's row order)"""
+    outdeg = np.diff(np.asarray(ptr).astype(np.int64))
+    indeg = np.bincount(np.asarray(dst).astype(np.int64), minlength=n)
+    order = np.lexsort((np.arange(n), -indeg, outdeg == 0))
+    n_nd = int((outdeg > 0).sum())
+    return indeg[order[:n_nd]].tolist(), indeg[order[n_nd:]].tolist(), order[:n_nd], order[n_nd:]
+
+
+def topic_sizes(n, k):
+    return [max(1, n // (1 + 5 * j)) for j in range(k)]               # K different sizes: the topics stop at different sweeps
+
+
 # ---- hand-built deltas for ss_graph_apply_delta (tests/test_gpu_graph_paths.py; predicates checked in test_graph_layout_cpu.py) ----
 def rows_of(n, ptr, dst):
     return [dst[int(ptr[v]):int(ptr[v + 1])].copy() for v in range(n)]
