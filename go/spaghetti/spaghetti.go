@@ -396,6 +396,37 @@ func (ix *Index) DropDocView() {
 	check(ix.ctx, C.ss_index_drop_doc_view(ix.h), "ss_index_drop_doc_view")
 }
 
+// SigEmpty fills every slot of the signature of a doc without terms (SS_SIG_EMPTY); MaxSigSlots is the most slots a signature has.
+const SigEmpty = uint32(C.SS_SIG_EMPTY)
+const MaxSigSlots = int(C.SS_MAX_SIG_SLOTS)
+
+// BuildSignatures builds a MinHash signature of nSlots (4, 8, .., 32) words per doc from the doc view's term sets
+// (ss_index_build_signatures; needs BuildDocView).  A snapshot of its own: TfIdfBuild, ApplyDelta and Resize free it, dropping the
+// view does not.  4*nSlots bytes per doc of device memory.
+func (ix *Index) BuildSignatures(nSlots int) {
+	check(ix.ctx, C.ss_index_build_signatures(ix.h, C.int32_t(nSlots)), "ss_index_build_signatures")
+}
+func (ix *Index) DropSignatures() {
+	check(ix.ctx, C.ss_index_drop_signatures(ix.h), "ss_index_drop_signatures")
+}
+
+// ReadSignatures returns the signature of every doc of docs, one row each.
+func (ix *Index) ReadSignatures(docs []uint32) [][]uint32 {
+	var nSlots C.int32_t
+	check(ix.ctx, C.ss_index_read_signatures(ix.h, C.uint64_t(0), nil, nil, &nSlots), "ss_index_read_signatures")
+	if len(docs) == 0 {
+		return nil
+	}
+	s := int(nSlots)
+	flat := make([]uint32, len(docs)*s)
+	check(ix.ctx, C.ss_index_read_signatures(ix.h, C.uint64_t(len(docs)), u32p(docs), u32p(flat), nil), "ss_index_read_signatures")
+	out := make([][]uint32, len(docs))
+	for i := range docs {
+		out[i] = flat[i*s : (i+1)*s]
+	}
+	return out
+}
+
 // DocTopTerms returns the m heaviest terms of every doc (weight descending, then term id; NaN last) and their weights:
 // what the reference keeps per page as Words_mapping cut by sortMap (retrieval/util.go:116-149).  Needs BuildDocView.
 func (ix *Index) DocTopTerms(docs []uint32, m int) ([][]uint32, [][]float32) {
@@ -707,6 +738,56 @@ func (s *Scorer) ScoreTopKCollapsed(qPtr, qTerms []uint32, queryLen []int32, top
 		return nil, err
 	}
 	return collapsedPages(nq, kk, raw, nHits, same, kept), nil
+}
+
+// DedupedPage is one page of a query's results without near-duplicate rows: Similar[i] = rows of the whole window that Hits[i] leads,
+// itself included ("Similar[i]-1 very similar results omitted"); Kept = rows the whole window keeps.
+type DedupedPage struct {
+	Hits    []Hit
+	Similar []uint32
+	Kept    int
+}
+
+// DedupHits drops from every window hits[q], in the order given, the rows whose body signature agrees in at least minMatch slots
+// with an earlier kept row's (ss_dedup_hits), and returns page [first, first+k) of the kept rows.  The rows may come from any
+// scoring call; the body table needs BuildSignatures.
+func (s *Scorer) DedupHits(hits [][]Hit, minMatch, first, k int) ([]DedupedPage, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	kIn := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > kIn {
+			kIn = len(hits[q])
+		}
+	}
+	in := make([]C.ss_hit, nq*kIn)
+	nIn := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			in[q*kIn+j] = C.ss_hit{doc: C.uint32_t(h.Doc), title: C.double(h.Title), body: C.double(h.Body), pagerank: C.double(h.PageRank),
+				final: C.double(h.Final)}
+		}
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, kept, similar := make([]int32, nq), make([]int32, nq), make([]uint32, nq*kk)
+	rc := C.ss_dedup_hits(s.h, C.int32_t(nq), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), C.int32_t(minMatch),
+		C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), u32p(similar), i32p(kept))
+	if err := statusErr(s.ctx, rc, "ss_dedup_hits"); err != nil {
+		return nil, err
+	}
+	pages := collapsedPages(nq, kk, raw, nHits, similar, kept)
+	out := make([]DedupedPage, nq)
+	for q, p := range pages {
+		out[q] = DedupedPage{p.Hits, p.Same, p.Kept}
+	}
+	return out, nil
 }
 
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every

@@ -43,7 +43,9 @@ extern "C" {
  * ss_passage and ss_best_passages (per result row the body window that covers most of the query's terms);
  * SS_NO_GROUP, ss_scorer_set_doc_groups, ss_collapse_hits and ss_score_topk_collapsed (at most g rows per site, with paging);
  * SS_MAX_WORD_BYTES, SS_MAX_EDIT_DIST, SS_MAX_SUGGEST, ss_lexicon, ss_lexicon_create / _set_freq / _get_info / _read_order / _destroy,
- * ss_lexicon_prefix and ss_lexicon_suggest (the words of the vocabulary on the device: word list by prefix, spelling suggestions). */
+ * ss_lexicon_prefix and ss_lexicon_suggest (the words of the vocabulary on the device: word list by prefix, spelling suggestions);
+ * SS_MAX_SIG_SLOTS, SS_SIG_EMPTY, ss_index_build_signatures / _drop_signatures / _read_signatures and ss_dedup_hits (a MinHash
+ * signature per doc, near-duplicate rows dropped from a result window). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -608,6 +610,62 @@ int32_t ss_score_topk_collapsed(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
                                 int32_t k_window, int32_t g, int32_t first, int32_t k,
                                 ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
                                 uint32_t* same_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
+
+/* Near-duplicate results: a MinHash signature per doc and a walk over one result window that drops the rows whose signature agrees
+ * with an earlier kept row's ("some very similar results were omitted").  The reference ranks mirrors, print views and session-id
+ * URLs as separate pages (retrieval/main_retrieve.go:99-103), and ss_collapse_hits only helps when the copies share a site key.
+ * Integer arithmetic only, defined bit for bit:
+ *   Hash.       With all arithmetic mod 2^32:   x = t + 0x9E3779B9 * (s + 1);
+ *                                                x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16;
+ *               h(t, s) = x.  h(0,0) = 0x92CA2F0E, h(1,0) = 0x96A0F96B, h(0,1) = 0x3CD6E3F3, h(12345,3) = 0x8EE55794,
+ *               h(0xFFFFFFFE,31) = 0x26D56D90, h(70000,15) = 0x231FE950.
+ *   Signature.  sig[d][s] = the minimum over the terms t of doc d's row of the doc view (ss_index_build_doc_view) of h(t, s), for
+ *               s < n_slots.  Weights are not read.  A doc with an empty row has every slot = SS_SIG_EMPTY.  Row {3, 7, 70000} with
+ *               4 slots gives 0x2316A329, 0x2C85567E, 0x41B9D641, 0x343B1A79.  A non-empty row is never all SS_SIG_EMPTY when
+ *               n_slots >= 2: the mix is a bijection and the slots' offsets differ, so in one slot exactly one term value reaches
+ *               0xFFFFFFFF and no term does so in two slots.
+ * ss_index_build_signatures: n_slots in {4, 8, .., SS_MAX_SIG_SLOTS} (a row is then a multiple of 16 bytes); any other value up to
+ * SS_MAX_SIG_SLOTS (zero and below included) is SS_ERR_INVALID, a larger one SS_ERR_UNSUPPORTED; a table without a doc view is
+ * SS_ERR_STATE.  None of these touches signatures that exist.  The signatures are a snapshot and a pure function of the table: two
+ * builds give identical bytes.  Resident size 4 * n_slots bytes per doc (640 MB at 10M docs and 16 slots).  Building where signatures
+ * exist frees the old ones FIRST, and a build that fails (SS_ERR_OOM, SS_ERR_HIP) leaves the table WITHOUT signatures.
+ * ss_tfidf_build, ss_index_apply_delta(_pos), ss_index_resize (and ss_index_destroy) free them; ss_index_drop_doc_view and a rebuild
+ * of the view do not: the signatures are a snapshot of their own.  Without signatures ss_index_drop_signatures,
+ * ss_index_read_signatures and ss_dedup_hits return SS_ERR_STATE.  The calls wait for their work.
+ * ss_index_read_signatures: sig_out[i][0 .. n_slots) = sig[docs[i]]; *n_slots_out (nullable) = n_slots.  A doc id >= n_docs (or a
+ * NULL docs / sig_out with n > 0) is SS_ERR_INVALID before anything is enqueued, sig_out untouched; a doc may appear more than once. */
+#define SS_MAX_SIG_SLOTS 32
+#define SS_SIG_EMPTY 0xFFFFFFFFu
+int32_t ss_index_build_signatures(ss_index* idx, int32_t n_slots);
+int32_t ss_index_drop_signatures(ss_index* idx);
+int32_t ss_index_read_signatures(ss_index* idx, uint64_t n, const uint32_t* docs /*[n], host or device*/,
+                                 uint32_t* sig_out /*[n][n_slots], host or device*/, int32_t* n_slots_out /*nullable*/);
+
+/* ss_dedup_hits: drop the near-duplicate rows of given windows.  Reads the signatures of the scorer's BODY table.  Defined bit for bit:
+ *   Window.     As in ss_collapse_hits: hits[q * k_in .. q * k_in + n_hits[q]), in the order given.  Only .doc of a row is read and
+ *               nothing is re-sorted.
+ *   Signature.  A row's signature is sig[doc] when doc < n_docs and sig[doc] is not all SS_SIG_EMPTY.  Otherwise the row is on its
+ *               own: never a duplicate, and never the leader of any row but itself, even when another row has an equal doc.  No doc
+ *               id makes the kernel read outside the table.
+ *   match(i, j) = the number of slots s < n_slots in which the signatures of rows i and j are equal.
+ *   Walk.       For j ascending: row j is a duplicate iff some KEPT row i < j has match(i, j) >= min_match; its leader is the smallest
+ *               such i.  Otherwise j is kept and leads itself.  A dropped row shields nothing: with A ~ B and B ~ C but not A ~ C,
+ *               B is dropped and C is kept.
+ *   Output.     With the kept rows in window order K_0 .. K_{n_kept-1}: hits_out[q * k + r] = the 40 bytes of K_{first + r} for
+ *               r < n_hits_out[q] = clamp(n_kept - first, 0, k), exactly as ss_collapse_hits copies them.  similar_out[q * k + r]
+ *               (nullable) = the number of rows of the whole window led by that row, itself included.  n_kept_out[q] (nullable) =
+ *               n_kept.  Entries past n_hits_out[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: those of ss_collapse_hits (NULL handle or array, n_q < 0,
+ * k_in < 1, k < 1, first < 0, hits_out overlapping hits: SS_ERR_INVALID; k_in or k above SS_MAX_TOPK: SS_ERR_UNSUPPORTED; a host
+ * n_hits[q] outside [0, k_in]: SS_ERR_INVALID, a device one is clamped by the kernel; n_q == 0 is SS_OK), with no signatures on the
+ * body table: SS_ERR_STATE in place of the group table's, and min_match < 1 or min_match > n_slots: SS_ERR_INVALID in place of g's.
+ * Pointers host or device: when all given pointers are device memory the call only enqueues on the ctx stream and NEVER waits, so
+ * score -> dedup -> collapse -> explain -> passages chains on one stream; otherwise it stages through blocks the scorer owns and
+ * returns when the outputs are written.  No fused scoring form and no _submit / _collect form. */
+int32_t ss_dedup_hits(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
+                      int32_t min_match, int32_t first, int32_t k,
+                      ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                      uint32_t* similar_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
 
 /* ---- term lexicon: cmd/server/server.go:54-85 (/wordlist/{pre}), database/database.go:414-454 (IterateInv) -------------
  * The words of forw[0] keyed by dense term id, resident on the device.  The reference answers /wordlist/{pre} by walking every key

@@ -21,6 +21,8 @@ SS_NO_GROUP = 0xFFFFFFFF
 SS_MAX_WORD_BYTES = 64
 SS_MAX_EDIT_DIST = 3
 SS_MAX_SUGGEST = 64
+SS_MAX_SIG_SLOTS = 32
+SS_SIG_EMPTY = 0xFFFFFFFF
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -127,6 +129,10 @@ PROTOTYPES = {
     "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
     "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_index_build_signatures": (_i32, [_vp, _i32]),
+    "ss_index_drop_signatures": (_i32, [_vp]),
+    "ss_index_read_signatures": (_i32, [_vp, _u64, _vp, _vp, C.POINTER(_i32)]),
+    "ss_dedup_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_lexicon_create": (_i32, [_vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ss_lexicon_set_freq": (_i32, [_vp, _vp]),
     "ss_lexicon_get_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),

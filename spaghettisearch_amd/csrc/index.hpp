@@ -35,6 +35,16 @@ struct ss_index {
         dv_w.release();
         has_doc_view = false;
     }
+    // MinHash signatures (dedup.hip, optional): sig u32[n_docs][sig_slots], row d = per slot the least hash of the terms of the view's
+    // row d.  A snapshot of its own: whatever changes postings drops it, dropping or rebuilding the view does not.
+    ss::DevBuf<uint32_t> sig;
+    int32_t sig_slots = 0;
+    bool has_signatures = false;
+    void drop_signatures() {
+        sig.release();
+        sig_slots = 0;
+        has_signatures = false;
+    }
 };
 
 namespace ss {

@@ -512,6 +512,7 @@ int32_t ss_index_apply_delta_pos(ss_index* idx, uint64_t n_del_docs, const uint3
     SS_HIP(ctx, hipStreamSynchronize(st));
     // commit
     idx->drop_doc_view();                        // a snapshot of the postings that go
+    idx->drop_signatures();                      // ... and so are the signatures
     idx->post_doc = std::move(out_doc);
     idx->post_w = std::move(out_w);
     idx->term_ptr = std::move(new_ptr);
@@ -536,6 +537,7 @@ int32_t ss_index_resize(ss_index* idx, uint64_t n_docs_new, uint64_t n_terms_new
     hipStream_t st = ctx->stream;
     const uint64_t T = idx->n_terms, N = idx->n_docs, P = idx->n_post;
     idx->drop_doc_view();                        // its doc_ptr has one entry per doc of the old size
+    idx->drop_signatures();                      // ... and the signatures one row
     if (n_terms_new > T) {                                   // new terms: empty lists behind the last posting
         ss::DevBuf<uint64_t> tp;
         SS_HIP(ctx, tp.alloc(n_terms_new + 1));

@@ -167,6 +167,10 @@ struct ss_scorer {
     ss::DevBuf<ss_hit> d_col_hits, d_col_out;
     ss::DevBuf<int32_t> d_col_n, d_col_nout, d_col_kept;
     ss::DevBuf<uint32_t> d_col_same;
+    // ss_dedup_hits (dedup.hip): d_dd_*: device blocks of HOST arrays (grow-only; a call that uses one waits before it returns).
+    ss::DevBuf<ss_hit> d_dd_hits, d_dd_out;
+    ss::DevBuf<int32_t> d_dd_n, d_dd_nout, d_dd_kept;
+    ss::DevBuf<uint32_t> d_dd_sim;
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.

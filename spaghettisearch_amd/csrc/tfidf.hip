@@ -1095,6 +1095,7 @@ int32_t ss_tfidf_build(ss_index* idx, uint64_t total_docs, float* w_out, double*
     hipStream_t st = ctx->stream;
     const uint64_t P = idx->n_post, T = idx->n_terms, N = idx->n_docs;
     idx->drop_doc_view();                        // the weights change: a doc view holds the old ones
+    idx->drop_signatures();                      // (made from a view of the table as it stood: freed with it, as the header says)
     // every allocation happens BEFORE the start event: ss_last_kernel_ms(2) brackets device work only
     // (a 5 GB hipMalloc inside the window once put ~1 s of host-side allocator time into the "kernel" time)
     ss::DevBuf<float> idf;

@@ -456,6 +456,32 @@ class InvertedIndex:
         check(self.ctx.lib.ss_index_doc_top_terms(self.h, n, _ptr(docs), int(m), _ptr(terms), _ptr(w), _ptr(n_out)), self.ctx.h)
         return terms, w, n_out
 
+    def build_signatures(self, n_slots: int = 16) -> None:
+        """ss_index_build_signatures: a MinHash signature of n_slots (4, 8, .., 32) uint32 per doc from the doc view's term sets
+        (build_doc_view first).  A snapshot of its own: tfidf_build, apply_delta and resize free it, dropping the view does not."""
+        check(self.ctx.lib.ss_index_build_signatures(self.h, int(n_slots)), self.ctx.h)
+
+    def drop_signatures(self) -> None:
+        check(self.ctx.lib.ss_index_drop_signatures(self.h), self.ctx.h)
+
+    def read_signatures(self, docs, out=None):
+        """ss_index_read_signatures: -> sig uint32[n][n_slots], row i = the signature of docs[i] (SS_SIG_EMPTY throughout for a doc
+        without body terms).  docs: numpy or torch; out: the caller's array (numpy uint32 or a torch int32 device tensor holding at
+        least n * n_slots words), returned as it is."""
+        docs = _as(docs, "uint32")
+        n = int(docs.numel() if _is_torch(docs) else docs.size)
+        n_slots = C.c_int32(0)
+        check(self.ctx.lib.ss_index_read_signatures(self.h, 0, None, None, C.byref(n_slots)), self.ctx.h)
+        if out is None:
+            out = np.zeros((n, n_slots.value), dtype=np.uint32)
+        else:
+            out = _as(out, "uint32")
+            if (out.numel() if _is_torch(out) else out.size) < n * n_slots.value:
+                raise ValueError("output buffer too small")
+        self.ctx.ready(docs, out)
+        check(self.ctx.lib.ss_index_read_signatures(self.h, n, _ptr(docs), _ptr(out), None), self.ctx.h)
+        return out
+
     def set_doc_freq(self, df) -> None:
         """ss_index_set_doc_freq: whole-corpus document frequencies when this table is one doc-range shard
         (uint64[n_terms]; None = local list lengths).  Call before tfidf_build."""
@@ -798,6 +824,31 @@ class Scorer:
         if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_same, o_kept
+
+    def dedup_hits(self, hits, n_hits, min_match: int, k: int, first: int = 0, k_in: Optional[int] = None, out=None,
+                   want_similar: bool = True, want_kept: bool = True):
+        """ss_dedup_hits: drop the near-duplicate rows of every window hits[q][: n_hits[q]] — a row whose body signature agrees in at
+        least min_match slots with an earlier kept row's — and return page [first, first + k) of the kept rows in window order
+        -> (hits [n_q][k], n_hits [n_q], similar [n_q][k] | None, n_kept [n_q] | None); similar = the rows of the window a kept row
+        leads, itself included.  The body table needs signatures (InvertedIndex.build_signatures).  hits / n_hits, k_in and out as in
+        collapse_hits: with device arrays throughout the library only enqueues."""
+        n_hits = _as(n_hits, "int32")
+        n_q = int(n_hits.numel() if _is_torch(n_hits) else n_hits.size)
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k_in is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k_in = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k_in) * HIT_DTYPE.itemsize:
+            raise ValueError("hits too small")
+        o_hits, o_n, o_sim, o_kept = self._collapse_out(n_q, int(k), out, want_similar, want_kept)
+        self.ctx.ready(hits, n_hits, o_hits, o_n, o_sim, o_kept)
+        check(self.ctx.lib.ss_dedup_hits(self.h, n_q, int(k_in), _ptr(hits), _ptr(n_hits), int(min_match), int(first), int(k),
+                                         _ptr(o_hits), _ptr(o_n), _ptr(o_sim), _ptr(o_kept)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sim, o_kept
 
     def score_topk_collapsed(self, q_ptr, q_terms, k_window: int, g: int, k: int, first: int = 0, query_len=None, topic_probs=None,
                              mask_id=None, out=None, want_same: bool = True, want_kept: bool = True):

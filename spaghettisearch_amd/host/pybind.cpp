@@ -59,6 +59,10 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Results", &retrieval::CollapsedPage::Results)
         .def_readonly("Same", &retrieval::CollapsedPage::Same)
         .def_readonly("Kept", &retrieval::CollapsedPage::Kept);
+    py::class_<retrieval::DedupedPage>(m, "DedupedPage")
+        .def_readonly("Results", &retrieval::DedupedPage::Results)
+        .def_readonly("Similar", &retrieval::DedupedPage::Similar)
+        .def_readonly("Kept", &retrieval::DedupedPage::Kept);
 
     auto as_dbs = [](std::vector<db::MemDB*>& v) {
         std::vector<db::DB*> out;
@@ -157,6 +161,15 @@ PYBIND11_MODULE(_host, m) {
             auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
             return di.RetrieveBatchCollapsed(queries, k_window, g, first, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("k_window"), py::arg("g"), py::arg("first") = 0, py::arg("k") = 50,
+           py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("SetNearDuplicates", &retrieval::DeviceIndex::SetNearDuplicates, py::arg("n_slots"))
+        .def("NearDuplicateSlots", &retrieval::DeviceIndex::NearDuplicateSlots)
+        .def("RetrieveBatchDeduped", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, int min_match,
+                                        int first, int k, py::object topic_probs, bool live_topic_probs) {
+            if (topic_probs.is_none()) return di.RetrieveBatchDeduped(queries, k_window, min_match, first, k, nullptr, live_topic_probs);
+            auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
+            return di.RetrieveBatchDeduped(queries, k_window, min_match, first, k, &tp, live_topic_probs);
+        }, py::arg("queries"), py::arg("k_window"), py::arg("min_match"), py::arg("first") = 0, py::arg("k") = 50,
            py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetQueryOperators", &retrieval::DeviceIndex::SetQueryOperators, py::arg("on"))
         .def("SetSimilarPages", &retrieval::DeviceIndex::SetSimilarPages, py::arg("on"))

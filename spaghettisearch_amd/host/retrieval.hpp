@@ -69,6 +69,15 @@ struct CollapsedPage {
     int Kept = 0;
 };
 
+// One page of a query's results without near-duplicate pages (DeviceIndex::RetrieveBatchDeduped; no reference counterpart).
+// Similar[i]: how many rows of the query's window Results[i] stands for, itself included ("Similar[i] - 1 very similar results
+// omitted"); Kept: how many rows the whole window keeps, i.e. how far paging can go.
+struct DedupedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<uint32_t> Similar;
+    int Kept = 0;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -281,6 +290,8 @@ public:
     // again on every scorer this index creates.  has_doc_groups: SetDocGroups was called (an empty map is a table of SS_NO_GROUP).
     std::map<std::string, std::string> doc_group_keys;
     bool has_doc_groups = false;
+    int near_dup_slots = 0;                         // SetNearDuplicates: the body table keeps MinHash signatures of this many slots (4 B each per doc)
+    bool signatures_built = false;                  // the body table holds signatures that this object built and nothing has freed since
     // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
     // = title + body list length per term.  upload() drops it (the term ids are new): call SetLexicon again after load().
     ss_lexicon* lexicon = nullptr;
@@ -371,7 +382,7 @@ public:
         if (title) { ss_index_destroy(title); title = nullptr; }
         if (body) { ss_index_destroy(body); body = nullptr; }
         drop_lexicon();
-        mags_resident = flat_stale = doc_view_built = false;
+        mags_resident = flat_stale = doc_view_built = signatures_built = false;
         const size_t n = flat.doc_names.size(), T = flat.term_names.size();
         check(ss_index_create(default_ctx(), n, T, flat.title.term_ptr.data(), flat.title.post_doc.data(), flat.title.post_w.data(), &title), "ss_index_create(title)");
         check(ss_index_create(default_ctx(), n, T, flat.body.term_ptr.data(), flat.body.post_doc.data(), flat.body.post_w.data(), &body), "ss_index_create(body)");
@@ -386,6 +397,7 @@ public:
         register_masks();
         register_groups();
         build_doc_view();
+        build_signatures();
     }
 
     // Similar pages (no reference counterpart; default off: nothing is built and memory is as it was).  On, the body table's
@@ -403,6 +415,29 @@ public:
         doc_view_built = true;
     }
     bool HasDocView() const { return doc_view_built; }
+    // Near-duplicate results (no reference counterpart; default off).  n_slots = 4, 8, .., 32: the body table gets a MinHash
+    // signature per doc (ss_index_build_signatures), built now and again after every upload / ApplyDelta (a delta frees the
+    // signatures with the postings they were made from); 0 frees them.  The signatures are made from the body table's doc view:
+    // a view built only for them (SetSimilarPages off) is freed again once they exist.
+    void SetNearDuplicates(int n_slots) {
+        if (n_slots == 0) {
+            near_dup_slots = 0;
+            if (body && signatures_built) { signatures_built = false; spaghetti::check(ss_index_drop_signatures(body), "ss_index_drop_signatures(body)"); }
+            return;
+        }
+        const int before = near_dup_slots;
+        near_dup_slots = n_slots;
+        try { build_signatures(); } catch (...) { near_dup_slots = before; throw; }
+    }
+    void build_signatures() {
+        if (!near_dup_slots || !body) return;
+        if (!doc_view_built) spaghetti::check(ss_index_build_doc_view(body), "ss_index_build_doc_view(body)");
+        const int32_t rc = ss_index_build_signatures(body, near_dup_slots);
+        if (rc == SS_OK || (rc != SS_ERR_INVALID && rc != SS_ERR_UNSUPPORTED)) signatures_built = rc == SS_OK;   // (a refused n_slots leaves what exists)
+        if (!doc_view_built) (void)ss_index_drop_doc_view(body);
+        spaghetti::check(rc, "ss_index_build_signatures(body)");
+    }
+    int NearDuplicateSlots() const { return signatures_built ? near_dup_slots : 0; }
     // the m heaviest body words of a page (word hashes; weight descending, then dense term id), empty for an unknown hash
     std::vector<std::string> DocTopTerms(const std::string& docHash, int m = 5) {
         using namespace spaghetti;
@@ -784,6 +819,7 @@ public:
                 try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
                 try { di.register_groups(); } catch (...) {}                // (RetrieveBatchCollapsed then reports the missing table)
                 try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
+                try { di.build_signatures(); } catch (...) {}               // (RetrieveBatchDeduped then reports the missing signatures)
             }
         } scorer_guard{*this};
         bool resized = false;
@@ -795,7 +831,7 @@ public:
             terms.name.resize(t_before);
         };
         if (scorer) { ss_scorer_destroy(scorer); scorer = nullptr; }      // scorers on a table go before its delta
-        doc_view_built = false;                                           // resize / the delta free the view; every way out builds it again
+        doc_view_built = signatures_built = false;                        // resize / the delta free the view and the signatures; every way out builds them again
         try {
             if (n != n_before || T != t_before) {
                 check(ss_index_resize(title, n, T), "ss_index_resize(title)");
@@ -903,6 +939,7 @@ public:
         register_masks();                                                 // the new scorer, the ids as they stand now
         register_groups();
         build_doc_view();                                                 // (the deltas freed it)
+        build_signatures();
         refresh_lexicon(ctx, forw[0], t_before);                          // new term ids: a new lexicon; otherwise the frequencies only
     }
 
@@ -1166,6 +1203,34 @@ public:
         for (size_t q = 0; q < nq; q++) {
             out[q].Results = ranks[q];
             out[q].Same.assign(same.begin() + q * kk, same.begin() + q * kk + n_page[q]);
+            out[q].Kept = n_kept[q];
+        }
+        return out;
+    }
+    // RetrieveBatch without near-duplicate pages (SetNearDuplicates): page [first, first + k) of every query's ranking after the
+    // rows whose body signature agrees with an earlier kept row's in at least min_match slots have been dropped, taken over the
+    // first k_window rows of the ranking (k_window <= SS_MAX_TOPK; 1 <= min_match <= the signatures' slots).  The rows are scored
+    // by ss_score_topk_phrase and go through ss_dedup_hits.  Query operators are not read here.
+    std::vector<DedupedPage> RetrieveBatchDeduped(const std::vector<std::string>& queries, int k_window, int min_match, int first = 0,
+                                                  int k = 50, const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                  bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (!signatures_built) throw std::runtime_error("RetrieveBatchDeduped: no signatures (SetNearDuplicates)");
+        if (query_operators) throw std::runtime_error("RetrieveBatchDeduped: query operators are not read here (SetQueryOperators(false))");
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
+        std::vector<ss_hit> page(nq * kk), rows(nq * (size_t)std::max(k_window, 1));
+        std::vector<int32_t> n_page(nq), n_kept(nq), n_rows(nq);
+        std::vector<uint32_t> similar(nq * kk);
+        check(ss_score_topk_phrase(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                   t.probs.empty() ? nullptr : t.probs.data(), k_window, rows.data(), n_rows.data()), "ss_score_topk_phrase");
+        check(ss_dedup_hits(scorer, t.nq, k_window, rows.data(), n_rows.data(), min_match, first, k, page.data(), n_page.data(), similar.data(),
+                            n_kept.data()), "ss_dedup_hits");
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<DedupedPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Similar.assign(similar.begin() + q * kk, similar.begin() + q * kk + n_page[q]);
             out[q].Kept = n_kept[q];
         }
         return out;
