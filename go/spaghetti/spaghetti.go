@@ -228,6 +228,89 @@ func (g *Graph) ApplyDelta(nNodesNew uint64, changed []uint32, newPtr []uint64, 
 	g.N = nNodesNew
 }
 
+// Directions of TopLinks / HitLinks.
+const (
+	LinksParents  = int(C.SS_LINKS_PARENTS)
+	LinksChildren = int(C.SS_LINKS_CHILDREN)
+	MaxLinks      = int(C.SS_MAX_LINKS)
+)
+
+// SetLinkKey registers the per-node key that orders TopLinks / HitLinks (one value per node, say one topic's PageRank row;
+// copied); nil clears it.  A successful ApplyDelta clears it too.
+func (g *Graph) SetLinkKey(key []float64) {
+	check(g.ctx, C.ss_graph_set_link_key(g.h, f64p(key)), "ss_graph_set_link_key")
+}
+
+// Links is one row of TopLinks / HitLinks: the best distinct parents or children of a node (key descending, then id; NaN last;
+// ascending id without a key) and the number of edges of the row, duplicates counted.
+type Links struct {
+	Nodes  []uint32
+	Degree uint32
+}
+
+func linkRows(rows, m int, links []uint32, nOut []int32, degree []uint32, written func(int) bool) []Links {
+	out := make([]Links, rows)
+	for r := 0; r < rows; r++ {
+		if written(r) {
+			out[r] = Links{append([]uint32(nil), links[r*m:r*m+int(nOut[r])]...), degree[r]}
+		}
+	}
+	return out
+}
+
+// TopLinks is ss_graph_top_links: what Rank_combined.Parents / .Children (retrieval/util.go:25-36) carry, as node ids.  A node id
+// the graph does not hold gives an empty row.
+func (g *Graph) TopLinks(dir int, nodes []uint32, m int) ([]Links, error) {
+	n := len(nodes)
+	if n == 0 {
+		return nil, nil
+	}
+	links := make([]uint32, n*m)
+	nOut := make([]int32, n)
+	degree := make([]uint32, n)
+	rc := C.ss_graph_top_links(g.h, C.int32_t(dir), C.uint64_t(n), u32p(nodes), C.int32_t(m), u32p(links), i32p(nOut), u32p(degree))
+	if err := statusErr(g.ctx, rc, "ss_graph_top_links"); err != nil {
+		return nil, err
+	}
+	return linkRows(n, m, links, nOut, degree, func(int) bool { return true }), nil
+}
+
+// HitLinks is ss_graph_hit_links: out[q][j] describes hits[q][j].Doc taken as a node id.  Only the hits' Doc is read.
+func (g *Graph) HitLinks(dir int, hits [][]Hit, m int) ([][]Links, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	k := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > k {
+			k = len(hits[q])
+		}
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nHits[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			raw[q*k+j].doc = C.uint32_t(h.Doc)
+		}
+	}
+	links := make([]uint32, nq*k*m)
+	nOut := make([]int32, nq*k)
+	degree := make([]uint32, nq*k)
+	rc := C.ss_graph_hit_links(g.h, C.int32_t(dir), C.int32_t(nq), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits),
+		C.int32_t(m), u32p(links), i32p(nOut), u32p(degree))
+	if err := statusErr(g.ctx, rc, "ss_graph_hit_links"); err != nil {
+		return nil, err
+	}
+	flat := linkRows(nq*k, m, links, nOut, degree, func(r int) bool { return r%k < int(nHits[r/k]) })
+	out := make([][]Links, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = flat[q*k : q*k+len(hits[q])]
+	}
+	return out, nil
+}
+
 // PageRankTeleport is the opt-in topic-sensitive run (SURVEY.md §8f-3): sets[k] = DISTINCT node ids of topic k's
 // teleport set (empty = the reference's uniform teleport for that topic).  rank[k*N+v], iters[k].
 func (g *Graph) PageRankTeleport(d, eps float64, nTopic []int32, sets [][]uint32) ([]float64, []int32) {

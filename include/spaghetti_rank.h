@@ -45,7 +45,9 @@ extern "C" {
  * SS_MAX_WORD_BYTES, SS_MAX_EDIT_DIST, SS_MAX_SUGGEST, ss_lexicon, ss_lexicon_create / _set_freq / _get_info / _read_order / _destroy,
  * ss_lexicon_prefix and ss_lexicon_suggest (the words of the vocabulary on the device: word list by prefix, spelling suggestions);
  * SS_MAX_SIG_SLOTS, SS_SIG_EMPTY, ss_index_build_signatures / _drop_signatures / _read_signatures and ss_dedup_hits (a MinHash
- * signature per doc, near-duplicate rows dropped from a result window). */
+ * signature per doc, near-duplicate rows dropped from a result window);
+ * SS_MAX_LINKS, SS_LINKS_PARENTS / _CHILDREN, ss_graph_set_link_key, ss_graph_top_links and ss_graph_hit_links (the best parents or
+ * children of a page by a registered per-node key, and its edge count). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -167,6 +169,53 @@ int32_t ss_graph_apply_delta(ss_graph* g, uint64_t n_nodes_new, uint64_t n_chang
                              const uint64_t* new_ptr /*[n_changed+1]*/, const uint32_t* new_children);
 int32_t ss_graph_get_info(const ss_graph* g, ss_graph_info* info);
 int32_t ss_graph_destroy(ss_graph* g);
+
+/* Links of a hit: the best parents ("linked from") and children ("links to") of a page, and how many it has.  The reference's result
+ * card carries both (Rank_combined.Parents / .Children, retrieval/util.go:25-36): resultFormat (util.go:56-92) takes the first five
+ * stored children and the first five parents of a Go map iteration — a different five on every request — and resolves each to a URL
+ * (get_metadata.go:224-292).  Here the five are the BEST five by a per-node key the caller registers (one topic's PageRank row, say),
+ * read from the graph that is resident for PageRank anyway; resolving ids to URLs stays host work.  Defined bit for bit:
+ *   Key.        ss_graph_set_link_key registers key [n_nodes] float64 (host or device memory, copied: 8 bytes per node); NULL clears.
+ *               It lives until it is replaced or cleared, until ss_graph_apply_delta SUCCEEDS (the node count may change; a failed
+ *               delta leaves it) and until the graph is destroyed.  It may be set while PageRank states exist on the graph and is
+ *               independent of them.
+ *   Edges.      The children edges of node v are out_dst[out_ptr[v] .. out_ptr[v+1]) of the graph as it stands (as created, or as last
+ *               patched by ss_graph_apply_delta); the parent edges of v are one entry u per edge u -> v.  Duplicate edges and
+ *               self-loops are edges like any other.
+ *   degree.     The number of edges of the row, duplicates counted, saturated at 2^32 - 1.
+ *   Candidates. The DISTINCT node ids among the row's edges (a self-loop makes v a candidate of its own row).
+ *   Order.      With a key: key[u] descending as float64 VALUES (-0.0 and +0.0 are equal), then ascending node id; NaN keys last,
+ *               among themselves by id — the convention of ss_related_terms.  Without a key: ascending node id.
+ *   Output.     Row i of links_out [n][m] holds the first n_out[i] = min(m, #candidates) candidates in that order; entries past
+ *               n_out[i] are left untouched.  degree_out (nullable) is written for every row that is written.
+ *   Nothing.    A node id >= n_nodes gives n_out = 0 and degree = 0, both written: defined, not an error, in both calls and whether
+ *               the ids are host or device memory; no id makes a kernel read outside the graph.
+ *   Hits form.  ss_graph_hit_links: entry (q, j) describes hits[q * k + j].doc taken as a node id.  Of a hit only .doc is read, and
+ *               n_hits[q]; entries with j >= n_hits[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle, a NULL required pointer with n or n_q above 0,
+ * dir not SS_LINKS_PARENTS / SS_LINKS_CHILDREN, m < 1, k < 1, n_q < 0: SS_ERR_INVALID; m > SS_MAX_LINKS, k > SS_MAX_TOPK, n * m or
+ * n_q * k * m >= 2^31, or a graph that is not (rank 0, world 1) — a shard holds only its own rows' in-edges; requires a (0,1) graph
+ * like ss_pagerank_run: SS_ERR_UNSUPPORTED; n_hits[q] outside [0, k]: SS_ERR_INVALID when n_hits is host memory, clamped by the
+ * kernel when it is device memory.  n == 0 or n_q == 0 is SS_OK and does nothing.
+ * Every pointer may be host or device memory.  When all given pointers are device memory the calls only enqueue on the ctx stream and
+ * NEVER wait, so ss_graph_hit_links can sit behind ss_best_passages; otherwise they stage through blocks the graph owns and return
+ * when the outputs are written.  One exception: the temporaries are sized from the largest degree of the direction, and the largest
+ * OUT-degree is not on the host after ss_graph_create (max_indeg is).  The first call for SS_LINKS_CHILDREN on a graph computes it on
+ * the device and waits for it, once; the value is kept until ss_graph_apply_delta succeeds.
+ * Rows longer than option "links.wave_max" (default 1024, 32 .. 4096) are cut into chunks of option "links.chunk_edges" (default 1024,
+ * 32 .. 4096) edges that are selected independently and then merged: the same bytes for every value.  The temporaries hold
+ * n * m * ceil(largest degree / chunk) ids; SS_ERR_OOM if that memory cannot be had.  No copy of the edges is made.
+ * Serialised on the ctx like the scoring calls; no _submit / _collect form. */
+#define SS_MAX_LINKS      64
+#define SS_LINKS_PARENTS  0
+#define SS_LINKS_CHILDREN 1
+int32_t ss_graph_set_link_key(ss_graph* g, const double* key /*[n_nodes], NULL clears*/);
+int32_t ss_graph_top_links(ss_graph* g, int32_t dir, uint64_t n, const uint32_t* nodes /*[n]*/, int32_t m,
+                           uint32_t* links_out /*[n][m]*/, int32_t* n_out /*[n]*/, uint32_t* degree_out /*[n] nullable*/);
+int32_t ss_graph_hit_links(ss_graph* g, int32_t dir, int32_t n_q, int32_t k,
+                           const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/, int32_t m,
+                           uint32_t* links_out /*[n_q][k][m]*/, int32_t* n_out /*[n_q][k]*/,
+                           uint32_t* degree_out /*[n_q][k] nullable*/);
 
 /* ---- PageRank: ranking/pagerank.go:14-145 ------------------------------ */
 /* One call = the whole of UpdateTopicSensitivePagerank's compute: all k_topics

@@ -23,6 +23,9 @@ SS_MAX_EDIT_DIST = 3
 SS_MAX_SUGGEST = 64
 SS_MAX_SIG_SLOTS = 32
 SS_SIG_EMPTY = 0xFFFFFFFF
+SS_MAX_LINKS = 64
+SS_LINKS_PARENTS = 0
+SS_LINKS_CHILDREN = 1
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -79,6 +82,9 @@ PROTOTYPES = {
     "ss_graph_apply_delta": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp]),
     "ss_graph_get_info": (_i32, [_vp, C.POINTER(SsGraphInfo)]),
     "ss_graph_destroy": (_i32, [_vp]),
+    "ss_graph_set_link_key": (_i32, [_vp, _vp]),
+    "ss_graph_top_links": (_i32, [_vp, _i32, _u64, _vp, _i32, _vp, _vp, _vp]),
+    "ss_graph_hit_links": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ss_pagerank_run": (_i32, [_vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp]),
     "ss_pr_create": (_i32, [_vp, _f64, _f64, _i32, _i32, _vp, C.POINTER(_vp)]),
     "ss_pr_destroy": (_i32, [_vp]),

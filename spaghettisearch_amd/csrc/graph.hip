@@ -736,6 +736,8 @@ int32_t ss_graph_apply_delta(ss_graph* g, uint64_t n_nodes_new, uint64_t n_chang
         g->n = n_keep;
         g->e = e_keep;
         (void)build(g, nullptr, nullptr);
+    } else {
+        g->links.forget();                                 // the link key was per node of the old node set; the largest out-degree is stale
     }
     return rc;
 }

@@ -62,6 +62,25 @@ struct ss_graph {
     }
     ~ss_graph() { settle(); }
 
+    // Links of a hit (links.hip): the ordering key the caller registered, what the calls learn about the graph,
+    // and their grow-only blocks.  A successful ss_graph_apply_delta calls forget(): the node count may have changed.
+    struct Links {
+        ss::DevBuf<double> key;        // [n] copy of the caller's key
+        bool has_key = false;
+        bool max_outdeg_known = false; // the largest out-degree: asked of the device once, by the first call for children
+        uint64_t max_outdeg = 0;
+        ss::DevBuf<uint64_t> d_max;    // [1]
+        ss::DevBuf<uint64_t> row_base, row_len, req_off;   // the plan: per requested row its edge range; the prefix of the rows' work items
+        ss::DevBuf<uint32_t> partial;  // [work items][m] the chunks' winners
+        ss::DevBuf<uint32_t> d_ids, d_links, d_deg;        // staging of host arrays
+        ss::DevBuf<int32_t> d_nhits, d_n;
+        void forget() {
+            key.release();
+            has_key = false;
+            max_outdeg_known = false;
+        }
+    } links;
+
     uint32_t n_local() const { return sl_nd + sl_d; }
     // internal id of local row
     uint64_t int_id(uint32_t lrow) const {

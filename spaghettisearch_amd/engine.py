@@ -264,6 +264,71 @@ class Graph:
               self.ctx.h)
         return iters
 
+    def set_link_key(self, key) -> None:
+        """ss_graph_set_link_key: register the per-node key that orders top_links / hit_links (float64 [n_nodes], numpy or torch;
+        copied), or None to clear.  A successful apply_delta clears it."""
+        if key is None:
+            check(self.ctx.lib.ss_graph_set_link_key(self.h, None), self.ctx.h)
+            return
+        key = _as(key, "float64")
+        if (key.numel() if _is_torch(key) else key.size) < self.n:
+            raise ValueError("key must hold n_nodes values")
+        self.ctx.ready(key)
+        check(self.ctx.lib.ss_graph_set_link_key(self.h, _ptr(key)), self.ctx.h)
+
+    def _links_out(self, rows: int, m: int, want_degree: bool, out):
+        count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+        if out is not None:
+            links, n_out, degree = _as(out[0], "uint32"), _as(out[1], "int32"), _as(out[2], "uint32") if len(out) > 2 else None
+            if count(links) < rows * m or count(n_out) < rows or (degree is not None and count(degree) < rows):
+                raise ValueError("output buffers too small")
+            return links, n_out, degree
+        return np.zeros(rows * m, dtype=np.uint32), np.zeros(rows, dtype=np.int32), np.zeros(rows, dtype=np.uint32) if want_degree else None
+
+    def top_links(self, nodes, direction: int, m: int = 5, want_degree: bool = True, out=None):
+        """ss_graph_top_links: the m best distinct parents (direction = _lib.SS_LINKS_PARENTS) or children (SS_LINKS_CHILDREN) of every
+        node of `nodes` by the registered key (descending, then node id; NaN last; ascending id without a key), and the rows' edge
+        counts -> (links uint32[n][m], n_out int32[n], degree uint32[n] | None); entries past n_out[i] keep what the array held
+        (zeros here).  out = (links, n_out[, degree | None]): the caller's arrays (numpy, or torch int32 device tensors; returned as
+        they are); with device nodes and outputs the library only enqueues."""
+        nodes = _as(nodes, "uint32")
+        n = int(nodes.numel() if _is_torch(nodes) else nodes.size)
+        links, n_out, degree = self._links_out(n, int(m), want_degree, out)
+        self.ctx.ready(nodes, links, n_out, degree)
+        check(self.ctx.lib.ss_graph_top_links(self.h, int(direction), n, _ptr(nodes), int(m), _ptr(links), _ptr(n_out), _ptr(degree)), self.ctx.h)
+        if out is None:
+            links = links.reshape(n, int(m))
+        elif any(_is_torch(a) for a in (links, n_out, degree)) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return links, n_out, degree
+
+    def hit_links(self, hits, n_hits, direction: int, m: int = 5, want_degree: bool = True, out=None, k: Optional[int] = None):
+        """ss_graph_hit_links: top_links for the rows of a scoring call, hits[q][j].doc taken as a node id -> (links uint32[n_q][k][m],
+        n_out int32[n_q][k], degree uint32[n_q][k] | None).  hits [n_q][k] / n_hits [n_q]: numpy HIT_DTYPE / int32, or the torch uint8 /
+        int32 device tensors score_topk's `out` takes; k defaults to what hits holds per query.  Entries behind a query's last hit keep
+        what the arrays held.  out as in top_links."""
+        n_hits = _as(n_hits, "int32")
+        n_q = int(n_hits.numel() if _is_torch(n_hits) else n_hits.size)
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k) * HIT_DTYPE.itemsize:
+            raise ValueError("hits too small")
+        k = int(k)
+        links, n_out, degree = self._links_out(n_q * k, int(m), want_degree, out)
+        self.ctx.ready(hits, n_hits, links, n_out, degree)
+        check(self.ctx.lib.ss_graph_hit_links(self.h, int(direction), n_q, k, _ptr(hits), _ptr(n_hits), int(m), _ptr(links), _ptr(n_out),
+                                              _ptr(degree)), self.ctx.h)
+        if out is None:
+            links, n_out = links.reshape(n_q, k, int(m)), n_out.reshape(n_q, k)
+            degree = degree.reshape(n_q, k) if degree is not None else None
+        elif any(_is_torch(a) for a in (links, n_out, degree)) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return links, n_out, degree
+
     def close(self) -> None:
         if self.h:
             self.ctx.lib.ss_graph_destroy(self.h)

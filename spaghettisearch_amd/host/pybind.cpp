@@ -102,6 +102,11 @@ PYBIND11_MODULE(_host, m) {
             auto f = as_dbs(forward);
             r.Run(ctx, d, eps, f);
         })
+        .def("SetLinkKey", &ranking::ResidentPagerank::SetLinkKey, py::arg("topic") = std::string())
+        .def("TopLinks", [](ranking::ResidentPagerank& r, const std::vector<std::string>& docHashes, int32_t dir, int32_t m) {
+            auto l = r.TopLinks(docHashes, dir, m);
+            return py::make_tuple(l.links, l.degree);
+        }, py::arg("docHashes"), py::arg("dir"), py::arg("m") = 5)
         .def_readonly("name", &ranking::ResidentPagerank::name)
         .def_readonly("rebuilds", &ranking::ResidentPagerank::rebuilds);
     auto page_info = [](const py::dict& d) {

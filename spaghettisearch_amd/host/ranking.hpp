@@ -130,6 +130,8 @@ public:
     std::vector<uint8_t> is_parent;                  // [node] has a forw[2] row
     std::vector<uint32_t> indeg;                     // [node] references from the child lists
     int rebuilds = 0;                                // ApplyDelta calls that had to re-flatten (a node was orphaned)
+    std::vector<std::string> last_cats;              // the categories of the last Run, in the order of its rank rows
+    std::vector<double> last_rank;                   // [categories][nodes] of the last Run; emptied by Build and ApplyDelta
 
     ResidentPagerank() = default;
     ResidentPagerank(const ResidentPagerank&) = delete;
@@ -140,6 +142,8 @@ public:
     void Build(db::Context& ctx, std::vector<db::DB*>& forward) {
         using namespace spaghetti;
         if (g) { ss_graph_destroy(g); g = nullptr; }
+        last_cats.clear();
+        last_rank.clear();
         const std::vector<db::KV> nodes = forward[2]->Iterate(ctx);
         std::vector<std::vector<std::string>> children(nodes.size());
         std::vector<std::string> all;
@@ -230,6 +234,8 @@ public:
             name.resize(n_before);
         }
         check(rc, "ss_graph_apply_delta");
+        last_cats.clear();                         // (the library has dropped the link key with the old node set)
+        last_rank.clear();
         indeg = std::move(deg);
         is_parent = std::move(par);
         kids_of.resize(name.size());
@@ -292,6 +298,49 @@ public:
             bw->BatchSet(ctx, name[v], jsonmini::dump(PR));
         }
         bw->Flush(ctx);
+        last_cats = std::move(cat_name);
+        last_rank = std::move(rank);
+    }
+
+    // Links of a hit (ss_graph_set_link_key): order parents and children by `topic`'s PageRank row of the last Run; an empty
+    // topic clears the key (ascending node id, which is no order a user would see: the ids are the host's).
+    void SetLinkKey(const std::string& topic) {
+        using namespace spaghetti;
+        if (!g) throw std::runtime_error("ResidentPagerank::SetLinkKey: no graph (Build first)");
+        if (topic.empty()) { check(ss_graph_set_link_key(g, nullptr), "ss_graph_set_link_key"); return; }
+        const size_t n = name.size();
+        for (size_t k = 0; k < last_cats.size(); k++)
+            if (last_cats[k] == topic && last_rank.size() == last_cats.size() * n) {
+                check(ss_graph_set_link_key(g, last_rank.data() + k * n), "ss_graph_set_link_key");
+                return;
+            }
+        throw std::runtime_error("ResidentPagerank::SetLinkKey: no rank row of topic '" + topic + "' for this graph (Run after the last Build / ApplyDelta)");
+    }
+
+    // ss_graph_top_links by doc hash: per hash the m best parents (dir = SS_LINKS_PARENTS) or children (SS_LINKS_CHILDREN) as hashes,
+    // and the row's edge count.  A hash that is not a node gives an empty row and degree 0.
+    struct Links {
+        std::vector<std::vector<std::string>> links;
+        std::vector<uint32_t> degree;
+    };
+    Links TopLinks(const std::vector<std::string>& docHashes, int32_t dir, int32_t m) {
+        using namespace spaghetti;
+        Links out;
+        const size_t n = docHashes.size();
+        out.links.resize(n);
+        out.degree.assign(n, 0);
+        if (!g || n == 0) return out;
+        std::vector<uint32_t> nodes(n);
+        for (size_t i = 0; i < n; i++) {
+            auto it = id.find(docHashes[i]);
+            nodes[i] = it == id.end() ? 0xFFFFFFFFu : it->second;      // outside the graph: an empty row by definition
+        }
+        std::vector<uint32_t> links(n * (size_t)std::max(m, 1));
+        std::vector<int32_t> n_out(n, 0);
+        check(ss_graph_top_links(g, dir, n, nodes.data(), m, links.data(), n_out.data(), out.degree.data()), "ss_graph_top_links");
+        for (size_t i = 0; i < n; i++)
+            for (int32_t j = 0; j < n_out[i]; j++) out.links[i].push_back(name[links[i * (size_t)m + j]]);
+        return out;
     }
 };
 
