@@ -24,6 +24,7 @@ import (
 	"fmt"
 	"math"
 	"os"
+	"runtime"
 	"strconv"
 	"sync"
 	"time"
@@ -59,8 +60,10 @@ type Index struct {
 	NPost  uint64
 }
 type Scorer struct {
-	h   *C.ss_scorer
-	ctx *Ctx
+	h       *C.ss_scorer
+	ctx     *Ctx
+	nDocs   uint64 // the title table's doc count when the scorer was created: sizes DocFieldMasks' words
+	nFields int    // fields registered by SetDocFields: sizes HitFields' values
 }
 
 var (
@@ -532,7 +535,9 @@ func (ix *Index) DocTopTerms(docs []uint32, m int) ([][]uint32, [][]float32) {
 func (c *Ctx) NewScorer(title, body *Index) *Scorer {
 	var h *C.ss_scorer
 	check(c, C.ss_scorer_create(c.h, title.h, body.h, &h), "ss_scorer_create")
-	return &Scorer{h, c}
+	var nDocs, nTerms, nPost C.uint64_t
+	check(c, C.ss_index_get_info(title.h, &nDocs, &nTerms, &nPost), "ss_index_get_info")
+	return &Scorer{h: h, ctx: c, nDocs: uint64(nDocs)}
 }
 func (s *Scorer) Close() { C.ss_scorer_destroy(s.h) }
 func (s *Scorer) SetPrior(kTopics int, rank []float64) {
@@ -869,6 +874,180 @@ func (s *Scorer) DedupHits(hits [][]Hit, minMatch, first, k int) ([]DedupedPage,
 	out := make([]DedupedPage, nq)
 	for q, p := range pages {
 		out[q] = DedupedPage{p.Hits, p.Same, p.Kept}
+	}
+	return out, nil
+}
+
+// DocRange is one range clause over the doc fields (ss_doc_range): it matches doc d iff Lo <= value[Field][d] <= Hi.
+type DocRange struct {
+	Field  int32
+	Lo, Hi int64
+}
+
+func docRanges(rng []DocRange) (*C.ss_doc_range, []C.ss_doc_range) {
+	if len(rng) == 0 {
+		return nil, nil
+	}
+	raw := make([]C.ss_doc_range, len(rng))
+	for i, r := range rng {
+		raw[i].field, raw[i].lo, raw[i].hi = C.int32_t(r.Field), C.int64_t(r.Lo), C.int64_t(r.Hi)
+	}
+	return (*C.ss_doc_range)(unsafe.Pointer(&raw[0])), raw
+}
+
+func i64p(s []int64) *C.int64_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.int64_t)(unsafe.Pointer(&s[0]))
+}
+
+// SetDocFields registers the per-doc field table (ss_scorer_set_doc_fields): values[f*nDocs+d] = field f of doc d, up to
+// C.SS_MAX_DOC_FIELDS fields (the shim's convention: field 0 = Mod_date as unix seconds, field 1 = Page_size; retrieval/util.go:28-29).
+// nFields 0 clears.  Register it again after an index update, like the allow-lists.  values must hold nFields * nDocs entries.
+func (s *Scorer) SetDocFields(nFields int, values []int64) {
+	if nFields > 0 && uint64(len(values)) < uint64(nFields)*s.nDocs {
+		panic(fmt.Errorf("SetDocFields: %d values for %d fields of %d docs", len(values), nFields, s.nDocs))
+	}
+	check(s.ctx, C.ss_scorer_set_doc_fields(s.h, C.int32_t(nFields), i64p(values)), "ss_scorer_set_doc_fields")
+	s.nFields = nFields
+	if len(values) == 0 {
+		s.nFields = 0
+	}
+}
+
+// DocFieldMasks builds allow-lists from range clauses on the device (ss_doc_field_masks): set i = the registered allow-list maskID[i]
+// (-1 / nil: every doc) AND every clause of rng[rngPtr[i]:rngPtr[i+1]].  The words come back in the layout SetDocMasks takes,
+// (nDocs+31)/32 per set with the scorer's own doc count.
+func (s *Scorer) DocFieldMasks(rngPtr []uint32, rng []DocRange, maskID []int32) ([]uint32, error) {
+	nSets := len(rngPtr) - 1
+	if nSets <= 0 {
+		return nil, nil
+	}
+	words := make([]uint32, uint64(nSets)*((s.nDocs+31)/32))
+	rp, keep := docRanges(rng)
+	rc := C.ss_doc_field_masks(s.h, C.int32_t(nSets), u32p(rngPtr), rp, i32p(maskID), u32p(words))
+	runtime.KeepAlive(keep)
+	if err := statusErr(s.ctx, rc, "ss_doc_field_masks"); err != nil {
+		return nil, err
+	}
+	return words, nil
+}
+
+// ScoreTopKFiltered = ScoreTopKConstrained plus range clauses per query over the doc fields (ss_score_topk_filtered): every result
+// of query q also matches each clause of rng[rngPtr[q]:rngPtr[q+1]]; rngPtr nil = none.
+func (s *Scorer) ScoreTopKFiltered(qPtr, qTerms, pPtr, pTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32,
+	reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange, k int) ([][]Hit, error) {
+	nq := len(qPtr) - 1
+	if nq == 0 {
+		return nil, nil
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	rp, keep := docRanges(rng)
+	rc := C.ss_score_topk_filtered(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), u32p(pPtr), u32p(pTerms), i32p(queryLen),
+		f64p(topicProbs), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr), u32p(excTerms), u32p(rngPtr), rp, C.int32_t(k),
+		(*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	runtime.KeepAlive(keep)
+	if err := statusErr(s.ctx, rc, "ss_score_topk_filtered"); err != nil {
+		return nil, err
+	}
+	out := make([][]Hit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Hit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*k+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
+// SortHitsByField sorts every window stably by a doc field, ascending or descending, rows outside the table last, and returns page
+// [first, first+k) with the rows' values (ss_sort_hits_by_field).  Only the hits' Doc is read to decide anything.
+func (s *Scorer) SortHitsByField(hits [][]Hit, field int, descending bool, first, k int) ([][]Hit, [][]int64, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	kIn := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > kIn {
+			kIn = len(hits[q])
+		}
+	}
+	in := make([]C.ss_hit, nq*kIn)
+	nIn := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			in[q*kIn+j] = C.ss_hit{doc: C.uint32_t(h.Doc), title: C.double(h.Title), body: C.double(h.Body), pagerank: C.double(h.PageRank),
+				final: C.double(h.Final)}
+		}
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	desc := 0
+	if descending {
+		desc = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, vals := make([]int32, nq), make([]int64, nq*kk)
+	rc := C.ss_sort_hits_by_field(s.h, C.int32_t(nq), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), C.int32_t(field),
+		C.int32_t(desc), C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), i64p(vals))
+	if err := statusErr(s.ctx, rc, "ss_sort_hits_by_field"); err != nil {
+		return nil, nil, err
+	}
+	out, outVals := make([][]Hit, nq), make([][]int64, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q], outVals[q] = make([]Hit, n), append([]int64(nil), vals[q*kk:q*kk+n]...)
+		for i := 0; i < n; i++ {
+			r := raw[q*kk+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, outVals, nil
+}
+
+// HitFields reads the field values of every hit (ss_hit_fields): out[q][j][f] for the fields SetDocFields registered;
+// C.SS_NO_FIELD_VALUE for a doc outside the table.
+func (s *Scorer) HitFields(hits [][]Hit) ([][][]int64, error) {
+	nq, nFields := len(hits), s.nFields
+	if nq == 0 {
+		return nil, nil
+	}
+	if nFields < 1 {
+		return nil, fmt.Errorf("HitFields: no doc fields registered (SetDocFields)")
+	}
+	kIn := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > kIn {
+			kIn = len(hits[q])
+		}
+	}
+	in := make([]C.ss_hit, nq*kIn)
+	nIn := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			in[q*kIn+j].doc = C.uint32_t(h.Doc)
+		}
+	}
+	vals := make([]int64, nq*kIn*nFields)
+	rc := C.ss_hit_fields(s.h, C.int32_t(nq), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), i64p(vals))
+	if err := statusErr(s.ctx, rc, "ss_hit_fields"); err != nil {
+		return nil, err
+	}
+	out := make([][][]int64, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([][]int64, len(hits[q]))
+		for j := range out[q] {
+			o := (q*kIn + j) * nFields
+			out[q][j] = append([]int64(nil), vals[o:o+nFields]...)
+		}
 	}
 	return out, nil
 }

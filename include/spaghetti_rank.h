@@ -47,7 +47,9 @@ extern "C" {
  * SS_MAX_SIG_SLOTS, SS_SIG_EMPTY, ss_index_build_signatures / _drop_signatures / _read_signatures and ss_dedup_hits (a MinHash
  * signature per doc, near-duplicate rows dropped from a result window);
  * SS_MAX_LINKS, SS_LINKS_PARENTS / _CHILDREN, ss_graph_set_link_key, ss_graph_top_links and ss_graph_hit_links (the best parents or
- * children of a page by a registered per-node key, and its edge count). */
+ * children of a page by a registered per-node key, and its edge count);
+ * SS_MAX_DOC_FIELDS, SS_MAX_RANGE_CLAUSES, SS_NO_FIELD_VALUE, ss_doc_range, ss_scorer_set_doc_fields, ss_doc_field_masks,
+ * ss_score_topk_filtered, ss_sort_hits_by_field and ss_hit_fields (per-doc integer fields: range filters, sort by field, read-out). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -715,6 +717,88 @@ int32_t ss_dedup_hits(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hit
                       int32_t min_match, int32_t first, int32_t k,
                       ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
                       uint32_t* similar_out /*[n_q][k], nullable*/, int32_t* n_kept_out /*[n_q], nullable*/);
+
+/* Doc fields: a few signed 64-bit values per doc (a modification date as unix seconds, a page size in bytes), range filters over them,
+ * a result window sorted by one of them, and their read-out per result row.  The reference's result card shows Mod_date and Page_size
+ * (retrieval/util.go:28-29, filled from DocInfo, database/noschema_schema.go:34-38) and can neither restrict nor sort by them.
+ * The table: values [n_fields][n_docs] field-major (n_docs = the scorer's), host or device memory, copied; n_fields = 0 / NULL clears.
+ * Replaces the previous table after the scorer's outstanding work (pipelined batches, tickets) has finished with it.  The table lives as
+ * long as the scorer: after an index update (destroy scorers before, re-create after) register it again.  8 bytes per doc and field.
+ * n_fields < 0 is SS_ERR_INVALID, n_fields > SS_MAX_DOC_FIELDS is SS_ERR_UNSUPPORTED; a call that fails leaves the old table in place.
+ * Every value is an ordinary value, SS_NO_FIELD_VALUE included: the read-outs write that one for a row whose doc is outside the table.
+ * A range clause {field, lo, hi} MATCHES doc d iff lo <= value[field][d] <= hi as signed 64-bit integers; lo > hi matches nothing;
+ * _pad is ignored. */
+#define SS_MAX_DOC_FIELDS 4
+#define SS_MAX_RANGE_CLAUSES 4            /* per query / per set */
+#define SS_NO_FIELD_VALUE INT64_MIN
+typedef struct ss_doc_range {
+    int32_t field;     /* 0 .. n_fields-1 */
+    int32_t _pad;
+    int64_t lo, hi;    /* both inclusive */
+} ss_doc_range;        /* 24 bytes */
+int32_t ss_scorer_set_doc_fields(ss_scorer* s, int32_t n_fields, const int64_t* values /*[n_fields][n_docs], 0 / NULL clears*/);
+
+/* Allow-lists from range clauses, built on the device ("past day / week / month / year", once per index refresh).  Defined bit for bit:
+ * bit (d & 31) of word d >> 5 of set i of words_out [n_sets][(n_docs+31)/32] is 1 iff d < n_docs, d is in the REGISTERED allow-list
+ * mask_id[i] (ss_scorer_set_doc_masks; -1 = every doc; mask_id NULL = all -1) and every clause of rng[rng_ptr[i] .. rng_ptr[i+1])
+ * matches d.  Bits at and past n_docs in the last word are 0.  A set without clauses is its mask; with mask_id -1 it is all ones up to
+ * n_docs.  Duplicate sets are sets like any other.  The layout is that of ss_scorer_set_doc_masks: the output can be registered as it is.
+ * Checks, all before anything is enqueued and with words_out untouched: NULL handle, rng_ptr or words_out (or rng with a clause),
+ * n_sets < 0, an rng_ptr that does not start at 0 or decreases, a clause field outside [0, n_fields), a mask_id below -1 or at / above
+ * n_masks: SS_ERR_INVALID; more than SS_MAX_RANGE_CLAUSES clauses in one set: SS_ERR_UNSUPPORTED; a clause but no field table:
+ * SS_ERR_STATE.  n_sets == 0 is SS_OK and does nothing.  rng_ptr / rng / mask_id are read on the host like the query arrays;
+ * words_out may be host or device memory; the call waits for its work.  A host words_out goes through a device block of the same
+ * size (SS_ERR_OOM if it cannot be had), kept by the scorer for the next call up to 64 MB and freed before the call returns beyond.
+ * k_field_masks reads each field column once per group of 64 sets (80 MB per field at 10M docs), forms the words by wave ballot and
+ * writes every word of every set exactly once: no atomics, no order dependence, no temporaries. */
+int32_t ss_doc_field_masks(ss_scorer* s, int32_t n_sets, const uint32_t* rng_ptr /*[n_sets+1]*/, const ss_doc_range* rng,
+                           const int32_t* mask_id /*[n_sets], -1 = every doc, NULL = all -1*/,
+                           uint32_t* words_out /*[n_sets][(n_docs+31)/32], host or device*/);
+
+/* ss_score_topk_constrained plus range clauses per query: "past week", "pages under 100 KB".  Doc d is allowed for query q iff it is
+ * allowed by ss_score_topk_constrained's rule AND matches every clause of rng[rng_ptr[q] .. rng_ptr[q+1]).  Row q = byte for byte what
+ * ss_score_topk_masked returns with that allowed set registered as the query's allow-list: NOT a post-filter of the unrestricted top-k.
+ * The clauses only filter.  The allowed sets are built on the device for the call, one per distinct (mask, required, excluded, clauses)
+ * combination (the clauses compared as sets: order and repeats do not matter), as in ss_score_topk_constrained: n_docs / 8 bytes each,
+ * SS_ERR_OOM if that memory cannot be had.  rng_ptr [n_q+1] (NULL = none) starts at 0 and never decreases, a clause field lies in
+ * [0, n_fields), else SS_ERR_INVALID; more than SS_MAX_RANGE_CLAUSES clauses in one query (as given, repeats counted) is
+ * SS_ERR_UNSUPPORTED; a clause but no field table is SS_ERR_STATE; the other checks are ss_score_topk_constrained's.  Every check comes
+ * before anything is enqueued and leaves the outputs untouched.  A call without a clause IS ss_score_topk_constrained (same kernels,
+ * bit-identical rows).  rng_ptr / rng are read on the host like the constraint arrays (device pointers cost one blocking copy each);
+ * outputs as ss_score_topk (device outputs: the call only enqueues, pipelined like any other batch).
+ * There is no filtered form of ss_score_topk_submit / _collect. */
+int32_t ss_score_topk_filtered(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                               const uint32_t* p_ptr, const uint32_t* p_terms, const int32_t* query_len,
+                               const double* topic_probs, const int32_t* mask_id,
+                               const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                               const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                               const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                               int32_t k, ss_hit* hits_out, int32_t* n_hits_out);
+
+/* ss_sort_hits_by_field: a result window sorted by a field ("newest first").  Defined bit for bit:
+ *   Window.     As in ss_collapse_hits: hits[q * k_in .. q * k_in + n_hits[q]), in the order given; only .doc of a row is read.
+ *   Order.      Rows with doc < n_docs by value[field][doc], ascending (descending == 0) or descending (descending != 0) as signed
+ *               64-bit integers, rows of equal value in window order (the sort is stable; the same doc twice is two rows).  Rows with
+ *               doc >= n_docs come LAST in both directions, among themselves in window order.  No doc id makes the kernel read outside
+ *               the table.
+ *   Output.     With the sorted rows S_0 .. S_{n-1}: hits_out[q * k + r] = the 40 bytes of S_{first + r} (_pad included) for
+ *               r < n_hits_out[q] = clamp(n - first, 0, k); values_out[q * k + r] (nullable) = that row's value, SS_NO_FIELD_VALUE
+ *               for a row with doc >= n_docs.  Entries past n_hits_out[q] are left untouched.
+ * ss_hit_fields: values_out[(q * k_in + j) * n_fields + f] = value[f][hits[q * k_in + j].doc] for j < n_hits[q] and every registered
+ * field f; SS_NO_FIELD_VALUE in every field for a row with doc >= n_docs; rows past n_hits[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle (or hits / n_hits / hits_out / n_hits_out /
+ * values_out of ss_hit_fields with n_q > 0), n_q < 0, k_in < 1, k < 1, first < 0, a field outside [0, n_fields), hits_out overlapping
+ * hits as address ranges: SS_ERR_INVALID; k_in or k above SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no field table registered: SS_ERR_STATE;
+ * n_hits[q] outside [0, k_in]: SS_ERR_INVALID when n_hits is host memory, clamped by the kernel when it is device memory.  n_q == 0
+ * is SS_OK and does nothing.
+ * Every pointer may be host or device memory: when all given pointers are device memory the calls only enqueue on the ctx stream and
+ * NEVER wait, so score -> dedup -> collapse -> sort -> explain chains on one stream; otherwise they stage through blocks the scorer
+ * owns and return when the outputs are written.  Serialised on the ctx like every scoring call; no _submit / _collect form. */
+int32_t ss_sort_hits_by_field(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/,
+                              const int32_t* n_hits /*[n_q]*/, int32_t field, int32_t descending, int32_t first, int32_t k,
+                              ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int64_t* values_out /*[n_q][k], nullable*/);
+int32_t ss_hit_fields(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
+                      int64_t* values_out /*[n_q][k_in][n_fields]*/);
 
 /* ---- term lexicon: cmd/server/server.go:54-85 (/wordlist/{pre}), database/database.go:414-454 (IterateInv) -------------
  * The words of forw[0] keyed by dense term id, resident on the device.  The reference answers /wordlist/{pre} by walking every key

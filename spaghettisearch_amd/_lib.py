@@ -26,6 +26,9 @@ SS_SIG_EMPTY = 0xFFFFFFFF
 SS_MAX_LINKS = 64
 SS_LINKS_PARENTS = 0
 SS_LINKS_CHILDREN = 1
+SS_MAX_DOC_FIELDS = 4
+SS_MAX_RANGE_CLAUSES = 4
+SS_NO_FIELD_VALUE = -(2 ** 63)
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -49,6 +52,10 @@ class SsTermMatch(C.Structure):
 
 class SsPassage(C.Structure):
     _fields_ = [("start", C.c_float), ("last", C.c_float), ("n_distinct", C.c_uint32), ("n_occ", C.c_uint32), ("token_mask", C.c_uint64)]
+
+
+class SsDocRange(C.Structure):
+    _fields_ = [("field", C.c_int32), ("_pad", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
 class SsGraphInfo(C.Structure):
@@ -139,6 +146,11 @@ PROTOTYPES = {
     "ss_index_drop_signatures": (_i32, [_vp]),
     "ss_index_read_signatures": (_i32, [_vp, _u64, _vp, _vp, C.POINTER(_i32)]),
     "ss_dedup_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_scorer_set_doc_fields": (_i32, [_vp, _i32, _vp]),
+    "ss_doc_field_masks": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ss_score_topk_filtered": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ss_sort_hits_by_field": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ss_hit_fields": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "ss_lexicon_create": (_i32, [_vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ss_lexicon_set_freq": (_i32, [_vp, _vp]),
     "ss_lexicon_get_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),

@@ -2,7 +2,7 @@
 //
 // A call runs under the context's lock as a row of steps, each with its own result struct:
 //   fetch_filter_inputs / fetch_inputs   the caller's arrays copied to the host and checked          -> BatchInputs
-//   resolve_constraints                  required / excluded terms -> one allowed set per combination -> ConstraintPlan
+//   resolve_constraints                  required / excluded terms, range clauses -> one allowed set per combination -> ConstraintPlan
 //   plan_batch                           phrase parts, kernel per query, slices, launch order         -> BatchPlan
 //   choose_route                         which kernels share which streams                            -> Route
 //   stage_plan                           the plan into this turn's pinned buffer, workspaces, params  -> StagedBatch
@@ -12,8 +12,9 @@
 // read of the scorer is a ScorerView, of the options a ScoreOptions, and an error comes back as a PlanError.  Everything up to and
 // including plan_batch can fail on the caller's input, and nothing before stage_plan enqueues work, takes a turn or touches
 // the outputs: a call that fails there leaves no trace.
-// The kernels are in score.hip, score_wave.hip, score_small.hip and constraint.hip, behind the launchers of scorer.hpp.
+// The kernels are in score.hip, score_wave.hip, score_small.hip, constraint.hip and field.hip, behind the launchers of scorer.hpp.
 #include <chrono>
+#include <tuple>
 #include "scorer.hpp"
 
 namespace {
@@ -31,6 +32,7 @@ struct CallArgs {
     const int32_t* mask_id;
     const QueryConstraints* cons;
     TurnRows* turn_rows;                        // ss::score_into_turn: the rows go to the plan turn's own block (hits_out / n_hits_out unused)
+    const QueryRanges* ranges;                  // ss_score_topk_filtered
 };
 
 // the options a call reads, each looked up once per call, in one place (a look-up builds a std::string key)
@@ -93,6 +95,9 @@ struct BatchInputs {
     int32_t n_q = 0, k = 0;
     int K = 0;                                  // the prior's topics
     bool has_mask_arg = false, has_constraints = false, has_phrase_arg = false, has_probs = false;
+    bool has_ranges = false;                    // a query of the call has a range clause (ss_score_topk_filtered)
+    std::vector<uint32_t> rng_ptr;
+    std::vector<ss_doc_range> rng;
     bool any_mask = false;                      // a query of the call has an allow-list (registered, or a set of resolve_constraints)
     bool dev_out = false;                       // both outputs live in device memory
     uint32_t n_tok = 0;
@@ -106,6 +111,12 @@ struct BatchInputs {
 struct ConstraintPlan {
     std::vector<ConstraintSet> sets;
     std::vector<ConstraintTerm> terms;
+    // range clauses: the sets k_field_masks writes or narrows, in groups.  The last n_field_only sets have clauses and no terms:
+    // k_constraint_masks leaves them out and k_field_masks builds them from the registered allow-list.
+    std::vector<FieldSet> fsets;
+    std::vector<ss_doc_range> fclauses;
+    std::vector<uint32_t> fgroups;
+    size_t n_field_only = 0;
 };
 
 struct SmallEnt { SmallHdr h; uint32_t loff; };
@@ -142,6 +153,7 @@ struct StagedBatch {
     bool one_copy = false;
     ScoreParams p{};
     ConstraintParams cp{};
+    FieldParams fp{};
 };
 
 struct Stamps { Clock::time_point begin, fetched, planned, staged, uploaded; };   // "score.trace"
@@ -171,10 +183,30 @@ int32_t fetch_filter_inputs(ss_scorer* s, const CallArgs& a, BatchInputs& in) {
         }
     }
     // query operators (ss_score_topk_constrained): required / excluded terms, checked here too
+    // range clauses (ss_score_topk_filtered), checked here too; a call without a clause is the constrained call
+    if (a.ranges && a.ranges->rng_ptr) {
+        const char* const entry = "ss_score_topk_filtered";
+        in.rng_ptr.resize(n_q + 1);
+        SS_TRY(fetch_ptr_array(ctx, entry, "rng", a.ranges->rng_ptr, (size_t)n_q, in.rng_ptr.data()));
+        if (in.rng_ptr[0] != 0) return ctx->fail(SS_ERR_INVALID, "%s: rng_ptr[0] is %u, not 0", entry, in.rng_ptr[0]);
+        const size_t n_cl = in.rng_ptr[n_q];
+        if (n_cl && !a.ranges->rng) return ctx->fail(SS_ERR_INVALID, "%s: rng is NULL", entry);
+        for (int q = 0; q < n_q; q++)
+            if (in.rng_ptr[q + 1] - in.rng_ptr[q] > SS_MAX_RANGE_CLAUSES)
+                return ctx->fail(SS_ERR_UNSUPPORTED, "%s: query %d has %u range clauses (max %d)", entry, q, in.rng_ptr[q + 1] - in.rng_ptr[q], SS_MAX_RANGE_CLAUSES);
+        if (n_cl && s->n_fields == 0) return ctx->fail(SS_ERR_STATE, "%s: no field table registered (ss_scorer_set_doc_fields)", entry);
+        in.rng.resize(n_cl);
+        if (n_cl) SS_HIP(ctx, ss::copy_in(ctx->stream, in.rng.data(), a.ranges->rng, n_cl * sizeof(ss_doc_range)));
+        for (size_t c = 0; c < n_cl; c++)
+            if (in.rng[c].field < 0 || in.rng[c].field >= s->n_fields)
+                return ctx->fail(SS_ERR_INVALID, "%s: clause %zu names field %d (the scorer has %d fields)", entry, c, in.rng[c].field, s->n_fields);
+        in.has_ranges = n_cl > 0;
+    }
     in.has_constraints = a.cons && (a.cons->req_ptr || a.cons->exc_ptr);
-    if (!in.has_constraints) return SS_OK;
+    if (!in.has_constraints && !in.has_ranges) return SS_OK;
     in.req_ptr.assign(n_q + 1, 0);
     in.exc_ptr.assign(n_q + 1, 0);
+    if (!in.has_constraints) return SS_OK;
     auto load = [&](const uint32_t* ptr, const uint32_t* terms, std::vector<uint32_t>& hp, std::vector<uint32_t>& ht, const char* what) -> int32_t {
         if (!ptr) return SS_OK;
         SS_TRY(fetch_ptr_array(ctx, "ss_score_topk_constrained", what, ptr, (size_t)n_q, hp.data()));
@@ -233,18 +265,64 @@ bool outputs_on_device(const CallArgs& a) {
 // Required / excluded terms (ss_score_topk_constrained) resolved to one allowed set per distinct (mask, required, excluded)
 // combination, which k_constraint_masks builds on the device in the call's set buffer.  The scoring kernels take the sets as the
 // masked call takes registered allow-lists: q_mask / SmallHdr carry the set's index, written here into in.mask.
+// The sets with range clauses (ss_score_topk_filtered), for k_field_masks; set_cl[i]: the clauses of set i.  A set with clauses and no
+// terms is built by k_field_masks alone, from the registered allow-list: those sets move to the end of the set buffer —
+// k_constraint_masks builds the ones in front of them — and the queries' set indices follow.  A set with terms and clauses is narrowed
+// in place behind k_constraint_masks.
+void plan_field_sets(BatchInputs& in, const std::vector<std::vector<ss_doc_range>>& set_cl, ConstraintPlan& cp) {
+    const size_t n = cp.sets.size();
+    auto field_only = [&](size_t i) { return !set_cl[i].empty() && cp.sets[i].n_req + cp.sets[i].n_exc == 0; };
+    std::vector<int32_t> new_of(n);
+    std::vector<size_t> old_of;
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t i = 0; i < n; i++)
+            if (field_only(i) == (pass == 1)) {
+                new_of[i] = (int32_t)old_of.size();
+                old_of.push_back(i);
+                cp.n_field_only += pass;
+            }
+    std::vector<ConstraintSet> sets(n);
+    for (size_t j = 0; j < n; j++) sets[j] = cp.sets[old_of[j]];
+    cp.sets.swap(sets);
+    for (int32_t& m : in.mask)
+        if (m >= 0) m = new_of[m];
+    const uint32_t group = ss::field_mask_group();
+    for (size_t j = 0; j < n; j++) {
+        const std::vector<ss_doc_range>& cl = set_cl[old_of[j]];
+        if (cl.empty()) continue;
+        if (cp.fsets.size() % group == 0) cp.fgroups.push_back(0u);
+        cp.fsets.push_back(FieldSet{(uint32_t)j, j >= n - cp.n_field_only ? cp.sets[j].mask1 : FS_IN_PLACE, (uint32_t)cp.fclauses.size(), (uint32_t)cl.size()});
+        for (const ss_doc_range& c : cl) {
+            cp.fclauses.push_back(c);
+            cp.fgroups.back() |= 1u << c.field;
+        }
+    }
+}
+
 int32_t resolve_constraints(BatchInputs& in, const ScorerView& v, ConstraintPlan& cp, PlanError& err) {
-    if (!in.has_constraints) return SS_OK;
+    if (!in.has_constraints && !in.has_ranges) return SS_OK;
     const int32_t n_q = in.n_q;
     const std::vector<uint64_t>& tp = v.tp;
     const std::vector<uint64_t>& bp = v.bp;
     const std::vector<uint32_t>&rp = in.req_ptr, &rt = in.req_terms, &ep = in.exc_ptr, &et = in.exc_terms;
     auto df = [&](uint32_t t) -> uint64_t { return (uint64_t)t < v.n_terms ? (tp[t + 1] - tp[t]) + (bp[t + 1] - bp[t]) : 0; };
-    // a query's set key: {CS_EMPTY} (no doc can be allowed), {mask + 1, n_req, required ids, excluded ids}, or none at all
+    // a query's set key: {CS_EMPTY} (no doc can be allowed), {mask + 1, n_req, n_exc, required ids, excluded ids, five words per range
+    // clause: field, lo, hi}, or none at all
     std::vector<std::vector<uint32_t>> keys(n_q);
     bool constrained = false;
     std::vector<uint32_t> req, exc;
+    using Clause = std::tuple<int32_t, int64_t, int64_t>;
+    std::vector<Clause> cl;
     for (int q = 0; q < n_q; q++) {
+        // the clauses as a set (sorted, repeats dropped); one with lo > hi matches no doc
+        cl.clear();
+        bool no_doc = false;
+        for (uint32_t c = in.has_ranges ? in.rng_ptr[q] : 0u; c < (in.has_ranges ? in.rng_ptr[q + 1] : 0u); c++) {
+            cl.emplace_back(in.rng[c].field, in.rng[c].lo, in.rng[c].hi);
+            no_doc = no_doc || in.rng[c].lo > in.rng[c].hi;
+        }
+        std::sort(cl.begin(), cl.end());
+        cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
         req.assign(rt.begin() + rp[q], rt.begin() + rp[q + 1]);
         exc.assign(et.begin() + ep[q], et.begin() + ep[q + 1]);
         std::sort(req.begin(), req.end());
@@ -255,14 +333,19 @@ int32_t resolve_constraints(BatchInputs& in, const ScorerView& v, ConstraintPlan
             return err.set(SS_ERR_UNSUPPORTED, "ss_score_topk_constrained: query %d has %zu distinct required + excluded terms (max %d)", q,
                            req.size() + exc.size(), SS_MAX_CONSTRAINT_TERMS);
         // a term without postings (unknown ids included): required, no doc contains it; excluded, it excludes nothing
-        bool empty = false;
+        bool empty = no_doc;
         for (uint32_t t : req) empty = empty || df(t) == 0 || std::binary_search(exc.begin(), exc.end(), t);
         exc.erase(std::remove_if(exc.begin(), exc.end(), [&](uint32_t t) { return df(t) == 0; }), exc.end());
         if (empty) keys[q] = {CS_EMPTY};
-        else if (!req.empty() || !exc.empty()) {
-            keys[q] = {(uint32_t)((in.has_mask_arg ? in.mask[q] : -1) + 1), (uint32_t)req.size()};
+        else if (!req.empty() || !exc.empty() || !cl.empty()) {
+            keys[q] = {(uint32_t)((in.has_mask_arg ? in.mask[q] : -1) + 1), (uint32_t)req.size(), (uint32_t)exc.size()};
             keys[q].insert(keys[q].end(), req.begin(), req.end());
             keys[q].insert(keys[q].end(), exc.begin(), exc.end());
+            for (const Clause& c : cl) {
+                const uint64_t lo = (uint64_t)std::get<1>(c), hi = (uint64_t)std::get<2>(c);
+                const uint32_t w[5] = {(uint32_t)std::get<0>(c), (uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+                keys[q].insert(keys[q].end(), w, w + 5);
+            }
         }
         constrained = constrained || !keys[q].empty();
     }
@@ -271,29 +354,36 @@ int32_t resolve_constraints(BatchInputs& in, const ScorerView& v, ConstraintPlan
     // with an allow-list alone (a set without terms: the builder copies the list)
     in.mask.resize(n_q);
     std::map<std::vector<uint32_t>, int32_t> set_of;
+    std::vector<std::vector<ss_doc_range>> set_cl;          // (has_ranges) the clauses of every set
     for (int q = 0; q < n_q; q++) {
         const int32_t m = in.has_mask_arg ? in.mask[q] : -1;
-        if (keys[q].empty() && m >= 0) keys[q] = {(uint32_t)(m + 1), 0u};
+        if (keys[q].empty() && m >= 0) keys[q] = {(uint32_t)(m + 1), 0u, 0u};
         if (keys[q].empty()) { in.mask[q] = -1; continue; }
         auto it = set_of.find(keys[q]);
         if (it == set_of.end()) {
             const std::vector<uint32_t>& key = keys[q];
             ConstraintSet cs{CS_EMPTY, 0u, 0u, (uint32_t)cp.terms.size()};
+            std::vector<ss_doc_range> ranges;
             if (key[0] != CS_EMPTY) {
                 cs.mask1 = key[0];
                 cs.n_req = key[1];
-                cs.n_exc = (uint32_t)key.size() - 2 - key[1];
+                cs.n_exc = key[2];
+                const auto t_end = key.begin() + 3 + cs.n_req + cs.n_exc;
                 // the required terms rarest first: a block that one of them empties skips the others
-                std::vector<uint32_t> order(key.begin() + 2, key.end());
+                std::vector<uint32_t> order(key.begin() + 3, t_end);
                 std::stable_sort(order.begin(), order.begin() + cs.n_req, [&](uint32_t a, uint32_t b) { return df(a) < df(b); });
                 for (uint32_t t : order) cp.terms.push_back(ConstraintTerm{tp[t], tp[t + 1], bp[t], bp[t + 1]});
+                for (auto w = t_end; w != key.end(); w += 5)
+                    ranges.push_back(ss_doc_range{(int32_t)w[0], 0, (int64_t)((uint64_t)w[2] << 32 | w[1]), (int64_t)((uint64_t)w[4] << 32 | w[3])});
             }
             it = set_of.emplace(key, (int32_t)cp.sets.size()).first;
             cp.sets.push_back(cs);
+            if (in.has_ranges) set_cl.push_back(std::move(ranges));
         }
         in.mask[q] = it->second;
     }
     in.any_mask = true;
+    if (in.has_ranges) plan_field_sets(in, set_cl, cp);
     return SS_OK;
 }
 
@@ -719,7 +809,7 @@ struct PlanWriter {
 
 // THE list of the plan's sections: order, source, size, and whether the kernels see it.  Returns where k_score_small's table goes.
 unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, ScoreParams& p,
-                             ConstraintParams& cp) {
+                             ConstraintParams& cp, FieldParams& fp) {
     const size_t n_q = (size_t)in.n_q;
     const bool ph = pl.any_phrase;
     w.add(p.q_off, pl.qoff.data(), n_q + 1);
@@ -743,6 +833,9 @@ unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const Constra
     w.add(p.q_mask, in.mask.data(), in.any_mask ? n_q : 0, in.any_mask);
     w.add(cp.sets, cons.sets.data(), cons.sets.size());
     w.add(cp.terms, cons.terms.data(), cons.terms.size());
+    w.add(fp.sets, cons.fsets.data(), cons.fsets.size());
+    w.add(fp.clauses, cons.fclauses.data(), cons.fclauses.size());
+    w.add(fp.group_fields, cons.fgroups.data(), cons.fgroups.size());
     return small_tab;
 }
 
@@ -873,17 +966,27 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
         cp.n_words = (s->n_docs + 31) / 32;
         cp.n_blocks = ss::constraint_blocks(sb.set_stride);
     }
+    if (!cons.fsets.empty()) {
+        FieldParams& fp = sb.fp;
+        fp.values = s->fields.p;
+        fp.n_docs = s->n_docs;
+        fp.n_sets = (uint32_t)cons.fsets.size();
+        fp.reg_masks = s->masks.p; fp.reg_words = s->mask_words;
+        fp.out = t.d_sets.p;
+        fp.stride = sb.set_stride;
+        fp.n_words = (s->n_docs + 31) / 32;
+    }
 }
 
 // one pinned staging buffer (one H2D copy: enqueue), the workspaces, the kernel parameters
 int32_t stage_plan(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const Route& r,
                    StagedBatch& sb, Stamps& t) {
     PlanWriter measure;
-    plan_sections(measure, in, cons, pl, sb.p, sb.cp);
+    plan_sections(measure, in, cons, pl, sb.p, sb.cp, sb.fp);
     sb.plan_bytes = measure.o;
     SS_TRY(acquire_turn(s, sb.plan_bytes, cons.sets.size(), a.turn_rows, sb));
     PlanWriter w{s->turn[sb.turn].h_plan.p, s->turn[sb.turn].d_plan.p, 0};
-    unsigned char* tab = plan_sections(w, in, cons, pl, sb.p, sb.cp);
+    unsigned char* tab = plan_sections(w, in, cons, pl, sb.p, sb.cp, sb.fp);
     // k_score_small's table: the 1024-slot queries first, then the larger ones (launch_score_small)
     for (const std::vector<SmallEnt>* v : {&pl.small_a, &pl.small_b})
         for (const SmallEnt& en : *v) {
@@ -961,7 +1064,8 @@ int32_t enqueue(ss_scorer* s, const BatchInputs& in, const ConstraintPlan& cons,
     if (opt.timed) SS_HIP(ctx, hipEventRecord(ctx->ev[1][0], ctx->stream));
     SS_TRY(bind_streams(s, opt, r));
     if (n_csets) {                               // the allowed sets, in front of the kernels that read them (never k_score_wave)
-        ss::launch_constraint_masks(&sb.cp, (uint32_t)n_csets, r.sst);
+        ss::launch_constraint_masks(&sb.cp, (uint32_t)(n_csets - cons.n_field_only), r.sst);
+        if (!cons.fsets.empty()) ss::launch_field_masks(&sb.fp, r.sst);     // range clauses: the sets of clauses alone, and the others in place
         if (pl.n_small && r.small_st != r.sst) SS_HIP(ctx, turn.set_ev.wait_behind(r.sst, r.small_st));
     }
     if (pl.n_small) {                  // writes its queries' hits itself: the caller's stream, like every kernel that does — or stages them
@@ -1111,6 +1215,15 @@ int32_t ss_score_topk_constrained(ss_scorer* s, int32_t n_q, const uint32_t* q_p
                                   int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
     const QueryConstraints cons{req_ptr, req_terms, exc_ptr, exc_terms};
     return score_impl(s, CallArgs{n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, &cons});
+}
+
+int32_t ss_score_topk_filtered(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const uint32_t* p_ptr,
+                               const uint32_t* p_terms, const int32_t* query_len, const double* topic_probs, const int32_t* mask_id,
+                               const uint32_t* req_ptr, const uint32_t* req_terms, const uint32_t* exc_ptr, const uint32_t* exc_terms,
+                               const uint32_t* rng_ptr, const ss_doc_range* rng, int32_t k, ss_hit* hits_out, int32_t* n_hits_out) {
+    const QueryConstraints cons{req_ptr, req_terms, exc_ptr, exc_terms};
+    const QueryRanges ranges{rng_ptr, rng};
+    return score_impl(s, CallArgs{n_q, q_ptr, q_terms, p_ptr, p_terms, query_len, topic_probs, k, hits_out, n_hits_out, mask_id, &cons, nullptr, &ranges});
 }
 
 // Batches in flight with HOST results: submit runs the batch like a call with device outputs (nothing waits, consecutive batches

@@ -180,6 +180,24 @@ struct ConstraintParams {
     uint32_t n_blocks;                // workgroups per set
 };
 
+// k_field_masks (field.hip, ss_doc_field_masks / ss_score_topk_filtered): allow-lists from range clauses over the doc field table
+#define FS_IN_PLACE 0xFFFFFFFFu
+struct __attribute__((aligned(16))) FieldSet { uint32_t out_set, base1, c0, n_cl; };       // writes words [out_set][..]; base1: registered allow-list + 1 it starts from (0: every doc, FS_IN_PLACE: the words that stand in `out`); clauses c0 .. c0+n_cl
+static_assert(sizeof(FieldSet) == 16 && sizeof(ss_doc_range) == 24, "field set table layout");
+struct FieldParams {
+    const int64_t* values;            // the scorer's field table [n_fields][n_docs]
+    uint64_t n_docs;
+    const FieldSet* sets;             // [n_sets], walked in groups of FM_GROUP by the workgroups of one grid row
+    const ss_doc_range* clauses;
+    const uint32_t* group_fields;     // [groups] bit f: a clause of the group reads field f
+    uint32_t n_sets;
+    const uint32_t* reg_masks;        // as ConstraintParams
+    uint64_t reg_words;
+    uint32_t* out;                    // [..][stride]
+    uint64_t stride;                  // words per set (>= n_words)
+    uint64_t n_words;                 // (n_docs + 31) / 32
+};
+
 using ss::fkey;
 using ss::funkey;
 using ss::better;

@@ -37,6 +37,10 @@ void score_small_report();
 void score_wave_diag_dump();
 uint32_t constraint_blocks(uint64_t n_words);
 void launch_constraint_masks(const void* params, uint32_t n_sets, hipStream_t st);
+// field.hip (params: FieldParams): k_field_masks over the params' sets; the geometry for callers and tests
+uint32_t field_mask_docs();                     // docs of one workgroup
+uint32_t field_mask_group();                    // sets that share one read of the field columns
+void launch_field_masks(const void* params, hipStream_t st);
 }  // namespace ss
 
 // Where a scoring call left its rows when they stay inside the scorer (ss::score_into_turn): the block of the plan turn the call took.
@@ -171,6 +175,16 @@ struct ss_scorer {
     ss::DevBuf<ss_hit> d_dd_hits, d_dd_out;
     ss::DevBuf<int32_t> d_dd_n, d_dd_nout, d_dd_kept;
     ss::DevBuf<uint32_t> d_dd_sim;
+    // ss_scorer_set_doc_fields (field.hip): [n_fields][n_docs] signed 64-bit values per doc.  ss_doc_field_masks, ss_sort_hits_by_field,
+    // ss_hit_fields: d_fld_*: the set table of a mask call and device blocks of HOST arrays (grow-only; a call that uses one waits
+    // before it returns).
+    ss::DevBuf<int64_t> fields;
+    int32_t n_fields = 0;
+    ss::DevBuf<unsigned char> d_fld_tab;
+    ss::DevBuf<uint32_t> d_fld_words;
+    ss::DevBuf<ss_hit> d_fld_hits, d_fld_out;
+    ss::DevBuf<int32_t> d_fld_n, d_fld_nout;
+    ss::DevBuf<int64_t> d_fld_vals;
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
@@ -220,3 +234,5 @@ inline int32_t fetch_ptr_array(ss_ctx* ctx, const char* entry, const char* name,
 
 // the constraint arrays of ss_score_topk_constrained (NULL pointers: none)
 struct QueryConstraints { const uint32_t *req_ptr, *req_terms, *exc_ptr, *exc_terms; };
+// the range clauses of ss_score_topk_filtered (rng_ptr NULL: none)
+struct QueryRanges { const uint32_t* rng_ptr; const ss_doc_range* rng; };

@@ -21,6 +21,8 @@ TERM_MATCH_DTYPE = np.dtype([("title_w", "<f4"), ("body_w", "<f4"), ("flags", "<
 
 PASSAGE_DTYPE = np.dtype([("start", "<f4"), ("last", "<f4"), ("n_distinct", "<u4"), ("n_occ", "<u4"), ("token_mask", "<u8")])   # ss_passage
 
+DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("hi", "<i8")])   # ss_doc_range
+
 _NP2T = {"uint64": "int64", "uint32": "int32"}
 
 
@@ -593,6 +595,19 @@ def pack_doc_masks(sets, n_docs: int) -> np.ndarray:
     return np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(bits.shape[0], n_words).astype(np.uint32)
 
 
+def pack_doc_ranges(sets):
+    """Range clauses for Scorer.doc_field_masks / score_topk_filtered: `sets` is one list of (field, lo, hi) clauses per set or query
+    (an empty list: no clause) -> (rng_ptr uint32 [n + 1], clauses DOC_RANGE_DTYPE)."""
+    ptr = np.zeros(len(sets) + 1, dtype=np.uint32)
+    ptr[1:] = np.cumsum([len(c) for c in sets])
+    rng = np.zeros(int(ptr[-1]), dtype=DOC_RANGE_DTYPE)
+    flat = [c for cs in sets for c in cs]
+    rng["field"] = [c[0] for c in flat]
+    rng["lo"] = [c[1] for c in flat]
+    rng["hi"] = [c[2] for c in flat]
+    return ptr, rng
+
+
 class Scorer:
     """Batched OR-query cosine scorer + PageRank blend + top-k (ss_score_topk)."""
 
@@ -603,6 +618,7 @@ class Scorer:
         check(ctx.lib.ss_scorer_create(ctx.h, title.h, body.h, C.byref(h)), ctx.h)
         self.h = h
         self.k_topics = 0
+        self.n_fields = 0
 
     def set_prior(self, rank) -> None:
         """rank [K][n_docs] topic-major (ss_pagerank_run layout) or None to clear."""
@@ -935,6 +951,120 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_same, o_kept
 
+    def set_doc_fields(self, values) -> None:
+        """ss_scorer_set_doc_fields: register the per-doc field table (int64 [n_fields][n_docs] field-major, numpy or torch; up to
+        SS_MAX_DOC_FIELDS fields), or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
+        if values is None:
+            check(self.ctx.lib.ss_scorer_set_doc_fields(self.h, 0, None), self.ctx.h)
+            self.n_fields = 0
+            return
+        values = _as(values, "int64")
+        if values.ndim != 2 or int(values.shape[1]) != self.title.n_docs:
+            raise ValueError(f"field table must have shape [n_fields][{self.title.n_docs}], got {tuple(values.shape)}")
+        self.ctx.ready(values)
+        check(self.ctx.lib.ss_scorer_set_doc_fields(self.h, int(values.shape[0]), _ptr(values)), self.ctx.h)
+        self.n_fields = int(values.shape[0])
+
+    def doc_field_masks(self, ranges, mask_id=None, out=None):
+        """ss_doc_field_masks: allow-lists from range clauses, built on the device -> uint32 words [n_sets][(n_docs + 31) // 32] in
+        the layout set_doc_masks takes.  ranges: (rng_ptr [n_sets + 1], DOC_RANGE_DTYPE clauses) as pack_doc_ranges gives; mask_id
+        [n_sets]: the registered allow-list a set starts from (-1 / None: every doc).  out: the caller's array (numpy, or a torch
+        int32 device tensor), returned as it is."""
+        rng_ptr = _as(ranges[0], "uint32")
+        rng = np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE)
+        mask_id = _as(mask_id, "int32")
+        n_sets = int(rng_ptr.shape[0]) - 1
+        n_words = (self.title.n_docs + 31) // 32
+        if out is None:
+            out = np.zeros((n_sets, n_words), dtype=np.uint32)
+        elif (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) < n_sets * n_words * 4:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(rng_ptr, mask_id, out)
+        check(self.ctx.lib.ss_doc_field_masks(self.h, n_sets, _ptr(rng_ptr), _ptr(rng), _ptr(mask_id), _ptr(out)), self.ctx.h)
+        return out
+
+    def score_topk_filtered(self, q_ptr, q_terms, k: int, ranges=None, req=None, exc=None, mask_id=None, p_ptr=None, p_terms=None,
+                            query_len=None, topic_probs=None, out=None):
+        """ss_score_topk_filtered: score_topk_constrained where every doc of row q must also match each range clause of query q
+        (lo <= value[field][doc] <= hi over the table of set_doc_fields).  ranges: (rng_ptr [n_q + 1], DOC_RANGE_DTYPE clauses) as
+        pack_doc_ranges gives, or None.  The clauses only filter.  out: device outputs as in score_topk."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        p_ptr = _as(p_ptr, "uint32")
+        p_terms = _as(p_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        n_q = int(q_ptr.shape[0]) - 1
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, p_ptr, p_terms, query_len, topic_probs)
+        if out is not None:
+            hits, n_hits = out
+            if hits.numel() * hits.element_size() < n_q * k * HIT_DTYPE.itemsize or n_hits.numel() < n_q:
+                raise ValueError("output buffers too small")
+        else:
+            hits, n_hits = np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32)
+        check(self.ctx.lib.ss_score_topk_filtered(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(p_ptr), _ptr(p_terms), _ptr(query_len),
+                                                  _ptr(topic_probs), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                                  _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), k, _ptr(hits), _ptr(n_hits)), self.ctx.h)
+        if out is not None and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return hits, n_hits
+
+    def _window(self, hits, n_hits, k_in):
+        """(hits, n_hits, n_q, k_in) of a result window as collapse_hits takes it"""
+        n_hits = _as(n_hits, "int32")
+        n_q = int(n_hits.numel() if _is_torch(n_hits) else n_hits.size)
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k_in is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k_in = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k_in) * HIT_DTYPE.itemsize:
+            raise ValueError("hits too small")
+        return hits, n_hits, n_q, int(k_in)
+
+    def sort_hits_by_field(self, hits, n_hits, field: int, k: int, descending: bool = False, first: int = 0,
+                           k_in: Optional[int] = None, out=None, want_values: bool = True):
+        """ss_sort_hits_by_field: every window hits[q][: n_hits[q]] sorted stably by value[field][doc] (rows outside the table last),
+        page [first, first + k) -> (hits [n_q][k], n_hits [n_q], values [n_q][k] int64 | None).  hits / n_hits, k_in as in
+        collapse_hits.  out = (hits, n_hits, values | None): the caller's arrays, returned as they are; with device arrays throughout
+        the library only enqueues."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        if out is None:
+            out = (np.zeros((n_q, int(k)), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                   np.zeros((n_q, int(k)), dtype=np.int64) if want_values else None)
+        o_hits, o_n, o_vals = out
+        o_n, o_vals = _as(o_n, "int32"), _as(o_vals, "int64")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if (nbytes(o_hits) < n_q * int(k) * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4
+                or (o_vals is not None and nbytes(o_vals) < n_q * int(k) * 8)):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(hits, n_hits, o_hits, o_n, o_vals)
+        check(self.ctx.lib.ss_sort_hits_by_field(self.h, n_q, k_in, _ptr(hits), _ptr(n_hits), int(field), int(bool(descending)), int(first),
+                                                 int(k), _ptr(o_hits), _ptr(o_n), _ptr(o_vals)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_vals
+
+    def hit_fields(self, hits, n_hits, k_in: Optional[int] = None, out=None):
+        """ss_hit_fields: the field values of every row hits[q][: n_hits[q]] -> int64 [n_q][k_in][n_fields] (SS_NO_FIELD_VALUE for a
+        row outside the table; rows past n_hits[q] keep what the array held, zeros here).  out: the caller's array."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        n_fields = getattr(self, "n_fields", 0)
+        if out is None:
+            out = np.zeros((n_q, k_in, n_fields), dtype=np.int64)
+        elif (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) < n_q * k_in * n_fields * 8:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(hits, n_hits, out)
+        check(self.ctx.lib.ss_hit_fields(self.h, n_q, k_in, _ptr(hits), _ptr(n_hits), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return out
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""
@@ -965,7 +1095,7 @@ class Scorer:
 
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
-           "pack_doc_masks"]
+           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges"]
 
 
 def _flatten_words(words, ptr_dtype: str):

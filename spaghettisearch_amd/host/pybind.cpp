@@ -59,6 +59,9 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Results", &retrieval::CollapsedPage::Results)
         .def_readonly("Same", &retrieval::CollapsedPage::Same)
         .def_readonly("Kept", &retrieval::CollapsedPage::Kept);
+    py::class_<retrieval::FieldSortedPage>(m, "FieldSortedPage")
+        .def_readonly("Results", &retrieval::FieldSortedPage::Results)
+        .def_readonly("Values", &retrieval::FieldSortedPage::Values);
     py::class_<retrieval::DedupedPage>(m, "DedupedPage")
         .def_readonly("Results", &retrieval::DedupedPage::Results)
         .def_readonly("Similar", &retrieval::DedupedPage::Similar)
@@ -166,6 +169,24 @@ PYBIND11_MODULE(_host, m) {
             auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
             return di.RetrieveBatchCollapsed(queries, k_window, g, first, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("k_window"), py::arg("g"), py::arg("first") = 0, py::arg("k") = 50,
+           py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("SetDocFields", &retrieval::DeviceIndex::SetDocFields, py::arg("fields"))
+        .def("RetrieveBatchFiltered", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                                         const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges, int k,
+                                         py::object topic_probs, bool live_topic_probs) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            if (topic_probs.is_none()) return di.RetrieveBatchFiltered(queries, rs, k, nullptr, live_topic_probs);
+            auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
+            return di.RetrieveBatchFiltered(queries, rs, k, &tp, live_topic_probs);
+        }, py::arg("queries"), py::arg("ranges"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("SortByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int field, bool descending, int k_window,
+                               int first, int k, py::object topic_probs, bool live_topic_probs) {
+            if (topic_probs.is_none()) return di.SortByField(queries, field, descending, k_window, first, k, nullptr, live_topic_probs);
+            auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
+            return di.SortByField(queries, field, descending, k_window, first, k, &tp, live_topic_probs);
+        }, py::arg("queries"), py::arg("field"), py::arg("descending"), py::arg("k_window"), py::arg("first") = 0, py::arg("k") = 50,
            py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
         .def("SetNearDuplicates", &retrieval::DeviceIndex::SetNearDuplicates, py::arg("n_slots"))
         .def("NearDuplicateSlots", &retrieval::DeviceIndex::NearDuplicateSlots)

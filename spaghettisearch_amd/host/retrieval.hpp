@@ -78,6 +78,19 @@ struct DedupedPage {
     int Kept = 0;
 };
 
+// One range clause of DeviceIndex::RetrieveBatchFiltered: lo <= value <= hi on field 0 (Mod_date, unix seconds) or 1 (Page_size, bytes).
+struct FieldRange {
+    int32_t field = 0;
+    int64_t lo = 0, hi = 0;
+};
+
+// One page of a query's results sorted by a doc field (DeviceIndex::SortByField; no reference counterpart).  Values[i]: the field's
+// value of Results[i].
+struct FieldSortedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<int64_t> Values;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -290,6 +303,10 @@ public:
     // again on every scorer this index creates.  has_doc_groups: SetDocGroups was called (an empty map is a table of SS_NO_GROUP).
     std::map<std::string, std::string> doc_group_keys;
     bool has_doc_groups = false;
+    // Doc fields (SetDocFields): doc hash -> {Mod_date as unix seconds, Page_size} (retrieval/util.go:28-29), kept by hash like the site
+    // keys and registered again on every scorer this index creates.
+    std::map<std::string, std::pair<int64_t, int64_t>> doc_field_values;
+    bool has_doc_fields = false;
     int near_dup_slots = 0;                         // SetNearDuplicates: the body table keeps MinHash signatures of this many slots (4 B each per doc)
     bool signatures_built = false;                  // the body table holds signatures that this object built and nothing has freed since
     // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
@@ -396,6 +413,7 @@ public:
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();
         register_groups();
+        register_fields();
         build_doc_view();
         build_signatures();
     }
@@ -746,6 +764,29 @@ public:
         check(ss_scorer_set_doc_groups(scorer, group.data()), "ss_scorer_set_doc_groups");
     }
 
+    // Doc fields for range filters and sorting: doc hash -> {Mod_date as unix seconds, Page_size in bytes}, field 0 and field 1 of the
+    // scorer's table.  A doc the map does not name has SS_NO_FIELD_VALUE in both fields (no sensible range matches it); hashes the
+    // index does not hold are ignored.
+    void SetDocFields(const std::map<std::string, std::pair<int64_t, int64_t>>& fields) {
+        doc_field_values = fields;
+        has_doc_fields = true;
+        register_fields();
+    }
+    void register_fields() {
+        using namespace spaghetti;
+        if (!has_doc_fields || !scorer || !title) return;
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        std::vector<int64_t> values(2 * (size_t)n, SS_NO_FIELD_VALUE);
+        for (auto& kv : doc_field_values) {
+            auto it = docs.id.find(kv.first);
+            if (it == docs.id.end() || it->second >= n) continue;
+            values[it->second] = kv.second.first;
+            values[(size_t)n + it->second] = kv.second.second;
+        }
+        check(ss_scorer_set_doc_fields(scorer, 2, values.data()), "ss_scorer_set_doc_fields");
+    }
+
     // On-disk snapshot of the flattened tables with the md5-hex <-> dense-id maps: written once after
     // the offline rank update, read at every server start instead of decoding the JSON tables.
     void save_snapshot(const std::string& path) { sync_flat(); flat.save(path); }
@@ -818,6 +859,7 @@ public:
                 if (K > 0 && K <= SS_MAX_TOPICS && di.flat.prior.size() == K * nd) (void)ss_scorer_set_prior(di.scorer, (int32_t)K, di.flat.prior.data());
                 try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
                 try { di.register_groups(); } catch (...) {}                // (RetrieveBatchCollapsed then reports the missing table)
+                try { di.register_fields(); } catch (...) {}                // (RetrieveBatchFiltered then reports the missing table)
                 try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
                 try { di.build_signatures(); } catch (...) {}               // (RetrieveBatchDeduped then reports the missing signatures)
             }
@@ -938,6 +980,7 @@ public:
         if (K > 0 && K <= SS_MAX_TOPICS) check(ss_scorer_set_prior(scorer, (int32_t)K, flat.prior.data()), "ss_scorer_set_prior");
         register_masks();                                                 // the new scorer, the ids as they stand now
         register_groups();
+        register_fields();
         build_doc_view();                                                 // (the deltas freed it)
         build_signatures();
         refresh_lexicon(ctx, forw[0], t_before);                          // new term ids: a new lexicon; otherwise the frequencies only
@@ -1204,6 +1247,73 @@ public:
             out[q].Results = ranks[q];
             out[q].Same.assign(same.begin() + q * kk, same.begin() + q * kk + n_page[q]);
             out[q].Kept = n_kept[q];
+        }
+        return out;
+    }
+    // RetrieveBatch with range clauses per query over the doc fields (SetDocFields): row q holds the first k docs of query q's ranking
+    // that match every clause of ranges[q] (not a filter of the unrestricted top k).  With SetQueryOperators "+word" / "-word" are
+    // read as in RetrieveBatch; the query strings carry no range syntax.
+    std::vector<std::vector<Rank_combined>> RetrieveBatchFiltered(const std::vector<std::string>& queries,
+                                                                  const std::vector<std::vector<FieldRange>>& ranges, int k = 50,
+                                                                  const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                                  bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (!has_doc_fields) throw std::runtime_error("RetrieveBatchFiltered: no doc fields (SetDocFields)");
+        if (ranges.size() != queries.size()) throw std::runtime_error("RetrieveBatchFiltered: one list of ranges per query");
+        std::vector<uint32_t> rng_ptr{0}, req_ptr{0}, exc_ptr{0}, req_terms, exc_terms;
+        std::vector<ss_doc_range> rng;
+        for (auto& rs : ranges) {
+            for (auto& r : rs) rng.push_back(ss_doc_range{r.field, 0, r.lo, r.hi});
+            rng_ptr.push_back((uint32_t)rng.size());
+        }
+        std::vector<std::string> rewritten;
+        const std::vector<std::string>* qs = &queries;
+        if (query_operators) {
+            auto id_of = [&](const std::string& w) -> uint32_t {
+                auto it = terms.id.find(md5::hex(w));
+                return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+            };
+            for (auto& q : queries) {
+                const QueryOperators op = parseQueryOperators(q, laundry);
+                rewritten.push_back(op.query);
+                for (auto& w : op.required) req_terms.push_back(id_of(w));
+                for (auto& w : op.excluded) exc_terms.push_back(id_of(w));
+                req_ptr.push_back((uint32_t)req_terms.size());
+                exc_ptr.push_back((uint32_t)exc_terms.size());
+            }
+            qs = &rewritten;
+        }
+        const Tokenised t = tokenise(*qs, topicProbs, live_topic_probs);
+        std::vector<ss_hit> hits((size_t)t.nq * std::max(k, 1));
+        std::vector<int32_t> n_hits(t.nq);
+        check(ss_score_topk_filtered(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                     t.probs.empty() ? nullptr : t.probs.data(), nullptr, query_operators ? req_ptr.data() : nullptr,
+                                     req_terms.data(), query_operators ? exc_ptr.data() : nullptr, exc_terms.data(), rng_ptr.data(), rng.data(),
+                                     k, hits.data(), n_hits.data()), "ss_score_topk_filtered");
+        return to_ranks(t.nq, k, hits, n_hits);
+    }
+    // RetrieveBatch sorted by a doc field (SetDocFields): page [first, first + k) of the first k_window rows of every query's ranking,
+    // sorted stably by the field, ascending or descending ("newest first": field 0, descending).  Query operators are not read here.
+    std::vector<FieldSortedPage> SortByField(const std::vector<std::string>& queries, int field, bool descending, int k_window, int first = 0,
+                                             int k = 50, const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                             bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (!has_doc_fields) throw std::runtime_error("SortByField: no doc fields (SetDocFields)");
+        if (query_operators) throw std::runtime_error("SortByField: query operators are not read here (SetQueryOperators(false))");
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
+        std::vector<ss_hit> rows(nq * (size_t)std::max(k_window, 1)), page(nq * kk);
+        std::vector<int32_t> n_rows(nq), n_page(nq);
+        std::vector<int64_t> values(nq * kk);
+        check(ss_score_topk_phrase(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                   t.probs.empty() ? nullptr : t.probs.data(), k_window, rows.data(), n_rows.data()), "ss_score_topk_phrase");
+        check(ss_sort_hits_by_field(scorer, t.nq, k_window, rows.data(), n_rows.data(), field, descending ? 1 : 0, first, k, page.data(),
+                                    n_page.data(), values.data()), "ss_sort_hits_by_field");
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<FieldSortedPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Values.assign(values.begin() + q * kk, values.begin() + q * kk + n_page[q]);
         }
         return out;
     }
