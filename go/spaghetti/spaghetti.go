@@ -64,6 +64,7 @@ type Scorer struct {
 	ctx     *Ctx
 	nDocs   uint64 // the title table's doc count when the scorer was created: sizes DocFieldMasks' words
 	nFields int    // fields registered by SetDocFields: sizes HitFields' values
+	vecDim  int    // dim of the table registered by SetDocVectors: sizes the query vectors
 }
 
 var (
@@ -1050,6 +1051,134 @@ func (s *Scorer) HitFields(hits [][]Hit) ([][][]int64, error) {
 		}
 	}
 	return out, nil
+}
+
+func i8p(s []int8) *C.int8_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.int8_t)(unsafe.Pointer(&s[0]))
+}
+
+// VecHit is one row of VectorTopK: a doc and its exact integer dot product with the query vector.
+type VecHit struct {
+	Doc   uint32
+	Score int32
+}
+
+// SetDocVectors registers one int8 vector per doc (ss_scorer_set_doc_vectors): vec[d*dim+i] = position i of doc d, dim a multiple
+// of 64 up to C.SS_MAX_VEC_DIM.  dim 0 clears.  Register it again after an index update, like the allow-lists.
+func (s *Scorer) SetDocVectors(dim int, vec []int8) {
+	if dim > 0 && uint64(len(vec)) < uint64(dim)*s.nDocs {
+		panic(fmt.Errorf("SetDocVectors: %d values for %d docs of dim %d", len(vec), s.nDocs, dim))
+	}
+	check(s.ctx, C.ss_scorer_set_doc_vectors(s.h, C.int32_t(dim), i8p(vec)), "ss_scorer_set_doc_vectors")
+	s.vecDim = dim
+	if len(vec) == 0 {
+		s.vecDim = 0
+	}
+}
+
+// VectorTopK returns per query vector (qvec[q*dim:(q+1)*dim]) the exact k nearest docs by integer dot product, score descending
+// then doc ascending, among the docs of the registered allow-list maskID[q] (-1 / nil: every doc) (ss_vector_topk).
+func (s *Scorer) VectorTopK(qvec []int8, maskID []int32, k int) ([][]VecHit, error) {
+	if s.vecDim < 1 {
+		return nil, fmt.Errorf("VectorTopK: no doc vectors registered (SetDocVectors)")
+	}
+	nq := len(qvec) / s.vecDim
+	if nq == 0 {
+		return nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_vec_hit, nq*kk)
+	nHits := make([]int32, nq)
+	rc := C.ss_vector_topk(s.h, C.int32_t(nq), i8p(qvec), i32p(maskID), C.int32_t(k), (*C.ss_vec_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	if err := statusErr(s.ctx, rc, "ss_vector_topk"); err != nil {
+		return nil, err
+	}
+	out := make([][]VecHit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]VecHit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*kk+i]
+			out[q][i] = VecHit{uint32(r.doc), int32(r.score)}
+		}
+	}
+	return out, nil
+}
+
+// vecWindow lays hits out as [nq][kIn] ss_hit rows with their counts
+func vecWindow(hits [][]Hit) ([]C.ss_hit, []int32, int) {
+	nq, kIn := len(hits), 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > kIn {
+			kIn = len(hits[q])
+		}
+	}
+	in := make([]C.ss_hit, nq*kIn)
+	nIn := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			in[q*kIn+j] = C.ss_hit{doc: C.uint32_t(h.Doc), title: C.double(h.Title), body: C.double(h.Body), pagerank: C.double(h.PageRank),
+				final: C.double(h.Final)}
+		}
+	}
+	return in, nIn, kIn
+}
+
+// HitVectorScores returns the score of every hit under its query's vector (ss_hit_vector_scores); C.SS_NO_VEC_SCORE for a doc
+// outside the table.
+func (s *Scorer) HitVectorScores(qvec []int8, hits [][]Hit) ([][]int32, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	in, nIn, kIn := vecWindow(hits)
+	vals := make([]int32, nq*kIn)
+	rc := C.ss_hit_vector_scores(s.h, C.int32_t(nq), i8p(qvec), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), i32p(vals))
+	if err := statusErr(s.ctx, rc, "ss_hit_vector_scores"); err != nil {
+		return nil, err
+	}
+	out := make([][]int32, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = append([]int32(nil), vals[q*kIn:q*kIn+len(hits[q])]...)
+	}
+	return out, nil
+}
+
+// RerankHitsByVector sorts every window stably by its rows' scores under the query's vector, descending, rows outside the table
+// last, and returns page [first, first+k) with the rows' scores (ss_rerank_hits_by_vector).
+func (s *Scorer) RerankHitsByVector(qvec []int8, hits [][]Hit, first, k int) ([][]Hit, [][]int32, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	in, nIn, kIn := vecWindow(hits)
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, vals := make([]int32, nq), make([]int32, nq*kk)
+	rc := C.ss_rerank_hits_by_vector(s.h, C.int32_t(nq), i8p(qvec), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn),
+		C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), i32p(vals))
+	if err := statusErr(s.ctx, rc, "ss_rerank_hits_by_vector"); err != nil {
+		return nil, nil, err
+	}
+	out, outVals := make([][]Hit, nq), make([][]int32, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q], outVals[q] = make([]Hit, n), append([]int32(nil), vals[q*kk:q*kk+n]...)
+		for i := 0; i < n; i++ {
+			r := raw[q*kk+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, outVals, nil
 }
 
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every

@@ -49,7 +49,9 @@ extern "C" {
  * SS_MAX_LINKS, SS_LINKS_PARENTS / _CHILDREN, ss_graph_set_link_key, ss_graph_top_links and ss_graph_hit_links (the best parents or
  * children of a page by a registered per-node key, and its edge count);
  * SS_MAX_DOC_FIELDS, SS_MAX_RANGE_CLAUSES, SS_NO_FIELD_VALUE, ss_doc_range, ss_scorer_set_doc_fields, ss_doc_field_masks,
- * ss_score_topk_filtered, ss_sort_hits_by_field and ss_hit_fields (per-doc integer fields: range filters, sort by field, read-out). */
+ * ss_score_topk_filtered, ss_sort_hits_by_field and ss_hit_fields (per-doc integer fields: range filters, sort by field, read-out);
+ * SS_MAX_VEC_DIM, SS_NO_VEC_SCORE, ss_vec_hit, ss_scorer_set_doc_vectors, ss_vector_topk, ss_hit_vector_scores and
+ * ss_rerank_hits_by_vector (one int8 vector per doc: exact nearest neighbours by integer dot product, a window re-ranked by it). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -799,6 +801,66 @@ int32_t ss_sort_hits_by_field(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_
                               ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int64_t* values_out /*[n_q][k], nullable*/);
 int32_t ss_hit_fields(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
                       int64_t* values_out /*[n_q][k_in][n_fields]*/);
+
+/* Doc vectors: one signed 8-bit embedding per doc, the exact k nearest docs of a query vector, and a lexical result window re-ordered
+ * by meaning.  No reference counterpart: every way the reference finds a page is a posting of a typed word.  Producing the embeddings
+ * is the caller's work, as tokenising is; the caller brings [n_docs][dim] and [n_q][dim] int8.
+ * The table: vec [n_docs][dim] doc-major (n_docs = the scorer's), host or device memory, copied; dim = 0 / NULL clears.  dim is a
+ * multiple of 64 in [64, SS_MAX_VEC_DIM], anything else is SS_ERR_INVALID.  n_docs * dim bytes (1.28 GB at 10M docs and dim 128):
+ * SS_ERR_OOM if that cannot be had.  Replaces the previous table after the scorer's outstanding work (pipelined batches, tickets) has
+ * finished with it.  The table lives as long as the scorer: after an index update (destroy scorers before, re-create after) register
+ * it again.  A call that fails leaves the old table in place.  Every int8 value is an ordinary value, -128 included; a doc whose vector
+ * is all zero is a doc like any other.
+ * Defined bit for bit:
+ *   score(q, d) = the sum over i < dim of (int32)qvec[q][i] * (int32)vec[d][i], in exact 32-bit integer arithmetic (|score| <= 2^24).
+ *               Nothing is normalised on the device: a caller who wants cosine quantises unit vectors. */
+#define SS_MAX_VEC_DIM   1024          /* dim is a multiple of 64 in [64, 1024] */
+#define SS_NO_VEC_SCORE  INT32_MIN     /* never a real score: |score| <= 1024*128*128 = 2^24 */
+typedef struct ss_vec_hit { uint32_t doc; int32_t score; } ss_vec_hit;   /* 8 bytes */
+int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec /*[n_docs][dim] doc-major; 0 / NULL clears*/);
+
+/* ss_vector_topk: exact nearest neighbours, not an approximate search and not a post-filter.  Defined bit for bit:
+ *   Candidates. Every doc d < n_docs in the REGISTERED allow-list mask_id[q] (ss_scorer_set_doc_masks; -1 = every doc; mask_id NULL =
+ *               all -1).  What ss_doc_field_masks writes can be registered as it is ("semantic search in the past week").
+ *   Order.      score(q, d) descending, then d ascending.
+ *   Output.     Row q = the first n_hits_out[q] = min(k, number of candidates) rows of that order; entries past that are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle (or qvec / hits_out / n_hits_out with n_q > 0),
+ * n_q < 0, k < 1, a mask_id below -1 or at / above n_masks: SS_ERR_INVALID; k > SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no vector table
+ * registered: SS_ERR_STATE.  n_q == 0 is SS_OK and does nothing.  mask_id is read on the host like the query arrays of the scoring
+ * calls (a device pointer costs one blocking copy); qvec and the outputs may be host or device memory: with all of them on the device
+ * the call only enqueues on the ctx stream and NEVER waits, otherwise it stages through blocks the scorer owns and returns when the
+ * outputs are written.  The chunks' partial lists take n_q * chunks * k * 8 bytes of device memory (bounded by 256 MB unless option
+ * "vec.chunk_docs" asks for more chunks): SS_ERR_OOM if that cannot be had.  More than 65535 blocks of queries: SS_ERR_UNSUPPORTED.
+ * k_vec_topk multiplies tiles of 64 docs with blocks of up to 64 queries on the int8 matrix cores, reads every doc byte once per
+ * block of queries and keeps, per query and chunk of docs, the k largest keys ((uint32)score ^ 0x80000000) << 32 | (0xFFFFFFFF - doc);
+ * k_vec_merge merges the chunks.  A key names its doc, so the rows do not depend on the order in which tiles finish. */
+int32_t ss_vector_topk(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, const int32_t* mask_id /*[n_q], NULL = all -1*/,
+                       int32_t k, ss_vec_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/);
+
+/* ss_hit_vector_scores: scores_out[q * k_in + j] = score(q, hits[q * k_in + j].doc) for j < n_hits[q]; SS_NO_VEC_SCORE for a row with
+ * doc >= n_docs; rows past n_hits[q] are left untouched; only .doc of a row is read.
+ * ss_rerank_hits_by_vector: ss_sort_hits_by_field with the key score(q, doc), always descending.  Defined bit for bit:
+ *   Window.     As in ss_collapse_hits: hits[q * k_in .. q * k_in + n_hits[q]), in the order given; only .doc of a row is read.
+ *   Order.      Rows with doc < n_docs by score(q, doc) descending, rows of equal score in window order (the sort is stable; the
+ *               same doc twice is two rows).  Rows with doc >= n_docs come LAST, among themselves in window order.  No doc id makes
+ *               the kernel read outside the table.
+ *   Output.     With the sorted rows S_0 .. S_{n-1}: hits_out[q * k + r] = the 40 bytes of S_{first + r} (_pad included) for
+ *               r < n_hits_out[q] = clamp(n - first, 0, k); scores_out[q * k + r] (nullable) = that row's score, SS_NO_VEC_SCORE for
+ *               a row with doc >= n_docs.  Entries past n_hits_out[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle (or qvec / hits / n_hits / hits_out /
+ * n_hits_out / scores_out of ss_hit_vector_scores with n_q > 0), n_q < 0, k_in < 1, k < 1, first < 0, hits_out overlapping hits as
+ * address ranges: SS_ERR_INVALID; k_in or k above SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no vector table registered: SS_ERR_STATE;
+ * n_hits[q] outside [0, k_in]: SS_ERR_INVALID when n_hits is host memory, clamped by the kernel when it is device memory.  n_q == 0
+ * is SS_OK and does nothing.
+ * Every pointer may be host or device memory: when all given pointers are device memory the calls only enqueue on the ctx stream and
+ * NEVER wait, so score (lexical window) -> dedup -> collapse -> rerank -> explain chains on one stream; otherwise they stage through
+ * blocks the scorer owns and return when the outputs are written.  Serialised on the ctx like every scoring call; no _submit /
+ * _collect form. */
+int32_t ss_hit_vector_scores(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/,
+                             const int32_t* n_hits /*[n_q]*/, int32_t* scores_out /*[n_q][k_in]*/);
+int32_t ss_rerank_hits_by_vector(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, int32_t k_in,
+                                 const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
+                                 ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
 
 /* ---- term lexicon: cmd/server/server.go:54-85 (/wordlist/{pre}), database/database.go:414-454 (IterateInv) -------------
  * The words of forw[0] keyed by dense term id, resident on the device.  The reference answers /wordlist/{pre} by walking every key

@@ -29,6 +29,8 @@ SS_LINKS_CHILDREN = 1
 SS_MAX_DOC_FIELDS = 4
 SS_MAX_RANGE_CLAUSES = 4
 SS_NO_FIELD_VALUE = -(2 ** 63)
+SS_MAX_VEC_DIM = 1024
+SS_NO_VEC_SCORE = -(2 ** 31)
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -56,6 +58,10 @@ class SsPassage(C.Structure):
 
 class SsDocRange(C.Structure):
     _fields_ = [("field", C.c_int32), ("_pad", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+class SsVecHit(C.Structure):
+    _fields_ = [("doc", C.c_uint32), ("score", C.c_int32)]
 
 
 class SsGraphInfo(C.Structure):
@@ -151,6 +157,10 @@ PROTOTYPES = {
     "ss_score_topk_filtered": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ss_sort_hits_by_field": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_hit_fields": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "ss_scorer_set_doc_vectors": (_i32, [_vp, _i32, _vp]),
+    "ss_vector_topk": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "ss_hit_vector_scores": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "ss_rerank_hits_by_vector": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ss_lexicon_create": (_i32, [_vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ss_lexicon_set_freq": (_i32, [_vp, _vp]),
     "ss_lexicon_get_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),

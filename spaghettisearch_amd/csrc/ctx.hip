@@ -357,6 +357,9 @@ static const char* const k_option_names[] = {
                             //    32 .. 4096, clamped: links_plan.hpp); a longer one is cut into chunks and merged
     "links.chunk_edges",    // ... edges per chunk of such a row (default 1024, 32 .. 4096, clamped); tests set both small to reach the split
                             //    path on small graphs; the rows are the same bytes for every value
+    "vec.chunk_docs",       // ss_vector_topk: docs per chunk of k_vec_topk, rounded up to a multiple of 64 (default 0: from the device's compute
+                            //    units, the query blocks and a bound on the partial lists: vector_plan.hpp); tests set it to 64 to put many
+                            //    chunk seams into a few hundred docs; the rows are the same bytes for every value
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

@@ -185,6 +185,20 @@ struct ss_scorer {
     ss::DevBuf<ss_hit> d_fld_hits, d_fld_out;
     ss::DevBuf<int32_t> d_fld_n, d_fld_nout;
     ss::DevBuf<int64_t> d_fld_vals;
+    // ss_scorer_set_doc_vectors (vector.hip): [n_docs][vec_dim] signed 8-bit values, vec_dim 0 = no table.  ss_vector_topk: the chunks'
+    // partial key lists, the queries' mask ids (through a pinned block whose last copy ev_vec_mid stands behind) and the dynamic LDS
+    // already granted to k_vec_topk<QT>.  d_vec_*: device blocks of HOST arrays and of the re-rank's scores (grow-only; a call that
+    // uses one for a host array waits before it returns).
+    ss::DevBuf<int8_t> vec;
+    int32_t vec_dim = 0;
+    ss::DevBuf<uint64_t> d_vec_part;
+    ss::DevBuf<int8_t> d_vec_q;
+    ss::DevBuf<int32_t> d_vec_mid, d_vec_n, d_vec_wn, d_vec_scores, d_vec_nout, d_vec_sout;
+    ss::PinBuf h_vec_mid;
+    ss::Event ev_vec_mid;
+    int vec_lds_attr[5] = {0, 0, 0, 0, 0};
+    ss::DevBuf<ss_vec_hit> d_vec_hits;
+    ss::DevBuf<ss_hit> d_vec_win, d_vec_out;
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.

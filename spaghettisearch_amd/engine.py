@@ -23,6 +23,8 @@ PASSAGE_DTYPE = np.dtype([("start", "<f4"), ("last", "<f4"), ("n_distinct", "<u4
 
 DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("hi", "<i8")])   # ss_doc_range
 
+VEC_HIT_DTYPE = np.dtype([("doc", "<u4"), ("score", "<i4")])   # ss_vec_hit
+
 _NP2T = {"uint64": "int64", "uint32": "int32"}
 
 
@@ -619,6 +621,7 @@ class Scorer:
         self.h = h
         self.k_topics = 0
         self.n_fields = 0
+        self.vec_dim = 0
 
     def set_prior(self, rank) -> None:
         """rank [K][n_docs] topic-major (ss_pagerank_run layout) or None to clear."""
@@ -1065,6 +1068,92 @@ class Scorer:
             self.ctx.synchronize()
         return out
 
+    def set_doc_vectors(self, vec) -> None:
+        """ss_scorer_set_doc_vectors: register one int8 vector per doc (int8 [n_docs][dim] doc-major, numpy or torch, dim a multiple of
+        64 up to SS_MAX_VEC_DIM), or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
+        if vec is None:
+            check(self.ctx.lib.ss_scorer_set_doc_vectors(self.h, 0, None), self.ctx.h)
+            self.vec_dim = 0
+            return
+        vec = _as(vec, "int8")
+        if vec.ndim != 2 or int(vec.shape[0]) != self.title.n_docs:
+            raise ValueError(f"vector table must have shape [{self.title.n_docs}][dim], got {tuple(vec.shape)}")
+        self.ctx.ready(vec)
+        check(self.ctx.lib.ss_scorer_set_doc_vectors(self.h, int(vec.shape[1]), _ptr(vec)), self.ctx.h)
+        self.vec_dim = int(vec.shape[1])
+
+    def _qvec(self, qvec):
+        qvec = _as(qvec, "int8")
+        if qvec.ndim != 2 or (getattr(self, "vec_dim", 0) and int(qvec.shape[1]) != self.vec_dim):
+            raise ValueError(f"query vectors must have shape [n_q][{getattr(self, 'vec_dim', 0)}], got {tuple(qvec.shape)}")
+        return qvec, int(qvec.shape[0])
+
+    def vector_topk(self, qvec, k: int, mask_id=None, device_out: bool = False, out=None):
+        """ss_vector_topk: per query vector the exact k nearest docs by integer dot product over the table of set_doc_vectors (score
+        descending, doc ascending), restricted to the registered allow-list mask_id[q] (-1 / None: every doc) ->
+        (hits VEC_HIT_DTYPE [n_q][k], n_hits int32 [n_q]).  device_out: torch device tensors (hits as int32 [n_q][k][2]: doc bits,
+        score); out = (hits, n_hits): the caller's arrays, returned as they are.  With device arrays throughout the library only
+        enqueues."""
+        qvec, n_q = self._qvec(qvec)
+        mask_id = _as(mask_id, "int32")
+        if out is None:
+            if device_out:
+                import torch
+                dev = qvec.device if _is_torch(qvec) and qvec.is_cuda else torch.device("cuda", self.ctx.device_id)
+                out = (torch.zeros((n_q, int(k), 2), dtype=torch.int32, device=dev), torch.zeros(n_q, dtype=torch.int32, device=dev))
+            else:
+                out = (np.zeros((n_q, int(k)), dtype=VEC_HIT_DTYPE), np.zeros(n_q, dtype=np.int32))
+        hits, n_hits = out
+        n_hits = _as(n_hits, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(hits) < n_q * int(k) * 8 or nbytes(n_hits) < n_q * 4):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qvec, mask_id, hits, n_hits)
+        check(self.ctx.lib.ss_vector_topk(self.h, n_q, _ptr(qvec), _ptr(mask_id), int(k), _ptr(hits), _ptr(n_hits)), self.ctx.h)
+        if _is_torch(hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return hits, n_hits
+
+    def hit_vector_scores(self, qvec, hits, n_hits, k_in: Optional[int] = None, out=None):
+        """ss_hit_vector_scores: the score of every row hits[q][: n_hits[q]] under query vector q -> int32 [n_q][k_in]
+        (SS_NO_VEC_SCORE for a row outside the table; rows past n_hits[q] keep what the array held, zeros here).  out: the caller's
+        array."""
+        qvec, _ = self._qvec(qvec)
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        if out is None:
+            out = np.zeros((n_q, k_in), dtype=np.int32)
+        elif (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) < n_q * k_in * 4:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(qvec, hits, n_hits, out)
+        check(self.ctx.lib.ss_hit_vector_scores(self.h, n_q, _ptr(qvec), k_in, _ptr(hits), _ptr(n_hits), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return out
+
+    def rerank_hits_by_vector(self, qvec, hits, n_hits, k: int, first: int = 0, k_in: Optional[int] = None, out=None,
+                              want_scores: bool = True):
+        """ss_rerank_hits_by_vector: every window hits[q][: n_hits[q]] sorted stably by its score under query vector q, descending
+        (rows outside the table last), page [first, first + k) -> (hits [n_q][k], n_hits [n_q], scores [n_q][k] int32 | None).
+        hits / n_hits, k_in as in collapse_hits.  out = (hits, n_hits, scores | None): the caller's arrays, returned as they are;
+        with device arrays throughout the library only enqueues."""
+        qvec, _ = self._qvec(qvec)
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        if out is None:
+            out = (np.zeros((n_q, int(k)), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                   np.zeros((n_q, int(k)), dtype=np.int32) if want_scores else None)
+        o_hits, o_n, o_sc = out
+        o_n, o_sc = _as(o_n, "int32"), _as(o_sc, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(o_hits) < n_q * int(k) * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4
+                           or (o_sc is not None and nbytes(o_sc) < n_q * int(k) * 4)):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qvec, hits, n_hits, o_hits, o_n, o_sc)
+        check(self.ctx.lib.ss_rerank_hits_by_vector(self.h, n_q, _ptr(qvec), k_in, _ptr(hits), _ptr(n_hits), int(first), int(k),
+                                                    _ptr(o_hits), _ptr(o_n), _ptr(o_sc)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sc
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""
@@ -1095,7 +1184,7 @@ class Scorer:
 
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
-           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges"]
+           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE"]
 
 
 def _flatten_words(words, ptr_dtype: str):

@@ -62,6 +62,12 @@ PYBIND11_MODULE(_host, m) {
     py::class_<retrieval::FieldSortedPage>(m, "FieldSortedPage")
         .def_readonly("Results", &retrieval::FieldSortedPage::Results)
         .def_readonly("Values", &retrieval::FieldSortedPage::Values);
+    py::class_<retrieval::VectorHit>(m, "VectorHit")
+        .def_readonly("DocHash", &retrieval::VectorHit::DocHash)
+        .def_readonly("Score", &retrieval::VectorHit::Score);
+    py::class_<retrieval::VectorRerankedPage>(m, "VectorRerankedPage")
+        .def_readonly("Results", &retrieval::VectorRerankedPage::Results)
+        .def_readonly("Scores", &retrieval::VectorRerankedPage::Scores);
     py::class_<retrieval::DedupedPage>(m, "DedupedPage")
         .def_readonly("Results", &retrieval::DedupedPage::Results)
         .def_readonly("Similar", &retrieval::DedupedPage::Similar)
@@ -188,6 +194,11 @@ PYBIND11_MODULE(_host, m) {
             return di.SortByField(queries, field, descending, k_window, first, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("field"), py::arg("descending"), py::arg("k_window"), py::arg("first") = 0, py::arg("k") = 50,
            py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("SetDocVectors", &retrieval::DeviceIndex::SetDocVectors, py::arg("vectors"))
+        .def("VectorSearch", &retrieval::DeviceIndex::VectorSearch, py::arg("queryVectors"), py::arg("k") = 50,
+             py::arg("masks") = std::vector<std::string>())
+        .def("RerankByVector", &retrieval::DeviceIndex::RerankByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("first") = 0,
+             py::arg("k") = 50)
         .def("SetNearDuplicates", &retrieval::DeviceIndex::SetNearDuplicates, py::arg("n_slots"))
         .def("NearDuplicateSlots", &retrieval::DeviceIndex::NearDuplicateSlots)
         .def("RetrieveBatchDeduped", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, int min_match,

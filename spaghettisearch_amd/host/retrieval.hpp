@@ -91,6 +91,19 @@ struct FieldSortedPage {
     std::vector<int64_t> Values;
 };
 
+// One row of DeviceIndex::VectorSearch: a doc and its exact integer dot product with the query vector (no reference counterpart).
+struct VectorHit {
+    std::string DocHash;
+    int32_t Score = 0;
+};
+
+// One page of a query's results re-ranked by vector score (DeviceIndex::RerankByVector).  Scores[i]: the score of Results[i],
+// SS_NO_VEC_SCORE for a row whose doc hash the index does not hold.
+struct VectorRerankedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<int32_t> Scores;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -307,6 +320,10 @@ public:
     // keys and registered again on every scorer this index creates.
     std::map<std::string, std::pair<int64_t, int64_t>> doc_field_values;
     bool has_doc_fields = false;
+    // Doc vectors (SetDocVectors): doc hash -> int8 embedding of doc_vector_dim values, kept by hash like the fields and registered
+    // again on every scorer this index creates.
+    std::map<std::string, std::vector<int8_t>> doc_vectors;
+    int doc_vector_dim = 0;
     int near_dup_slots = 0;                         // SetNearDuplicates: the body table keeps MinHash signatures of this many slots (4 B each per doc)
     bool signatures_built = false;                  // the body table holds signatures that this object built and nothing has freed since
     // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
@@ -414,6 +431,7 @@ public:
         register_masks();
         register_groups();
         register_fields();
+        register_vectors();
         build_doc_view();
         build_signatures();
     }
@@ -787,6 +805,105 @@ public:
         check(ss_scorer_set_doc_fields(scorer, 2, values.data()), "ss_scorer_set_doc_fields");
     }
 
+    // Doc vectors for VectorSearch / RerankByVector: doc hash -> int8 embedding, all of one length (a multiple of 64 up to
+    // SS_MAX_VEC_DIM).  A doc the map does not name has the zero vector (score 0 under every query); hashes the index does not hold
+    // are ignored.  An empty map clears the table.
+    void SetDocVectors(const std::map<std::string, std::vector<int8_t>>& vectors) {
+        int dim = 0;
+        for (auto& kv : vectors) {
+            if (dim == 0) dim = (int)kv.second.size();
+            if ((int)kv.second.size() != dim) throw std::runtime_error("SetDocVectors: vectors of different lengths");
+        }
+        if (!vectors.empty() && (dim < 64 || dim > SS_MAX_VEC_DIM || dim % 64))
+            throw std::runtime_error("SetDocVectors: the length must be a multiple of 64 in [64, SS_MAX_VEC_DIM]");
+        doc_vectors = vectors;
+        doc_vector_dim = dim;
+        register_vectors();
+    }
+    void register_vectors() {
+        using namespace spaghetti;
+        if (!scorer || !title) return;
+        if (doc_vector_dim == 0) { check(ss_scorer_set_doc_vectors(scorer, 0, nullptr), "ss_scorer_set_doc_vectors"); return; }
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        std::vector<int8_t> table((size_t)n * doc_vector_dim, 0);
+        for (auto& kv : doc_vectors) {
+            auto it = docs.id.find(kv.first);
+            if (it == docs.id.end() || it->second >= n) continue;
+            std::copy(kv.second.begin(), kv.second.end(), table.begin() + (size_t)it->second * doc_vector_dim);
+        }
+        check(ss_scorer_set_doc_vectors(scorer, doc_vector_dim, table.data()), "ss_scorer_set_doc_vectors");
+    }
+    std::vector<int8_t> flatten_query_vectors(const char* who, const std::vector<std::vector<int8_t>>& queryVectors) const {
+        if (doc_vector_dim == 0) throw std::runtime_error(std::string(who) + ": no doc vectors (SetDocVectors)");
+        std::vector<int8_t> flat;
+        for (auto& v : queryVectors) {
+            if ((int)v.size() != doc_vector_dim) throw std::runtime_error(std::string(who) + ": a query vector of the wrong length");
+            flat.insert(flat.end(), v.begin(), v.end());
+        }
+        return flat;
+    }
+    // Exact nearest neighbours: per query vector the k docs of the largest integer dot product, ties by dense doc id, among the docs of
+    // the set masks[q] names (SetDocMasks; "" or an empty list: the whole index).
+    std::vector<std::vector<VectorHit>> VectorSearch(const std::vector<std::vector<int8_t>>& queryVectors, int k = 50,
+                                                     const std::vector<std::string>& masks = {}) {
+        using namespace spaghetti;
+        const std::vector<int8_t> flat = flatten_query_vectors("VectorSearch", queryVectors);
+        const size_t nq = queryVectors.size();
+        if (!masks.empty() && masks.size() != nq) throw std::runtime_error("VectorSearch: one mask name per query");
+        std::vector<int32_t> mask_id(nq, -1);
+        for (size_t q = 0; q < masks.size(); q++) {
+            if (masks[q].empty()) continue;
+            auto it = mask_index.find(masks[q]);
+            if (it == mask_index.end()) throw std::runtime_error("VectorSearch: no doc mask named '" + masks[q] + "' (SetDocMasks)");
+            mask_id[q] = it->second;
+        }
+        std::vector<ss_vec_hit> hits(nq * (size_t)std::max(k, 1));
+        std::vector<int32_t> n_hits(nq);
+        check(ss_vector_topk(scorer, (int32_t)nq, flat.data(), mask_id.data(), k, hits.data(), n_hits.data()), "ss_vector_topk");
+        std::vector<std::vector<VectorHit>> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_hits[q]; i++) {
+                const ss_vec_hit& h = hits[q * (size_t)k + i];
+                out[q].push_back(VectorHit{docs.name[h.doc], h.score});
+            }
+        return out;
+    }
+    // A window of result rows per query (RetrieveBatch's, or any other call's) re-ordered by vector score, descending and stable;
+    // page [first, first + k).  Rows whose doc hash the index does not hold come last.
+    std::vector<VectorRerankedPage> RerankByVector(const std::vector<std::vector<int8_t>>& queryVectors,
+                                                   const std::vector<std::vector<Rank_combined>>& rows, int first = 0, int k = 50) {
+        using namespace spaghetti;
+        const std::vector<int8_t> flat = flatten_query_vectors("RerankByVector", queryVectors);
+        const size_t nq = queryVectors.size(), kk = (size_t)std::max(k, 1);
+        if (rows.size() != nq) throw std::runtime_error("RerankByVector: one window per query vector");
+        size_t k_in = 1;
+        for (auto& r : rows) k_in = std::max(k_in, r.size());
+        std::vector<ss_hit> win(nq * k_in), page(nq * kk);
+        std::vector<int32_t> n_rows(nq), n_page(nq), scores(nq * kk);
+        for (size_t q = 0; q < nq; q++) {
+            n_rows[q] = (int32_t)rows[q].size();
+            for (size_t j = 0; j < rows[q].size(); j++) {
+                const Rank_combined& r = rows[q][j];
+                auto it = docs.id.find(r.DocHash);
+                ss_hit h{};
+                h.doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;
+                h._pad = (uint32_t)j;                                     // the window position: how the page finds its row again
+                h.title = r.TitleRank; h.body = r.BodyRank; h.pagerank = r.PageRank; h.final = r.FinalRank;
+                win[q * k_in + j] = h;
+            }
+        }
+        check(ss_rerank_hits_by_vector(scorer, (int32_t)nq, flat.data(), (int32_t)k_in, win.data(), n_rows.data(), first, k, page.data(),
+                                       n_page.data(), scores.data()), "ss_rerank_hits_by_vector");
+        std::vector<VectorRerankedPage> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_page[q]; i++) {
+                out[q].Results.push_back(rows[q][page[q * kk + i]._pad]);
+                out[q].Scores.push_back(scores[q * kk + i]);
+            }
+        return out;
+    }
+
     // On-disk snapshot of the flattened tables with the md5-hex <-> dense-id maps: written once after
     // the offline rank update, read at every server start instead of decoding the JSON tables.
     void save_snapshot(const std::string& path) { sync_flat(); flat.save(path); }
@@ -860,6 +977,7 @@ public:
                 try { di.register_masks(); } catch (...) { di.mask_index.clear(); }
                 try { di.register_groups(); } catch (...) {}                // (RetrieveBatchCollapsed then reports the missing table)
                 try { di.register_fields(); } catch (...) {}                // (RetrieveBatchFiltered then reports the missing table)
+                try { di.register_vectors(); } catch (...) {}               // (VectorSearch then reports the missing table)
                 try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
                 try { di.build_signatures(); } catch (...) {}               // (RetrieveBatchDeduped then reports the missing signatures)
             }
@@ -981,6 +1099,7 @@ public:
         register_masks();                                                 // the new scorer, the ids as they stand now
         register_groups();
         register_fields();
+        register_vectors();
         build_doc_view();                                                 // (the deltas freed it)
         build_signatures();
         refresh_lexicon(ctx, forw[0], t_before);                          // new term ids: a new lexicon; otherwise the frequencies only
