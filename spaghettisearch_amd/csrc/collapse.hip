@@ -13,21 +13,20 @@
 //                              (`same`).  keep = rank < g goes back to window order, a workgroup prefix sum of it numbers the kept rows,
 //                              and the rows numbered [first, first + k) are copied out, five lanes to a row (8 bytes each), so that a
 //                              wave's stores are one contiguous run.  Only .doc of a row is read to decide anything.
-// Device hits / n_hits / outputs: the call only enqueues on the context's stream.  Otherwise the host arrays go through scorer-owned
-// grow-only device blocks and only the entries the definition names are copied back.
-#include "scorer.hpp"
+// The window in, the paging checks and the outputs' way back: hit_window.hpp.
+#include "hit_window.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 constexpr uint64_t CL_DEAD = ~0ull;                       // the key of a slot behind the window: sorts behind every live key
 constexpr uint32_t CL_J_BITS = 10;                        // j < SS_MAX_TOPK = 2^10
 constexpr uint32_t CL_KEEP = 0x80000000u;                 // s_ks[j] = same | (kept ? CL_KEEP : 0)
 constexpr uint32_t CL_NONE = 0xFFFFFFFFu;                 // s_pos[j] of a row that is not kept
 static_assert(SS_MAX_TOPK == (1 << CL_J_BITS), "a window index takes CL_J_BITS bits of a key");
-constexpr uint32_t CL_ROW_WORDS = sizeof(ss_hit) / 8;      // a row as 8-byte words
-static_assert(sizeof(ss_hit) == 40 && alignof(ss_hit) == 8, "a row is five 8-byte words");
 
 struct CollapseParams {
     const uint32_t* group;                                // [n_docs]
@@ -61,11 +60,9 @@ __global__ __launch_bounds__(BLOCK) void k_collapse_hits(CollapseParams p) {
     __shared__ uint32_t s_pos[CAP];                       // by window index: the row's number among the kept rows, CL_NONE if not kept
     __shared__ uint32_t s_wsum[WAVES];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;   // <= k_in <= CAP: checked by the launcher
+    const uint32_t n = hw::window_len(p.n_hits[q], p.k_in);   // <= k_in <= CAP: checked by the launcher
     const ss_hit* const rows = p.hits + (size_t)q * p.k_in;
-    uint32_t np = 1;
-    while (np < n) np <<= 1;                              // (the same value in every thread)
+    const uint32_t np = hw::pow2_at_least(n);             // (the same value in every thread)
     // ---- the keys
     for (uint32_t j = tid; j < np; j += BLOCK) {
         uint64_t key = CL_DEAD;
@@ -80,21 +77,13 @@ __global__ __launch_bounds__(BLOCK) void k_collapse_hits(CollapseParams p) {
     }
     __syncthreads();
     // ---- bitonic sort, ascending: a group's rows end up side by side in window order
-    for (uint32_t k2 = 2; k2 <= np; k2 <<= 1) {
-        for (uint32_t j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (uint32_t i = tid; i < np; i += BLOCK) {
-                const uint32_t o = i ^ j2;
-                if (o > i) {
-                    const uint64_t a = s_key[i], b = s_key[o];
-                    if ((a > b) == ((i & k2) == 0)) {
-                        s_key[i] = b;
-                        s_key[o] = a;
-                    }
-                }
-            }
-            __syncthreads();
+    hw::bitonic_sort<BLOCK>(np, [&](uint32_t i, uint32_t o, bool up) {
+        const uint64_t a = s_key[i], b = s_key[o];
+        if ((a > b) == up) {
+            s_key[i] = b;
+            s_key[o] = a;
         }
-    }
+    });
     // ---- rank inside the group and the group's size, back to window order
     for (uint32_t i = tid; i < n; i += BLOCK) {           // (the n live keys are the first n)
         const uint64_t key = s_key[i];
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(BLOCK) void k_collapse_hits(CollapseParams p) {
         const uint32_t j = tid * PER + c;
         if (j < n) s_pos[j] = (s_ks[j] & CL_KEEP) ? before++ : CL_NONE;
     }
-    const uint32_t n_out = n_kept > p.first ? (n_kept - p.first < p.k ? n_kept - p.first : p.k) : 0u;   // <= k, <= n
+    const uint32_t n_out = hw::page_len(n_kept, p.first, p.k);                   // <= k, <= n
     __syncthreads();
     // ---- which window row every output slot takes
     uint32_t* const s_src = reinterpret_cast<uint32_t*>(s_key);                  // [n_out], n_out <= n <= CAP
@@ -144,13 +133,7 @@ __global__ __launch_bounds__(BLOCK) void k_collapse_hits(CollapseParams p) {
         if (pos != CL_NONE && pos >= p.first && pos - p.first < n_out) s_src[pos - p.first] = j;
     }
     __syncthreads();
-    // ---- the rows, as 8-byte words: lane x moves word x % 5 of slot x / 5
-    const uint64_t* const in_w = reinterpret_cast<const uint64_t*>(rows);
-    uint64_t* const out_w = reinterpret_cast<uint64_t*>(p.hits_out + (size_t)q * p.k);
-    for (uint32_t x = tid; x < n_out * CL_ROW_WORDS; x += BLOCK) {
-        const uint32_t r = x / CL_ROW_WORDS, w = x - r * CL_ROW_WORDS;
-        out_w[x] = in_w[(size_t)s_src[r] * CL_ROW_WORDS + w];
-    }
+    hw::copy_page<BLOCK>(rows, p.hits_out + (size_t)q * p.k, n_out, [&](uint32_t r) { return s_src[r]; });
     if (p.same_out)
         for (uint32_t r = tid; r < n_out; r += BLOCK) p.same_out[(size_t)q * p.k + r] = s_ks[s_src[r]] & ~CL_KEEP;
     if (tid == 0) {
@@ -174,26 +157,21 @@ struct CollapseArgs {
 };
 
 // The kernel behind rows that are in device memory, and the way back of host outputs.  `last_reader` (nullable) is recorded behind the
-// kernel.  Returns without waiting when every output is device memory and `wait` is false.
-int32_t collapse_run(ss_scorer* s, const CollapseArgs& a, ss::Event* last_reader, bool wait) {
+// kernel.  Returns without waiting when every output is device memory and `staged` is false.
+int32_t collapse_run(ss_scorer* s, const CollapseArgs& a, ss::Event* last_reader, bool staged) {
     ss_ctx* ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    const size_t nq = (size_t)a.n_q, n_rows = nq * (size_t)a.k;
-    const bool dev_h = ss::on_device(a.hits_out), dev_n = ss::on_device(a.n_hits_out);
-    const bool dev_s = a.same_out && ss::on_device(a.same_out), dev_k = a.n_kept_out && ss::on_device(a.n_kept_out);
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_col_out, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_col_nout, nq));
-    if (a.same_out && !dev_s) SS_HIP(ctx, ensure(s->d_col_same, n_rows));
-    if (a.n_kept_out && !dev_k) SS_HIP(ctx, ensure(s->d_col_kept, nq));
+    hw::RowsOut o;
+    SS_TRY(hw::rows_out_prepare(s, (size_t)a.n_q, (size_t)a.k, a.hits_out, a.n_hits_out, a.n_kept_out, a.same_out, sizeof(uint32_t), &o));
     CollapseParams p{};
     p.group = s->groups.p;
     p.n_docs = s->n_docs;
     p.hits = a.hits;
     p.n_hits = a.n_hits;
-    p.hits_out = dev_h ? a.hits_out : s->d_col_out.p;
-    p.n_hits_out = dev_n ? a.n_hits_out : s->d_col_nout.p;
-    p.same_out = !a.same_out ? nullptr : dev_s ? a.same_out : s->d_col_same.p;
-    p.n_kept_out = !a.n_kept_out ? nullptr : dev_k ? a.n_kept_out : s->d_col_kept.p;
+    p.hits_out = o.hits;
+    p.n_hits_out = o.n_hits;
+    p.same_out = static_cast<uint32_t*>(o.extra);
+    p.n_kept_out = o.n_kept;
     p.k_in = (uint32_t)a.k_in; p.g = (uint32_t)a.g; p.first = (uint32_t)a.first; p.k = (uint32_t)a.k;
     if (a.k_in <= CL_SMALL * CL_SMALL_PER)
         hipLaunchKernelGGL((k_collapse_hits<CL_SMALL, CL_SMALL_PER>), dim3((unsigned)a.n_q), dim3(CL_SMALL), 0, st, p);
@@ -201,47 +179,7 @@ int32_t collapse_run(ss_scorer* s, const CollapseArgs& a, ss::Event* last_reader
         hipLaunchKernelGGL((k_collapse_hits<CL_LARGE, CL_LARGE_PER>), dim3((unsigned)a.n_q), dim3(CL_LARGE), 0, st, p);
     SS_HIP(ctx, hipGetLastError());
     if (last_reader) SS_HIP(ctx, last_reader->record(st));
-    const bool all_dev = dev_h && dev_n && (!a.same_out || dev_s) && (!a.n_kept_out || dev_k);
-    if (all_dev) {
-        if (wait) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;                                     // ordered on the ctx stream; nothing comes back
-    }
-    // ---- host outputs: the counts whole, of the rows exactly the entries the kernel wrote
-    std::vector<int32_t> h_n(nq), h_kept;
-    std::vector<ss_hit> h_rows;
-    std::vector<uint32_t> h_same;
-    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), p.n_hits_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (a.n_kept_out && !dev_k) {
-        h_kept.resize(nq);
-        SS_HIP(ctx, hipMemcpyAsync(h_kept.data(), p.n_kept_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (!dev_h) {
-        h_rows.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_rows.data(), p.hits_out, n_rows * sizeof(ss_hit), hipMemcpyDeviceToHost, st));
-    }
-    if (a.same_out && !dev_s) {
-        h_same.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_same.data(), p.same_out, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (!dev_n) std::memcpy(a.n_hits_out, h_n.data(), nq * sizeof(int32_t));
-    if (a.n_kept_out && !dev_k) std::memcpy(a.n_kept_out, h_kept.data(), nq * sizeof(int32_t));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)h_n[q], o = q * (size_t)a.k;
-        if (!dev_h) std::memcpy(a.hits_out + o, h_rows.data() + o, cnt * sizeof(ss_hit));
-        if (a.same_out && !dev_s) std::memcpy(a.same_out + o, h_same.data() + o, cnt * sizeof(uint32_t));
-    }
-    return SS_OK;
-}
-
-// the checks the two entry points share (k_in: the window's width); SS_OK = go on
-int32_t check_paging(ss_ctx* ctx, const char* entry, const char* window, int32_t n_q, int32_t k_in, int32_t g, int32_t first, int32_t k) {
-    if (n_q < 0) return ctx->fail(SS_ERR_INVALID, "%s: n_q < 0", entry);
-    if (k_in < 1 || k < 1 || g < 1 || first < 0)
-        return ctx->fail(SS_ERR_INVALID, "%s: %s = %d, k = %d, g = %d must be >= 1 and first = %d >= 0", entry, window, k_in, k, g, first);
-    if (k_in > SS_MAX_TOPK || k > SS_MAX_TOPK)
-        return ctx->fail(SS_ERR_UNSUPPORTED, "%s: %s = %d or k = %d exceeds SS_MAX_TOPK = %d", entry, window, k_in, k, SS_MAX_TOPK);
-    return SS_OK;
+    return hw::rows_out_finish(s, o, staged);
 }
 
 int32_t collapse_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t g, int32_t first,
@@ -249,39 +187,16 @@ int32_t collapse_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hit
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // ---- the checks: nothing is enqueued and no output is touched before the last of them has passed
-    SS_TRY(check_paging(ctx, "ss_collapse_hits", "k_in", n_q, k_in, g, first, k));
-    if (n_q > 0 && (!hits || !n_hits || !hits_out || !n_hits_out))
-        return ctx->fail(SS_ERR_INVALID, "ss_collapse_hits: hits, n_hits, hits_out or n_hits_out is NULL");
-    const size_t nq = (size_t)n_q, n_rows_in = nq * (size_t)k_in;
-    if (n_q > 0) {
-        const uintptr_t ib = (uintptr_t)hits, ie = ib + n_rows_in * sizeof(ss_hit);
-        const uintptr_t ob = (uintptr_t)hits_out, oe = ob + nq * (size_t)k * sizeof(ss_hit);
-        if (ib < oe && ob < ie) return ctx->fail(SS_ERR_INVALID, "ss_collapse_hits: hits_out overlaps hits");
-    }
+    SS_TRY(hw::check_paging(ctx, "ss_collapse_hits", "k_in", n_q, k_in, k, first, "g", g));
+    SS_TRY(hw::check_page_arrays(ctx, "ss_collapse_hits", n_q, k_in, k, hits, n_hits, hits_out, n_hits_out));
     if (!s->has_groups) return ctx->fail(SS_ERR_STATE, "ss_collapse_hits: no group table registered (ss_scorer_set_doc_groups)");
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits);
-    std::vector<int32_t> h_n;
-    if (!dev_n) {
-        h_n.assign(n_hits, n_hits + nq);
-        for (size_t q = 0; q < nq; q++)
-            if (h_n[q] < 0 || h_n[q] > k_in)
-                return ctx->fail(SS_ERR_INVALID, "ss_collapse_hits: n_hits[%zu] = %d outside 0 .. k_in = %d", q, h_n[q], k_in);
-    }
-    // (host rows and counts: the caller's array and h_n outlive their copies, a call with any host array waits before it returns)
-    if (!dev_h) {
-        SS_HIP(ctx, ensure(s->d_col_hits, n_rows_in));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_col_hits.p, hits, n_rows_in * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    }
-    if (!dev_n) {
-        SS_HIP(ctx, ensure(s->d_col_n, nq));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_col_n.p, h_n.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    const CollapseArgs a{n_q, k_in, g, first, k, dev_h ? hits : s->d_col_hits.p, dev_n ? n_hits : s->d_col_n.p,
-                         hits_out, n_hits_out, same_out, n_kept_out};
-    return collapse_run(s, a, nullptr, !dev_h || !dev_n);
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_collapse_hits", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
+    const CollapseArgs a{n_q, k_in, g, first, k, w.hits, w.n_hits, hits_out, n_hits_out, same_out, n_kept_out};
+    return collapse_run(s, a, nullptr, w.staged);
 }
 
 int32_t score_collapsed_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
@@ -290,7 +205,7 @@ int32_t score_collapsed_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, c
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // ---- the checks of this call; the scoring call below makes its own (mask ids, the prior, the queries) before it enqueues anything
-    SS_TRY(check_paging(ctx, "ss_score_topk_collapsed", "k_window", n_q, k_window, g, first, k));
+    SS_TRY(hw::check_paging(ctx, "ss_score_topk_collapsed", "k_window", n_q, k_window, k, first, "g", g));
     if (!q_ptr || (n_q > 0 && (!hits_out || !n_hits_out)))
         return ctx->fail(SS_ERR_INVALID, "ss_score_topk_collapsed: q_ptr, hits_out or n_hits_out is NULL");
     if (!s->has_groups) return ctx->fail(SS_ERR_STATE, "ss_score_topk_collapsed: no group table registered (ss_scorer_set_doc_groups)");
@@ -342,24 +257,16 @@ int32_t ss_scorer_set_doc_groups(ss_scorer* s, const uint32_t* group) {
 
 int32_t ss_collapse_hits(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t g, int32_t first,
                          int32_t k, ss_hit* hits_out, int32_t* n_hits_out, uint32_t* same_out, int32_t* n_kept_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return collapse_impl(s, n_q, k_in, hits, n_hits, g, first, k, hits_out, n_hits_out, same_out, n_kept_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_collapse_hits: host allocation failed");
-    }
+    return hw::guarded(s, "ss_collapse_hits", [&] { return collapse_impl(s, n_q, k_in, hits, n_hits, g, first, k, hits_out, n_hits_out, same_out, n_kept_out); });
 }
 
 int32_t ss_score_topk_collapsed(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
                                 const double* topic_probs, const int32_t* mask_id, int32_t k_window, int32_t g, int32_t first, int32_t k,
                                 ss_hit* hits_out, int32_t* n_hits_out, uint32_t* same_out, int32_t* n_kept_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
+    return hw::guarded(s, "ss_score_topk_collapsed", [&] {
         return score_collapsed_impl(s, n_q, q_ptr, q_terms, query_len, topic_probs, mask_id, k_window, g, first, k, hits_out, n_hits_out,
                                     same_out, n_kept_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_score_topk_collapsed: host allocation failed");
-    }
+    });
 }
 
 }  // extern "C"

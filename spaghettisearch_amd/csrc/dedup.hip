@@ -21,13 +21,14 @@
 //                              128 KB, L2-resident; a leader's row is one address for the whole wave) by both instances: 1024 rows of 32
 //                              slots do not fit a static LDS block.  Kept rows are numbered from the tiles' kept masks and copied
 //                              out as collapse.hip does, five lanes to a row.
-// Device hits / n_hits / outputs: the call only enqueues on the context's stream.  Otherwise the host arrays go through scorer-owned
-// grow-only device blocks and only the entries the definition names are copied back.
-#include "scorer.hpp"
+// The window in, the paging checks and the outputs' way back: hit_window.hpp.
+#include "hit_window.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 // ---------------------------------------------------------------- signatures
 constexpr uint32_t SG_GROUP = 8;                          // lanes of a sub-wave group
@@ -207,8 +208,6 @@ int32_t read_signatures(ss_index* idx, uint64_t n, const uint32_t* docs, uint32_
 constexpr uint32_t DD_NONE = 0xFFFFFFFFu;                 // s_doc of a row on its own (no doc id reaches it); s_lead of a row without a leader yet
 constexpr uint32_t DD_TILE = 64;                          // rows of a tile: one per lane of the resolving wave, one bit each of a 64-bit mask
 constexpr int DD_SLOT_WORDS = SS_MAX_SIG_SLOTS / 4;       // a signature as 16-byte words, at most
-constexpr uint32_t DD_ROW_WORDS = sizeof(ss_hit) / 8;     // a result row as 8-byte words
-static_assert(sizeof(ss_hit) == 40 && alignof(ss_hit) == 8, "a row is five 8-byte words");
 
 struct DedupParams {
     const uint32_t* sig;                                  // [n_docs][n_slots]
@@ -248,8 +247,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_hits(DedupParams p) {
     __shared__ uint64_t s_mask[WAVES][DD_TILE];           // per wave: its slice of every row's mask over the tile's own rows
     __shared__ uint32_t s_n_list;
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;   // <= k_in <= CAP: checked by the launcher
+    const uint32_t n = hw::window_len(p.n_hits[q], p.k_in);   // <= k_in <= CAP: checked by the launcher
     const ss_hit* const rows = p.hits + (size_t)q * p.k_in;
     const uint32_t nb = p.n_slots / 4;                    // <= DD_SLOT_WORDS: checked by the build
     const uint4* const sig4 = reinterpret_cast<const uint4*>(p.sig);
@@ -329,7 +327,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_hits(DedupParams p) {
     for (uint32_t j = tid; j < n; j += BLOCK) atomicAdd(&s_sim[s_lead[j]], 1u);
     uint32_t n_kept = 0;
     for (uint32_t t = 0; t < n_tiles; t++) n_kept += (uint32_t)__popcll(s_kept[t]);
-    const uint32_t n_out = n_kept > p.first ? (n_kept - p.first < p.k ? n_kept - p.first : p.k) : 0u;   // <= k, <= n
+    const uint32_t n_out = hw::page_len(n_kept, p.first, p.k);                   // <= k, <= n
     uint32_t* const s_src = s_list;                       // [n_out], n_out <= n <= CAP (the list was last read before the last barrier)
     for (uint32_t j = tid; j < n; j += BLOCK) {
         const uint32_t t = j / DD_TILE, l = j % DD_TILE;
@@ -340,13 +338,7 @@ __global__ __launch_bounds__(BLOCK) void k_dedup_hits(DedupParams p) {
         if (pos >= p.first && pos - p.first < n_out) s_src[pos - p.first] = j;
     }
     __syncthreads();
-    // ---- the rows, as 8-byte words: lane x moves word x % 5 of slot x / 5
-    const uint64_t* const in_w = reinterpret_cast<const uint64_t*>(rows);
-    uint64_t* const out_w = reinterpret_cast<uint64_t*>(p.hits_out + (size_t)q * p.k);
-    for (uint32_t x = tid; x < n_out * DD_ROW_WORDS; x += BLOCK) {
-        const uint32_t r = x / DD_ROW_WORDS, w = x - r * DD_ROW_WORDS;
-        out_w[x] = in_w[(size_t)s_src[r] * DD_ROW_WORDS + w];
-    }
+    hw::copy_page<BLOCK>(rows, p.hits_out + (size_t)q * p.k, n_out, [&](uint32_t r) { return s_src[r]; });
     if (p.sim_out)
         for (uint32_t r = tid; r < n_out; r += BLOCK) p.sim_out[(size_t)q * p.k + r] = s_sim[s_src[r]];
     if (tid == 0) {
@@ -364,19 +356,8 @@ int32_t dedup_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, 
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // ---- the checks: nothing is enqueued and no output is touched before the last of them has passed
-    if (n_q < 0) return ctx->fail(SS_ERR_INVALID, "ss_dedup_hits: n_q < 0");
-    if (k_in < 1 || k < 1 || min_match < 1 || first < 0)
-        return ctx->fail(SS_ERR_INVALID, "ss_dedup_hits: k_in = %d, k = %d, min_match = %d must be >= 1 and first = %d >= 0", k_in, k, min_match, first);
-    if (k_in > SS_MAX_TOPK || k > SS_MAX_TOPK)
-        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_dedup_hits: k_in = %d or k = %d exceeds SS_MAX_TOPK = %d", k_in, k, SS_MAX_TOPK);
-    if (n_q > 0 && (!hits || !n_hits || !hits_out || !n_hits_out))
-        return ctx->fail(SS_ERR_INVALID, "ss_dedup_hits: hits, n_hits, hits_out or n_hits_out is NULL");
-    const size_t nq = (size_t)n_q, n_rows_in = nq * (size_t)k_in, n_rows = nq * (size_t)k;
-    if (n_q > 0) {
-        const uintptr_t ib = (uintptr_t)hits, ie = ib + n_rows_in * sizeof(ss_hit);
-        const uintptr_t ob = (uintptr_t)hits_out, oe = ob + n_rows * sizeof(ss_hit);
-        if (ib < oe && ob < ie) return ctx->fail(SS_ERR_INVALID, "ss_dedup_hits: hits_out overlaps hits");
-    }
+    SS_TRY(hw::check_paging(ctx, "ss_dedup_hits", "k_in", n_q, k_in, k, first, "min_match", min_match));
+    SS_TRY(hw::check_page_arrays(ctx, "ss_dedup_hits", n_q, k_in, k, hits, n_hits, hits_out, n_hits_out));
     const ss_index* const body = s->body;
     if (!body->has_signatures) return ctx->fail(SS_ERR_STATE, "ss_dedup_hits: the body table has no signatures (ss_index_build_signatures)");
     if (min_match > body->sig_slots)
@@ -384,76 +365,28 @@ int32_t dedup_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, 
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const bool dev_i = ss::on_device(hits), dev_in = ss::on_device(n_hits);
-    std::vector<int32_t> h_n;
-    if (!dev_in) {
-        h_n.assign(n_hits, n_hits + nq);
-        for (size_t q = 0; q < nq; q++)
-            if (h_n[q] < 0 || h_n[q] > k_in)
-                return ctx->fail(SS_ERR_INVALID, "ss_dedup_hits: n_hits[%zu] = %d outside 0 .. k_in = %d", q, h_n[q], k_in);
-    }
-    // (host rows and counts: the caller's array and h_n outlive their copies, a call with any host array waits before it returns)
-    if (!dev_i) {
-        SS_HIP(ctx, ensure(s->d_dd_hits, n_rows_in));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_dd_hits.p, hits, n_rows_in * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    }
-    if (!dev_in) {
-        SS_HIP(ctx, ensure(s->d_dd_n, nq));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_dd_n.p, h_n.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    const bool dev_h = ss::on_device(hits_out), dev_n = ss::on_device(n_hits_out);
-    const bool dev_s = similar_out && ss::on_device(similar_out), dev_k = n_kept_out && ss::on_device(n_kept_out);
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_dd_out, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_dd_nout, nq));
-    if (similar_out && !dev_s) SS_HIP(ctx, ensure(s->d_dd_sim, n_rows));
-    if (n_kept_out && !dev_k) SS_HIP(ctx, ensure(s->d_dd_kept, nq));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_dedup_hits", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
+    hw::RowsOut o;
+    SS_TRY(hw::rows_out_prepare(s, (size_t)n_q, (size_t)k, hits_out, n_hits_out, n_kept_out, similar_out, sizeof(uint32_t), &o));
     DedupParams p{};
     p.sig = body->sig.p;
     p.n_docs = body->n_docs;
     p.n_slots = (uint32_t)body->sig_slots;
-    p.hits = dev_i ? hits : s->d_dd_hits.p;
-    p.n_hits = dev_in ? n_hits : s->d_dd_n.p;
-    p.hits_out = dev_h ? hits_out : s->d_dd_out.p;
-    p.n_hits_out = dev_n ? n_hits_out : s->d_dd_nout.p;
-    p.sim_out = !similar_out ? nullptr : dev_s ? similar_out : s->d_dd_sim.p;
-    p.n_kept_out = !n_kept_out ? nullptr : dev_k ? n_kept_out : s->d_dd_kept.p;
+    p.hits = w.hits;
+    p.n_hits = w.n_hits;
+    p.hits_out = o.hits;
+    p.n_hits_out = o.n_hits;
+    p.sim_out = static_cast<uint32_t*>(o.extra);
+    p.n_kept_out = o.n_kept;
     p.k_in = (uint32_t)k_in; p.min_match = (uint32_t)min_match; p.first = (uint32_t)first; p.k = (uint32_t)k;
     if (k_in <= DD_SMALL * DD_SMALL_PER)
         hipLaunchKernelGGL((k_dedup_hits<DD_SMALL, DD_SMALL_PER>), dim3((unsigned)n_q), dim3(DD_SMALL), 0, st, p);
     else
         hipLaunchKernelGGL((k_dedup_hits<DD_LARGE, DD_LARGE_PER>), dim3((unsigned)n_q), dim3(DD_LARGE), 0, st, p);
     SS_HIP(ctx, hipGetLastError());
-    const bool all_dev = dev_h && dev_n && (!similar_out || dev_s) && (!n_kept_out || dev_k);
-    if (all_dev) {
-        if (!dev_i || !dev_in) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;                                     // ordered on the ctx stream; nothing comes back
-    }
-    // ---- host outputs: the counts whole, of the rows exactly the entries the kernel wrote
-    std::vector<int32_t> h_nout(nq), h_kept;
-    std::vector<ss_hit> h_rows;
-    std::vector<uint32_t> h_sim;
-    SS_HIP(ctx, hipMemcpyAsync(h_nout.data(), p.n_hits_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (n_kept_out && !dev_k) {
-        h_kept.resize(nq);
-        SS_HIP(ctx, hipMemcpyAsync(h_kept.data(), p.n_kept_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (!dev_h) {
-        h_rows.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_rows.data(), p.hits_out, n_rows * sizeof(ss_hit), hipMemcpyDeviceToHost, st));
-    }
-    if (similar_out && !dev_s) {
-        h_sim.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_sim.data(), p.sim_out, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (!dev_n) std::memcpy(n_hits_out, h_nout.data(), nq * sizeof(int32_t));
-    if (n_kept_out && !dev_k) std::memcpy(n_kept_out, h_kept.data(), nq * sizeof(int32_t));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)h_nout[q], o = q * (size_t)k;
-        if (!dev_h) std::memcpy(hits_out + o, h_rows.data() + o, cnt * sizeof(ss_hit));
-        if (similar_out && !dev_s) std::memcpy(similar_out + o, h_sim.data() + o, cnt * sizeof(uint32_t));
-    }
-    return SS_OK;
+    return hw::rows_out_finish(s, o, w.staged);
 }
 
 }  // namespace
@@ -488,21 +421,12 @@ int32_t ss_index_read_signatures(ss_index* idx, uint64_t n, const uint32_t* docs
     if (!idx->has_signatures) return ctx->fail(SS_ERR_STATE, "ss_index_read_signatures: the table has no signatures (ss_index_build_signatures)");
     if (n && (!docs || !sig_out)) return ctx->fail(SS_ERR_INVALID, "ss_index_read_signatures: NULL argument");
     SS_HIP(ctx, hipSetDevice(ctx->device));
-    try {
-        return read_signatures(idx, n, docs, sig_out, n_slots_out);
-    } catch (const std::bad_alloc&) {
-        return ctx->fail(SS_ERR_OOM, "ss_index_read_signatures: host allocation failed");
-    }
+    return hw::guarded(ctx, "ss_index_read_signatures", [&] { return read_signatures(idx, n, docs, sig_out, n_slots_out); });
 }
 
 int32_t ss_dedup_hits(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t min_match, int32_t first,
                       int32_t k, ss_hit* hits_out, int32_t* n_hits_out, uint32_t* similar_out, int32_t* n_kept_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return dedup_impl(s, n_q, k_in, hits, n_hits, min_match, first, k, hits_out, n_hits_out, similar_out, n_kept_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_dedup_hits: host allocation failed");
-    }
+    return hw::guarded(s, "ss_dedup_hits", [&] { return dedup_impl(s, n_q, k_in, hits, n_hits, min_match, first, k, hits_out, n_hits_out, similar_out, n_kept_out); });
 }
 
 }  // extern "C"

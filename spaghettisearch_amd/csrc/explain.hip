@@ -4,8 +4,7 @@
 // kernel edited.
 //
 //   checks                     arguments, q_ptr, t_stride, host n_hits — all before anything is enqueued
-//   the queries' table         ptr [n_q + 1] | tokens, through a pinned block of one of TURNS explain turns (rewritten only after the
-//                              wait for that turn's event, recorded behind the kernel that read its device copy)
+//   the queries' table         ptr [n_q + 1] | tokens, through one of the TURNS explain turns (hit_window.hpp: query_table_fill)
 //   k_explain_hits             one lane per entry (query q, hit j, token i).  Inside a query the lanes run over j fastest, so the 64
 //                              lanes of a wave search the SAME two lists (one token, title and body) for 64 docs: the probes of the
 //                              upper levels fall into shared cache lines and every lane runs the same number of steps.  A lane runs its
@@ -13,13 +12,14 @@
 //                              weights.  Position lists of up to EX_OWN values are read by their own lane; longer ones are taken one
 //                              at a time by the whole wave, 64 values per step, and reduced with shuffles.  Every entry is written by
 //                              exactly one lane; nothing else is written.
-// Device hits / n_hits / out: the call only enqueues on the context's stream.  Otherwise the host arrays go through scorer-owned
-// grow-only device blocks and only the entries the definition names are copied back.
-#include "scorer.hpp"
+// The window in and the way back of a host `out`: hit_window.hpp.
+#include "hit_window.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 constexpr int EX_TPB = 256;
 constexpr uint32_t EX_OWN = 16;                           // position lists up to this length are read by their own lane
@@ -48,8 +48,7 @@ __device__ __forceinline__ uint32_t pos_key(float v) {
 __global__ __launch_bounds__(EX_TPB) void k_explain_hits(ExplainParams p) {
     const uint32_t q = blockIdx.x / p.blocks_per_q;
     const uint32_t e = (blockIdx.x - q * p.blocks_per_q) * EX_TPB + threadIdx.x;   // the entry inside the query: token-major, hit fastest
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n_hits = nr < 0 ? 0u : (uint32_t)nr > p.k ? p.k : (uint32_t)nr;
+    const uint32_t n_hits = hw::window_len(p.n_hits[q], p.k);
     const uint32_t q0 = p.q_ptr[q];
     uint32_t n_tok = p.q_ptr[q + 1] - q0;
     n_tok = n_tok > p.t_stride ? p.t_stride : n_tok;      // (the host has refused longer queries; the table is the call's own)
@@ -146,32 +145,17 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
             return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: query %zu has %u tokens, t_stride = %d", q, h_ptr[q + 1] - h_ptr[q], t_stride);
     const size_t tok0 = h_ptr[0], n_tok = h_ptr[nq] - tok0;
     if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: q_terms is NULL");
-    const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits), dev_o = ss::on_device(out);
-    std::vector<int32_t> h_n;
-    if (!dev_n) {
-        h_n.assign(n_hits, n_hits + nq);
-        for (size_t q = 0; q < nq; q++)
-            if (h_n[q] < 0 || h_n[q] > k) return ctx->fail(SS_ERR_INVALID, "ss_explain_hits: n_hits[%zu] = %d outside 0 .. k = %d", q, h_n[q], k);
-    }
-    // ---- the queries' table in the pinned block of the next explain turn: ptr [n_q + 1] (from 0) | tokens
-    ExplainTurn& turn = s->exp[s->exp_turn];
-    SS_HIP(ctx, turn.ev.wait());                          // the call TURNS calls ago has read this turn's blocks
-    const size_t q_words = nq + 1 + n_tok;
-    SS_HIP(ctx, turn.h_q.ensure(q_words * sizeof(uint32_t)));
-    uint32_t* const hq = turn.h_q.as<uint32_t>();
-    for (size_t q = 0; q <= nq; q++) hq[q] = h_ptr[q] - (uint32_t)tok0;
-    SS_HIP(ctx, ss::copy_in(st, hq + nq + 1, q_terms ? q_terms + tok0 : nullptr, n_tok * sizeof(uint32_t)));
-    SS_HIP(ctx, ensure(turn.d_q, q_words));
-    const size_t n_rows = nq * (size_t)k, n_ent = n_rows * (size_t)t_stride;
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_exp_hits, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_exp_n, nq));
-    if (!dev_o) SS_HIP(ctx, ensure(s->d_exp_out, n_ent));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_explain_hits", "k", n_q, k, hits, n_hits, &w));
+    // ---- the queries' table in the pinned block of the next explain turn, the blocks of host arrays; then the pipeline
+    QueryTurn& turn = s->exp[s->exp_turn];
+    hw::QueryTable tab;
+    SS_TRY(hw::query_table_fill(ctx, turn, h_ptr, q_terms, 1, &tab));
+    hw::EntriesOut o;
+    SS_TRY(hw::entries_out_prepare(s, out, nq * (size_t)k * (size_t)t_stride * sizeof(ss_term_match), &o));
+    SS_TRY(hw::window_stage(s, &w));
     s->exp_turn = (s->exp_turn + 1) % ss_scorer::TURNS;
-    // ---- the pipeline
-    SS_HIP(ctx, hipMemcpyAsync(turn.d_q.p, hq, q_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    // (host rows and counts: the caller's array and h_n outlive their copies, a call with any host array waits before it returns)
-    if (!dev_h) SS_HIP(ctx, hipMemcpyAsync(s->d_exp_hits.p, hits, n_rows * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    if (!dev_n) SS_HIP(ctx, hipMemcpyAsync(s->d_exp_n.p, h_n.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SS_HIP(ctx, hw::query_table_upload(ctx, turn, tab));
     ExplainParams p{};
     p.t_ptr = s->title->term_ptr.p; p.t_doc = s->title->post_doc.p; p.t_w = s->title->post_w.p; p.t_terms = s->title->n_terms;
     p.b_ptr = s->body->term_ptr.p; p.b_doc = s->body->post_doc.p; p.b_w = s->body->post_w.p; p.b_terms = s->body->n_terms;
@@ -180,36 +164,16 @@ int32_t explain_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uin
     p.n_docs = s->n_docs;
     p.q_ptr = turn.d_q.p;
     p.q_terms = turn.d_q.p + nq + 1;
-    p.hits = dev_h ? hits : s->d_exp_hits.p;
-    p.n_hits = dev_n ? n_hits : s->d_exp_n.p;
-    p.out = dev_o ? out : s->d_exp_out.p;
+    p.hits = w.hits;
+    p.n_hits = w.n_hits;
+    p.out = static_cast<ss_term_match*>(o.dev);
     p.n_q = (uint32_t)n_q; p.k = (uint32_t)k; p.t_stride = (uint32_t)t_stride;
     p.blocks_per_q = ss::div_up((uint64_t)k * (uint64_t)t_stride, EX_TPB);
     hipLaunchKernelGGL(k_explain_hits, dim3(p.n_q * p.blocks_per_q), dim3(EX_TPB), 0, st, p);   // (< 2^31 / 256 * 2 blocks)
     SS_HIP(ctx, hipGetLastError());
     SS_HIP(ctx, turn.ev.record(st));                      // the turn's pinned block and its device copy are read until here
-    if (dev_h && dev_n && dev_o) return SS_OK;            // ordered on the ctx stream; nothing comes back, nothing is waited for
-    // ---- staged: wait; a host `out` gets exactly the entries the kernel wrote.  (Device n_hits with a host out: the counts come back
-    // too, clamped as the kernel clamps them.)
-    if (!dev_o) {
-        std::vector<ss_term_match> h_out(n_ent);
-        if (dev_n) {
-            h_n.resize(nq);
-            SS_HIP(ctx, hipMemcpyAsync(h_n.data(), n_hits, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        SS_HIP(ctx, hipMemcpyAsync(h_out.data(), s->d_exp_out.p, n_ent * sizeof(ss_term_match), hipMemcpyDeviceToHost, st));
-        SS_HIP(ctx, hipStreamSynchronize(st));
-        for (size_t q = 0; q < nq; q++) {
-            const size_t nt = hq[q + 1] - hq[q], nh = (size_t)std::min(std::max(h_n[q], 0), k);
-            for (size_t j = 0; j < nh && nt; j++) {
-                const size_t o = (q * (size_t)k + j) * (size_t)t_stride;
-                std::memcpy(out + o, h_out.data() + o, nt * sizeof(ss_term_match));
-            }
-        }
-    } else {
-        SS_HIP(ctx, hipStreamSynchronize(st));
-    }
-    return SS_OK;
+    // every array in device memory: nothing is waited for.  A host `out`: of every row the query's own tokens, the table's ptr
+    return hw::entries_out_finish(s, o, w, sizeof(ss_term_match), (size_t)t_stride, tab.h);
 }
 
 }  // namespace
@@ -218,12 +182,7 @@ extern "C" {
 
 int32_t ss_explain_hits(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, int32_t k, const ss_hit* hits,
                         const int32_t* n_hits, int32_t t_stride, ss_term_match* out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return explain_impl(s, n_q, q_ptr, q_terms, k, hits, n_hits, t_stride, out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_explain_hits: host allocation failed");
-    }
+    return hw::guarded(s, "ss_explain_hits", [&] { return explain_impl(s, n_q, q_ptr, q_terms, k, hits, n_hits, t_stride, out); });
 }
 
 }  // extern "C"

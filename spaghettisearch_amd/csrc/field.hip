@@ -15,13 +15,14 @@
 //                          the value with its sign bit flipped (complemented for descending).  The window index makes the order total,
 //                          so the bitonic network gives the stable result.  The page's rows are copied five lanes to a row.
 //   k_hit_fields           a gather: one thread per (row, field).
-// Device arrays throughout: ss_sort_hits_by_field / ss_hit_fields only enqueue on the context's stream.  Otherwise host arrays go through
-// scorer-owned grow-only device blocks and only the entries the definition names are copied back.
-#include "scorer.hpp"
+// ss_sort_hits_by_field / ss_hit_fields: the window in, the paging checks and the outputs' way back are hit_window.hpp's.
+#include "hit_window.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 constexpr int FM_TPB = 512;                               // threads: 8 waves
 constexpr int FM_STEPS = 16;                              // steps of 64 docs a wave holds in registers (2 VGPRs per step and field)
@@ -112,8 +113,6 @@ __global__ __launch_bounds__(FM_TPB) void k_field_masks(FieldParams p, uint32_t 
 // ---- sort a window by a field ------------------------------------------------------------------------------------------------
 constexpr uint32_t SF_CLASS_SHIFT = 16;                   // tag = class << 16 | window index (< SS_MAX_TOPK = 2^10)
 constexpr uint32_t SF_OUTSIDE = 1, SF_DEAD = 2;
-constexpr uint32_t SF_ROW_WORDS = sizeof(ss_hit) / 8;
-static_assert(sizeof(ss_hit) == 40 && alignof(ss_hit) == 8, "a row is five 8-byte words");
 
 struct SortFieldParams {
     const int64_t* column;                                // [n_docs] the field's values
@@ -138,11 +137,9 @@ __global__ __launch_bounds__(BLOCK) void k_sort_hits_by_field(SortFieldParams p)
     __shared__ uint64_t s_key[CAP];
     __shared__ uint32_t s_tag[CAP];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;   // <= k_in <= CAP: checked by the launcher
+    const uint32_t n = hw::window_len(p.n_hits[q], p.k_in);   // <= k_in <= CAP: checked by the launcher
     const ss_hit* const rows = p.hits + (size_t)q * p.k_in;
-    uint32_t np = 1;
-    while (np < n) np <<= 1;
+    const uint32_t np = hw::pow2_at_least(n);
     const uint64_t flip = p.descending ? ~0ull : 0ull;
     for (uint32_t j = tid; j < np; j += BLOCK) {
         uint64_t key = 0;
@@ -159,31 +156,17 @@ __global__ __launch_bounds__(BLOCK) void k_sort_hits_by_field(SortFieldParams p)
         s_tag[j] = tag;
     }
     __syncthreads();
-    for (uint32_t k2 = 2; k2 <= np; k2 <<= 1) {
-        for (uint32_t j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (uint32_t i = tid; i < np; i += BLOCK) {
-                const uint32_t o = i ^ j2;
-                if (o > i) {
-                    const uint64_t ka = s_key[i], kb = s_key[o];
-                    const uint32_t ta = s_tag[i], tb = s_tag[o];
-                    if (sf_after(ka, ta, kb, tb) == ((i & k2) == 0)) {
-                        s_key[i] = kb; s_tag[i] = tb;
-                        s_key[o] = ka; s_tag[o] = ta;
-                    }
-                }
-            }
-            __syncthreads();
+    hw::bitonic_sort<BLOCK>(np, [&](uint32_t i, uint32_t o, bool up) {
+        const uint64_t ka = s_key[i], kb = s_key[o];
+        const uint32_t ta = s_tag[i], tb = s_tag[o];
+        if (sf_after(ka, ta, kb, tb) == up) {
+            s_key[i] = kb; s_tag[i] = tb;
+            s_key[o] = ka; s_tag[o] = ta;
         }
-    }
+    });
     // ---- the page: sorted positions [first, first + n_out), all below n
-    const uint32_t n_out = n > p.first ? (n - p.first < p.k ? n - p.first : p.k) : 0u;
-    const uint64_t* const in_w = reinterpret_cast<const uint64_t*>(rows);
-    uint64_t* const out_w = reinterpret_cast<uint64_t*>(p.hits_out + (size_t)q * p.k);
-    for (uint32_t x = tid; x < n_out * SF_ROW_WORDS; x += BLOCK) {
-        const uint32_t r = x / SF_ROW_WORDS, w = x - r * SF_ROW_WORDS;
-        const uint32_t j = s_tag[p.first + r] & ((1u << SF_CLASS_SHIFT) - 1u);
-        out_w[x] = in_w[(size_t)j * SF_ROW_WORDS + w];
-    }
+    const uint32_t n_out = hw::page_len(n, p.first, p.k);
+    hw::copy_page<BLOCK>(rows, p.hits_out + (size_t)q * p.k, n_out, [&](uint32_t r) { return s_tag[p.first + r] & ((1u << SF_CLASS_SHIFT) - 1u); });
     if (p.values_out)
         for (uint32_t r = tid; r < n_out; r += BLOCK) {
             const uint32_t tag = s_tag[p.first + r];
@@ -212,9 +195,7 @@ __global__ __launch_bounds__(256) void k_hit_fields(HitFieldParams p) {
     const uint32_t f = (uint32_t)(x - row * p.n_fields);
     const uint64_t q = row / p.k_in;
     const uint32_t j = (uint32_t)(row - q * p.k_in);
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;
-    if (j >= n) return;
+    if (j >= hw::window_len(p.n_hits[q], p.k_in)) return;
     const uint32_t d = p.hits[row].doc;
     p.out[x] = (uint64_t)d < p.n_docs ? p.values[(uint64_t)f * p.n_docs + d] : SS_NO_FIELD_VALUE;
 }
@@ -301,102 +282,39 @@ int32_t field_masks_impl(ss_scorer* s, int32_t n_sets, const uint32_t* rng_ptr, 
     return SS_OK;
 }
 
-// the checks ss_sort_hits_by_field and ss_hit_fields share, then the window's arrays on the device: SS_OK = go on
-struct WindowArgs { const ss_hit* hits; const int32_t* n_hits; bool staged; };
-int32_t window_to_device(ss_scorer* s, const char* entry, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, WindowArgs* w) {
-    ss_ctx* ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    const size_t nq = (size_t)n_q, n_rows_in = nq * (size_t)k_in;
-    const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits);
-    if (!dev_n) {
-        for (size_t q = 0; q < nq; q++)
-            if (n_hits[q] < 0 || n_hits[q] > k_in)
-                return ctx->fail(SS_ERR_INVALID, "%s: n_hits[%zu] = %d outside 0 .. k_in = %d", entry, q, n_hits[q], k_in);
-    }
-    // (host rows and counts: the caller's arrays outlive their copies, a call with any host array waits before it returns)
-    if (!dev_h) {
-        SS_HIP(ctx, ensure(s->d_fld_hits, n_rows_in));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_fld_hits.p, hits, n_rows_in * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    }
-    if (!dev_n) {
-        SS_HIP(ctx, ensure(s->d_fld_n, nq));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_fld_n.p, n_hits, nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    w->hits = dev_h ? hits : s->d_fld_hits.p;
-    w->n_hits = dev_n ? n_hits : s->d_fld_n.p;
-    w->staged = !dev_h || !dev_n;
-    return SS_OK;
-}
-
 int32_t sort_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t field, int32_t descending,
                   int32_t first, int32_t k, ss_hit* hits_out, int32_t* n_hits_out, int64_t* values_out) {
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // ---- the checks: nothing is enqueued and no output is touched before the last of them has passed
-    if (n_q < 0) return ctx->fail(SS_ERR_INVALID, "ss_sort_hits_by_field: n_q < 0");
-    if (k_in < 1 || k < 1 || first < 0)
-        return ctx->fail(SS_ERR_INVALID, "ss_sort_hits_by_field: k_in = %d, k = %d must be >= 1 and first = %d >= 0", k_in, k, first);
-    if (k_in > SS_MAX_TOPK || k > SS_MAX_TOPK)
-        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_sort_hits_by_field: k_in = %d or k = %d exceeds SS_MAX_TOPK = %d", k_in, k, SS_MAX_TOPK);
-    if (n_q > 0 && (!hits || !n_hits || !hits_out || !n_hits_out))
-        return ctx->fail(SS_ERR_INVALID, "ss_sort_hits_by_field: hits, n_hits, hits_out or n_hits_out is NULL");
-    const size_t nq = (size_t)n_q, n_rows = nq * (size_t)k;
-    if (n_q > 0) {
-        const uintptr_t ib = (uintptr_t)hits, ie = ib + nq * (size_t)k_in * sizeof(ss_hit);
-        const uintptr_t ob = (uintptr_t)hits_out, oe = ob + n_rows * sizeof(ss_hit);
-        if (ib < oe && ob < ie) return ctx->fail(SS_ERR_INVALID, "ss_sort_hits_by_field: hits_out overlaps hits");
-    }
+    SS_TRY(hw::check_paging(ctx, "ss_sort_hits_by_field", "k_in", n_q, k_in, k, first));
+    SS_TRY(hw::check_page_arrays(ctx, "ss_sort_hits_by_field", n_q, k_in, k, hits, n_hits, hits_out, n_hits_out));
     if (s->n_fields == 0) return ctx->fail(SS_ERR_STATE, "ss_sort_hits_by_field: no field table registered (ss_scorer_set_doc_fields)");
     if (field < 0 || field >= s->n_fields)
         return ctx->fail(SS_ERR_INVALID, "ss_sort_hits_by_field: field %d (the scorer has %d fields)", field, s->n_fields);
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    WindowArgs w{};
-    SS_TRY(window_to_device(s, "ss_sort_hits_by_field", n_q, k_in, hits, n_hits, &w));
-    const bool dev_h = ss::on_device(hits_out), dev_n = ss::on_device(n_hits_out), dev_v = values_out && ss::on_device(values_out);
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_fld_out, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_fld_nout, nq));
-    if (values_out && !dev_v) SS_HIP(ctx, ensure(s->d_fld_vals, n_rows));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_sort_hits_by_field", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
+    hw::RowsOut o;
+    SS_TRY(hw::rows_out_prepare(s, (size_t)n_q, (size_t)k, hits_out, n_hits_out, nullptr, values_out, sizeof(int64_t), &o));
     SortFieldParams p{};
     p.column = s->fields.p + (size_t)field * (size_t)s->n_docs;
     p.n_docs = s->n_docs;
     p.hits = w.hits;
     p.n_hits = w.n_hits;
-    p.hits_out = dev_h ? hits_out : s->d_fld_out.p;
-    p.n_hits_out = dev_n ? n_hits_out : s->d_fld_nout.p;
-    p.values_out = !values_out ? nullptr : dev_v ? values_out : s->d_fld_vals.p;
+    p.hits_out = o.hits;
+    p.n_hits_out = o.n_hits;
+    p.values_out = static_cast<int64_t*>(o.extra);
     p.k_in = (uint32_t)k_in; p.first = (uint32_t)first; p.k = (uint32_t)k; p.descending = descending != 0;
     if (k_in <= SF_SMALL * SF_SMALL_PER)
         hipLaunchKernelGGL((k_sort_hits_by_field<SF_SMALL, SF_SMALL_PER>), dim3((unsigned)n_q), dim3(SF_SMALL), 0, st, p);
     else
         hipLaunchKernelGGL((k_sort_hits_by_field<SF_LARGE, SF_LARGE_PER>), dim3((unsigned)n_q), dim3(SF_LARGE), 0, st, p);
     SS_HIP(ctx, hipGetLastError());
-    if (dev_h && dev_n && (!values_out || dev_v)) {
-        if (w.staged) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;                                     // ordered on the ctx stream; nothing comes back
-    }
-    // ---- host outputs: the counts whole, of the rows exactly the entries the kernel wrote
-    std::vector<int32_t> h_n(nq);
-    std::vector<ss_hit> h_rows;
-    std::vector<int64_t> h_vals;
-    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), p.n_hits_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (!dev_h) {
-        h_rows.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_rows.data(), p.hits_out, n_rows * sizeof(ss_hit), hipMemcpyDeviceToHost, st));
-    }
-    if (values_out && !dev_v) {
-        h_vals.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_vals.data(), p.values_out, n_rows * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    }
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (!dev_n) std::memcpy(n_hits_out, h_n.data(), nq * sizeof(int32_t));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)h_n[q], o = q * (size_t)k;
-        if (!dev_h) std::memcpy(hits_out + o, h_rows.data() + o, cnt * sizeof(ss_hit));
-        if (values_out && !dev_v) std::memcpy(values_out + o, h_vals.data() + o, cnt * sizeof(int64_t));
-    }
-    return SS_OK;
+    return hw::rows_out_finish(s, o, w.staged);
 }
 
 int32_t hit_fields_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int64_t* values_out) {
@@ -410,37 +328,24 @@ int32_t hit_fields_impl(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* h
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    WindowArgs w{};
-    SS_TRY(window_to_device(s, "ss_hit_fields", n_q, k_in, hits, n_hits, &w));
-    const size_t nq = (size_t)n_q, nf = (size_t)s->n_fields, total = nq * (size_t)k_in * nf;
-    const bool dev_v = ss::on_device(values_out);
-    if (!dev_v) SS_HIP(ctx, ensure(s->d_fld_vals, total));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_hit_fields", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
+    const size_t nf = (size_t)s->n_fields, total = (size_t)n_q * (size_t)k_in * nf;
+    hw::EntriesOut o;
+    SS_TRY(hw::entries_out_prepare(s, values_out, total * sizeof(int64_t), &o));
     HitFieldParams p{};
     p.values = s->fields.p;
     p.n_docs = s->n_docs;
     p.hits = w.hits;
     p.n_hits = w.n_hits;
-    p.out = dev_v ? values_out : s->d_fld_vals.p;
+    p.out = static_cast<int64_t*>(o.dev);
     p.k_in = (uint32_t)k_in;
     p.n_fields = (uint32_t)nf;
     p.total = total;
     hipLaunchKernelGGL(k_hit_fields, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
     SS_HIP(ctx, hipGetLastError());
-    if (dev_v) {
-        if (w.staged) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;
-    }
-    // ---- a host output: of the rows exactly the entries the kernel wrote (the counts: the caller's when they are host memory)
-    std::vector<int64_t> h_vals(total);
-    std::vector<int32_t> h_n(nq);
-    SS_HIP(ctx, hipMemcpyAsync(h_vals.data(), p.out, total * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), w.n_hits, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)std::min<int32_t>(std::max<int32_t>(h_n[q], 0), k_in), o = q * (size_t)k_in * nf;
-        std::memcpy(values_out + o, h_vals.data() + o, cnt * nf * sizeof(int64_t));
-    }
-    return SS_OK;
+    return hw::entries_out_finish(s, o, w, sizeof(int64_t), nf);
 }
 
 }  // namespace
@@ -499,31 +404,16 @@ int32_t ss_scorer_set_doc_fields(ss_scorer* s, int32_t n_fields, const int64_t* 
 
 int32_t ss_doc_field_masks(ss_scorer* s, int32_t n_sets, const uint32_t* rng_ptr, const ss_doc_range* rng, const int32_t* mask_id,
                            uint32_t* words_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return field_masks_impl(s, n_sets, rng_ptr, rng, mask_id, words_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_doc_field_masks: host allocation failed");
-    }
+    return hw::guarded(s, "ss_doc_field_masks", [&] { return field_masks_impl(s, n_sets, rng_ptr, rng, mask_id, words_out); });
 }
 
 int32_t ss_sort_hits_by_field(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t field,
                               int32_t descending, int32_t first, int32_t k, ss_hit* hits_out, int32_t* n_hits_out, int64_t* values_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return sort_impl(s, n_q, k_in, hits, n_hits, field, descending, first, k, hits_out, n_hits_out, values_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_sort_hits_by_field: host allocation failed");
-    }
+    return hw::guarded(s, "ss_sort_hits_by_field", [&] { return sort_impl(s, n_q, k_in, hits, n_hits, field, descending, first, k, hits_out, n_hits_out, values_out); });
 }
 
 int32_t ss_hit_fields(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int64_t* values_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return hit_fields_impl(s, n_q, k_in, hits, n_hits, values_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_hit_fields: host allocation failed");
-    }
+    return hw::guarded(s, "ss_hit_fields", [&] { return hit_fields_impl(s, n_q, k_in, hits, n_hits, values_out); });
 }
 
 }  // extern "C"

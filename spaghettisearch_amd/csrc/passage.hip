@@ -3,10 +3,9 @@
 // kernel edited.
 //
 //   checks                     arguments, q_ptr, host n_hits — all before anything is enqueued
-//   the queries' table         ptr [n_q + 1] | tokens | first, through a pinned block of one of TURNS passage turns (rewritten only after
-//                              the wait for that turn's event, recorded behind the kernel that read its device copy).  first[i] = the
-//                              first token index of the query with token i's term: the device never de-duplicates, a term's SLOT is
-//                              that index.
+//   the queries' table         ptr [n_q + 1] | tokens | first, through one of the TURNS passage turns (hit_window.hpp:
+//                              query_table_fill).  first[i] = the first token index of the query with token i's term: the device
+//                              never de-duplicates, a term's SLOT is that index.
 //   k_best_passages            one wave (a workgroup of 64) per (query, hit).  Lane i < n_tok owns token i; the lanes with
 //                              first == i search the body list of their term for the doc (the plain lower bound of k_explain_hits)
 //                              and take the posting's position list.  N = the lists' lengths together.
@@ -20,13 +19,14 @@
 //                              of times.
 //                              The lanes' best windows (most slots, then most occurrences, then the smallest key) are reduced
 //                              with shuffles; the token mask is one ballot over the tokens' slots; lanes 0 .. 5 store one dword each.
-// Device hits / n_hits / out: the call only enqueues on the context's stream.  Otherwise the host arrays go through scorer-owned
-// grow-only device blocks and only the entries the definition names are copied back.
-#include "scorer.hpp"
+// The window in and the way back of a host `out`: hit_window.hpp.
+#include "hit_window.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 constexpr int PS_TPB = 64;                                // one wave
 constexpr uint32_t PS_NONE = 0xFFFFFFFFu;                 // position key of "no value >= 0" (keys are bits of non-NaN floats >= 0)
@@ -68,9 +68,7 @@ __global__ __launch_bounds__(PS_TPB) void k_best_passages(PassageParams p) {
     uint64_t* const s_pe = ps_lds + 64;
     uint64_t* const ev = ps_lds + 128;                    // [pow2 >= cap] events
     const uint32_t q = blockIdx.x / p.k, j = blockIdx.x - q * p.k;
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n_hits = nr < 0 ? 0u : (uint32_t)nr > p.k ? p.k : (uint32_t)nr;
-    if (j >= n_hits) return;                              // (the whole wave)
+    if (j >= hw::window_len(p.n_hits[q], p.k)) return;    // (the whole wave)
     const uint32_t lane = threadIdx.x;
     const uint32_t q0 = p.q_ptr[q];
     uint32_t n_tok = p.q_ptr[q + 1] - q0;
@@ -240,40 +238,27 @@ int32_t passages_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const ui
                              SS_MAX_QUERY_TERMS);
     const size_t tok0 = h_ptr[0], n_tok = h_ptr[nq] - tok0;
     if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "ss_best_passages: q_terms is NULL");
-    const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits), dev_o = ss::on_device(out);
-    std::vector<int32_t> h_n;
-    if (!dev_n) {
-        h_n.assign(n_hits, n_hits + nq);
-        for (size_t q = 0; q < nq; q++)
-            if (h_n[q] < 0 || h_n[q] > k) return ctx->fail(SS_ERR_INVALID, "ss_best_passages: n_hits[%zu] = %d outside 0 .. k = %d", q, h_n[q], k);
-    }
-    // ---- the queries' table in the pinned block of the next passage turn: ptr [n_q + 1] (from 0) | tokens | first
-    PassageTurn& turn = s->pas[s->pas_turn];
-    SS_HIP(ctx, turn.ev.wait());                          // the call TURNS calls ago has read this turn's blocks
-    const size_t q_words = nq + 1 + 2 * n_tok;
-    SS_HIP(ctx, turn.h_q.ensure(q_words * sizeof(uint32_t)));
-    uint32_t* const hq = turn.h_q.as<uint32_t>();
-    for (size_t q = 0; q <= nq; q++) hq[q] = h_ptr[q] - (uint32_t)tok0;
-    uint32_t* const h_tok = hq + nq + 1;
-    uint32_t* const h_first = h_tok + n_tok;
-    SS_HIP(ctx, ss::copy_in(st, h_tok, q_terms ? q_terms + tok0 : nullptr, n_tok * sizeof(uint32_t)));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_best_passages", "k", n_q, k, hits, n_hits, &w));
+    // ---- the queries' table in the pinned block of the next passage turn (ptr | tokens | first), the blocks of host arrays; then the
+    // pipeline
+    QueryTurn& turn = s->pas[s->pas_turn];
+    hw::QueryTable tab;
+    SS_TRY(hw::query_table_fill(ctx, turn, h_ptr, q_terms, 2, &tab));
+    const uint32_t* const h_tok = tab.h + nq + 1;
+    uint32_t* const h_first = tab.h + nq + 1 + n_tok;
     for (size_t q = 0; q < nq; q++)
-        for (uint32_t i = hq[q]; i < hq[q + 1]; i++) {
-            uint32_t f = hq[q];
+        for (uint32_t i = tab.h[q]; i < tab.h[q + 1]; i++) {
+            uint32_t f = tab.h[q];
             while (h_tok[f] != h_tok[i]) f++;
-            h_first[i] = f - hq[q];
+            h_first[i] = f - tab.h[q];
         }
-    SS_HIP(ctx, ensure(turn.d_q, q_words));
     const size_t n_rows = nq * (size_t)k;
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_pas_hits, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_pas_n, nq));
-    if (!dev_o) SS_HIP(ctx, ensure(s->d_pas_out, n_rows));
+    hw::EntriesOut o;
+    SS_TRY(hw::entries_out_prepare(s, out, n_rows * sizeof(ss_passage), &o));
+    SS_TRY(hw::window_stage(s, &w));
     s->pas_turn = (s->pas_turn + 1) % ss_scorer::TURNS;
-    // ---- the pipeline
-    SS_HIP(ctx, hipMemcpyAsync(turn.d_q.p, hq, q_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    // (host rows and counts: the caller's array and h_n outlive their copies, a call with any host array waits before it returns)
-    if (!dev_h) SS_HIP(ctx, hipMemcpyAsync(s->d_pas_hits.p, hits, n_rows * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    if (!dev_n) SS_HIP(ctx, hipMemcpyAsync(s->d_pas_n.p, h_n.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SS_HIP(ctx, hw::query_table_upload(ctx, turn, tab));
     PassageParams p{};
     p.b_ptr = s->body->term_ptr.p; p.b_doc = s->body->post_doc.p; p.b_terms = s->body->n_terms;
     p.b_pos_ptr = s->body->pos_ptr.p;
@@ -282,9 +267,9 @@ int32_t passages_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const ui
     p.q_ptr = turn.d_q.p;
     p.q_terms = turn.d_q.p + nq + 1;
     p.q_first = p.q_terms + n_tok;
-    p.hits = dev_h ? hits : s->d_pas_hits.p;
-    p.n_hits = dev_n ? n_hits : s->d_pas_n.p;
-    p.out = reinterpret_cast<uint32_t*>(dev_o ? out : s->d_pas_out.p);
+    p.hits = w.hits;
+    p.n_hits = w.n_hits;
+    p.out = static_cast<uint32_t*>(o.dev);
     p.k = (uint32_t)k;
     p.cap = (uint32_t)std::min(std::max(ctx->opt("passage.lds_events", PS_CAP_DEFAULT), (int64_t)1), PS_CAP_MAX);
     p.width = (double)width;
@@ -294,25 +279,7 @@ int32_t passages_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const ui
     hipLaunchKernelGGL(k_best_passages, dim3((unsigned)n_rows), dim3(PS_TPB), lds, st, p);   // (n_rows < 2^31)
     SS_HIP(ctx, hipGetLastError());
     SS_HIP(ctx, turn.ev.record(st));                      // the turn's pinned block and its device copy are read until here
-    if (dev_h && dev_n && dev_o) return SS_OK;            // ordered on the ctx stream; nothing comes back, nothing is waited for
-    // ---- staged: wait; a host `out` gets exactly the entries the kernel wrote.  (Device n_hits with a host out: the counts come back
-    // too, clamped as the kernel clamps them.)
-    if (!dev_o) {
-        std::vector<ss_passage> h_out(n_rows);
-        if (dev_n) {
-            h_n.resize(nq);
-            SS_HIP(ctx, hipMemcpyAsync(h_n.data(), n_hits, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        SS_HIP(ctx, hipMemcpyAsync(h_out.data(), s->d_pas_out.p, n_rows * sizeof(ss_passage), hipMemcpyDeviceToHost, st));
-        SS_HIP(ctx, hipStreamSynchronize(st));
-        for (size_t q = 0; q < nq; q++) {
-            const size_t nh = (size_t)std::min(std::max(h_n[q], 0), k);
-            if (nh) std::memcpy(reinterpret_cast<unsigned char*>(out) + q * (size_t)k * sizeof(ss_passage), h_out.data() + q * (size_t)k, nh * sizeof(ss_passage));
-        }
-    } else {
-        SS_HIP(ctx, hipStreamSynchronize(st));
-    }
-    return SS_OK;
+    return hw::entries_out_finish(s, o, w, sizeof(ss_passage));   // every array in device memory: nothing is waited for
 }
 
 }  // namespace
@@ -321,12 +288,7 @@ extern "C" {
 
 int32_t ss_best_passages(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, int32_t k, const ss_hit* hits,
                          const int32_t* n_hits, int32_t width, ss_passage* out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return passages_impl(s, n_q, q_ptr, q_terms, k, hits, n_hits, width, out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_best_passages: host allocation failed");
-    }
+    return hw::guarded(s, "ss_best_passages", [&] { return passages_impl(s, n_q, q_ptr, q_terms, k, hits, n_hits, width, out); });
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // scorer.hpp — the scorer object and everything of the scoring path that crosses a translation unit: score.hip (slice, phrase
 // and merge kernels, scorer lifecycle), score_wave.hip, score_small.hip and constraint.hip (their kernels and launchers) and
 // score_call.hip (the host side of a scoring call).  Every file that defines one of the ss:: functions below includes this
-// header, so a definition is checked against the one prototype its callers see.
+// header, so a definition is checked against the one prototype its callers see.  The calls that post-process a window of result rows
+// (explain, passage, collapse, dedup, field and vector .hip) share the staging of their host arrays: hit_window.hpp on top of this file,
+// the scorer's HitWindowBlocks and QueryTurn below.
 // Launchers take the kernel parameters as `const void* params`: ScoreParams / ConstraintParams live in score_common.hpp's
 // anonymous namespace (every translation unit has its own copy of the device code) and cannot appear in a shared prototype.
 #pragma once
@@ -83,21 +85,23 @@ struct Turn {
     ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
 };
 
-// ss_explain_hits (explain.hip): the call takes no plan turn (it scores nothing), so it has turns of its own.  Per turn: the pinned
-// block the queries' table goes up through, its device copy, and an event behind the kernel that read them (waited for before the
-// block is rewritten: the call never waits for its own copy).
-struct ExplainTurn {
+// ss_explain_hits / ss_best_passages: neither takes a plan turn (they score nothing), so each has TURNS turns of its own.  Per turn: the
+// pinned block the queries' table goes up through (ss::hitwin::query_table_fill), its device copy, and an event behind the kernel that
+// read them (waited for before the block is rewritten: the call never waits for its own copy).
+struct QueryTurn {
     ss::PinBuf h_q;
     ss::DevBuf<uint32_t> d_q;
     ss::Event ev;
 };
 
-// ss_best_passages (passage.hip): turns of its own, as ss_explain_hits has.  The queries' table carries one more word per token (the
-// first token index of the token's term).
-struct PassageTurn {
-    ss::PinBuf h_q;
-    ss::DevBuf<uint32_t> d_q;
-    ss::Event ev;
+// Device blocks of the HOST arrays of the calls that take a window of result rows (hit_window.hpp), one set for all of them, grow-only.
+// The invariant: a call that touches one of these blocks synchronizes the context's stream before it returns.  So nothing in flight
+// reads a block when a later call grows (frees) it, and whichever entry point comes next may take every block for its own arrays.
+struct HitWindowBlocks {
+    ss::DevBuf<ss_hit> rows_in, rows_out;      // hits [n_q][k_in], hits_out [n_q][k]
+    ss::DevBuf<int32_t> n_in, n_out, kept_out; // n_hits, n_hits_out, n_kept_out [n_q]
+    ss::DevBuf<unsigned char> extra;           // the one further output of a call, as bytes: per output row (same, similar, values, scores)
+                                               // or per entry of the input window (ss_term_match, ss_passage, field values, scores)
 };
 
 struct ss_scorer {
@@ -150,55 +154,33 @@ struct ss_scorer {
     ss::DevBuf<float> d_rel_w;
     ss::DevBuf<int32_t> d_rel_cnt;
     ss::DevBuf<double> d_rel_out_score;
-    // ss_explain_hits: its own turns; d_exp_hits / _n / _out: device blocks of HOST arrays (grow-only; a call that uses one waits
-    // before it returns).
-    ExplainTurn exp[TURNS];
-    int exp_turn = 0;
-    ss::DevBuf<ss_hit> d_exp_hits;
-    ss::DevBuf<int32_t> d_exp_n;
-    ss::DevBuf<ss_term_match> d_exp_out;
-    // ss_best_passages: its own turns; d_pas_hits / _n / _out: device blocks of HOST arrays (grow-only; a call that uses one waits
-    // before it returns).
-    PassageTurn pas[TURNS];
-    int pas_turn = 0;
-    ss::DevBuf<ss_hit> d_pas_hits;
-    ss::DevBuf<int32_t> d_pas_n;
-    ss::DevBuf<ss_passage> d_pas_out;
-    // ss_scorer_set_doc_groups (collapse.hip): [n_docs] the group of every doc, SS_NO_GROUP = a group of its own.  ss_collapse_hits /
-    // ss_score_topk_collapsed: d_col_*: device blocks of HOST arrays (grow-only; a call that uses one waits before it returns).
+    // ss_explain_hits / ss_best_passages: their own turns.  win: the device blocks of host arrays of every call that takes a window.
+    QueryTurn exp[TURNS], pas[TURNS];
+    int exp_turn = 0, pas_turn = 0;
+    HitWindowBlocks win;
+    // ss_scorer_set_doc_groups (collapse.hip): [n_docs] the group of every doc, SS_NO_GROUP = a group of its own.
     ss::DevBuf<uint32_t> groups;
     bool has_groups = false;
-    ss::DevBuf<ss_hit> d_col_hits, d_col_out;
-    ss::DevBuf<int32_t> d_col_n, d_col_nout, d_col_kept;
-    ss::DevBuf<uint32_t> d_col_same;
-    // ss_dedup_hits (dedup.hip): d_dd_*: device blocks of HOST arrays (grow-only; a call that uses one waits before it returns).
-    ss::DevBuf<ss_hit> d_dd_hits, d_dd_out;
-    ss::DevBuf<int32_t> d_dd_n, d_dd_nout, d_dd_kept;
-    ss::DevBuf<uint32_t> d_dd_sim;
-    // ss_scorer_set_doc_fields (field.hip): [n_fields][n_docs] signed 64-bit values per doc.  ss_doc_field_masks, ss_sort_hits_by_field,
-    // ss_hit_fields: d_fld_*: the set table of a mask call and device blocks of HOST arrays (grow-only; a call that uses one waits
-    // before it returns).
+    // ss_scorer_set_doc_fields (field.hip): [n_fields][n_docs] signed 64-bit values per doc.  ss_doc_field_masks: the set table of a
+    // call and the device block of a HOST words_out (grow-only; the call waits before it returns).
     ss::DevBuf<int64_t> fields;
     int32_t n_fields = 0;
     ss::DevBuf<unsigned char> d_fld_tab;
     ss::DevBuf<uint32_t> d_fld_words;
-    ss::DevBuf<ss_hit> d_fld_hits, d_fld_out;
-    ss::DevBuf<int32_t> d_fld_n, d_fld_nout;
-    ss::DevBuf<int64_t> d_fld_vals;
     // ss_scorer_set_doc_vectors (vector.hip): [n_docs][vec_dim] signed 8-bit values, vec_dim 0 = no table.  ss_vector_topk: the chunks'
-    // partial key lists, the queries' mask ids (through a pinned block whose last copy ev_vec_mid stands behind) and the dynamic LDS
-    // already granted to k_vec_topk<QT>.  d_vec_*: device blocks of HOST arrays and of the re-rank's scores (grow-only; a call that
-    // uses one for a host array waits before it returns).
+    // partial key lists, the queries' mask ids (through a pinned block whose last copy ev_vec_mid stands behind), the dynamic LDS
+    // already granted to k_vec_topk<QT> and the device blocks of HOST hits_out / n_hits_out (d_vec_hits, d_vec_n: grow-only; the call
+    // waits before it returns).  d_vec_q: query vectors that are host memory or not 16-byte aligned.  d_vec_scores: the re-rank's
+    // scores between its two kernels.
     ss::DevBuf<int8_t> vec;
     int32_t vec_dim = 0;
     ss::DevBuf<uint64_t> d_vec_part;
     ss::DevBuf<int8_t> d_vec_q;
-    ss::DevBuf<int32_t> d_vec_mid, d_vec_n, d_vec_wn, d_vec_scores, d_vec_nout, d_vec_sout;
+    ss::DevBuf<int32_t> d_vec_mid, d_vec_n, d_vec_scores;
     ss::PinBuf h_vec_mid;
     ss::Event ev_vec_mid;
     int vec_lds_attr[5] = {0, 0, 0, 0, 0};
     ss::DevBuf<ss_vec_hit> d_vec_hits;
-    ss::DevBuf<ss_hit> d_vec_win, d_vec_out;
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.

@@ -21,13 +21,16 @@
 //   k_vec_hit_scores    a gather: 16 lanes per (query, row) pair, 16 bytes per lane and step, summed over the group.
 //   k_vec_sort_hits     k_sort_hits_by_field's network over (class, key, window index) with the key taken from the scores
 //                       k_vec_hit_scores wrote: written anew here so that field.hip's calls enqueue what they did.
-// No float anywhere.  Device arrays throughout: the calls only enqueue on the context's stream.
-#include "scorer.hpp"
+// No float anywhere.  Device arrays throughout: the calls only enqueue on the context's stream.  ss_hit_vector_scores /
+// ss_rerank_hits_by_vector: the window in, the paging checks and the outputs' way back are hit_window.hpp's.
+#include "hit_window.hpp"
 #include "vector_plan.hpp"
 
 #include <algorithm>
 
 namespace {
+
+namespace hw = ss::hitwin;
 
 constexpr uint32_t VT_TILE = ss::vec::TILE, VT_WAVES = ss::vec::WAVES;
 constexpr int VT_TPB = VT_WAVES * 64;
@@ -316,9 +319,7 @@ __global__ __launch_bounds__(256) void k_vec_hit_scores(VecScoreParams p) {
     if (pair >= p.total) return;                                                  // (a whole group of 16)
     const uint64_t q = pair / p.k_in;
     const uint32_t j = (uint32_t)(pair - q * p.k_in);
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;
-    if (j >= n) return;
+    if (j >= hw::window_len(p.n_hits[q], p.k_in)) return;
     const uint32_t d = p.hits[pair].doc;
     if ((uint64_t)d >= p.n_docs) {
         if (sub == 0) p.out[pair] = SS_NO_VEC_SCORE;
@@ -342,8 +343,6 @@ __global__ __launch_bounds__(256) void k_vec_hit_scores(VecScoreParams p) {
 // ---- a window sorted by its scores -------------------------------------------------------------------------------------------
 constexpr uint32_t VS_CLASS_SHIFT = 16;                   // tag = class << 16 | window index (< SS_MAX_TOPK = 2^10)
 constexpr uint32_t VS_OUTSIDE = 1, VS_DEAD = 2;
-constexpr uint32_t VS_ROW_WORDS = sizeof(ss_hit) / 8;
-static_assert(sizeof(ss_hit) == 40 && alignof(ss_hit) == 8, "a row is five 8-byte words");
 
 struct VecSortParams {
     const int32_t* scores;             // [n_q][k_in] from k_vec_hit_scores
@@ -367,11 +366,9 @@ __global__ __launch_bounds__(BLOCK) void k_vec_sort_hits(VecSortParams p) {
     __shared__ uint32_t s_key[CAP];
     __shared__ uint32_t s_tag[CAP];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const int32_t nr = p.n_hits[q];
-    const uint32_t n = nr < 0 ? 0u : (uint32_t)nr > p.k_in ? p.k_in : (uint32_t)nr;   // <= k_in <= CAP: checked by the launcher
+    const uint32_t n = hw::window_len(p.n_hits[q], p.k_in);   // <= k_in <= CAP: checked by the launcher
     const ss_hit* const rows = p.hits + (size_t)q * p.k_in;
-    uint32_t np = 1;
-    while (np < n) np <<= 1;
+    const uint32_t np = hw::pow2_at_least(n);
     for (uint32_t j = tid; j < np; j += BLOCK) {
         uint32_t key = 0, tag = VS_DEAD << VS_CLASS_SHIFT | j;
         if (j < n) {
@@ -386,30 +383,16 @@ __global__ __launch_bounds__(BLOCK) void k_vec_sort_hits(VecSortParams p) {
         s_tag[j] = tag;
     }
     __syncthreads();
-    for (uint32_t k2 = 2; k2 <= np; k2 <<= 1) {
-        for (uint32_t j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (uint32_t i = tid; i < np; i += BLOCK) {
-                const uint32_t o = i ^ j2;
-                if (o > i) {
-                    const uint32_t ka = s_key[i], kb = s_key[o], ta = s_tag[i], tb = s_tag[o];
-                    if (vs_after(ka, ta, kb, tb) == ((i & k2) == 0)) {
-                        s_key[i] = kb; s_tag[i] = tb;
-                        s_key[o] = ka; s_tag[o] = ta;
-                    }
-                }
-            }
-            __syncthreads();
+    hw::bitonic_sort<BLOCK>(np, [&](uint32_t i, uint32_t o, bool up) {
+        const uint32_t ka = s_key[i], kb = s_key[o], ta = s_tag[i], tb = s_tag[o];
+        if (vs_after(ka, ta, kb, tb) == up) {
+            s_key[i] = kb; s_tag[i] = tb;
+            s_key[o] = ka; s_tag[o] = ta;
         }
-    }
+    });
     // ---- the page: sorted positions [first, first + n_out), all below n
-    const uint32_t n_out = n > p.first ? (n - p.first < p.k ? n - p.first : p.k) : 0u;
-    const uint64_t* const in_w = reinterpret_cast<const uint64_t*>(rows);
-    uint64_t* const out_w = reinterpret_cast<uint64_t*>(p.hits_out + (size_t)q * p.k);
-    for (uint32_t x = tid; x < n_out * VS_ROW_WORDS; x += BLOCK) {
-        const uint32_t rr = x / VS_ROW_WORDS, w = x - rr * VS_ROW_WORDS;
-        const uint32_t j = s_tag[p.first + rr] & ((1u << VS_CLASS_SHIFT) - 1u);
-        out_w[x] = in_w[(size_t)j * VS_ROW_WORDS + w];
-    }
+    const uint32_t n_out = hw::page_len(n, p.first, p.k);
+    hw::copy_page<BLOCK>(rows, p.hits_out + (size_t)q * p.k, n_out, [&](uint32_t r) { return s_tag[p.first + r] & ((1u << VS_CLASS_SHIFT) - 1u); });
     if (p.scores_out)
         for (uint32_t rr = tid; rr < n_out; rr += BLOCK) {
             const uint32_t tag = s_tag[p.first + rr];
@@ -549,33 +532,7 @@ int32_t topk_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, const int32_t* 
     return SS_OK;
 }
 
-// the window's arrays on the device (as field.hip's window_to_device, with the vector calls' own blocks): SS_OK = go on
-struct VecWindow { const ss_hit* hits; const int32_t* n_hits; bool staged; };
-int32_t vec_window(ss_scorer* s, const char* entry, int32_t n_q, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, VecWindow* w) {
-    ss_ctx* ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    const size_t nq = (size_t)n_q, n_rows_in = nq * (size_t)k_in;
-    const bool dev_h = ss::on_device(hits), dev_n = ss::on_device(n_hits);
-    if (!dev_n) {
-        for (size_t q = 0; q < nq; q++)
-            if (n_hits[q] < 0 || n_hits[q] > k_in)
-                return ctx->fail(SS_ERR_INVALID, "%s: n_hits[%zu] = %d outside 0 .. k_in = %d", entry, q, n_hits[q], k_in);
-    }
-    if (!dev_h) {
-        SS_HIP(ctx, ensure(s->d_vec_win, n_rows_in));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_vec_win.p, hits, n_rows_in * sizeof(ss_hit), hipMemcpyHostToDevice, st));
-    }
-    if (!dev_n) {
-        SS_HIP(ctx, ensure(s->d_vec_wn, nq));
-        SS_HIP(ctx, hipMemcpyAsync(s->d_vec_wn.p, n_hits, nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    w->hits = dev_h ? hits : s->d_vec_win.p;
-    w->n_hits = dev_n ? n_hits : s->d_vec_wn.p;
-    w->staged = !dev_h || !dev_n;
-    return SS_OK;
-}
-
-void launch_hit_scores(ss_scorer* s, const int8_t* qvec, const VecWindow& w, int32_t n_q, int32_t k_in, int32_t* out, hipStream_t st) {
+void launch_hit_scores(ss_scorer* s, const int8_t* qvec, const hw::WindowIn& w, int32_t n_q, int32_t k_in, int32_t* out, hipStream_t st) {
     VecScoreParams p{};
     p.vec = s->vec.p;
     p.n_docs = s->n_docs;
@@ -601,30 +558,16 @@ int32_t hit_scores_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    VecWindow w{};
-    SS_TRY(vec_window(s, "ss_hit_vector_scores", n_q, k_in, hits, n_hits, &w));
-    const size_t nq = (size_t)n_q, total = nq * (size_t)k_in;
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_hit_vector_scores", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
     const int8_t* d_q = nullptr;
-    SS_TRY(qvec_to_device(s, qvec, nq * (size_t)s->vec_dim, &d_q, &w.staged));
-    const bool dev_o = ss::on_device(scores_out);
-    if (!dev_o) SS_HIP(ctx, ensure(s->d_vec_scores, total));
-    int32_t* const out = dev_o ? scores_out : s->d_vec_scores.p;
-    launch_hit_scores(s, d_q, w, n_q, k_in, out, st);
+    SS_TRY(qvec_to_device(s, qvec, (size_t)n_q * (size_t)s->vec_dim, &d_q, &w.staged));
+    hw::EntriesOut o;
+    SS_TRY(hw::entries_out_prepare(s, scores_out, (size_t)n_q * (size_t)k_in * sizeof(int32_t), &o));
+    launch_hit_scores(s, d_q, w, n_q, k_in, static_cast<int32_t*>(o.dev), st);
     SS_HIP(ctx, hipGetLastError());
-    if (dev_o) {
-        if (w.staged) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;
-    }
-    // ---- a host output: of the rows exactly the entries the kernel wrote
-    std::vector<int32_t> h_s(total), h_n(nq);
-    SS_HIP(ctx, hipMemcpyAsync(h_s.data(), out, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), w.n_hits, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)std::min<int32_t>(std::max<int32_t>(h_n[q], 0), k_in), o = q * (size_t)k_in;
-        std::memcpy(scores_out + o, h_s.data() + o, cnt * sizeof(int32_t));
-    }
-    return SS_OK;
+    return hw::entries_out_finish(s, o, w, sizeof(int32_t));
 }
 
 int32_t rerank_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in, const ss_hit* hits, const int32_t* n_hits, int32_t first, int32_t k,
@@ -632,71 +575,37 @@ int32_t rerank_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in,
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     // ---- the checks: nothing is enqueued and no output is touched before the last of them has passed
-    if (n_q < 0) return ctx->fail(SS_ERR_INVALID, "ss_rerank_hits_by_vector: n_q < 0");
-    if (k_in < 1 || k < 1 || first < 0)
-        return ctx->fail(SS_ERR_INVALID, "ss_rerank_hits_by_vector: k_in = %d, k = %d must be >= 1 and first = %d >= 0", k_in, k, first);
-    if (k_in > SS_MAX_TOPK || k > SS_MAX_TOPK)
-        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_rerank_hits_by_vector: k_in = %d or k = %d exceeds SS_MAX_TOPK = %d", k_in, k, SS_MAX_TOPK);
-    if (n_q > 0 && (!qvec || !hits || !n_hits || !hits_out || !n_hits_out))
-        return ctx->fail(SS_ERR_INVALID, "ss_rerank_hits_by_vector: qvec, hits, n_hits, hits_out or n_hits_out is NULL");
-    const size_t nq = (size_t)n_q, n_rows = nq * (size_t)k;
-    if (n_q > 0) {
-        const uintptr_t ib = (uintptr_t)hits, ie = ib + nq * (size_t)k_in * sizeof(ss_hit);
-        const uintptr_t ob = (uintptr_t)hits_out, oe = ob + n_rows * sizeof(ss_hit);
-        if (ib < oe && ob < ie) return ctx->fail(SS_ERR_INVALID, "ss_rerank_hits_by_vector: hits_out overlaps hits");
-    }
+    SS_TRY(hw::check_paging(ctx, "ss_rerank_hits_by_vector", "k_in", n_q, k_in, k, first));
+    if (n_q > 0 && !qvec) return ctx->fail(SS_ERR_INVALID, "ss_rerank_hits_by_vector: qvec is NULL");
+    SS_TRY(hw::check_page_arrays(ctx, "ss_rerank_hits_by_vector", n_q, k_in, k, hits, n_hits, hits_out, n_hits_out));
     if (s->vec_dim == 0) return ctx->fail(SS_ERR_STATE, "ss_rerank_hits_by_vector: no vector table registered (ss_scorer_set_doc_vectors)");
     if (n_q == 0) return SS_OK;
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    VecWindow w{};
-    SS_TRY(vec_window(s, "ss_rerank_hits_by_vector", n_q, k_in, hits, n_hits, &w));
+    hw::WindowIn w;
+    SS_TRY(hw::window_check(ctx, "ss_rerank_hits_by_vector", "k_in", n_q, k_in, hits, n_hits, &w));
+    SS_TRY(hw::window_stage(s, &w));
     const int8_t* d_q = nullptr;
-    SS_TRY(qvec_to_device(s, qvec, nq * (size_t)s->vec_dim, &d_q, &w.staged));
-    const bool dev_h = ss::on_device(hits_out), dev_n = ss::on_device(n_hits_out), dev_v = scores_out && ss::on_device(scores_out);
-    SS_HIP(ctx, ensure(s->d_vec_scores, nq * (size_t)k_in));
-    if (!dev_h) SS_HIP(ctx, ensure(s->d_vec_out, n_rows));
-    if (!dev_n) SS_HIP(ctx, ensure(s->d_vec_nout, nq));
-    if (scores_out && !dev_v) SS_HIP(ctx, ensure(s->d_vec_sout, n_rows));
+    SS_TRY(qvec_to_device(s, qvec, (size_t)n_q * (size_t)s->vec_dim, &d_q, &w.staged));
+    SS_HIP(ctx, ensure(s->d_vec_scores, (size_t)n_q * (size_t)k_in));
+    hw::RowsOut o;
+    SS_TRY(hw::rows_out_prepare(s, (size_t)n_q, (size_t)k, hits_out, n_hits_out, nullptr, scores_out, sizeof(int32_t), &o));
     launch_hit_scores(s, d_q, w, n_q, k_in, s->d_vec_scores.p, st);
     SS_HIP(ctx, hipGetLastError());
     VecSortParams p{};
     p.scores = s->d_vec_scores.p;
     p.hits = w.hits;
     p.n_hits = w.n_hits;
-    p.hits_out = dev_h ? hits_out : s->d_vec_out.p;
-    p.n_hits_out = dev_n ? n_hits_out : s->d_vec_nout.p;
-    p.scores_out = !scores_out ? nullptr : dev_v ? scores_out : s->d_vec_sout.p;
+    p.hits_out = o.hits;
+    p.n_hits_out = o.n_hits;
+    p.scores_out = static_cast<int32_t*>(o.extra);
     p.k_in = (uint32_t)k_in; p.first = (uint32_t)first; p.k = (uint32_t)k;
     if (k_in <= VS_SMALL * VS_SMALL_PER)
         hipLaunchKernelGGL((k_vec_sort_hits<VS_SMALL, VS_SMALL_PER>), dim3((unsigned)n_q), dim3(VS_SMALL), 0, st, p);
     else
         hipLaunchKernelGGL((k_vec_sort_hits<VS_LARGE, VS_LARGE_PER>), dim3((unsigned)n_q), dim3(VS_LARGE), 0, st, p);
     SS_HIP(ctx, hipGetLastError());
-    if (dev_h && dev_n && (!scores_out || dev_v)) {
-        if (w.staged) SS_HIP(ctx, hipStreamSynchronize(st));
-        return SS_OK;                                     // ordered on the ctx stream; nothing comes back
-    }
-    // ---- host outputs: the counts whole, of the rows exactly the entries the kernel wrote
-    std::vector<int32_t> h_n(nq), h_sc;
-    std::vector<ss_hit> h_rows;
-    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), p.n_hits_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (!dev_h) {
-        h_rows.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_rows.data(), p.hits_out, n_rows * sizeof(ss_hit), hipMemcpyDeviceToHost, st));
-    }
-    if (scores_out && !dev_v) {
-        h_sc.resize(n_rows);
-        SS_HIP(ctx, hipMemcpyAsync(h_sc.data(), p.scores_out, n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (!dev_n) std::memcpy(n_hits_out, h_n.data(), nq * sizeof(int32_t));
-    for (size_t q = 0; q < nq; q++) {
-        const size_t cnt = (size_t)h_n[q], o = q * (size_t)k;
-        if (!dev_h) std::memcpy(hits_out + o, h_rows.data() + o, cnt * sizeof(ss_hit));
-        if (scores_out && !dev_v) std::memcpy(scores_out + o, h_sc.data() + o, cnt * sizeof(int32_t));
-    }
-    return SS_OK;
+    return hw::rows_out_finish(s, o, w.staged);
 }
 
 }  // namespace
@@ -740,32 +649,17 @@ int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec) 
 }
 
 int32_t ss_vector_topk(ss_scorer* s, int32_t n_q, const int8_t* qvec, const int32_t* mask_id, int32_t k, ss_vec_hit* hits_out, int32_t* n_hits_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return topk_impl(s, n_q, qvec, mask_id, k, hits_out, n_hits_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_vector_topk: host allocation failed");
-    }
+    return hw::guarded(s, "ss_vector_topk", [&] { return topk_impl(s, n_q, qvec, mask_id, k, hits_out, n_hits_out); });
 }
 
 int32_t ss_hit_vector_scores(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in, const ss_hit* hits, const int32_t* n_hits,
                              int32_t* scores_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return hit_scores_impl(s, n_q, qvec, k_in, hits, n_hits, scores_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_hit_vector_scores: host allocation failed");
-    }
+    return hw::guarded(s, "ss_hit_vector_scores", [&] { return hit_scores_impl(s, n_q, qvec, k_in, hits, n_hits, scores_out); });
 }
 
 int32_t ss_rerank_hits_by_vector(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in, const ss_hit* hits, const int32_t* n_hits,
                                  int32_t first, int32_t k, ss_hit* hits_out, int32_t* n_hits_out, int32_t* scores_out) {
-    if (!s) return SS_ERR_INVALID;
-    try {
-        return rerank_impl(s, n_q, qvec, k_in, hits, n_hits, first, k, hits_out, n_hits_out, scores_out);
-    } catch (const std::bad_alloc&) {
-        return s->ctx->fail(SS_ERR_OOM, "ss_rerank_hits_by_vector: host allocation failed");
-    }
+    return hw::guarded(s, "ss_rerank_hits_by_vector", [&] { return rerank_impl(s, n_q, qvec, k_in, hits, n_hits, first, k, hits_out, n_hits_out, scores_out); });
 }
 
 }  // extern "C"
