@@ -4,6 +4,7 @@
 // HBM layout:  term_ptr u64[T+1] | post_doc u32[P] (strictly ascending inside a term) |
 //              post_w f32[P] (normalised tf until ss_tfidf_build, tf*idf after) | mag f64[n_docs]
 // Host keeps df per term (u32[T]) so that query planning needs no device round trip.
+// index.hip: create / destroy / read / set_*; tfidf.hip: the weight and magnitude build; index_update.hip: deltas and resize.
 #pragma once
 #include "common.hpp"
 

@@ -1,4 +1,5 @@
-// tfidf.hip — inverted-index upload + TF-IDF weight/magnitude build for gfx950.
+// tfidf.hip — TF-IDF weight/magnitude build for gfx950: the kernels, their launches and the two entry points that run them
+// (ss_tfidf_build, ss_index_refresh_magnitudes).  The table itself is index.hip; how a table is partitioned is tfidf_plan.hpp.
 //
 // Replaces ranking/term_weighting.go:10-57 (UpdateTermWeights) and the sqrt of
 // saveMagnitude (:72,:97,:105):
@@ -8,15 +9,16 @@
 //   mag   = sqrt(mag2)                                                (:72)
 // HBM-bound: 12 B/posting (doc id, read w, write w) + 8 B per doc and term.
 #include "index.hpp"
+#include "tfidf_plan.hpp"
 #include <cstdlib>
 #include <algorithm>
 
-#include <algorithm>
-#include <memory>
-
 namespace {
 
+using namespace ss::tfidf;                   // the geometry constants, Options, Plan
+
 constexpr int TPB = 256;
+static_assert(CH == TPB * 16, "k_weight and k_weight_count: 16 postings per thread");
 
 // Go's math.Log / math.Log2 (go1.12 src/math/log.go, log10.go; FreeBSD e_log.c algorithm),
 // restated for the device.  Same IEEE operation sequence as oracle/oracle.c:orc_go_log2
@@ -62,50 +64,8 @@ __global__ void k_idf(const uint64_t* __restrict__ term_ptr, const uint64_t* __r
     idf[t] = (float)go_log2(total_docs / df);                       // term_weighting.go:37
 }
 
-// validate: term_ptr non-decreasing, doc ids in range, count adjacent non-ascending pairs
-__global__ void k_check_ptr(const uint64_t* __restrict__ term_ptr, uint64_t n_terms, const uint32_t* __restrict__ post_doc,
-                            unsigned long long* __restrict__ n_boundary_desc, uint32_t* __restrict__ err) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_terms) return;
-    const uint64_t a = term_ptr[t], b = term_ptr[t + 1];
-    if (b < a) { atomicOr(err, 1u); return; }
-    // a legitimate descent can only sit at the start of a non-empty list
-    if (b > a && a > 0 && post_doc[a] <= post_doc[a - 1]) atomicAdd(n_boundary_desc, 1ull);
-}
-__global__ void k_check_df(const uint64_t* __restrict__ term_ptr, const uint64_t* __restrict__ df, uint64_t n_terms,
-                           uint32_t* __restrict__ err) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_terms) return;
-    if (df[t] < term_ptr[t + 1] - term_ptr[t]) atomicOr(err, 1u);
-}
-// positional postings: pos_ptr must be non-decreasing (k_phrase_match reads pos[pos_ptr[i] .. pos_ptr[i+1]))
-__global__ void k_check_pos(const uint64_t* __restrict__ pos_ptr, uint64_t n_post, uint32_t* __restrict__ err) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    bool bad = false;
-    for (; i < n_post; i += stride) bad = bad || pos_ptr[i + 1] < pos_ptr[i];
-    if (bad) atomicOr(err, 1u);
-}
-__global__ void k_check_docs(const uint32_t* __restrict__ post_doc, uint64_t n_post, uint64_t n_docs,
-                             unsigned long long* __restrict__ n_desc, uint32_t* __restrict__ err) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    unsigned long long local = 0;
-    bool bad = false;
-    for (; i < n_post; i += stride) {
-        const uint32_t d = post_doc[i];
-        if (d >= n_docs) bad = true;
-        if (i > 0 && d <= post_doc[i - 1]) local++;
-    }
-    if (bad) atomicOr(err, 2u);
-    // wave-reduce then one atomic per wave
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(n_desc, local);
-}
-
 // One block per chunk of CH consecutive postings.  The block finds the terms its chunk spans
 // with two binary searches, then every posting finds its own term inside that (short) range.
-constexpr int CH = TPB * 16;
 __global__ __launch_bounds__(TPB) void k_weight(const uint64_t* __restrict__ term_ptr, uint64_t n_terms,
                                                 const uint32_t* __restrict__ post_doc, float* __restrict__ post_w,
                                                 const float* __restrict__ idf, uint64_t n_post, double* __restrict__ mag2) {
@@ -151,7 +111,6 @@ __global__ __launch_bounds__(TPB) void k_weight(const uint64_t* __restrict__ ter
 //                    LDS ticket per posting); k_scatter<true> also computes w = tf*idf and writes it back in place
 //   k_bucket_sum     one workgroup per bucket: float64 LDS accumulators, sqrt, write mag
 // float32 squares summed in float64 are exact, so the order inside a bucket does not matter (same as the atomics).
-constexpr int NB_MAX = 4096;                 // most buckets (LDS histogram of a block)
 constexpr int PER_THREAD = CH / TPB;         // postings per thread and block
 
 __device__ __forceinline__ void chunk_term_range(const uint64_t* __restrict__ term_ptr, uint64_t n_terms, uint64_t base, uint64_t last,
@@ -174,10 +133,6 @@ __device__ __forceinline__ void chunk_term_range(const uint64_t* __restrict__ te
 // altogether: k_weight_count and k_scatter pass over them, and k_bucket_sum reads bucket b's run of every head list straight
 // from post_doc / post_w, weighting it on the way (w = tf*idf written once) — 12 bytes per head posting, the algorithmic
 // minimum, instead of the 36 a partitioned posting costs.  Which lists are head only moves work between two exact paths.
-#ifndef SS_HEAD_CAP
-#define SS_HEAD_CAP 1024
-#endif
-constexpr int HEAD_CAP = SS_HEAD_CAP;               // most head lists (their run table sits in LDS beside the accumulators: 12 B each)
 struct HeadArgs {
     const uint32_t* n;                       // number of head lists (device word; 0 = no head path)
     const uint32_t* term;                    // [HEAD_CAP] their term ids, ascending
@@ -186,8 +141,7 @@ struct HeadArgs {
     const uint32_t* bounds;                  // [nb + 1][HEAD_CAP]: postings of list i with doc < b << shift
 };
 // Threshold: the smallest power-of-two multiple of `thr` that leaves at most HEAD_CAP lists (so that the LONGEST lists are the
-// head lists when many qualify).  hist[j] counts the lists with length >= thr << j.
-constexpr int HEAD_LEVELS = 24;
+// head lists when many qualify).  hist[j] counts the lists with length >= thr << j, j < HEAD_LEVELS.
 __global__ void k_head_hist(const uint64_t* __restrict__ term_ptr, uint64_t n_terms, uint64_t thr, uint32_t* __restrict__ hist) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_terms) return;
@@ -379,19 +333,7 @@ __global__ __launch_bounds__(1024) void k_bucket_offsets(const uint32_t* __restr
 // 641M-posting table, 1.9x write amplification).  The block therefore sorts its SC_CH records by bucket in LDS first
 // (histogram -> exclusive scan -> LDS ticket per record) and then writes them out in LDS order: consecutive lanes write
 // consecutive records of a bucket's run.
-#ifndef SS_SC_TPB
-#define SS_SC_TPB 1024
-#endif
-constexpr int SC_TPB = SS_SC_TPB;
-#ifndef SS_SC_PT
-#define SS_SC_PT (8192 / SS_SC_TPB)
-#endif
-constexpr int SC_PT = SS_SC_PT;                // records per thread
-constexpr int SC_CH = SC_TPB * SC_PT;         // records per chunk (staged in LDS)
-constexpr int SC_BPT_MAX = NB_MAX / SC_TPB;
-constexpr int SC_PF = (1024 + SC_TPB - 1) / SC_TPB;   // entries of the next chunk's term window a thread prefetches (windows up to 1024 terms)
-static_assert(SC_CH <= 65535, "staging positions are 16-bit");
-// LDS: rec[SC_CH] (8 B: doc, float32 square), then per bucket (nbt = the bucket count rounded up to even): the chunk's count (16 bits,
+// LDS (scatter_lds_bytes): rec[SC_CH] (8 B: doc, float32 square), then per bucket (nbt = the bucket count rounded up to even): the chunk's count (16 bits,
 // two buckets to a word — the returning ds_add of the count is also the record's rank), the first staging position (16 bits) and the
 // output position of the chunk's run (32 bits); the block's output cursors live in the registers of the buckets' owner threads and a
 // record's bucket is read off its doc id.  10M docs (1222 buckets): 64 + 9.6 KB (before late round 4: 64 + 32 + 16 KB with 32-bit
@@ -400,7 +342,6 @@ static_assert(SC_CH <= 65535, "staging positions are 16-bit");
 // 64 VGPRs 6.6, one workgroup of 1024 5.4-5.6 (5.85 with the old layout; 4096-record chunks in two workgroups had measured 5 % slower
 // in round 3).  Every resident block keeps a half-written line open per bucket, and twice the blocks are twice the lines an XCD's L2
 // has to hold until the block's next chunk completes them (DESIGN K2/K3).
-inline size_t scatter_lds_bytes(uint32_t nbt) { return (size_t)SC_CH * 8 + (size_t)nbt * 8 + 64; }
 // WEIGHT (round 4: weight and scatter in ONE pass over the postings): w = tf * idf is computed here, written back in place and
 // squared on the way into the record — the separate weighting pass read and wrote every tail posting once more (12 of its 36
 // bytes; the count pass in front of this kernel now reads doc ids only).  A thread takes SC_PT CONSECUTIVE postings, finds the
@@ -415,7 +356,6 @@ __device__ unsigned long long g_sc_ph[8];
 #else
 #define SC_PH(i) do { } while (0)
 #endif
-constexpr int SC_WIN = SC_CH;                  // term-window entries staged per chunk (a chunk spans at most SC_CH + 1 non-empty terms; beyond: global search)
 template <bool WEIGHT, int BPT>
 #ifndef SS_SC_MINW
 #define SS_SC_MINW 1
@@ -769,9 +709,6 @@ __global__ void k_sumsq_atomic(const uint32_t* __restrict__ post_doc, const floa
 #define SS_TPB_B 1024
 #endif
 constexpr int TPB_B = SS_TPB_B;
-#ifndef SS_HEAD_PIECE
-#define SS_HEAD_PIECE 2048
-#endif
 #ifndef SS_HEAD_U
 #define SS_HEAD_U 16
 #endif
@@ -779,9 +716,7 @@ constexpr int TPB_B = SS_TPB_B;
 #define SS_BS_U 8
 #endif
 constexpr int BS_U = SS_BS_U;                // partitioned records of a thread in flight
-constexpr int HEAD_PIECE = SS_HEAD_PIECE;    // head postings a wave takes at a time
 constexpr int HEAD_U = SS_HEAD_U;            // loads of a lane in flight per array (4: 1.19 ms for the head part of the 641M table, 8: see DESIGN)
-inline size_t bucket_lds_bytes(int shift) { return ((size_t)1 << shift) * 8 + (size_t)(3 * HEAD_CAP + 4) * 4; }
 // One workgroup per bucket: float64 accumulators in LDS take (A) the bucket's partitioned records and (B) the bucket's run of
 // every head list, read in place — WEIGHT: tf in, w = tf*idf out (term_weighting.go:42), otherwise the weights as they stand.
 template <bool WEIGHT>
@@ -909,30 +844,18 @@ struct BucketPass {
     ss::DevBuf<uint2> packed;
     ss::DevBuf<uint32_t> h_n, h_term, h_bounds, h_hist;  // head lists (see HeadArgs)
     ss::DevBuf<uint64_t> h_hs, h_he;
-    uint64_t head_thr = 0;                       // shortest list that takes the head path; 0 = no head path
-    uint32_t nb = 0, nblk = 0, bpt = 2, nbt = 2;
-    uint64_t per = 0;
-    int shift = 13;
+    Plan plan;                                   // of the table the buffers were sized for
 };
-int32_t bucket_pass_prepare(ss_ctx* ctx, uint64_t P, uint32_t nb, int shift, BucketPass& bp) {
-    bp.nb = nb;
-    bp.shift = shift;
-    // blocks own contiguous ranges whose length is a multiple of both passes' chunk sizes; ~1024 ranges
-    const uint64_t unit = std::max<uint64_t>(SC_CH, CH);
-    static_assert(SC_CH % CH == 0 || CH % SC_CH == 0, "a range must be whole chunks of both passes");
-    const uint64_t target_blocks = (uint64_t)std::max<int64_t>(1, ctx->opt("tfidf.blocks", 4096));
-    bp.per = std::max<uint64_t>(unit, ss::div_up(ss::div_up(P, target_blocks), unit) * unit);
-    bp.nblk = (uint32_t)ss::div_up(P, bp.per);
-    SS_HIP(ctx, bp.mat.alloc((size_t)nb * bp.nblk));
+// allocates what `plan` (a bucketed one) asks for and raises the kernels' dynamic-LDS grants to its sizes
+int32_t bucket_pass_prepare(ss_ctx* ctx, uint64_t P, const Plan& plan, BucketPass& bp) {
+    bp.plan = plan;
+    const uint32_t nb = plan.nb;
+    SS_HIP(ctx, bp.mat.alloc((size_t)nb * plan.nblk));
     SS_HIP(ctx, bp.cnt.alloc(nb));
     SS_HIP(ctx, bp.off.alloc(nb + 1));
     SS_HIP(ctx, bp.cur.alloc(nb));
     SS_HIP(ctx, bp.packed.alloc(P));
-    // head lists: average run of at least "tfidf.head_min_run" postings per bucket (0 switches the head path off), and longer
-    // than two chunks of either pass (head_skip relies on it)
-    const int64_t min_run = ctx->opt("tfidf.head_min_run", 64);
-    bp.head_thr = min_run > 0 ? std::max<uint64_t>((uint64_t)min_run * nb, 2 * unit + 1) : 0;
-    if (bp.head_thr) {
+    if (plan.head_thr) {
         SS_HIP(ctx, bp.h_n.alloc(1));
         SS_HIP(ctx, bp.h_hist.alloc(HEAD_LEVELS));
         SS_HIP(ctx, bp.h_term.alloc(HEAD_CAP));
@@ -940,11 +863,9 @@ int32_t bucket_pass_prepare(ss_ctx* ctx, uint64_t P, uint32_t nb, int shift, Buc
         SS_HIP(ctx, bp.h_he.alloc(HEAD_CAP));
         SS_HIP(ctx, bp.h_bounds.alloc((size_t)(nb + 1) * HEAD_CAP));
     }
-    bp.bpt = (ss::div_up(nb, (uint32_t)SC_TPB) + 1u) & ~1u;                  // even: a thread's buckets are whole words of the packed counts
-    bp.nbt = (nb + 1u) & ~1u;
-    if (bp.bpt > (uint32_t)SC_BPT_MAX) return ctx->fail(SS_ERR_UNSUPPORTED, "tfidf: %u buckets exceed the partition's %d", nb, NB_MAX);
-    if (ctx->tfidf_scatter_lds < (int)scatter_lds_bytes(bp.nbt)) {
-        const int lds = (int)scatter_lds_bytes(bp.nbt);
+    if (plan.too_many_buckets) return ctx->fail(SS_ERR_UNSUPPORTED, "tfidf: %u buckets exceed the partition's %d", nb, NB_MAX);
+    if (ctx->tfidf_scatter_lds < (int)plan.scatter_lds_bytes) {
+        const int lds = (int)plan.scatter_lds_bytes;
         SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -953,42 +874,45 @@ int32_t bucket_pass_prepare(ss_ctx* ctx, uint64_t P, uint32_t nb, int shift, Buc
         SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_scatter<false, SC_BPT_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         ctx->tfidf_scatter_lds = lds;
     }
-    if (ctx->tfidf_bucket_lds < (int)bucket_lds_bytes(shift)) {
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_sum<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bucket_lds_bytes(shift)));
-        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_sum<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bucket_lds_bytes(shift)));
-        ctx->tfidf_bucket_lds = (int)bucket_lds_bytes(shift);
+    if (ctx->tfidf_bucket_lds < (int)plan.bucket_lds_bytes) {
+        const int lds = (int)plan.bucket_lds_bytes;
+        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_sum<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        SS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket_sum<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ctx->tfidf_bucket_lds = lds;
     }
     return SS_OK;
 }
 // weight: also w = tf*idf in place (ss_tfidf_build); otherwise the magnitudes of the weights as they stand
 void bucket_pass_launch(ss_index* idx, hipStream_t st, BucketPass& bp, bool weight, const float* idf) {
     const uint64_t P = idx->n_post, N = idx->n_docs, T = idx->n_terms;
+    const Plan& pl = bp.plan;
     HeadArgs head{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (bp.head_thr && T) {
+    if (pl.head_thr && T) {
         (void)hipMemsetAsync(bp.h_n.p, 0, sizeof(uint32_t), st);
         (void)hipMemsetAsync(bp.h_hist.p, 0, HEAD_LEVELS * sizeof(uint32_t), st);
-        hipLaunchKernelGGL(k_head_hist, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, T, bp.head_thr, bp.h_hist.p);
-        hipLaunchKernelGGL(k_head_select, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, T, bp.head_thr, (const uint32_t*)bp.h_hist.p,
+        hipLaunchKernelGGL(k_head_hist, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, T, pl.head_thr, bp.h_hist.p);
+        hipLaunchKernelGGL(k_head_select, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, T, pl.head_thr, (const uint32_t*)bp.h_hist.p,
                            bp.h_n.p, bp.h_term.p);
         hipLaunchKernelGGL(k_head_sort, dim3(1), dim3(1024), 0, st, idx->term_ptr.p, bp.h_n.p, bp.h_term.p, bp.h_hs.p, bp.h_he.p);
-        hipLaunchKernelGGL(k_head_bounds, dim3((bp.nb + 1) * (HEAD_CAP / 256)), dim3(256), 0, st, (const uint32_t*)idx->post_doc.p, (const uint32_t*)bp.h_n.p,
-                           (const uint64_t*)bp.h_hs.p, (const uint64_t*)bp.h_he.p, bp.shift, bp.nb, bp.h_bounds.p);
+        hipLaunchKernelGGL(k_head_bounds, dim3((pl.nb + 1) * (HEAD_CAP / 256)), dim3(256), 0, st, (const uint32_t*)idx->post_doc.p, (const uint32_t*)bp.h_n.p,
+                           (const uint64_t*)bp.h_hs.p, (const uint64_t*)bp.h_he.p, pl.shift, pl.nb, bp.h_bounds.p);
         head = HeadArgs{bp.h_n.p, bp.h_term.p, bp.h_hs.p, bp.h_he.p, bp.h_bounds.p};
     }
     // the count pass reads doc ids only; the weights are multiplied by k_scatter<true> on its way through the postings
-    hipLaunchKernelGGL(k_weight_count, dim3(bp.nblk), dim3(TPB), 0, st, (const uint32_t*)idx->post_doc.p, P, bp.per, bp.shift, bp.nb, bp.nblk,
+    hipLaunchKernelGGL(k_weight_count, dim3(pl.nblk), dim3(TPB), 0, st, (const uint32_t*)idx->post_doc.p, P, pl.per, pl.shift, pl.nb, pl.nblk,
                        bp.mat.p, head);
-    hipLaunchKernelGGL(k_bucket_rowscan, dim3(bp.nb), dim3(64), 0, st, bp.mat.p, bp.nblk, bp.cnt.p);
-    hipLaunchKernelGGL(k_bucket_offsets, dim3(1), dim3(1024), 0, st, bp.cnt.p, bp.nb, bp.off.p, bp.cur.p);
-    // (the owner threads' cursor registers are sized by the buckets per thread: 2 up to 1024 buckets, 4 up to 2048, 8 beyond)
+    hipLaunchKernelGGL(k_bucket_rowscan, dim3(pl.nb), dim3(64), 0, st, bp.mat.p, pl.nblk, bp.cnt.p);
+    hipLaunchKernelGGL(k_bucket_offsets, dim3(1), dim3(1024), 0, st, bp.cnt.p, pl.nb, bp.off.p, bp.cur.p);
+    // (the owner threads' cursor registers are sized by the instance the plan names; its third arm is for variant builds of fewer than
+    //  NB_MAX / 4 threads — at the product's 1024 SC_BPT_MAX is 4 and bpt never exceeds it: see make_plan)
 #define SS_SCATTER_LAUNCH(W, B)                                                                                                                     \
-    hipLaunchKernelGGL((k_scatter<W, B>), dim3(bp.nblk), dim3(SC_TPB), scatter_lds_bytes(bp.nbt), st, (const uint32_t*)idx->post_doc.p, idx->post_w.p, P, \
-                       bp.per, bp.shift, bp.nb, bp.nblk, bp.bpt, bp.nbt, (const uint32_t*)bp.mat.p, (const uint32_t*)bp.off.p, bp.packed.p, head,   \
+    hipLaunchKernelGGL((k_scatter<W, B>), dim3(pl.nblk), dim3(SC_TPB), pl.scatter_lds_bytes, st, (const uint32_t*)idx->post_doc.p, idx->post_w.p, P, \
+                       pl.per, pl.shift, pl.nb, pl.nblk, pl.bpt, pl.nbt, (const uint32_t*)bp.mat.p, (const uint32_t*)bp.off.p, bp.packed.p, head,   \
                        (const uint64_t*)idx->term_ptr.p, T, idf)
     if (weight) {
-        if (bp.bpt <= 2) SS_SCATTER_LAUNCH(true, 2); else if (bp.bpt <= 4) SS_SCATTER_LAUNCH(true, 4); else SS_SCATTER_LAUNCH(true, SC_BPT_MAX);
+        if (pl.bpt_inst == 2) SS_SCATTER_LAUNCH(true, 2); else if (pl.bpt_inst == 4) SS_SCATTER_LAUNCH(true, 4); else SS_SCATTER_LAUNCH(true, SC_BPT_MAX);
     } else {
-        if (bp.bpt <= 2) SS_SCATTER_LAUNCH(false, 2); else if (bp.bpt <= 4) SS_SCATTER_LAUNCH(false, 4); else SS_SCATTER_LAUNCH(false, SC_BPT_MAX);
+        if (pl.bpt_inst == 2) SS_SCATTER_LAUNCH(false, 2); else if (pl.bpt_inst == 4) SS_SCATTER_LAUNCH(false, 4); else SS_SCATTER_LAUNCH(false, SC_BPT_MAX);
     }
 #undef SS_SCATTER_LAUNCH
 #ifdef SS_SC_PHASES
@@ -999,93 +923,52 @@ void bucket_pass_launch(ss_index* idx, hipStream_t st, BucketPass& bp, bool weig
         unsigned long long tot = 0;
         for (int i = 0; i < 8; i++) tot += h[i];
         fprintf(stderr, "[k_scatter phases, %u blocks, cycles of wave 0 summed] wait-for-previous-write-out+barrier %.1f%%  window staged %.1f%%  weights %.1f%%  count %.1f%%  scan %.1f%%  "
-                        "stage+next loads issued %.1f%%  write-out %.1f%%  loop top %.1f%%  (total %.3g cycles = %.1f k per block)\n", bp.nblk,
+                        "stage+next loads issued %.1f%%  write-out %.1f%%  loop top %.1f%%  (total %.3g cycles = %.1f k per block)\n", pl.nblk,
                 100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, 100.0 * h[4] / tot, 100.0 * h[5] / tot, 100.0 * h[6] / tot, 100.0 * h[7] / tot,
-                (double)tot, (double)tot / bp.nblk / 1e3);
+                (double)tot, (double)tot / pl.nblk / 1e3);
         unsigned long long z[8] = {};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sc_ph), z, sizeof(z));
     }
 #endif
-    if (weight) hipLaunchKernelGGL(k_bucket_sum<true>, dim3(bp.nb), dim3(TPB_B), bucket_lds_bytes(bp.shift), st, bp.packed.p, bp.off.p, N, bp.shift,
+    if (weight) hipLaunchKernelGGL(k_bucket_sum<true>, dim3(pl.nb), dim3(TPB_B), pl.bucket_lds_bytes, st, bp.packed.p, bp.off.p, N, pl.shift,
                                    idx->mag.p, idx->mag2.p, (const uint32_t*)idx->post_doc.p, idx->post_w.p, idf, head);
-    else hipLaunchKernelGGL(k_bucket_sum<false>, dim3(bp.nb), dim3(TPB_B), bucket_lds_bytes(bp.shift), st, bp.packed.p, bp.off.p, N, bp.shift,
+    else hipLaunchKernelGGL(k_bucket_sum<false>, dim3(pl.nb), dim3(TPB_B), pl.bucket_lds_bytes, st, bp.packed.p, bp.off.p, N, pl.shift,
                             idx->mag.p, idx->mag2.p, (const uint32_t*)idx->post_doc.p, idx->post_w.p, idf, head);
+}
+
+// What ss_tfidf_build and ss_index_refresh_magnitudes share: plan the table under the context's "tfidf.*" options, allocate what a
+// bucketed plan asks for (into the caller's `bp`: it lives until the caller has waited for the stream), then enqueue the pass over
+// idx->mag, which the caller has zeroed on the stream by the time begin() returns.  Large tables: the bucketed pass (no global float64 atomics).  Small ones: one atomic per posting — weight: k_weight,
+// which also multiplies w = tf*idf in place, otherwise k_sumsq_atomic — then the mag2 copy and the square roots.
+// begin() runs between the allocations and the first launch: whatever the caller wants in front of the device work.
+template <class Begin>
+int32_t magnitude_pass(ss_index* idx, hipStream_t st, BucketPass& bp, bool weight, const float* idf, Begin begin) {
+    ss_ctx* ctx = idx->ctx;
+    const uint64_t P = idx->n_post, T = idx->n_terms, N = idx->n_docs;
+    Options o;
+    o.blocks = ctx->opt("tfidf.blocks", o.blocks);
+    o.bucket_shift = ctx->opt("tfidf.bucket_shift", o.bucket_shift);
+    o.head_min_run = ctx->opt("tfidf.head_min_run", o.head_min_run);
+    o.bucket_min = ctx->opt("tfidf.bucket_min", o.bucket_min);
+    const Plan plan = make_plan(N, P, o);
+    if (plan.bucketed) SS_TRY(bucket_pass_prepare(ctx, P, plan, bp));
+    SS_TRY(begin());
+    if (plan.bucketed) {
+        bucket_pass_launch(idx, st, bp, weight, idf);
+        return SS_OK;
+    }
+    if (P && weight) hipLaunchKernelGGL(k_weight, dim3(ss::div_up(P, CH)), dim3(TPB), 0, st, idx->term_ptr.p, T, idx->post_doc.p,
+                                        idx->post_w.p, idf, P, idx->mag.p);
+    else if (P) hipLaunchKernelGGL(k_sumsq_atomic, dim3(std::min<unsigned>(ss::div_up(P, TPB), 16384u)), dim3(TPB), 0, st, (const uint32_t*)idx->post_doc.p,
+                                   (const float*)idx->post_w.p, P, idx->mag.p);
+    SS_HIP(ctx, hipMemcpyAsync(idx->mag2.p, idx->mag.p, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_sqrt, dim3(ss::div_up(N, TPB)), dim3(TPB), 0, st, idx->mag.p, N);
+    return SS_OK;
 }
 
 }  // namespace
 
 extern "C" {
-
-int32_t ss_index_create(ss_ctx* ctx, uint64_t n_docs, uint64_t n_terms, const uint64_t* term_ptr,
-                        const uint32_t* post_doc, const float* post_tf, ss_index** out) {
-    if (!ctx) return SS_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!out) return ctx->fail(SS_ERR_INVALID, "ss_index_create: out is NULL");
-    *out = nullptr;
-    if (!term_ptr) return ctx->fail(SS_ERR_INVALID, "ss_index_create: term_ptr is NULL");
-    if (n_docs == 0 || n_docs >= 0xFFFFFFF0ull || n_terms >= 0xFFFFFFF0ull)
-        return ctx->fail(SS_ERR_INVALID, "ss_index_create: n_docs/n_terms out of range");
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    std::unique_ptr<ss_index> idx(new (std::nothrow) ss_index());
-    if (!idx) return ctx->fail(SS_ERR_OOM, "ss_index_create: host OOM");
-    idx->ctx = ctx;
-    idx->n_docs = n_docs;
-    idx->n_terms = n_terms;
-    idx->h_term_ptr.resize(n_terms + 1);
-    SS_HIP(ctx, idx->term_ptr.alloc(n_terms + 1));
-    SS_HIP(ctx, hipMemcpyAsync(idx->term_ptr.p, term_ptr, (n_terms + 1) * sizeof(uint64_t), hipMemcpyDefault, st));
-    SS_HIP(ctx, hipMemcpyAsync(idx->h_term_ptr.data(), idx->term_ptr.p, (n_terms + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    if (idx->h_term_ptr[0] != 0) return ctx->fail(SS_ERR_INVALID, "ss_index_create: term_ptr[0] != 0");
-    const uint64_t P = idx->h_term_ptr[n_terms];
-    idx->n_post = P;
-    if (P && (!post_doc || !post_tf)) return ctx->fail(SS_ERR_INVALID, "ss_index_create: NULL postings");
-    SS_HIP(ctx, idx->post_doc.alloc(P));
-    SS_HIP(ctx, idx->post_w.alloc(P));
-    SS_HIP(ctx, idx->mag.alloc(n_docs));
-    SS_HIP(ctx, idx->mag2.alloc(n_docs));
-    if (P) {
-        SS_HIP(ctx, hipMemcpyAsync(idx->post_doc.p, post_doc, P * sizeof(uint32_t), hipMemcpyDefault, st));
-        SS_HIP(ctx, hipMemcpyAsync(idx->post_w.p, post_tf, P * sizeof(float), hipMemcpyDefault, st));
-    }
-    SS_HIP(ctx, hipMemsetAsync(idx->mag.p, 0, n_docs * sizeof(double), st));
-
-    // validation (the scorer relies on strictly ascending doc ids inside a term)
-    ss::DevBuf<unsigned long long> d_cnt;
-    ss::DevBuf<uint32_t> d_err;
-    SS_HIP(ctx, d_cnt.alloc(2));
-    SS_HIP(ctx, d_err.alloc(1));
-    SS_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
-    SS_HIP(ctx, hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), st));
-    if (n_terms) hipLaunchKernelGGL(k_check_ptr, dim3(ss::div_up(n_terms, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, n_terms,
-                                    idx->post_doc.p, d_cnt.p, d_err.p);
-    if (P) hipLaunchKernelGGL(k_check_docs, dim3(std::min<unsigned>(ss::div_up(P, TPB), 16384u)), dim3(TPB), 0, st,
-                              idx->post_doc.p, P, n_docs, d_cnt.p + 1, d_err.p);
-    unsigned long long h_cnt[2] = {0, 0};
-    uint32_t h_err = 0;
-    SS_HIP(ctx, ss::fetch(ctx, st, h_cnt, d_cnt.p, sizeof(h_cnt), &h_err, d_err.p, sizeof(h_err)));
-    SS_HIP(ctx, hipGetLastError());
-    if (h_err & 1) return ctx->fail(SS_ERR_INVALID, "ss_index_create: term_ptr is not non-decreasing");
-    if (h_err & 2) return ctx->fail(SS_ERR_INVALID, "ss_index_create: posting holds a doc id >= n_docs");
-    if (h_cnt[1] != h_cnt[0])
-        return ctx->fail(SS_ERR_UNSORTED, "ss_index_create: %llu posting(s) not strictly ascending by doc id inside a term",
-                         h_cnt[1] - h_cnt[0]);
-    *out = idx.release();
-    return SS_OK;
-}
-
-int32_t ss_index_destroy(ss_index* idx) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (idx->users > 0) return ctx->fail(SS_ERR_STATE, "ss_index_destroy: index still used by %d scorer(s)", idx->users);
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    delete idx;
-    return SS_OK;
-}
 
 int32_t ss_tfidf_build(ss_index* idx, uint64_t total_docs, float* w_out, double* mag_out, float* idf_out) {
     if (!idx) return SS_ERR_INVALID;
@@ -1100,30 +983,15 @@ int32_t ss_tfidf_build(ss_index* idx, uint64_t total_docs, float* w_out, double*
     // (a 5 GB hipMalloc inside the window once put ~1 s of host-side allocator time into the "kernel" time)
     ss::DevBuf<float> idf;
     SS_HIP(ctx, idf.alloc(T));
-    // large tables: bucketed magnitude pass (no global float64 atomics); small ones: one atomic per posting
-    int shift = 13;                                                   // 8192 docs per bucket = 64 KB of float64 LDS accumulators
-    shift = (int)std::max<int64_t>(10, std::min<int64_t>(14, ctx->opt("tfidf.bucket_shift", shift)));
-    if ((N >> shift) >= (uint64_t)NB_MAX) shift = 14;
-    const uint64_t nb64 = ss::div_up(std::max<uint64_t>(N, 1), (uint64_t)1 << shift);
-    // "tfidf.bucket_min" (tests, A/B): smallest table that takes the bucketed pass; a huge value forces the atomics
-    const uint64_t min_p = (uint64_t)ctx->opt("tfidf.bucket_min", (int64_t)1 << 22);
-    const bool bucketed = P >= std::max<uint64_t>(min_p, 1) && P < ((uint64_t)1 << 32) && nb64 <= (uint64_t)NB_MAX;
-    const uint32_t nb = (uint32_t)nb64;
     BucketPass bp;
-    if (bucketed) SS_TRY(bucket_pass_prepare(ctx, P, nb, shift, bp));
-    SS_HIP(ctx, hipStreamSynchronize(st));       // allocator work (and anything queued before) is over when the clock starts
-    SS_HIP(ctx, hipEventRecord(ctx->ev[2][0], st));
-    SS_HIP(ctx, hipMemsetAsync(idx->mag.p, 0, N * sizeof(double), st));
-    if (T) hipLaunchKernelGGL(k_idf, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p,
-                              idx->has_df_global ? idx->df_global.p : nullptr, T, (double)total_docs, idf.p);
-    if (bucketed) {
-        bucket_pass_launch(idx, st, bp, true, idf.p);
-    } else {
-        if (P) hipLaunchKernelGGL(k_weight, dim3(ss::div_up(P, CH)), dim3(TPB), 0, st, idx->term_ptr.p, T, idx->post_doc.p,
-                                  idx->post_w.p, idf.p, P, idx->mag.p);
-        SS_HIP(ctx, hipMemcpyAsync(idx->mag2.p, idx->mag.p, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_sqrt, dim3(ss::div_up(N, TPB)), dim3(TPB), 0, st, idx->mag.p, N);
-    }
+    SS_TRY(magnitude_pass(idx, st, bp, true, idf.p, [&]() -> int32_t {
+        SS_HIP(ctx, hipStreamSynchronize(st));   // allocator work (and anything queued before) is over when the clock starts
+        SS_HIP(ctx, hipEventRecord(ctx->ev[2][0], st));
+        SS_HIP(ctx, hipMemsetAsync(idx->mag.p, 0, N * sizeof(double), st));
+        if (T) hipLaunchKernelGGL(k_idf, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p,
+                                  idx->has_df_global ? idx->df_global.p : nullptr, T, (double)total_docs, idf.p);
+        return SS_OK;
+    }));
     idx->mag2_valid = true;
     SS_HIP(ctx, hipEventRecord(ctx->ev[2][1], st));
     ctx->ev_valid[2] = true;
@@ -1142,136 +1010,14 @@ int32_t ss_index_refresh_magnitudes(ss_index* idx, double* mag_out) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint64_t P = idx->n_post, N = idx->n_docs;
-    int shift = 13;                                                   // the same partition as ss_tfidf_build: option, clamp, switch to 14
-    shift = (int)std::max<int64_t>(10, std::min<int64_t>(14, ctx->opt("tfidf.bucket_shift", shift)));
-    if ((N >> shift) >= (uint64_t)NB_MAX) shift = 14;
-    const uint64_t nb64 = ss::div_up(std::max<uint64_t>(N, 1), (uint64_t)1 << shift);
-    const uint64_t min_p = (uint64_t)ctx->opt("tfidf.bucket_min", (int64_t)1 << 22);     // tests, A/B (as in ss_tfidf_build)
-    const bool bucketed = P >= std::max<uint64_t>(min_p, 1) && P < ((uint64_t)1 << 32) && nb64 <= (uint64_t)NB_MAX;
-    SS_HIP(ctx, hipMemsetAsync(idx->mag.p, 0, N * sizeof(double), st));
-    if (bucketed) {
-        BucketPass bp;
-        SS_TRY(bucket_pass_prepare(ctx, P, (uint32_t)nb64, shift, bp));
-        bucket_pass_launch(idx, st, bp, false, nullptr);
-        SS_HIP(ctx, hipGetLastError());
-        SS_HIP(ctx, hipStreamSynchronize(st));
-    } else {
-        if (P) hipLaunchKernelGGL(k_sumsq_atomic, dim3(std::min<unsigned>(ss::div_up(P, TPB), 16384u)), dim3(TPB), 0, st, (const uint32_t*)idx->post_doc.p,
-                                  (const float*)idx->post_w.p, P, idx->mag.p);
-        SS_HIP(ctx, hipMemcpyAsync(idx->mag2.p, idx->mag.p, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_sqrt, dim3(ss::div_up(N, TPB)), dim3(TPB), 0, st, idx->mag.p, N);
-        SS_HIP(ctx, hipGetLastError());
-    }
+    SS_HIP(ctx, hipMemsetAsync(idx->mag.p, 0, idx->n_docs * sizeof(double), st));
+    BucketPass bp;
+    SS_TRY(magnitude_pass(idx, st, bp, false, nullptr, []() -> int32_t { return SS_OK; }));
+    SS_HIP(ctx, hipGetLastError());
     idx->mag2_valid = true;
     idx->weighted = true;
-    if (mag_out) SS_HIP(ctx, hipMemcpyAsync(mag_out, idx->mag.p, N * sizeof(double), hipMemcpyDefault, st));
+    if (mag_out) SS_HIP(ctx, hipMemcpyAsync(mag_out, idx->mag.p, idx->n_docs * sizeof(double), hipMemcpyDefault, st));
     SS_HIP(ctx, hipStreamSynchronize(st));
-    return SS_OK;
-}
-
-int32_t ss_index_get_info(const ss_index* idx, uint64_t* n_docs, uint64_t* n_terms, uint64_t* n_post) {
-    if (!idx) return SS_ERR_INVALID;
-    if (n_docs) *n_docs = idx->n_docs;
-    if (n_terms) *n_terms = idx->n_terms;
-    if (n_post) *n_post = idx->n_post;
-    return SS_OK;
-}
-
-int32_t ss_index_read(ss_index* idx, uint64_t* term_ptr_out, uint32_t* post_doc_out, float* post_w_out) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (term_ptr_out) SS_HIP(ctx, hipMemcpyAsync(term_ptr_out, idx->term_ptr.p, (idx->n_terms + 1) * sizeof(uint64_t), hipMemcpyDefault, st));
-    if (post_doc_out && idx->n_post) SS_HIP(ctx, hipMemcpyAsync(post_doc_out, idx->post_doc.p, idx->n_post * sizeof(uint32_t), hipMemcpyDefault, st));
-    if (post_w_out && idx->n_post) SS_HIP(ctx, hipMemcpyAsync(post_w_out, idx->post_w.p, idx->n_post * sizeof(float), hipMemcpyDefault, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    return SS_OK;
-}
-
-int32_t ss_index_read_positions(ss_index* idx, uint64_t* pos_ptr_out, float* pos_out) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!idx->pos_ptr.p) return ctx->fail(SS_ERR_STATE, "ss_index_read_positions: the table holds no positional postings");
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (pos_ptr_out) SS_HIP(ctx, hipMemcpyAsync(pos_ptr_out, idx->pos_ptr.p, (idx->n_post + 1) * sizeof(uint64_t), hipMemcpyDefault, st));
-    if (pos_out && idx->pos.n) SS_HIP(ctx, hipMemcpyAsync(pos_out, idx->pos.p, idx->pos.n * sizeof(float), hipMemcpyDefault, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    return SS_OK;
-}
-
-int32_t ss_index_set_doc_freq(ss_index* idx, const uint64_t* df) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (idx->weighted) return ctx->fail(SS_ERR_STATE, "ss_index_set_doc_freq: table is already weighted");
-    if (!df) { idx->has_df_global = false; idx->df_global.release(); return SS_OK; }
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const uint64_t T = idx->n_terms;
-    SS_HIP(ctx, idx->df_global.alloc(T));
-    ss::DevBuf<uint32_t> err;
-    SS_HIP(ctx, err.alloc(1));
-    SS_HIP(ctx, hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
-    if (T) {
-        SS_HIP(ctx, hipMemcpyAsync(idx->df_global.p, df, T * sizeof(uint64_t), hipMemcpyDefault, st));
-        hipLaunchKernelGGL(k_check_df, dim3(ss::div_up(T, TPB)), dim3(TPB), 0, st, idx->term_ptr.p, idx->df_global.p, T, err.p);
-    }
-    uint32_t h_err = 0;
-    SS_HIP(ctx, ss::fetch(ctx, st, &h_err, err.p, sizeof(uint32_t)));
-    if (h_err) {
-        idx->df_global.release();
-        idx->has_df_global = false;
-        return ctx->fail(SS_ERR_INVALID, "ss_index_set_doc_freq: a document frequency is smaller than the local list");
-    }
-    idx->has_df_global = true;
-    return SS_OK;
-}
-
-int32_t ss_index_set_positions(ss_index* idx, const uint64_t* pos_ptr, const float* pos) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!pos_ptr) return ctx->fail(SS_ERR_INVALID, "ss_index_set_positions: pos_ptr is NULL");
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const uint64_t P = idx->n_post;
-    SS_HIP(ctx, idx->pos_ptr.alloc(P + 1));
-    SS_HIP(ctx, hipMemcpyAsync(idx->pos_ptr.p, pos_ptr, (P + 1) * sizeof(uint64_t), hipMemcpyDefault, st));
-    uint64_t ends[2] = {0, 0};
-    SS_HIP(ctx, ss::fetch(ctx, st, &ends[0], idx->pos_ptr.p, sizeof(uint64_t), &ends[1], idx->pos_ptr.p + P, sizeof(uint64_t)));
-    if (ends[0] != 0) { idx->pos_ptr.release(); return ctx->fail(SS_ERR_INVALID, "ss_index_set_positions: pos_ptr[0] != 0"); }
-    if (P) {
-        // monotone + first 0 + last = total  =>  every range lies inside pos[0, total)
-        ss::DevBuf<uint32_t> err;
-        SS_HIP(ctx, err.alloc(1));
-        SS_HIP(ctx, hipMemsetAsync(err.p, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_check_pos, dim3(std::min<unsigned>(ss::div_up(P, TPB), 16384u)), dim3(TPB), 0, st, idx->pos_ptr.p, P, err.p);
-        uint32_t h_err = 0;
-        SS_HIP(ctx, ss::fetch(ctx, st, &h_err, err.p, sizeof(uint32_t)));
-        if (h_err) { idx->pos_ptr.release(); return ctx->fail(SS_ERR_INVALID, "ss_index_set_positions: pos_ptr is not non-decreasing"); }
-    }
-    if (ends[1] && !pos) { idx->pos_ptr.release(); return ctx->fail(SS_ERR_INVALID, "ss_index_set_positions: pos is NULL"); }
-    SS_HIP(ctx, idx->pos.alloc(ends[1]));
-    if (ends[1]) SS_HIP(ctx, hipMemcpyAsync(idx->pos.p, pos, ends[1] * sizeof(float), hipMemcpyDefault, st));
-    SS_HIP(ctx, hipStreamSynchronize(st));
-    return SS_OK;
-}
-
-int32_t ss_index_set_weighted(ss_index* idx, const double* mag) {
-    if (!idx) return SS_ERR_INVALID;
-    ss_ctx* ctx = idx->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!mag) return ctx->fail(SS_ERR_INVALID, "ss_index_set_weighted: mag is NULL");
-    SS_HIP(ctx, hipSetDevice(ctx->device));
-    SS_HIP(ctx, hipMemcpyAsync(idx->mag.p, mag, idx->n_docs * sizeof(double), hipMemcpyDefault, ctx->stream));
-    SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    idx->weighted = true;
-    idx->mag2_valid = false;       // given magnitudes: their squares are not the exact sums an incremental update needs
     return SS_OK;
 }
 

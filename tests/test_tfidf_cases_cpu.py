@@ -9,18 +9,15 @@
     one posting.
   * oracle.tfidf (C) and oracle_np.tfidf (numpy), two restatements of term_weighting.go, agree bit for bit on every case when the
     numpy one is given the C oracle's idf.
-  * The model's constants are the ones in csrc/tfidf.hip.
+  * The model's constants are the ones in csrc/tfidf_plan.hpp.
 """
-import os
-import re
-
 import numpy as np
 import pytest
 
 from tests import tfidf_cases as tc
+from tests import tfidf_plan
 
 _REACHED = {}          # case name -> paths reached (model + oracle values); read by test_every_path_has_a_case
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spaghettisearch_amd", "csrc", "tfidf.hip")
 
 
 def bits(a):
@@ -34,31 +31,16 @@ def same_bits_or_nan(got, want):
     return np.array_equal(np.isnan(got), nan) and np.array_equal(bits(got)[~nan], bits(want)[~nan])
 
 
-def test_constants_match_the_source():
-    text = open(SRC).read()
-    env = {}
-    for m in re.finditer(r"^\s*#define\s+(SS_\w+)\s+(.+?)\s*$", text, re.M):
-        env.setdefault(m.group(1), m.group(2))
-    for m in re.finditer(r"^\s*constexpr int (\w+) = ([^;]+);", text, re.M):
-        env.setdefault(m.group(1), m.group(2))
-
-    def val(name):
-        expr = env[name]
-        for _ in range(8):
-            expr = re.sub(r"[A-Za-z_]\w*", lambda m: f"({env[m.group(0)]})", expr)
-        return eval(expr.replace("/", "//"), {"__builtins__": {}})
-
-    got = {n: val(n) for n in ("CH", "SC_CH", "SC_TPB", "SC_PT", "SC_WIN", "NB_MAX", "HEAD_CAP", "HEAD_LEVELS", "HEAD_PIECE")}
-    got["SC_PF"] = val("SC_PF") * val("SC_TPB")
+def test_constants_match_the_source(tmp_path):
+    """The model's constants are the ones the compiled header holds (tests/tfidf_plan_harness.cpp prints them); the host arithmetic the
+    model restates is held against the header's, line by line, in tests/test_tfidf_plan_cpu.py."""
+    got, _, _ = tfidf_plan.run(tfidf_plan.build(tmp_path))
+    got["SC_PF"] *= got["SC_TPB"]                                            # (entries per thread -> the largest window the prefetch takes)
     want = {n: getattr(tc, n) for n in got}
     print(got)
     assert got == want
+    assert set(got) == {"CH", "SC_CH", "SC_TPB", "SC_PT", "SC_WIN", "SC_PF", "SC_BPT_MAX", "NB_MAX", "HEAD_CAP", "HEAD_LEVELS", "HEAD_PIECE"}
     assert (tc.CH, tc.SC_CH, tc.SC_TPB, tc.NB_MAX, tc.HEAD_CAP, tc.HEAD_LEVELS, tc.HEAD_PIECE) == (4096, 8192, 1024, 4096, 1024, 24, 2048)
-    # the host arithmetic the model restates
-    for line in ('ctx->opt("tfidf.blocks", 4096)', 'ctx->opt("tfidf.head_min_run", 64)', "2 * unit + 1", 'ctx->opt("tfidf.bucket_min", (int64_t)1 << 22)',
-                 "if ((N >> shift) >= (uint64_t)NB_MAX) shift = 14;"):
-        assert line in text, line
-    assert text.count('ctx->opt("tfidf.bucket_shift", shift)') == 2          # the build and the magnitudes-only pass partition alike
 
 
 def check_case(oracle, name):

@@ -1,4 +1,4 @@
-"""Tables built to reach the partition paths of the TF-IDF build (csrc/tfidf.hip), and a model that says which they reach.
+"""Tables built to reach the partition paths of the TF-IDF build (csrc/tfidf.hip, csrc/tfidf_plan.hpp), and a model that says which they reach.
 
 No GPU and no library here: numpy only.
 
@@ -6,8 +6,8 @@ No GPU and no library here: numpy only.
     options the case runs under ("tfidf.*") and, for a table that stands for one doc-range shard, "df_extra": per term the number of
     postings the term has on other shards (df_global = local length + df_extra).  `expect_paths` names the paths the case is
     built for.
-  * paths(n_docs, term_ptr, post_doc, options): a plain restatement of the HOST arithmetic of bucket_pass_prepare / ss_tfidf_build
-    (shift, bucket count, block ranges, head threshold and level) plus a walk over the chunks of every block that follows the
+  * paths(n_docs, term_ptr, post_doc, options): a plain restatement of the HOST arithmetic of csrc/tfidf_plan.hpp (geometry():
+    shift, bucket count, block ranges, head threshold; tests/test_tfidf_plan_cpu.py holds it against the header) and of the head level, plus a walk over the chunks of every block that follows the
     control flow of k_scatter<true> (head ranges, head-only chunks, the term window and where it starts).  It computes no weight and
     no magnitude: expectations come from the oracle alone.
   * value_paths(...): which float32 edges the ORACLE's results of a case show (zero / denormal / overflowing squares, idf <= 0).
@@ -22,7 +22,8 @@ from fractions import Fraction
 
 import numpy as np
 
-# ---- the constants of tfidf.hip the model relies on (test_tfidf_cases_cpu.py reads them out of the source text) ----------------
+# ---- the constants of csrc/tfidf_plan.hpp the model relies on (test_tfidf_cases_cpu.py holds them against the ones the header's
+# ---- harness prints) ------------------------------------------------------------------------------------------------------------
 CH = 4096                 # postings per chunk of k_weight_count (and k_weight)
 SC_CH = 8192              # postings per chunk of k_scatter
 SC_TPB = 1024             # threads of a k_scatter block (one probe of the coarse window search each)
@@ -30,6 +31,7 @@ SC_PT = SC_CH // SC_TPB   # consecutive postings per thread
 SC_WIN = SC_CH            # most window entries staged per chunk
 SC_PF = 1024              # largest window the prefetch takes
 NB_MAX = 4096
+SC_BPT_MAX = NB_MAX // SC_TPB   # most buckets an owner thread of k_scatter keeps cursors for
 HEAD_CAP = 1024
 HEAD_LEVELS = 24
 HEAD_PIECE = 2048
@@ -49,7 +51,7 @@ def _div_up(a, b):
 
 
 def geometry(n_docs, n_post, options):
-    """bucket_pass_prepare / ss_tfidf_build, host side."""
+    """make_plan of csrc/tfidf_plan.hpp, restated.  The fields behind "bucketed" exist for bucketed tables only."""
     o = lib_options(options)
     N, P = int(n_docs), int(n_post)
     shift = max(10, min(14, o.get("tfidf.bucket_shift", 13)))
@@ -57,7 +59,7 @@ def geometry(n_docs, n_post, options):
     if forced:
         shift = 14
     nb = _div_up(max(N, 1), 1 << shift)
-    min_p = o.get("tfidf.bucket_min", 1 << 22)
+    min_p = o.get("tfidf.bucket_min", 1 << 22) % (1 << 64)       # the library reads the option as uint64: a negative value is a huge one
     g = {"shift": shift, "shift_forced": forced, "nb": nb,
          "bucketed": P >= max(min_p, 1) and P < (1 << 32) and nb <= NB_MAX}
     if not g["bucketed"]:
@@ -66,8 +68,11 @@ def geometry(n_docs, n_post, options):
     blocks = max(1, o.get("tfidf.blocks", 4096))
     per = max(unit, _div_up(_div_up(P, blocks), unit) * unit)
     min_run = o.get("tfidf.head_min_run", 64)
-    g.update(per=per, nblk=_div_up(P, per), bpt=(_div_up(nb, SC_TPB) + 1) & ~1, nbt=(nb + 1) & ~1,
-             head_thr=max(min_run * nb, 2 * unit + 1) if min_run > 0 else 0)
+    bpt, nbt = (_div_up(nb, SC_TPB) + 1) & ~1, (nb + 1) & ~1
+    g.update(per=per, nblk=_div_up(P, per), bpt=bpt, nbt=nbt,
+             head_thr=max(min_run * nb, 2 * unit + 1) if min_run > 0 else 0,
+             bpt_inst=2 if bpt <= 2 else 4 if bpt <= 4 else SC_BPT_MAX, too_many_buckets=bpt > SC_BPT_MAX,
+             scatter_lds_bytes=SC_CH * 8 + nbt * 8 + 64, bucket_lds_bytes=(1 << shift) * 8 + (3 * HEAD_CAP + 4) * 4)
     return g
 
 
