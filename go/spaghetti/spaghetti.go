@@ -1181,6 +1181,142 @@ func (s *Scorer) RerankHitsByVector(qvec []int8, hits [][]Hit, first, k int) ([]
 	return out, outVals, nil
 }
 
+// FuseParams says how FuseHits / HybridTopK merge the two rankings (ss_fuse_params): Mode C.SS_FUSE_RRF (wLex/(RrfC+lexical rank) +
+// wVec/(RrfC+vector rank)) or C.SS_FUSE_WEIGHTED (wLex*FinalRank + wVec*vector score).
+type FuseParams struct {
+	Mode, RrfC int
+	WLex, WVec float64
+}
+
+// FusedHit is one row of a fused page: the completed lexical row, its fused score, its vector score and its 1-based rank in each
+// list (0: the list does not hold the doc).
+type FusedHit struct {
+	Hit
+	Score            float64
+	VecScore         int32
+	LexRank, VecRank uint16
+}
+
+// FusedPage is one page of a query's fused ranking; Union = the distinct docs of both lists.
+type FusedPage struct {
+	Hits  []FusedHit
+	Union int
+}
+
+func fusedPages(nq, kk int, raw []C.ss_hit, fused []C.ss_fused, nHits, union []int32) []FusedPage {
+	out := make([]FusedPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q].Union = int(union[q])
+		out[q].Hits = make([]FusedHit, n)
+		for i := 0; i < n; i++ {
+			r, f := raw[q*kk+i], fused[q*kk+i]
+			out[q].Hits[i] = FusedHit{Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)},
+				float64(f.score), int32(f.vec_score), uint16(f.lex_rank), uint16(f.vec_rank)}
+		}
+	}
+	return out
+}
+
+// ScoreDocs returns the row that query q's ranking holds for every doc of docs[q], whether or not the doc would reach any top-k
+// (ss_score_docs): FinalRank for the output of VectorTopK, SimilarTopK or GraphHitLinks.  A doc outside the tables gives a zero row.
+func (s *Scorer) ScoreDocs(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, docs [][]uint32) ([][]Hit, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 || len(docs) != nq {
+		return nil, nil
+	}
+	kIn := 1
+	for q := 0; q < nq; q++ {
+		if len(docs[q]) > kIn {
+			kIn = len(docs[q])
+		}
+	}
+	in, nIn := make([]uint32, nq*kIn), make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nIn[q] = int32(len(docs[q]))
+		copy(in[q*kIn:], docs[q])
+	}
+	raw := make([]C.ss_hit, nq*kIn)
+	rc := C.ss_score_docs(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), C.int32_t(kIn), u32p(in), i32p(nIn),
+		(*C.ss_hit)(unsafe.Pointer(&raw[0])))
+	if err := statusErr(s.ctx, rc, "ss_score_docs"); err != nil {
+		return nil, err
+	}
+	out := make([][]Hit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Hit, len(docs[q]))
+		for i := range out[q] {
+			r := raw[q*kIn+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
+// FuseHits merges the lexical list lex[q] and the vector list vec[q] of every query into one ranking by fp and returns page
+// [first, first+k) (ss_fuse_hits).  A doc only one list holds is completed on the device: its lexical row as ScoreDocs gives it, its
+// vector score as HitVectorScores does; the rows given are trusted.
+func (s *Scorer) FuseHits(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, qvec []int8, lex [][]Hit, vec [][]VecHit,
+	fp FuseParams, first, k int) ([]FusedPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 || len(lex) != nq || len(vec) != nq {
+		return nil, nil
+	}
+	in, nLex, kLex := vecWindow(lex)
+	kVec := 1
+	for q := 0; q < nq; q++ {
+		if len(vec[q]) > kVec {
+			kVec = len(vec[q])
+		}
+	}
+	vin, nVec := make([]C.ss_vec_hit, nq*kVec), make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nVec[q] = int32(len(vec[q]))
+		for j, v := range vec[q] {
+			vin[q*kVec+j] = C.ss_vec_hit{doc: C.uint32_t(v.Doc), score: C.int32_t(v.Score)}
+		}
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	cfp := C.ss_fuse_params{mode: C.int32_t(fp.Mode), rrf_c: C.int32_t(fp.RrfC), w_lex: C.double(fp.WLex), w_vec: C.double(fp.WVec)}
+	raw, fused := make([]C.ss_hit, nq*kk), make([]C.ss_fused, nq*kk)
+	nHits, union := make([]int32, nq), make([]int32, nq)
+	rc := C.ss_fuse_hits(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), i8p(qvec), C.int32_t(kLex),
+		(*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nLex), C.int32_t(kVec), (*C.ss_vec_hit)(unsafe.Pointer(&vin[0])), i32p(nVec),
+		(*C.ss_fuse_params)(unsafe.Pointer(&cfp)), C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits),
+		(*C.ss_fused)(unsafe.Pointer(&fused[0])), i32p(union))
+	if err := statusErr(s.ctx, rc, "ss_fuse_hits"); err != nil {
+		return nil, err
+	}
+	return fusedPages(nq, kk, raw, fused, nHits, union), nil
+}
+
+// HybridTopK = ScoreTopKMasked without phrases and VectorTopK, both at k = kWindow under maskID (nil = none), then FuseHits on
+// their rows, in one library call: neither window leaves the device (ss_hybrid_topk).
+func (s *Scorer) HybridTopK(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, qvec []int8, maskID []int32, kWindow int,
+	fp FuseParams, first, k int) ([]FusedPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	cfp := C.ss_fuse_params{mode: C.int32_t(fp.Mode), rrf_c: C.int32_t(fp.RrfC), w_lex: C.double(fp.WLex), w_vec: C.double(fp.WVec)}
+	raw, fused := make([]C.ss_hit, nq*kk), make([]C.ss_fused, nq*kk)
+	nHits, union := make([]int32, nq), make([]int32, nq)
+	rc := C.ss_hybrid_topk(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), i8p(qvec), i32p(maskID),
+		C.int32_t(kWindow), (*C.ss_fuse_params)(unsafe.Pointer(&cfp)), C.int32_t(first), C.int32_t(k),
+		(*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), (*C.ss_fused)(unsafe.Pointer(&fused[0])), i32p(union))
+	if err := statusErr(s.ctx, rc, "ss_hybrid_topk"); err != nil {
+		return nil, err
+	}
+	return fusedPages(nq, kk, raw, fused, nHits, union), nil
+}
+
 // ScoreTopKConstrained = ScoreTopKMasked with query operators: reqPtr/reqTerms name each query's required terms ("+word": every
 // result contains it, title or body), excPtr/excTerms its excluded ones ("-word": no result does); nil pointers = none.  The
 // constraint terms only filter; put a required word in qTerms too for it to be scored.

@@ -51,7 +51,9 @@ extern "C" {
  * SS_MAX_DOC_FIELDS, SS_MAX_RANGE_CLAUSES, SS_NO_FIELD_VALUE, ss_doc_range, ss_scorer_set_doc_fields, ss_doc_field_masks,
  * ss_score_topk_filtered, ss_sort_hits_by_field and ss_hit_fields (per-doc integer fields: range filters, sort by field, read-out);
  * SS_MAX_VEC_DIM, SS_NO_VEC_SCORE, ss_vec_hit, ss_scorer_set_doc_vectors, ss_vector_topk, ss_hit_vector_scores and
- * ss_rerank_hits_by_vector (one int8 vector per doc: exact nearest neighbours by integer dot product, a window re-ranked by it). */
+ * ss_rerank_hits_by_vector (one int8 vector per doc: exact nearest neighbours by integer dot product, a window re-ranked by it);
+ * SS_FUSE_RRF / _WEIGHTED, ss_fuse_params, ss_fused, ss_score_docs, ss_fuse_hits and ss_hybrid_topk (the lexical row of any given doc,
+ * a lexical and a vector list fused into one ranked, paged list, and both searches plus the fusion in one call). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -861,6 +863,87 @@ int32_t ss_hit_vector_scores(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_
 int32_t ss_rerank_hits_by_vector(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, int32_t k_in,
                                  const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
                                  ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
+
+/* Hybrid search: the lexical and the vector ranking of one query fused into one ranked, paged list, and the lexical row of ANY given
+ * doc.  No reference counterpart.  Until here the two rankings could only be bridged by ss_rerank_hits_by_vector, which reorders docs
+ * the lexical call found: a page that matches the meaning of a query but holds none of its words never stood beside the lexical hits.
+ *
+ * ss_score_docs: the row that query q's ranking holds for doc d, whether or not d would reach any top-k.  Defined bit for bit:
+ *   Sums.       T = the sum of (double)title_w(t, d) and B = the sum of (double)body_w(t, d) over the query's tokens IN THE ORDER GIVEN,
+ *               each starting from 0.0; a token that occurs twice is added twice; a token equal to SS_UNKNOWN_TERM or at / above
+ *               n_terms adds nothing; a missing posting adds nothing.  (The order of oracle_np.score_topk's np.add.at.  The merge
+ *               of ss_score_topk adds a repeated token's weight times its count, in first-occurrence order and through atomics: the
+ *               same value wherever those sums are exact.)
+ *   Row.        title, body and final are final_rank (get_metadata.go:53-69) of T, B, the magnitudes, qmag = sqrt((double)query_len[q])
+ *               (query_len NULL: the token count) and sqd; a field in which the doc has no posting of any token takes magnitude 1.0, as
+ *               in the merge, so a doc with no posting at all has title = body = 0.0 and final = (0.33 * sqd + 0.0 + 0.0) * 100.0.
+ *               sqd = pagerank = topic_dot in topic order; 0.0 when topic_probs is NULL or no prior is registered.
+ *   Output.     hits_out[q * k_in + j] for j < n_in[q] = that row of doc docs[q * k_in + j], _pad 0.  A doc at or above n_docs gives
+ *               an all-zero row with .doc set to the given id, and no table is read.  Entries past n_in[q] are left untouched.
+ *   No phrases, masks or operators: those decide WHICH docs rank, not a doc's row.
+ * Checks, all before anything is enqueued and with the output untouched: NULL handle or q_ptr (or docs / n_in / hits_out, or q_terms
+ * with tokens, with n_q > 0), n_q < 0, k_in < 1, a q_ptr that decreases: SS_ERR_INVALID; k_in > SS_MAX_TOPK, n_q * k_in >= 2^31:
+ * SS_ERR_UNSUPPORTED; n_in[q] outside [0, k_in]: SS_ERR_INVALID when n_in is host memory, clamped by the kernel when it is device
+ * memory.  n_q == 0 is SS_OK and does nothing.  The query arrays (q_ptr, q_terms, query_len, topic_probs) are read on the host like
+ * every query array; docs, n_in and hits_out may be host or device memory: with all three on the device the call only enqueues on the
+ * ctx stream and NEVER waits, otherwise it stages through blocks the scorer owns and returns when the output is written.
+ * k_score_docs: 16 lanes per (query, doc); a lane searches one (token, field) list (the merge's interpolation search), then every lane
+ * of the group adds the weights found in token order: no atomics. */
+int32_t ss_score_docs(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
+                      const double* topic_probs, int32_t k_in, const uint32_t* docs /*[n_q][k_in]*/, const int32_t* n_in /*[n_q]*/,
+                      ss_hit* hits_out /*[n_q][k_in]*/);
+
+/* ss_fuse_hits: two ranked lists of one query fused into one.  Defined bit for bit, per query q:
+ *   Lists.      The lexical list is lex[q * k_lex .. + n_lex[q]), the vector list vec[q * k_vec .. + n_vec[q]), each in the order given.
+ *   Ranks.      A doc's rank in a list is 1 + the position of its FIRST occurrence; later occurrences are ignored.  Rows with doc at
+ *               or above n_docs are ignored but keep their position: ranks are positions.  A doc absent from a list has rank 0.
+ *   Candidates. The distinct valid docs of both lists; n_union_out[q] (nullable) = their number (at most k_lex + k_vec).
+ *   Rows.       Every candidate gets a full row: its ss_hit is the 40 bytes given in lex (the first occurrence) if it has a lexical
+ *               rank, else the row ss_score_docs returns for it; its vec_score is the .score given in vec (the first occurrence) if it
+ *               has a vector rank, else score(q, d) as ss_hit_vector_scores defines it.  Given rows are trusted, not recomputed.
+ *   Score.      Every operation rounded once, nothing contracted:
+ *               SS_FUSE_RRF       (lex_rank ? w_lex / (double)(rrf_c + lex_rank) : 0.0) + (vec_rank ? w_vec / (double)(rrf_c + vec_rank) : 0.0)
+ *                                 (the sum rrf_c + rank in 64-bit integers);
+ *               SS_FUSE_WEIGHTED  w_lex * row.final + w_vec * (double)vec_score.  The caller scales w_vec to its embedding.
+ *   Order.      Score descending by numeric comparison (-0.0 ties 0.0), then doc ascending; a NaN score comes last, NaN rows by doc
+ *               ascending among themselves.
+ *   Output.     With the ordered candidates S_0 .. S_{n-1}: hits_out[q * k + r] = the row of S_{first + r} for r < n_hits_out[q] =
+ *               clamp(n - first, 0, k), as in ss_collapse_hits; fused_out[q * k + r] (nullable) = its score, vec_score and the two
+ *               ranks.  A NaN score is stored as the quiet NaN 0x7FF8000000000000, whatever operation made it; every other score as
+ *               computed (-0.0 stays -0.0).  Entries past n_hits_out[q] are left untouched.
+ * Checks, all before anything is enqueued and with the outputs untouched: NULL handle, q_ptr or fp, n_q < 0, (with n_q > 0) NULL qvec,
+ * lex, n_lex, vec, n_vec, hits_out or n_hits_out, a mode other than the two, rrf_c < 1, a w_lex or w_vec that is not finite, k_lex,
+ * k_vec or k below 1, first < 0, hits_out overlapping lex as address ranges, a q_ptr that decreases: SS_ERR_INVALID; k_lex, k_vec or k
+ * above SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no vector table registered: SS_ERR_STATE; n_lex[q] outside [0, k_lex] or n_vec[q] outside
+ * [0, k_vec]: SS_ERR_INVALID when the count array is host memory, clamped by the kernel when it is device memory.  n_q == 0 is SS_OK
+ * and does nothing.  The query arrays are read on the host; qvec, the lists, their counts and the outputs may each be host or device
+ * memory: with all of them on the device the call only enqueues on the ctx stream and NEVER waits, so hybrid -> dedup -> collapse ->
+ * explain -> passages chains on one stream; otherwise it stages through blocks the scorer owns and returns when the outputs are
+ * written.  Four launches whose sizes depend on nothing read back: k_fuse_hits (one workgroup per query: (doc, list, position) keys
+ * sorted in LDS, ranks and the docs that lack a side), k_score_docs and k_vec_hit_scores over those docs, k_fuse_page (scores, the sort
+ * of up to 2048 keys, the page).  Serialised on the ctx like every scoring call; no _submit / _collect form.
+ *
+ * ss_hybrid_topk: row q = what ss_fuse_hits returns when lex is the row ss_score_topk_masked returns for q at k = k_window (no phrase,
+ * this query_len, topic_probs and mask_id[q]) and vec the row ss_vector_topk returns for q at k = k_window under the same mask_id[q].
+ * Both windows stay in memory the scorer owns, as in ss_score_topk_collapsed; only the page is written.  The checks are those of
+ * ss_fuse_hits (k_window in the place of k_lex and k_vec) and, behind them, those of the two calls it makes; with qvec and the outputs
+ * in device memory the call never waits. */
+#define SS_FUSE_RRF      0   /* reciprocal rank fusion */
+#define SS_FUSE_WEIGHTED 1   /* weighted sum of FinalRank and the vector score */
+typedef struct ss_fuse_params { int32_t mode; int32_t rrf_c; double w_lex; double w_vec; } ss_fuse_params;   /* 24 bytes */
+typedef struct ss_fused { double score; int32_t vec_score; uint16_t lex_rank; uint16_t vec_rank; } ss_fused;   /* 16 bytes; rank 0 = absent */
+int32_t ss_fuse_hits(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
+                     const double* topic_probs, const int8_t* qvec /*[n_q][dim]*/,
+                     int32_t k_lex, const ss_hit* lex /*[n_q][k_lex]*/, const int32_t* n_lex /*[n_q]*/,
+                     int32_t k_vec, const ss_vec_hit* vec /*[n_q][k_vec]*/, const int32_t* n_vec /*[n_q]*/,
+                     const ss_fuse_params* fp, int32_t first, int32_t k,
+                     ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                     ss_fused* fused_out /*[n_q][k], nullable*/, int32_t* n_union_out /*[n_q], nullable*/);
+int32_t ss_hybrid_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const int32_t* query_len,
+                       const double* topic_probs, const int8_t* qvec /*[n_q][dim]*/, const int32_t* mask_id /*[n_q], NULL = none*/,
+                       int32_t k_window, const ss_fuse_params* fp, int32_t first, int32_t k,
+                       ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                       ss_fused* fused_out /*[n_q][k], nullable*/, int32_t* n_union_out /*[n_q], nullable*/);
 
 /* ---- term lexicon: cmd/server/server.go:54-85 (/wordlist/{pre}), database/database.go:414-454 (IterateInv) -------------
  * The words of forw[0] keyed by dense term id, resident on the device.  The reference answers /wordlist/{pre} by walking every key

@@ -31,6 +31,8 @@ SS_MAX_RANGE_CLAUSES = 4
 SS_NO_FIELD_VALUE = -(2 ** 63)
 SS_MAX_VEC_DIM = 1024
 SS_NO_VEC_SCORE = -(2 ** 31)
+SS_FUSE_RRF = 0
+SS_FUSE_WEIGHTED = 1
 
 ERR_NAMES = {0: "SS_OK", 1: "SS_ERR_INVALID", 2: "SS_ERR_NO_DEVICE", 3: "SS_ERR_HIP", 4: "SS_ERR_OOM",
              5: "SS_ERR_UNSORTED", 6: "SS_ERR_STATE", 7: "SS_ERR_UNSUPPORTED", 8: "SS_ERR_COMM"}
@@ -62,6 +64,14 @@ class SsDocRange(C.Structure):
 
 class SsVecHit(C.Structure):
     _fields_ = [("doc", C.c_uint32), ("score", C.c_int32)]
+
+
+class SsFuseParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("rrf_c", C.c_int32), ("w_lex", C.c_double), ("w_vec", C.c_double)]
+
+
+class SsFused(C.Structure):
+    _fields_ = [("score", C.c_double), ("vec_score", C.c_int32), ("lex_rank", C.c_uint16), ("vec_rank", C.c_uint16)]
 
 
 class SsGraphInfo(C.Structure):
@@ -161,6 +171,9 @@ PROTOTYPES = {
     "ss_vector_topk": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_hit_vector_scores": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ss_rerank_hits_by_vector": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ss_score_docs": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ss_fuse_hits": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_hybrid_topk": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_lexicon_create": (_i32, [_vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "ss_lexicon_set_freq": (_i32, [_vp, _vp]),
     "ss_lexicon_get_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),

@@ -44,6 +44,15 @@ uint32_t field_mask_docs();                     // docs of one workgroup
 uint32_t field_mask_group();                    // sets that share one read of the field columns
 void launch_field_masks(const void* params, hipStream_t st);
 }  // namespace ss
+struct ss_scorer;
+namespace ss {
+// vector.hip, for hybrid.hip: the query vectors as the vector kernels load them (ss_vector_topk's staging: *staged is set when they
+// came from host memory, so the call waits before it returns), and k_vec_hit_scores as ss_hit_vector_scores launches it over rows
+// and counts in device memory
+int32_t vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged);
+void launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in,
+                           int32_t* d_out, hipStream_t st);
+}  // namespace ss
 
 // Where a scoring call left its rows when they stay inside the scorer (ss::score_into_turn): the block of the plan turn the call took.
 // The block is that turn's until the turn comes round again, i.e. until the scorer has waited for the turn's batch_ev: whoever reads it
@@ -182,6 +191,18 @@ struct ss_scorer {
     int vec_lds_attr[5] = {0, 0, 0, 0, 0};
     ss::DevBuf<ss_vec_hit> d_vec_hits;
     ss::DevBuf<ss_hit> d_hits;
+    // ss_score_docs / ss_fuse_hits / ss_hybrid_topk (hybrid.hip).  hyb: the turns the queries' table goes up through, as exp / pas.
+    // The blocks, grow-only, written and read on the context's stream only: the device copies of HOST docs / vec / n_vec (the call
+    // waits before it returns, as with HitWindowBlocks); between k_fuse_hits and k_fuse_page the candidates [n_q][3][k_lex + k_vec]
+    // (doc | lex_rank + vec_rank << 16 | slot) and the counts [3][n_q] (union, docs without a lexical row, docs without a vector
+    // score), those docs, their rows from k_score_docs and their scores from k_vec_hit_scores (whose input rows carry .doc only);
+    // ss_hybrid_topk's vector window.
+    QueryTurn hyb[TURNS];
+    int hyb_turn = 0;
+    ss::DevBuf<uint32_t> d_hyb_docs_in, d_hyb_cand, d_hyb_miss_docs;
+    ss::DevBuf<ss_vec_hit> d_hyb_vec_in, d_hyb_vec_win;
+    ss::DevBuf<int32_t> d_hyb_nvec_in, d_hyb_counts, d_hyb_miss_scores, d_hyb_nvec_win;
+    ss::DevBuf<ss_hit> d_hyb_miss_rows, d_hyb_miss_vec_rows;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

@@ -610,6 +610,18 @@ int32_t rerank_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in,
 
 }  // namespace
 
+// for hybrid.hip (scorer.hpp): the staging of the query vectors and the launch of k_vec_hit_scores, both as the calls above use them
+int32_t ss::vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged) {
+    return qvec_to_device(s, qvec, bytes, out, staged);
+}
+void ss::launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in,
+                               int32_t* d_out, hipStream_t st) {
+    hw::WindowIn w;
+    w.hits = d_hits;
+    w.n_hits = d_n_hits;
+    launch_hit_scores(s, d_qvec, w, n_q, k_in, d_out, st);
+}
+
 extern "C" {
 
 int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec) {

@@ -25,6 +25,9 @@ DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("
 
 VEC_HIT_DTYPE = np.dtype([("doc", "<u4"), ("score", "<i4")])   # ss_vec_hit
 
+FUSED_DTYPE = np.dtype([("score", "<f8"), ("vec_score", "<i4"), ("lex_rank", "<u2"), ("vec_rank", "<u2")])   # ss_fused
+FUSE_RRF, FUSE_WEIGHTED = 0, 1                                  # SS_FUSE_RRF, SS_FUSE_WEIGHTED
+
 _NP2T = {"uint64": "int64", "uint32": "int32"}
 
 
@@ -1154,6 +1157,108 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_sc
 
+    @staticmethod
+    def _fuse_params(mode: int, rrf_c: int, w_lex: float, w_vec: float):
+        from ._lib import SsFuseParams
+        return SsFuseParams(int(mode), int(rrf_c), float(w_lex), float(w_vec))
+
+    def _fuse_out(self, n_q: int, k: int, out, want_fused: bool, want_union: bool, like=None):
+        """(hits, n_hits, fused | None, n_union | None): the caller's arrays, or fresh numpy ones"""
+        if out is None:
+            out = (np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                   np.zeros((n_q, k), dtype=FUSED_DTYPE) if want_fused else None, np.zeros(n_q, dtype=np.int32) if want_union else None)
+        o_hits, o_n, o_fused, o_union = out
+        o_n, o_union = _as(o_n, "int32"), _as(o_union, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if k > 0 and (nbytes(o_hits) < n_q * k * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4
+                      or (o_fused is not None and nbytes(o_fused) < n_q * k * FUSED_DTYPE.itemsize)
+                      or (o_union is not None and nbytes(o_union) < n_q * 4)):
+            raise ValueError("output buffers too small")
+        return o_hits, o_n, o_fused, o_union
+
+    def score_docs(self, q_ptr, q_terms, docs, n_in=None, query_len=None, topic_probs=None, out=None):
+        """ss_score_docs: the row that query q's ranking holds for every doc docs[q][: n_in[q]], whether or not it would reach any
+        top-k -> hits HIT_DTYPE [n_q][k_in] (a doc outside the table: a zero row with its id; rows past n_in[q] keep what the array
+        held, zeros here).  docs uint32 [n_q][k_in] and n_in int32 [n_q] (None: all k_in), numpy or torch; out: the caller's array.
+        With docs, n_in and out on the device the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        docs = _as(docs, "uint32")
+        n_q = int(q_ptr.shape[0]) - 1
+        if docs.ndim != 2 or int(docs.shape[0]) != n_q:
+            raise ValueError(f"docs must have shape [{n_q}][k_in], got {tuple(docs.shape)}")
+        k_in = int(docs.shape[1])
+        if n_in is None:
+            n_in = np.full(n_q, k_in, dtype=np.int32)
+        n_in = _as(n_in, "int32")
+        if out is None:
+            out = np.zeros((n_q, k_in), dtype=HIT_DTYPE)
+        elif (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) < n_q * k_in * HIT_DTYPE.itemsize:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, docs, n_in, out)
+        check(self.ctx.lib.ss_score_docs(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), k_in, _ptr(docs),
+                                         _ptr(n_in), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return out
+
+    def fuse_hits(self, q_ptr, q_terms, qvec, lex, n_lex, vec, n_vec, k: int, mode: int = FUSE_RRF, rrf_c: int = 60, w_lex: float = 1.0,
+                  w_vec: float = 1.0, first: int = 0, k_lex: Optional[int] = None, k_vec: Optional[int] = None, query_len=None,
+                  topic_probs=None, out=None, want_fused: bool = True, want_union: bool = True):
+        """ss_fuse_hits: the lexical list lex[q][: n_lex[q]] (rows of any scoring call) and the vector list vec[q][: n_vec[q]]
+        (VEC_HIT_DTYPE rows of vector_topk, or the torch int32 [n_q][k][2] tensors it returns) fused per query by reciprocal rank
+        (FUSE_RRF: w_lex / (rrf_c + lex_rank) + w_vec / (rrf_c + vec_rank)) or by FUSE_WEIGHTED: w_lex * final + w_vec * vec_score;
+        a doc only one list holds is completed by score_docs / hit_vector_scores.  Page [first, first + k) of score descending, doc
+        ascending -> (hits [n_q][k], n_hits [n_q], fused FUSED_DTYPE [n_q][k] | None, n_union [n_q] | None).  out = the caller's four
+        arrays, returned as they are; with device arrays throughout the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        qvec, _ = self._qvec(qvec)
+        lex, n_lex, n_q, k_lex = self._window(lex, n_lex, k_lex)
+        n_vec = _as(n_vec, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        vec = vec.contiguous() if _is_torch(vec) else np.ascontiguousarray(vec, dtype=VEC_HIT_DTYPE)
+        if k_vec is None:
+            k_vec = nbytes(vec) // (n_q * VEC_HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(vec) < n_q * int(k_vec) * VEC_HIT_DTYPE.itemsize:
+            raise ValueError("vec too small")
+        o_hits, o_n, o_fused, o_union = self._fuse_out(n_q, int(k), out, want_fused, want_union)
+        fp = self._fuse_params(mode, rrf_c, w_lex, w_vec)
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, qvec, lex, n_lex, vec, n_vec, o_hits, o_n, o_fused, o_union)
+        check(self.ctx.lib.ss_fuse_hits(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), _ptr(qvec),
+                                        int(k_lex), _ptr(lex), _ptr(n_lex), int(k_vec), _ptr(vec), _ptr(n_vec), C.byref(fp), int(first),
+                                        int(k), _ptr(o_hits), _ptr(o_n), _ptr(o_fused), _ptr(o_union)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_fused, o_union
+
+    def hybrid_topk(self, q_ptr, q_terms, qvec, k_window: int, k: int, mode: int = FUSE_RRF, rrf_c: int = 60, w_lex: float = 1.0,
+                    w_vec: float = 1.0, first: int = 0, mask_id=None, query_len=None, topic_probs=None, out=None,
+                    want_fused: bool = True, want_union: bool = True):
+        """ss_hybrid_topk: fuse_hits applied to the rows score_topk_masked and vector_topk give at k = k_window under mask_id, without
+        either window leaving the device -> (hits [n_q][k], n_hits [n_q], fused | None, n_union | None).  out as in fuse_hits: with
+        device arrays the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        mask_id = _as(mask_id, "int32")
+        qvec, _ = self._qvec(qvec)
+        n_q = int(q_ptr.shape[0]) - 1
+        o_hits, o_n, o_fused, o_union = self._fuse_out(n_q, int(k), out, want_fused, want_union)
+        fp = self._fuse_params(mode, rrf_c, w_lex, w_vec)
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, qvec, mask_id, o_hits, o_n, o_fused, o_union)
+        check(self.ctx.lib.ss_hybrid_topk(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), _ptr(qvec),
+                                          _ptr(mask_id), int(k_window), C.byref(fp), int(first), int(k), _ptr(o_hits), _ptr(o_n),
+                                          _ptr(o_fused), _ptr(o_union)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_fused, o_union
+
     def submit(self, q_ptr, q_terms, k: int, query_len=None, topic_probs=None, p_ptr=None, p_terms=None):
         """ss_score_topk_submit: enqueue a batch whose hits go to host memory; -> ticket for collect().
         p_ptr / p_terms: the queries' quoted phrases as in score_topk_phrase (None: plain OR queries)."""
@@ -1184,7 +1289,7 @@ class Scorer:
 
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
-           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE"]
+           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED"]
 
 
 def _flatten_words(words, ptr_dtype: str):

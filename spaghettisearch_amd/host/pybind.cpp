@@ -68,6 +68,19 @@ PYBIND11_MODULE(_host, m) {
     py::class_<retrieval::VectorRerankedPage>(m, "VectorRerankedPage")
         .def_readonly("Results", &retrieval::VectorRerankedPage::Results)
         .def_readonly("Scores", &retrieval::VectorRerankedPage::Scores);
+    py::class_<retrieval::HybridParams>(m, "HybridParams")
+        .def(py::init<>())
+        .def_readwrite("weighted", &retrieval::HybridParams::weighted)
+        .def_readwrite("rrf_c", &retrieval::HybridParams::rrf_c)
+        .def_readwrite("w_lex", &retrieval::HybridParams::w_lex)
+        .def_readwrite("w_vec", &retrieval::HybridParams::w_vec);
+    py::class_<retrieval::HybridPage>(m, "HybridPage")
+        .def_readonly("Results", &retrieval::HybridPage::Results)
+        .def_readonly("Scores", &retrieval::HybridPage::Scores)
+        .def_readonly("VecScores", &retrieval::HybridPage::VecScores)
+        .def_readonly("LexRanks", &retrieval::HybridPage::LexRanks)
+        .def_readonly("VecRanks", &retrieval::HybridPage::VecRanks)
+        .def_readonly("Union", &retrieval::HybridPage::Union);
     py::class_<retrieval::DedupedPage>(m, "DedupedPage")
         .def_readonly("Results", &retrieval::DedupedPage::Results)
         .def_readonly("Similar", &retrieval::DedupedPage::Similar)
@@ -199,6 +212,14 @@ PYBIND11_MODULE(_host, m) {
              py::arg("masks") = std::vector<std::string>())
         .def("RerankByVector", &retrieval::DeviceIndex::RerankByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("first") = 0,
              py::arg("k") = 50)
+        .def("ScoreDocs", [](retrieval::DeviceIndex& di, const std::string& query, const std::vector<std::string>& docHashes) {
+            return di.ScoreDocs(query, docHashes);
+        }, py::arg("query"), py::arg("docHashes"))
+        .def("HybridSearch", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, const std::vector<std::vector<int8_t>>& queryVectors,
+                                int k_window, const retrieval::HybridParams& params, int first, int k, const std::vector<std::string>& masks) {
+            return di.HybridSearch(queries, queryVectors, k_window, params, first, k, masks);
+        }, py::arg("queries"), py::arg("queryVectors"), py::arg("k_window"), py::arg("params") = retrieval::HybridParams(), py::arg("first") = 0,
+           py::arg("k") = 50, py::arg("masks") = std::vector<std::string>())
         .def("SetNearDuplicates", &retrieval::DeviceIndex::SetNearDuplicates, py::arg("n_slots"))
         .def("NearDuplicateSlots", &retrieval::DeviceIndex::NearDuplicateSlots)
         .def("RetrieveBatchDeduped", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, int min_match,

@@ -104,6 +104,25 @@ struct VectorRerankedPage {
     std::vector<int32_t> Scores;
 };
 
+// How DeviceIndex::HybridSearch fuses the lexical and the vector ranking (ss_fuse_params): reciprocal rank fusion,
+// w_lex / (rrf_c + lexical rank) + w_vec / (rrf_c + vector rank), or (weighted) w_lex * FinalRank + w_vec * vector score.
+struct HybridParams {
+    bool weighted = false;
+    int rrf_c = 60;
+    double w_lex = 1.0, w_vec = 1.0;
+};
+
+// One page of a query's fused results (DeviceIndex::HybridSearch; no reference counterpart).  Per row its fused score, its vector
+// score and its 1-based rank in the lexical and in the vector window (0: the window does not hold it); Union: the distinct docs of
+// both windows, the length of the fused ranking.
+struct HybridPage {
+    std::vector<Rank_combined> Results;
+    std::vector<double> Scores;
+    std::vector<int32_t> VecScores;
+    std::vector<int> LexRanks, VecRanks;
+    int Union = 0;
+};
+
 // util.go:151-160: quoted phrases `".*?"`
 inline std::vector<std::string> getPhrase(const std::string& s) {
     std::vector<std::string> out;
@@ -901,6 +920,82 @@ public:
                 out[q].Results.push_back(rows[q][page[q * kk + i]._pad]);
                 out[q].Scores.push_back(scores[q * kk + i]);
             }
+        return out;
+    }
+
+    // The row that a query's ranking holds for each of the given docs, whether or not the doc would reach any top-k (ss_score_docs): the
+    // FinalRank of the output of VectorSearch, SimilarPages or TopLinks.  A doc hash the index does not hold gives a row of zeros
+    // under its hash.  Quoted phrases and query operators are not read here: they decide which docs rank, not a doc's row.
+    std::vector<Rank_combined> ScoreDocs(const std::string& query, const std::vector<std::string>& docHashes,
+                                         const std::map<std::string, double>* topicProbs = nullptr, bool live_topic_probs = false) {
+        using namespace spaghetti;
+        std::vector<std::map<std::string, double>> tp;
+        if (topicProbs) tp.push_back(*topicProbs);
+        const Tokenised t = tokenise({query}, topicProbs ? &tp : nullptr, live_topic_probs);
+        if (!t.p_terms.empty()) throw std::runtime_error("ScoreDocs: quoted phrases are not read here");
+        std::vector<Rank_combined> out(docHashes.size());
+        for (size_t lo = 0; lo < docHashes.size(); lo += SS_MAX_TOPK) {
+            const size_t n = std::min<size_t>(SS_MAX_TOPK, docHashes.size() - lo);
+            std::vector<uint32_t> ids(n);
+            for (size_t j = 0; j < n; j++) {
+                auto it = docs.id.find(docHashes[lo + j]);
+                ids[j] = it == docs.id.end() ? 0xFFFFFFFFu : it->second;
+            }
+            std::vector<ss_hit> rows(n);
+            const int32_t n_in = (int32_t)n;
+            check(ss_score_docs(scorer, 1, t.q_ptr.data(), t.q_terms.data(), t.q_len.data(), t.probs.empty() ? nullptr : t.probs.data(), (int32_t)n,
+                                ids.data(), &n_in, rows.data()), "ss_score_docs");
+            for (size_t j = 0; j < n; j++) {
+                Rank_combined& r = out[lo + j];
+                r.DocHash = docHashes[lo + j];
+                r.PageRank = rows[j].pagerank; r.FinalRank = rows[j].final; r.TitleRank = rows[j].title; r.BodyRank = rows[j].body;
+            }
+        }
+        return out;
+    }
+    // Lexical and vector search fused (ss_hybrid_topk): per query the first k_window rows of its lexical ranking and the k_window
+    // nearest docs of its vector, both among the docs of the set masks[q] names (SetDocMasks; "" or an empty list: the whole index),
+    // merged into one ranking by `params`; page [first, first + k).  A doc only one window holds is completed on the device, so every
+    // row carries its FinalRank and its vector score.  Quoted phrases and query operators are not read here.
+    std::vector<HybridPage> HybridSearch(const std::vector<std::string>& queries, const std::vector<std::vector<int8_t>>& queryVectors,
+                                         int k_window, const HybridParams& params = HybridParams(), int first = 0, int k = 50,
+                                         const std::vector<std::string>& masks = {},
+                                         const std::vector<std::map<std::string, double>>* topicProbs = nullptr, bool live_topic_probs = false) {
+        using namespace spaghetti;
+        const std::vector<int8_t> flat = flatten_query_vectors("HybridSearch", queryVectors);
+        const size_t nq = queries.size(), kk = (size_t)std::max(k, 1);
+        if (queryVectors.size() != nq) throw std::runtime_error("HybridSearch: one query vector per query");
+        if (!masks.empty() && masks.size() != nq) throw std::runtime_error("HybridSearch: one mask name per query");
+        if (query_operators) throw std::runtime_error("HybridSearch: query operators are not read here (SetQueryOperators(false))");
+        std::vector<int32_t> mask_id(nq, -1);
+        for (size_t q = 0; q < masks.size(); q++) {
+            if (masks[q].empty()) continue;
+            auto it = mask_index.find(masks[q]);
+            if (it == mask_index.end()) throw std::runtime_error("HybridSearch: no doc mask named '" + masks[q] + "' (SetDocMasks)");
+            mask_id[q] = it->second;
+        }
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        if (!t.p_terms.empty()) throw std::runtime_error("HybridSearch: quoted phrases are not read here");
+        const ss_fuse_params fp{params.weighted ? SS_FUSE_WEIGHTED : SS_FUSE_RRF, params.rrf_c, params.w_lex, params.w_vec};
+        std::vector<ss_hit> page(nq * kk);
+        std::vector<ss_fused> fused(nq * kk);
+        std::vector<int32_t> n_page(nq), n_union(nq);
+        check(ss_hybrid_topk(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.q_len.data(), t.probs.empty() ? nullptr : t.probs.data(),
+                             flat.data(), mask_id.data(), k_window, &fp, first, k, page.data(), n_page.data(), fused.data(), n_union.data()),
+              "ss_hybrid_topk");
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<HybridPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Union = n_union[q];
+            for (int i = 0; i < n_page[q]; i++) {
+                const ss_fused& f = fused[q * kk + i];
+                out[q].Scores.push_back(f.score);
+                out[q].VecScores.push_back(f.vec_score);
+                out[q].LexRanks.push_back(f.lex_rank);
+                out[q].VecRanks.push_back(f.vec_rank);
+            }
+        }
         return out;
     }
 
