@@ -60,11 +60,12 @@ type Index struct {
 	NPost  uint64
 }
 type Scorer struct {
-	h       *C.ss_scorer
-	ctx     *Ctx
-	nDocs   uint64 // the title table's doc count when the scorer was created: sizes DocFieldMasks' words
-	nFields int    // fields registered by SetDocFields: sizes HitFields' values
-	vecDim  int    // dim of the table registered by SetDocVectors: sizes the query vectors
+	h         *C.ss_scorer
+	ctx       *Ctx
+	nDocs     uint64 // the title table's doc count when the scorer was created: sizes DocFieldMasks' words
+	nFields   int    // fields registered by SetDocFields: sizes HitFields' values
+	vecDim    int    // dim of the table registered by SetDocVectors: sizes the query vectors
+	nVecLists int    // lists registered by SetVectorLists: sizes the probes of VectorTopKProbed
 }
 
 var (
@@ -1074,6 +1075,7 @@ func (s *Scorer) SetDocVectors(dim int, vec []int8) {
 	}
 	check(s.ctx, C.ss_scorer_set_doc_vectors(s.h, C.int32_t(dim), i8p(vec)), "ss_scorer_set_doc_vectors")
 	s.vecDim = dim
+	s.nVecLists = 0 // (the library drops the lists: they describe the old table)
 	if len(vec) == 0 {
 		s.vecDim = 0
 	}
@@ -1108,6 +1110,85 @@ func (s *Scorer) VectorTopK(qvec []int8, maskID []int32, k int) ([][]VecHit, err
 		}
 	}
 	return out, nil
+}
+
+// SetVectorLists registers a partition of the vector table (ss_scorer_set_vector_lists): centroids[l*dim+i] = position i of list l's
+// centroid, listOfDoc[d] = the list of doc d (below nLists) or C.SS_NO_LIST for a doc no probed search finds.  nLists 0 clears.  Needs
+// SetDocVectors, which also drops the lists.  The device keeps a second, list-major copy of the table.
+func (s *Scorer) SetVectorLists(nLists int, centroids []int8, listOfDoc []uint32) error {
+	if nLists > 0 && (s.vecDim < 1 || len(centroids) < nLists*s.vecDim || uint64(len(listOfDoc)) < s.nDocs) {
+		return fmt.Errorf("SetVectorLists: %d centroid values and %d docs for %d lists of dim %d over %d docs", len(centroids), len(listOfDoc), nLists, s.vecDim, s.nDocs)
+	}
+	rc := C.ss_scorer_set_vector_lists(s.h, C.int32_t(nLists), i8p(centroids), u32p(listOfDoc))
+	if err := statusErr(s.ctx, rc, "ss_scorer_set_vector_lists"); err != nil {
+		return err
+	}
+	s.nVecLists = nLists
+	return nil
+}
+
+// AssignVectorLists returns per doc of the vector table the list whose centroid has the largest integer dot product with the doc's
+// vector, ties to the lower list, and that score (ss_vector_assign_lists).  It registers nothing.
+func (s *Scorer) AssignVectorLists(nLists int, centroids []int8) ([]uint32, []int32, error) {
+	if s.vecDim < 1 {
+		return nil, nil, fmt.Errorf("AssignVectorLists: no doc vectors registered (SetDocVectors)")
+	}
+	if nLists < 1 || len(centroids) < nLists*s.vecDim {
+		return nil, nil, fmt.Errorf("AssignVectorLists: %d centroid values for %d lists of dim %d", len(centroids), nLists, s.vecDim)
+	}
+	lists := make([]uint32, s.nDocs)
+	scores := make([]int32, s.nDocs)
+	rc := C.ss_vector_assign_lists(s.h, C.int32_t(nLists), i8p(centroids), u32p(lists), i32p(scores))
+	if err := statusErr(s.ctx, rc, "ss_vector_assign_lists"); err != nil {
+		return nil, nil, err
+	}
+	return lists, scores, nil
+}
+
+// VectorTopKProbed is VectorTopK over the docs of the min(nProbe, nLists) lists whose centroids score highest under the query
+// (ss_vector_topk_probed): exact within them, and VectorTopK's rows when every list is probed and no doc is at C.SS_NO_LIST.  The
+// second result holds each query's probed lists in probe order.
+func (s *Scorer) VectorTopKProbed(qvec []int8, maskID []int32, k int, nProbe int) ([][]VecHit, [][]uint32, error) {
+	if s.vecDim < 1 {
+		return nil, nil, fmt.Errorf("VectorTopKProbed: no doc vectors registered (SetDocVectors)")
+	}
+	if s.nVecLists < 1 {
+		return nil, nil, fmt.Errorf("VectorTopKProbed: no vector lists registered (SetVectorLists)")
+	}
+	nq := len(qvec) / s.vecDim
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	np := nProbe
+	if np > s.nVecLists {
+		np = s.nVecLists
+	}
+	if np < 1 {
+		np = 1
+	}
+	raw := make([]C.ss_vec_hit, nq*kk)
+	nHits := make([]int32, nq)
+	probes := make([]uint32, nq*np)
+	rc := C.ss_vector_topk_probed(s.h, C.int32_t(nq), i8p(qvec), i32p(maskID), C.int32_t(k), C.int32_t(nProbe),
+		(*C.ss_vec_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), u32p(probes))
+	if err := statusErr(s.ctx, rc, "ss_vector_topk_probed"); err != nil {
+		return nil, nil, err
+	}
+	out := make([][]VecHit, nq)
+	lists := make([][]uint32, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]VecHit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*kk+i]
+			out[q][i] = VecHit{uint32(r.doc), int32(r.score)}
+		}
+		lists[q] = probes[q*np : (q+1)*np]
+	}
+	return out, lists, nil
 }
 
 // vecWindow lays hits out as [nq][kIn] ss_hit rows with their counts

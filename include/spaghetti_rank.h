@@ -53,7 +53,9 @@ extern "C" {
  * SS_MAX_VEC_DIM, SS_NO_VEC_SCORE, ss_vec_hit, ss_scorer_set_doc_vectors, ss_vector_topk, ss_hit_vector_scores and
  * ss_rerank_hits_by_vector (one int8 vector per doc: exact nearest neighbours by integer dot product, a window re-ranked by it);
  * SS_FUSE_RRF / _WEIGHTED, ss_fuse_params, ss_fused, ss_score_docs, ss_fuse_hits and ss_hybrid_topk (the lexical row of any given doc,
- * a lexical and a vector list fused into one ranked, paged list, and both searches plus the fusion in one call). */
+ * a lexical and a vector list fused into one ranked, paged list, and both searches plus the fusion in one call);
+ * SS_MAX_VEC_LISTS, SS_NO_LIST, ss_scorer_set_vector_lists, ss_vector_assign_lists and ss_vector_topk_probed (the vector table cut into
+ * lists around centroids: the exact top k over the docs of the n_probe lists nearest to a query, not over every doc). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -863,6 +865,52 @@ int32_t ss_hit_vector_scores(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_
 int32_t ss_rerank_hits_by_vector(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, int32_t k_in,
                                  const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
                                  ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
+
+/* Vector lists: the docs of the vector table cut into n_lists lists around centroids (an inverted-file partition), and the search over
+ * the n_probe lists nearest to a query.  No reference counterpart.  ss_vector_topk reads every doc byte for every block of queries; a
+ * probed search reads the centroids and the rows of the probed lists.  It is approximate only in WHICH docs it looks at: within them
+ * the answer is exact and defined bit for bit.
+ *   Lists.      ss_scorer_set_vector_lists registers a partition the caller brings, as they bring the embeddings: centroids
+ *               [n_lists][dim] int8 (dim = the vector table's), list_of_doc [n_docs] with every entry below n_lists or SS_NO_LIST (a doc
+ *               in no list: never found by a probed search); host or device memory, copied.  n_lists = 0 or centroids NULL clears.
+ *               It needs a registered vector table (SS_ERR_STATE without one) and has ss_scorer_set_doc_vectors' lifecycle: it
+ *               replaces the old lists behind the scorer's outstanding work, and a call that fails leaves the old lists in place.
+ *               ss_scorer_set_doc_vectors, whether it replaces or clears, drops the lists: they describe the old table.  The call may
+ *               wait; it reads every entry of list_of_doc on the host: one that is >= n_lists and not SS_NO_LIST, n_lists < 0 or above
+ *               SS_MAX_VEC_LISTS, a NULL list_of_doc: SS_ERR_INVALID.  Empty lists are legal.  The device sorts the docs by list
+ *               (stable: ascending doc inside a list) and keeps a SECOND, list-major copy of the vector rows with the doc of every row:
+ *               n_docs * dim bytes plus 4 bytes per doc on top of the doc-major table, which stays (ss_hit_vector_scores gathers from
+ *               it); SS_ERR_OOM if that cannot be had.
+ *   Probes.     P(q) = the first min(n_probe, n_lists) lists in the order score(q, centroid[l]) descending, then l ascending; score is
+ *               the 32-bit integer dot product of ss_vector_topk.  probes_out[q * min(n_probe, n_lists) + r] (nullable) = the r-th.
+ *   Candidates. Every doc d with list_of_doc[d] in P(q) that mask_id[q] allows (as ss_vector_topk: -1 / NULL = every doc).
+ *   Output.     Exactly as ss_vector_topk: score descending, then doc ascending; n_hits_out[q] = min(k, number of candidates); entries
+ *               past the count are left untouched.  So with n_probe >= n_lists and no doc at SS_NO_LIST the rows and counts are
+ *               ss_vector_topk's, byte for byte.
+ *   Assign.     ss_vector_assign_lists: list_out[d] = the list l of the largest score(vec[d], centroid[l]), ties to the lower l;
+ *               score_out[d] (nullable) = that score.  The expensive half of a k-means step and the natural way to produce
+ *               list_of_doc; it registers nothing and needs no lists, only the vector table (SS_ERR_STATE without one).  n_lists
+ *               outside [1, SS_MAX_VEC_LISTS], NULL centroids or list_out: SS_ERR_INVALID.  It is the exact top-1 search with the
+ *               centroids as the table and batches of doc rows as the queries (option "vec.assign_batch"); with every array on the
+ *               device it only enqueues.
+ * Checks of ss_vector_topk_probed, all before anything is enqueued and with the outputs untouched: those of ss_vector_topk, and
+ * n_probe < 1: SS_ERR_INVALID; n_probe > SS_MAX_TOPK: SS_ERR_UNSUPPORTED; no lists registered: SS_ERR_STATE.  mask_id is read on the
+ * host as in ss_vector_topk; with qvec and every output on the device the call only enqueues on the ctx stream and never waits.
+ * It enqueues k_vec_topk / k_vec_merge over the centroids (the probes), three small kernels that turn probes per query into runs of
+ * queries per list, k_vec_topk_lists (a work item is one segment of one list times one group of up to 64 queries that probe it; a list
+ * of any length is cut into segments, option "vec.list_seg_rows", so one list holding nearly every doc neither serialises nor
+ * overflows) and k_vec_merge_lists.  The partial lists are bounded as in ss_vector_topk (256 MB); a call whose queries need more is
+ * split into query batches on the host, still without waiting.  Serialised on the ctx like every scoring call; no _submit / _collect
+ * form. */
+#define SS_MAX_VEC_LISTS 65536
+#define SS_NO_LIST       0xFFFFFFFFu   /* a doc in no list: never found by a probed search */
+int32_t ss_scorer_set_vector_lists(ss_scorer* s, int32_t n_lists, const int8_t* centroids /*[n_lists][dim]; n_lists 0 / NULL clears*/,
+                                   const uint32_t* list_of_doc /*[n_docs]: < n_lists or SS_NO_LIST*/);
+int32_t ss_vector_assign_lists(ss_scorer* s, int32_t n_lists, const int8_t* centroids /*[n_lists][dim]*/, uint32_t* list_out /*[n_docs]*/,
+                               int32_t* score_out /*[n_docs], nullable*/);
+int32_t ss_vector_topk_probed(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, const int32_t* mask_id /*[n_q], NULL = all -1*/,
+                              int32_t k, int32_t n_probe, ss_vec_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                              uint32_t* probes_out /*[n_q][min(n_probe, n_lists)], nullable*/);
 
 /* Hybrid search: the lexical and the vector ranking of one query fused into one ranked, paged list, and the lexical row of ANY given
  * doc.  No reference counterpart.  Until here the two rankings could only be bridged by ss_rerank_hits_by_vector, which reorders docs

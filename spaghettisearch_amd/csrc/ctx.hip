@@ -360,6 +360,10 @@ static const char* const k_option_names[] = {
     "vec.chunk_docs",       // ss_vector_topk: docs per chunk of k_vec_topk, rounded up to a multiple of 64 (default 0: from the device's compute
                             //    units, the query blocks and a bound on the partial lists: vector_plan.hpp); tests set it to 64 to put many
                             //    chunk seams into a few hundred docs; the rows are the same bytes for every value
+    "vec.list_seg_rows",    // ss_vector_topk_probed: rows per segment of a list, rounded up to a multiple of 64 (default 0: vector_lists_plan.hpp);
+                            //    tests set it to 64 to put segment seams into short lists; the rows are the same bytes for every value
+    "vec.list_batch_q",     // ... queries per batch of one call (default 0: what keeps the partial lists in bound); tests set it small to split a call
+    "vec.assign_batch",     // ss_vector_assign_lists: doc rows per batch of the top-1 search over the centroids (default 0: vector_lists_plan.hpp)
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

@@ -52,6 +52,12 @@ namespace ss {
 int32_t vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged);
 void launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in,
                            int32_t* d_out, hipStream_t st);
+// vector.hip, for vector_lists.hip: k_vec_topk and k_vec_merge as ss_vector_topk launches them, over any table [n_rows > 0][vec_dim] of
+// int8 rows in device memory, without masks: d_qvec [n_q][vec_dim] 16-byte aligned, rows and counts to device memory.  Enqueues only.
+int32_t vec_table_topk(ss_scorer* s, const char* who, const int8_t* table, uint64_t n_rows, int32_t n_q, const int8_t* d_qvec, int32_t k,
+                       ss_vec_hit* d_hits, int32_t* d_n_hits);
+// vector_lists.hip, for vector.hip: ss_scorer_set_doc_vectors drops the lists, which describe the old table
+void vec_lists_drop(ss_scorer* s);
 }  // namespace ss
 
 // Where a scoring call left its rows when they stay inside the scorer (ss::score_into_turn): the block of the plan turn the call took.
@@ -190,6 +196,24 @@ struct ss_scorer {
     ss::Event ev_vec_mid;
     int vec_lds_attr[5] = {0, 0, 0, 0, 0};
     ss::DevBuf<ss_vec_hit> d_vec_hits;
+    // ss_scorer_set_vector_lists (vector_lists.hip; vl_n_lists 0 = none): the centroids [vl_n_lists][vec_dim], the list-major copy of
+    // the vector rows with the doc of every row, list_begin [vl_n_lists + 1] and, on the host, the list lengths in descending order
+    // (the plan's slot bound).  vl_rows: docs that are in a list.  ss_vector_topk_probed, all grow-only and used on the context's
+    // stream: the probe rows [n_q][P] and their counts, per list the queries' count / run begin / fill cursor (d_vl_cnt: 3 arrays), the
+    // runs of (query, probe rank) pairs, the items' scan, per pair its first partial slot and per query its slot count, the partial
+    // lists, the device blocks of HOST outputs, the dynamic LDS already granted to k_vec_topk_lists<QT>.  ss_vector_assign_lists: the
+    // centroids it is given and the top-1 rows of one batch.
+    int32_t vl_n_lists = 0;
+    uint64_t vl_rows = 0;
+    ss::DevBuf<int8_t> vl_centroids, vl_vec;
+    ss::DevBuf<uint32_t> vl_row_doc, vl_list_begin;
+    std::vector<uint32_t> vl_len_desc;
+    ss::DevBuf<ss_vec_hit> d_vl_probe, d_vl_hits, d_vl_assign;
+    ss::DevBuf<int32_t> d_vl_probe_n, d_vl_n, d_vl_assign_n, d_vl_mid;
+    ss::DevBuf<uint32_t> d_vl_cnt, d_vl_run, d_vl_slot, d_vl_nslots, d_vl_probes_out;
+    ss::DevBuf<uint64_t> d_vl_item_begin, d_vl_part;
+    ss::DevBuf<int8_t> d_vl_cent;
+    int vl_lds_attr[5] = {0, 0, 0, 0, 0};
     ss::DevBuf<ss_hit> d_hits;
     // ss_score_docs / ss_fuse_hits / ss_hybrid_topk (hybrid.hip).  hyb: the turns the queries' table goes up through, as exp / pas.
     // The blocks, grow-only, written and read on the context's stream only: the device copies of HOST docs / vec / n_vec (the call

@@ -24,6 +24,7 @@
 // No float anywhere.  Device arrays throughout: the calls only enqueue on the context's stream.  ss_hit_vector_scores /
 // ss_rerank_hits_by_vector: the window in, the paging checks and the outputs' way back are hit_window.hpp's.
 #include "hit_window.hpp"
+#include "vector_device.hpp"
 #include "vector_plan.hpp"
 
 #include <algorithm>
@@ -32,57 +33,15 @@ namespace {
 
 namespace hw = ss::hitwin;
 
-constexpr uint32_t VT_TILE = ss::vec::TILE, VT_WAVES = ss::vec::WAVES;
-constexpr int VT_TPB = VT_WAVES * 64;
-typedef int v4i __attribute__((ext_vector_type(4)));
+using ss::vecdev::VT_TILE;
+using ss::vecdev::VT_WAVES;
+using ss::vecdev::VT_TPB;
+using ss::vecdev::VM_TPB;
+using ss::vecdev::v4i;
+using ss::vecdev::vec_key;
+using ss::vecdev::vec_compact;
 static_assert(SS_MAX_VEC_DIM == ss::vec::MAX_DIM && SS_MAX_TOPK == ss::vec::MAX_K, "vector_plan.hpp states the ABI's limits");
 static_assert(sizeof(ss_vec_hit) == 8, "a row is one 8-byte word");
-
-__device__ __forceinline__ uint64_t vec_key(int32_t score, uint32_t doc) {
-    return (uint64_t)((uint32_t)score ^ 0x80000000u) << 32 | (uint64_t)(0xFFFFFFFFu - doc);
-}
-
-// The k-th largest (k >= 1) of n > = k distinct-or-not 64-bit keys, by all NT threads of the workgroup: 8 passes over the keys, most
-// significant digit first; s_hist: 256 counters, s_sel: 2 words.  Every thread returns the same value.  Control flow must be uniform.
-template <int NT>
-__device__ uint64_t block_select(const uint64_t* keys, uint32_t n, uint32_t k, uint32_t* s_hist, uint32_t* s_sel) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    uint64_t prefix = 0, mask = 0;
-    uint32_t need = k;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (uint32_t b = tid; b < 256; b += NT) s_hist[b] = 0;
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += NT) {
-            const uint64_t key = keys[i];
-            if ((key & mask) == prefix) atomicAdd(&s_hist[(uint32_t)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) {                                                           // wave 0: lane l owns bins 255 - 4l .. 252 - 4l
-            uint32_t c[4], sum = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) { c[b] = s_hist[255u - 4u * lane - (uint32_t)b]; sum += c[b]; }
-            uint32_t incl = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
-                if (lane >= (uint32_t)d) incl += o;
-            }
-            uint32_t run = incl - sum;
-            if (run < need && need <= incl) {                                     // exactly one lane
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    if (need <= run + c[b]) { s_sel[0] = 255u - 4u * lane - (uint32_t)b; s_sel[1] = run; break; }
-                    run += c[b];
-                }
-            }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)s_sel[0] << shift;
-        mask |= (uint64_t)255u << shift;
-        need -= s_sel[1];
-    }
-    return prefix;
-}
 
 struct VecTopkParams {
     const int8_t* vec;                 // [n_docs][dim]
@@ -94,24 +53,6 @@ struct VecTopkParams {
     uint64_t* part;                    // [n_q][n_chunks][k]
     uint32_t dim, n_q, k, chunk_docs, n_chunks, cap, row_stride;
 };
-
-// Cut query ql's list back to its k largest keys (n > k of them stand in buf); the k-th becomes the threshold.  Uniform.
-__device__ void vec_compact(uint64_t* buf, uint32_t n, uint32_t k, uint64_t* thr_out, uint32_t* cnt_out, uint32_t* s_hist, uint32_t* s_sel,
-                            uint16_t* s_holes) {
-    const uint32_t tid = threadIdx.x;
-    const uint64_t thr = block_select<VT_TPB>(buf, n, k, s_hist, s_sel);
-    if (tid == 0) { s_sel[2] = 0; s_sel[3] = 0; }
-    __syncthreads();
-    for (uint32_t i = tid; i < k; i += VT_TPB)                                    // slots of the first k that fall out ...
-        if (buf[i] < thr) s_holes[atomicAdd(&s_sel[2], 1u)] = (uint16_t)i;
-    __syncthreads();
-    for (uint32_t i = k + tid; i < n; i += VT_TPB) {                              // ... take the keys behind them that stay: as many, the keys are distinct
-        const uint64_t key = buf[i];
-        if (key >= thr) buf[s_holes[atomicAdd(&s_sel[3], 1u)]] = key;
-    }
-    if (tid == 0) { *thr_out = thr; *cnt_out = k; }
-    __syncthreads();
-}
 
 template <int QT>
 __global__ __launch_bounds__(VT_TPB) void k_vec_topk(VecTopkParams p) {
@@ -253,52 +194,12 @@ struct VecMergeParams {
     int32_t* n_hits_out;               // [n_q]
 };
 
-constexpr int VM_TPB = 256;
-
 __global__ __launch_bounds__(VM_TPB) void k_vec_merge(VecMergeParams p) {
     __shared__ uint64_t s_key[SS_MAX_TOPK];
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_sel[4];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, k = p.k;
-    const uint64_t* const keys = p.part + (uint64_t)q * p.n_slots;
-    if (tid == 0) { s_sel[2] = 0; s_sel[3] = 0; }
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint32_t i = tid; i < p.n_slots; i += VM_TPB) mine += keys[i] != 0;
-    if (mine) atomicAdd(&s_sel[2], mine);
-    __syncthreads();
-    const uint32_t valid = s_sel[2];
-    const uint32_t n_out = valid < k ? valid : k;
-    uint64_t thr = 1;                                                             // every key
-    if (valid > k) thr = block_select<VM_TPB>(keys, p.n_slots, k, s_hist, s_sel);
-    for (uint32_t i = tid; i < p.n_slots; i += VM_TPB) {
-        const uint64_t key = keys[i];
-        if (key >= thr) s_key[atomicAdd(&s_sel[3], 1u)] = key;                    // n_out of them: the keys are distinct
-    }
-    uint32_t np = 1;
-    while (np < n_out) np <<= 1;
-    __syncthreads();
-    for (uint32_t i = n_out + tid; i < np; i += VM_TPB) s_key[i] = 0;
-    __syncthreads();
-    for (uint32_t k2 = 2; k2 <= np; k2 <<= 1)
-        for (uint32_t j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-            for (uint32_t i = tid; i < np; i += VM_TPB) {
-                const uint32_t o = i ^ j2;
-                if (o > i) {
-                    const uint64_t a = s_key[i], b = s_key[o];
-                    if ((a < b) == ((i & k2) == 0)) { s_key[i] = b; s_key[o] = a; }   // descending
-                }
-            }
-            __syncthreads();
-        }
-    for (uint32_t i = tid; i < n_out; i += VM_TPB) {
-        const uint64_t key = s_key[i];
-        ss_vec_hit row;
-        row.doc = 0xFFFFFFFFu - (uint32_t)key;
-        row.score = (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u);
-        p.hits_out[(size_t)q * k + i] = row;
-    }
-    if (tid == 0) p.n_hits_out[q] = (int32_t)n_out;
+    const uint32_t q = blockIdx.x;
+    ss::vecdev::vec_merge_query(p.part + (uint64_t)q * p.n_slots, p.n_slots, p.k, p.hits_out + (size_t)q * p.k, p.n_hits_out + q, s_key, s_hist, s_sel);
 }
 
 // ---- scores of given rows ----------------------------------------------------------------------------------------------------
@@ -429,6 +330,41 @@ int32_t launch_topk(ss_scorer* s, const VecTopkParams& p, const ss::vec::Plan& p
     return SS_OK;
 }
 
+// k_vec_topk and k_vec_merge over the table [n_rows > 0][dim]: p carries the queries and their masks, the rest is filled in here
+int32_t enqueue_topk(ss_scorer* s, const char* who, const int8_t* table, uint64_t n_rows, VecTopkParams p, const ss::vec::Plan& pl, uint32_t n_q,
+                     uint32_t k, ss_vec_hit* o_hits, int32_t* o_n) {
+    ss_ctx* ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    {
+        const hipError_t e = ensure(s->d_vec_part, (size_t)pl.part_keys);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "%s: no device memory for %llu partial keys", who,
+                             (unsigned long long)pl.part_keys);
+        }
+    }
+    p.vec = table;
+    p.n_docs = n_rows;
+    p.masks = s->masks.p;
+    p.mask_words = s->mask_words;
+    p.part = s->d_vec_part.p;
+    p.dim = (uint32_t)s->vec_dim; p.n_q = n_q; p.k = k;
+    p.chunk_docs = pl.chunk_docs; p.n_chunks = pl.n_chunks; p.cap = pl.cap; p.row_stride = pl.row_stride;
+    if (pl.q_block == 64) SS_TRY(launch_topk<4>(s, p, pl, st));
+    else if (pl.q_block == 32) SS_TRY(launch_topk<2>(s, p, pl, st));
+    else SS_TRY(launch_topk<1>(s, p, pl, st));
+    SS_HIP(ctx, hipGetLastError());
+    VecMergeParams m{};
+    m.part = s->d_vec_part.p;
+    m.n_slots = pl.n_chunks * k;
+    m.k = k;
+    m.hits_out = o_hits;
+    m.n_hits_out = o_n;
+    hipLaunchKernelGGL(k_vec_merge, dim3((unsigned)n_q), dim3(VM_TPB), 0, st, m);
+    SS_HIP(ctx, hipGetLastError());
+    return SS_OK;
+}
+
 int32_t topk_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, const int32_t* mask_id, int32_t k, ss_vec_hit* hits_out, int32_t* n_hits_out) {
     ss_ctx* ctx = s->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -484,33 +420,7 @@ int32_t topk_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, const int32_t* 
                 p.q_mask = s->d_vec_mid.p;
             }
         }
-        {
-            const hipError_t e = ensure(s->d_vec_part, (size_t)pl.part_keys);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "ss_vector_topk: no device memory for %llu partial keys",
-                                 (unsigned long long)pl.part_keys);
-            }
-        }
-        p.vec = s->vec.p;
-        p.n_docs = s->n_docs;
-        p.masks = s->masks.p;
-        p.mask_words = s->mask_words;
-        p.part = s->d_vec_part.p;
-        p.dim = (uint32_t)s->vec_dim; p.n_q = (uint32_t)n_q; p.k = (uint32_t)k;
-        p.chunk_docs = pl.chunk_docs; p.n_chunks = pl.n_chunks; p.cap = pl.cap; p.row_stride = pl.row_stride;
-        if (pl.q_block == 64) SS_TRY(launch_topk<4>(s, p, pl, st));
-        else if (pl.q_block == 32) SS_TRY(launch_topk<2>(s, p, pl, st));
-        else SS_TRY(launch_topk<1>(s, p, pl, st));
-        SS_HIP(ctx, hipGetLastError());
-        VecMergeParams m{};
-        m.part = s->d_vec_part.p;
-        m.n_slots = pl.n_chunks * (uint32_t)k;
-        m.k = (uint32_t)k;
-        m.hits_out = o_hits;
-        m.n_hits_out = o_n;
-        hipLaunchKernelGGL(k_vec_merge, dim3((unsigned)n_q), dim3(VM_TPB), 0, st, m);
-        SS_HIP(ctx, hipGetLastError());
+        SS_TRY(enqueue_topk(s, "ss_vector_topk", s->vec.p, s->n_docs, p, pl, (uint32_t)n_q, (uint32_t)k, o_hits, o_n));
     }
     if (dev_h && dev_n) {
         if (staged) SS_HIP(ctx, hipStreamSynchronize(st));
@@ -622,6 +532,21 @@ void ss::launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit*
     launch_hit_scores(s, d_qvec, w, n_q, k_in, d_out, st);
 }
 
+// for vector_lists.hip (scorer.hpp): the exact top k of device query vectors over any table of int8 rows, as ss_vector_topk enqueues it
+int32_t ss::vec_table_topk(ss_scorer* s, const char* who, const int8_t* table, uint64_t n_rows, int32_t n_q, const int8_t* d_qvec, int32_t k,
+                           ss_vec_hit* d_hits, int32_t* d_n_hits) {
+    ss_ctx* ctx = s->ctx;
+    int lds_limit = 0;
+    SS_HIP(ctx, hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+    const ss::vec::Plan pl = ss::vec::plan(n_rows, (uint32_t)s->vec_dim, (uint64_t)n_q, (uint32_t)k, 0, (uint32_t)ctx->cu_count,
+                                           (uint32_t)std::min(lds_limit, 160 << 10));
+    if (pl.too_large) return ctx->fail(SS_ERR_OOM, "%s: the partial lists of %d queries over %u chunks do not fit", who, n_q, pl.n_chunks);
+    if (!pl.ok) return ctx->fail(SS_ERR_UNSUPPORTED, "%s: %d queries at k = %d and dim %d need more LDS than the device has or 65535 query blocks", who, n_q, k, s->vec_dim);
+    VecTopkParams p{};
+    p.qvec = d_qvec;
+    return enqueue_topk(s, who, table, n_rows, p, pl, (uint32_t)n_q, (uint32_t)k, d_hits, d_n_hits);
+}
+
 extern "C" {
 
 int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec) {
@@ -647,6 +572,7 @@ int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec) 
     for (hipStream_t ws : ctx->wave_stream)
         if (ws) SS_HIP(ctx, hipStreamSynchronize(ws));
     if (clear) {
+        ss::vec_lists_drop(s);                                                    // (they describe the old table)
         s->vec.release();
         s->vec_dim = 0;
         return SS_OK;
@@ -655,6 +581,7 @@ int32_t ss_scorer_set_doc_vectors(ss_scorer* s, int32_t dim, const int8_t* vec) 
         SS_HIP(ctx, hipMemcpyAsync(nb.p, vec, n, hipMemcpyDefault, ctx->stream));
         SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    ss::vec_lists_drop(s);
     s->vec = std::move(nb);
     s->vec_dim = dim;
     return SS_OK;

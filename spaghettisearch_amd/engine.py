@@ -625,6 +625,7 @@ class Scorer:
         self.k_topics = 0
         self.n_fields = 0
         self.vec_dim = 0
+        self.n_vec_lists = 0
 
     def set_prior(self, rank) -> None:
         """rank [K][n_docs] topic-major (ss_pagerank_run layout) or None to clear."""
@@ -1077,6 +1078,7 @@ class Scorer:
         if vec is None:
             check(self.ctx.lib.ss_scorer_set_doc_vectors(self.h, 0, None), self.ctx.h)
             self.vec_dim = 0
+            self.n_vec_lists = 0
             return
         vec = _as(vec, "int8")
         if vec.ndim != 2 or int(vec.shape[0]) != self.title.n_docs:
@@ -1084,6 +1086,7 @@ class Scorer:
         self.ctx.ready(vec)
         check(self.ctx.lib.ss_scorer_set_doc_vectors(self.h, int(vec.shape[1]), _ptr(vec)), self.ctx.h)
         self.vec_dim = int(vec.shape[1])
+        self.n_vec_lists = 0                        # (the library drops the lists: they describe the old table)
 
     def _qvec(self, qvec):
         qvec = _as(qvec, "int8")
@@ -1116,6 +1119,77 @@ class Scorer:
         if _is_torch(hits) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return hits, n_hits
+
+    def set_vector_lists(self, centroids, list_of_doc) -> None:
+        """ss_scorer_set_vector_lists: register a partition of the vector table: centroids int8 [n_lists][dim] and list_of_doc uint32
+        [n_docs] (every entry below n_lists, or NO_LIST for a doc no probed search finds), numpy or torch; None clears.  Needs
+        set_doc_vectors, which also drops the lists.  Keeps a second, list-major copy of the table on the device."""
+        if centroids is None:
+            check(self.ctx.lib.ss_scorer_set_vector_lists(self.h, 0, None, None), self.ctx.h)
+            self.n_vec_lists = 0
+            return
+        centroids, list_of_doc = _as(centroids, "int8"), _as(list_of_doc, "uint32")
+        if centroids.ndim != 2 or (getattr(self, "vec_dim", 0) and int(centroids.shape[1]) != self.vec_dim):
+            raise ValueError(f"centroids must have shape [n_lists][{getattr(self, 'vec_dim', 0)}], got {tuple(centroids.shape)}")
+        if list_of_doc.ndim != 1 or int(list_of_doc.shape[0]) != self.title.n_docs:
+            raise ValueError(f"list_of_doc must have shape [{self.title.n_docs}], got {tuple(list_of_doc.shape)}")
+        self.ctx.ready(centroids, list_of_doc)
+        check(self.ctx.lib.ss_scorer_set_vector_lists(self.h, int(centroids.shape[0]), _ptr(centroids), _ptr(list_of_doc)), self.ctx.h)
+        self.n_vec_lists = int(centroids.shape[0])
+
+    def assign_vector_lists(self, centroids, device_out: bool = False, out=None, want_scores: bool = True):
+        """ss_vector_assign_lists: per doc of the vector table the list of the centroid (int8 [n_lists][dim]) with the largest integer
+        dot product, ties to the lower list -> (list_of_doc uint32 [n_docs], scores int32 [n_docs] | None).  Registers nothing.
+        device_out: torch device tensors (the lists as int32 bits); out = (lists, scores | None): the caller's arrays."""
+        centroids = _as(centroids, "int8")
+        if centroids.ndim != 2 or (getattr(self, "vec_dim", 0) and int(centroids.shape[1]) != self.vec_dim):
+            raise ValueError(f"centroids must have shape [n_lists][{getattr(self, 'vec_dim', 0)}], got {tuple(centroids.shape)}")
+        n = self.title.n_docs
+        if out is None:
+            if device_out:
+                import torch
+                dev = torch.device("cuda", self.ctx.device_id)
+                out = (torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev) if want_scores else None)
+            else:
+                out = (np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32) if want_scores else None)
+        lists, scores = out
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if nbytes(lists) < n * 4 or (scores is not None and nbytes(scores) < n * 4):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(centroids, lists, scores)
+        check(self.ctx.lib.ss_vector_assign_lists(self.h, int(centroids.shape[0]), _ptr(centroids), _ptr(lists), _ptr(scores)), self.ctx.h)
+        if _is_torch(lists) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return lists, scores
+
+    def vector_topk_probed(self, qvec, k: int, n_probe: int, mask_id=None, device_out: bool = False, out=None, return_probes: bool = False):
+        """ss_vector_topk_probed: vector_topk over the docs of the min(n_probe, n_lists) lists of set_vector_lists whose centroids score
+        highest under the query (score descending, list ascending): exact within them, and vector_topk's bytes when every list is
+        probed and no doc is at NO_LIST -> (hits, n_hits), with return_probes (hits, n_hits, probes uint32 [n_q][min(n_probe,
+        n_lists)]).  device_out / out = (hits, n_hits[, probes]) as in vector_topk."""
+        qvec, n_q = self._qvec(qvec)
+        mask_id = _as(mask_id, "int32")
+        n_p = max(1, min(int(n_probe), getattr(self, "n_vec_lists", 0) or int(n_probe)))
+        if out is None:
+            if device_out:
+                import torch
+                dev = qvec.device if _is_torch(qvec) and qvec.is_cuda else torch.device("cuda", self.ctx.device_id)
+                out = (torch.zeros((n_q, int(k), 2), dtype=torch.int32, device=dev), torch.zeros(n_q, dtype=torch.int32, device=dev),
+                       torch.zeros((n_q, n_p), dtype=torch.int32, device=dev) if return_probes else None)
+            else:
+                out = (np.zeros((n_q, int(k)), dtype=VEC_HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                       np.zeros((n_q, n_p), dtype=np.uint32) if return_probes else None)
+        hits, n_hits = out[0], _as(out[1], "int32")
+        probes = out[2] if len(out) > 2 else None
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(hits) < n_q * int(k) * 8 or nbytes(n_hits) < n_q * 4 or (probes is not None and nbytes(probes) < n_q * n_p * 4)):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qvec, mask_id, hits, n_hits, probes)
+        check(self.ctx.lib.ss_vector_topk_probed(self.h, n_q, _ptr(qvec), _ptr(mask_id), int(k), int(n_probe), _ptr(hits), _ptr(n_hits),
+                                                 _ptr(probes)), self.ctx.h)
+        if _is_torch(hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return (hits, n_hits, probes) if return_probes or len(out) > 2 and probes is not None else (hits, n_hits)
 
     def hit_vector_scores(self, qvec, hits, n_hits, k_in: Optional[int] = None, out=None):
         """ss_hit_vector_scores: the score of every row hits[q][: n_hits[q]] under query vector q -> int32 [n_q][k_in]
@@ -1287,9 +1361,33 @@ class Scorer:
             self.ctx.lib.ss_scorer_destroy(self.h)
             self.h = None
 
+NO_LIST = 0xFFFFFFFF             # SS_NO_LIST
+
+
+def train_vector_lists(scorer: "Scorer", vec, n_lists: int, iters: int = 5, seed: int = 0):
+    """A convenience, not part of the ABI: k-means-style centroids for Scorer.set_vector_lists over the table `vec` (int8 [n_docs][dim],
+    registered on `scorer` by set_doc_vectors).  Centroids start as n_lists rows of vec drawn without replacement by
+    np.random.default_rng(seed); every iteration assigns on the device (assign_vector_lists) and replaces each centroid by
+    np.rint of the float64 mean of its docs, clipped to int8; an empty list keeps its centroid.  Returns (centroids int8
+    [n_lists][dim], list_of_doc uint32 [n_docs]) with list_of_doc the assignment to the centroids returned.  Defined as what
+    tests/vector_lists_model.py: train does."""
+    vec = np.ascontiguousarray(vec, dtype=np.int8)
+    n_docs = vec.shape[0]
+    rng = np.random.default_rng(seed)
+    centroids = vec[np.sort(rng.choice(n_docs, size=int(n_lists), replace=False))].copy()
+    for _ in range(int(iters)):
+        lists, _scores = scorer.assign_vector_lists(centroids, want_scores=False)
+        sums = np.zeros((int(n_lists), vec.shape[1]), np.float64)
+        np.add.at(sums, lists, vec.astype(np.float64))
+        cnt = np.bincount(lists, minlength=int(n_lists))
+        live = cnt > 0
+        centroids[live] = np.clip(np.rint(sums[live] / cnt[live, None]), -128, 127).astype(np.int8)
+    lists, _scores = scorer.assign_vector_lists(centroids, want_scores=False)
+    return centroids, lists
+
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
-           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED"]
+           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED", "NO_LIST", "train_vector_lists"]
 
 
 def _flatten_words(words, ptr_dtype: str):

@@ -210,6 +210,9 @@ PYBIND11_MODULE(_host, m) {
         .def("SetDocVectors", &retrieval::DeviceIndex::SetDocVectors, py::arg("vectors"))
         .def("VectorSearch", &retrieval::DeviceIndex::VectorSearch, py::arg("queryVectors"), py::arg("k") = 50,
              py::arg("masks") = std::vector<std::string>())
+        .def("SetVectorLists", &retrieval::DeviceIndex::SetVectorLists, py::arg("n_lists"), py::arg("centroids"))
+        .def("VectorSearchProbed", &retrieval::DeviceIndex::VectorSearchProbed, py::arg("queryVectors"), py::arg("k") = 50,
+             py::arg("n_probe") = 8, py::arg("masks") = std::vector<std::string>())
         .def("RerankByVector", &retrieval::DeviceIndex::RerankByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("first") = 0,
              py::arg("k") = 50)
         .def("ScoreDocs", [](retrieval::DeviceIndex& di, const std::string& query, const std::vector<std::string>& docHashes) {

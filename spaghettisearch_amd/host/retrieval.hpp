@@ -343,6 +343,10 @@ public:
     // again on every scorer this index creates.
     std::map<std::string, std::vector<int8_t>> doc_vectors;
     int doc_vector_dim = 0;
+    // Vector lists (SetVectorLists): the centroids [n_vector_lists][doc_vector_dim], kept and assigned again on every scorer the index
+    // creates, as the vectors are; a later SetDocVectors clears them.
+    std::vector<int8_t> list_centroids;
+    int n_vector_lists = 0;
     int near_dup_slots = 0;                         // SetNearDuplicates: the body table keeps MinHash signatures of this many slots (4 B each per doc)
     bool signatures_built = false;                  // the body table holds signatures that this object built and nothing has freed since
     // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
@@ -837,6 +841,8 @@ public:
             throw std::runtime_error("SetDocVectors: the length must be a multiple of 64 in [64, SS_MAX_VEC_DIM]");
         doc_vectors = vectors;
         doc_vector_dim = dim;
+        list_centroids.clear();                                                 // (the lists describe the old table)
+        n_vector_lists = 0;
         register_vectors();
     }
     void register_vectors() {
@@ -852,6 +858,33 @@ public:
             std::copy(kv.second.begin(), kv.second.end(), table.begin() + (size_t)it->second * doc_vector_dim);
         }
         check(ss_scorer_set_doc_vectors(scorer, doc_vector_dim, table.data()), "ss_scorer_set_doc_vectors");
+        register_vector_lists();
+    }
+    // Vector lists for VectorSearchProbed: n_lists centroids of the vectors' length.  Every doc goes to the list of the centroid with
+    // the largest integer dot product (ties to the lower list), assigned on the device; no centroids clears the lists.
+    void SetVectorLists(int n_lists, const std::vector<std::vector<int8_t>>& centroids) {
+        using namespace spaghetti;
+        if (n_lists < 0 || (size_t)n_lists != centroids.size()) throw std::runtime_error("SetVectorLists: n_lists centroids are needed");
+        if (!centroids.empty() && doc_vector_dim == 0) throw std::runtime_error("SetVectorLists: no doc vectors (SetDocVectors)");
+        if (centroids.size() > (size_t)SS_MAX_VEC_LISTS) throw std::runtime_error("SetVectorLists: more than SS_MAX_VEC_LISTS lists");
+        std::vector<int8_t> flat;
+        for (auto& c : centroids) {
+            if ((int)c.size() != doc_vector_dim) throw std::runtime_error("SetVectorLists: a centroid of the wrong length");
+            flat.insert(flat.end(), c.begin(), c.end());
+        }
+        list_centroids = std::move(flat);
+        n_vector_lists = (int)centroids.size();
+        if (n_vector_lists == 0 && scorer && doc_vector_dim) check(ss_scorer_set_vector_lists(scorer, 0, nullptr, nullptr), "ss_scorer_set_vector_lists");
+        register_vector_lists();
+    }
+    void register_vector_lists() {
+        using namespace spaghetti;
+        if (!scorer || !title || n_vector_lists == 0 || doc_vector_dim == 0) return;
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        std::vector<uint32_t> list_of_doc((size_t)n);
+        check(ss_vector_assign_lists(scorer, n_vector_lists, list_centroids.data(), list_of_doc.data(), nullptr), "ss_vector_assign_lists");
+        check(ss_scorer_set_vector_lists(scorer, n_vector_lists, list_centroids.data(), list_of_doc.data()), "ss_scorer_set_vector_lists");
     }
     std::vector<int8_t> flatten_query_vectors(const char* who, const std::vector<std::vector<int8_t>>& queryVectors) const {
         if (doc_vector_dim == 0) throw std::runtime_error(std::string(who) + ": no doc vectors (SetDocVectors)");
@@ -880,6 +913,34 @@ public:
         std::vector<ss_vec_hit> hits(nq * (size_t)std::max(k, 1));
         std::vector<int32_t> n_hits(nq);
         check(ss_vector_topk(scorer, (int32_t)nq, flat.data(), mask_id.data(), k, hits.data(), n_hits.data()), "ss_vector_topk");
+        std::vector<std::vector<VectorHit>> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_hits[q]; i++) {
+                const ss_vec_hit& h = hits[q * (size_t)k + i];
+                out[q].push_back(VectorHit{docs.name[h.doc], h.score});
+            }
+        return out;
+    }
+    // VectorSearch over the docs of the n_probe lists (SetVectorLists) whose centroids score highest under the query: exact within
+    // them, and VectorSearch's rows when every list is probed.
+    std::vector<std::vector<VectorHit>> VectorSearchProbed(const std::vector<std::vector<int8_t>>& queryVectors, int k = 50, int n_probe = 8,
+                                                           const std::vector<std::string>& masks = {}) {
+        using namespace spaghetti;
+        const std::vector<int8_t> flat = flatten_query_vectors("VectorSearchProbed", queryVectors);
+        if (n_vector_lists == 0) throw std::runtime_error("VectorSearchProbed: no vector lists (SetVectorLists)");
+        const size_t nq = queryVectors.size();
+        if (!masks.empty() && masks.size() != nq) throw std::runtime_error("VectorSearchProbed: one mask name per query");
+        std::vector<int32_t> mask_id(nq, -1);
+        for (size_t q = 0; q < masks.size(); q++) {
+            if (masks[q].empty()) continue;
+            auto it = mask_index.find(masks[q]);
+            if (it == mask_index.end()) throw std::runtime_error("VectorSearchProbed: no doc mask named '" + masks[q] + "' (SetDocMasks)");
+            mask_id[q] = it->second;
+        }
+        std::vector<ss_vec_hit> hits(nq * (size_t)std::max(k, 1));
+        std::vector<int32_t> n_hits(nq);
+        check(ss_vector_topk_probed(scorer, (int32_t)nq, flat.data(), mask_id.data(), k, n_probe, hits.data(), n_hits.data(), nullptr),
+              "ss_vector_topk_probed");
         std::vector<std::vector<VectorHit>> out(nq);
         for (size_t q = 0; q < nq; q++)
             for (int i = 0; i < n_hits[q]; i++) {
