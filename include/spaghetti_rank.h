@@ -55,7 +55,8 @@ extern "C" {
  * SS_FUSE_RRF / _WEIGHTED, ss_fuse_params, ss_fused, ss_score_docs, ss_fuse_hits and ss_hybrid_topk (the lexical row of any given doc,
  * a lexical and a vector list fused into one ranked, paged list, and both searches plus the fusion in one call);
  * SS_MAX_VEC_LISTS, SS_NO_LIST, ss_scorer_set_vector_lists, ss_vector_assign_lists and ss_vector_topk_probed (the vector table cut into
- * lists around centroids: the exact top k over the docs of the n_probe lists nearest to a query, not over every doc). */
+ * lists around centroids: the exact top k over the docs of the n_probe lists nearest to a query, not over every doc);
+ * ss_pr_lean_sweeps (how many sweeps of a state were launched in the lean form of option "pr.lean_sweeps"). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -264,6 +265,10 @@ int32_t ss_pr_destroy(ss_pr* pr);
 int32_t ss_pr_set_teleport(ss_pr* pr, const uint64_t* set_ptr /*[k_topics+1]*/, const uint32_t* set_nodes);
 int32_t ss_pr_begin(ss_pr* pr);
 int32_t ss_pr_step(ss_pr* pr, int32_t n_steps);
+/* Diagnostic: sweeps of this state launched in the lean form so far (option "pr.lean_sweeps", default on).  A state in
+ * fixed-iteration mode (eps < 0) on one rank, K >= 3, without teleport sets runs every sweep of an ss_pr_step call except the last
+ * two without loading or storing ranks; ranks, status and iteration counts behind the call are those of full sweeps. */
+int32_t ss_pr_lean_sweeps(ss_pr* pr, int64_t* n_out);
 int32_t ss_pr_finalize(ss_pr* pr);
 int32_t ss_pr_exchange_buffers(ss_pr* pr, void** send_dev, uint64_t* send_bytes,
                                void** recv_dev, uint64_t* recv_bytes);

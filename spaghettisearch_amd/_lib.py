@@ -116,6 +116,7 @@ PROTOTYPES = {
     "ss_pr_set_teleport": (_i32, [_vp, _vp, _vp]),
     "ss_pr_begin": (_i32, [_vp]),
     "ss_pr_step": (_i32, [_vp, _i32]),
+    "ss_pr_lean_sweeps": (_i32, [_vp, C.POINTER(C.c_int64)]),
     "ss_pr_finalize": (_i32, [_vp]),
     "ss_pr_exchange_buffers": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64)]),
     "ss_pr_exchange": (_i32, [_vp, _i32]),

@@ -307,6 +307,9 @@ static const char* const k_option_names[] = {
                             //    table order (default for k_pr_sweep and k_pr_sweep_n<2>)
     "pr.share_zero_rows",   // k_pr_sweep without teleport sets, one rank: default 1 = the non-dangling rows without in-edges share ONE table row per distinct
                             //    out-degree (the state gathers through its own remapped copy of in_src); 0 = a table row each.  Results are bit-identical
+    "pr.lean_sweeps",       // k_pr_sweep in fixed-iteration mode (eps < 0), one rank, no teleport sets: default 1 = the sweeps of a call whose ranks and L1
+                            //    change no caller can see (all but its last two) neither load nor store ranks and skip the dangling rows; 0 = every sweep
+                            //    in full.  Everything a caller can read is bit-identical
     "pr.item_turns",        // turns per V_DEG work item of k_pr_sweep (V_QUAD: twice that); default 4 up to 4M local rows, 8 beyond
     "graph.late_free",      // 0: ss_graph_create waits for its last kernels and frees its temporaries before it returns (default 1: they are freed
                             //    at the graph's next use, the caller's host work overlaps the row permutation)

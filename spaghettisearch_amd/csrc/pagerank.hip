@@ -349,10 +349,10 @@ void launch_read(ss_pr* pr, hipStream_t st, int by_orig, uint64_t stride, uint32
 namespace ss {
 unsigned begin_blocks(const ss_pr* pr) { return std::max(1u, std::min(2048u, ss::div_up((size_t)pr->g->n_local() * pr->gw, TPB))); }
 void pr_launch_begin(ss_pr* pr, hipStream_t st, unsigned nb) { SS_GW_DISPATCH(pr->gw, launch_begin, pr, st, nb); }
-void pr_launch_step(ss_pr* pr, hipStream_t st) {
+void pr_launch_step(ss_pr* pr, hipStream_t st, bool lean) {
     switch (pr->kernel) {
         case PR_STEP: pr_step_launch(pr, st); break;
-        case PR_SWEEP: pr_sweep_launch(pr, st); break;
+        case PR_SWEEP: pr_sweep_launch(pr, st, lean); break;
         case PR_SWEEP_N: pr_sweep_n_launch(pr, st); break;
     }
 }
@@ -466,6 +466,7 @@ void fill_params(ss_pr* pr, const Cut& cut, const PlanOptions& opt, double dampi
     p.stagger_code = opt.stagger >= 10 ? (uint32_t)(opt.stagger - 10) : 0u;
     p.class_order = pack_class_order(opt.class_order);
     p.n_order = pack_n_order(opt.n_class_order);
+    p.woff_lean = pr->lean ? pr->woff_lean.p : nullptr;
 }
 
 // pr.trace: 64-bit FNV-1a hashes of the plan (the host work table as uploaded, the per-wave offsets, the scalar fields of PrParams): two
@@ -619,6 +620,19 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
         if (trace) fprintf(stderr, "[pr trace]   deal: placement %.3f ms\n", t_ms(td1, t_now()));
     }
     const std::vector<WorkItem>& items = cut.items;
+    // The lean walk (option "pr.lean_sweeps", default on): a state on k_pr_sweep, one rank, not the two-vector form.  Whether a sweep
+    // runs lean is decided per launch (ss::pr_step); its items stand behind the others in the work table.
+    pr->lean = pr->kernel == PR_SWEEP && g->world == 1 && ctx->opt("pr.affine", 0) == 0 && ctx->opt("pr.lean_sweeps", 1) != 0;
+    static const std::vector<WorkItem> no_items;
+    const std::vector<WorkItem>* lean_items = &no_items;
+    const std::vector<uint32_t>* lean_woff = &no_woff;
+    if (pr->lean) {
+        const auto tl0 = t_now();
+        const LeanPlan lp = plan_lean_items(items, *woff, pr->nblocks * WAVES, g->sl_nd, (uint32_t)items.size());   // (behind the full table)
+        lean_items = &lp.items;
+        lean_woff = &lp.woff;
+        if (trace) fprintf(stderr, "[pr trace]   lean walk: %zu of %zu items, %.3f ms\n", lp.items.size() - 2, items.size() - 2, t_ms(tl0, t_now()));
+    }
 
     // the graph's build temporaries (ss_graph::late_free): its last kernels ran under the host work above
     g->settle();
@@ -648,10 +662,16 @@ int32_t ss_pr_create(ss_graph* g, double damping, double eps, int32_t max_iter, 
     SS_HIP(ctx, hipMemsetAsync(pr->rowticket.p, 0, pr->rowticket.bytes(), st));
     SS_HIP(ctx, pr->woff.alloc(std::max<size_t>(woff->size(), 8)));
     if (!woff->empty()) SS_HIP(ctx, hipMemcpyAsync(pr->woff.p, woff->data(), woff->size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    SS_HIP(ctx, pr->work.alloc(items.size()));
+    const size_t n_work = items.size() + lean_items->size();
+    SS_HIP(ctx, pr->work.alloc(n_work));
     SS_HIP(ctx, hipMemcpyAsync(pr->work.p, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+    if (pr->lean) {
+        SS_HIP(ctx, hipMemcpyAsync(pr->work.p + items.size(), lean_items->data(), lean_items->size() * sizeof(WorkItem), hipMemcpyHostToDevice, st));
+        SS_HIP(ctx, pr->woff_lean.alloc(std::max<size_t>(lean_woff->size(), 8)));
+        SS_HIP(ctx, hipMemcpyAsync(pr->woff_lean.p, lean_woff->data(), lean_woff->size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
     if (vitems)
-        hipLaunchKernelGGL(k_pr_item_ranges, dim3(ss::div_up(items.size(), TPB)), dim3(TPB), 0, st, pr->work.p, (uint32_t)items.size(), (const uint32_t*)g->in_ptr.p);
+        hipLaunchKernelGGL(k_pr_item_ranges, dim3(ss::div_up(n_work, TPB)), dim3(TPB), 0, st, pr->work.p, (uint32_t)n_work, (const uint32_t*)g->in_ptr.p);
     SS_HIP(ctx, pr->ctl.alloc(1));
     SS_HIP(ctx, hipMemsetAsync(pr->ctl.p, 0, sizeof(PrCtl), st));
     double h_x0[MAXK];
@@ -782,6 +802,7 @@ int32_t ss_pr_begin(ss_pr* pr) {
     ss::pr_launch_begin(pr, ctx->stream, ss::begin_blocks(pr));
     SS_HIP(ctx, hipGetLastError());
     pr->begun = true;
+    pr->sweeps_enq = 0;
     if (pr->g->world > 1) {
         pr->need_finalize = true;
         pr->finalize_is_begin = true;
@@ -791,6 +812,24 @@ int32_t ss_pr_begin(ss_pr* pr) {
 
 int32_t ss_pr_step(ss_pr* pr, int32_t n_steps) {
     if (!pr) return SS_ERR_INVALID;
+    return ss::pr_step(pr, n_steps, 2);           // a caller may read the ranks and the last L1 change behind every call
+}
+
+int32_t ss_pr_lean_sweeps(ss_pr* pr, int64_t* n_out) {
+    if (!pr || !n_out) return SS_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(pr->g->ctx->mu);
+    *n_out = pr->n_lean;
+    return SS_OK;
+}
+
+}  // extern "C"
+
+// Which sweeps of a call run lean (k_pr_sweep<GW, false, true>): only those whose rank array and L1 change nobody can see.  The state
+// is in fixed-iteration mode (eps < 0: no stop rule reads the change, no topic freezes), has a lean walk (ss_pr_create: k_pr_sweep,
+// one rank, "pr.lean_sweeps"), no teleport sets and not the two-vector form; the sweep is none of the call's last `full_tail` and
+// none of the last two before max_iter, where the run ends.  The last sweep's L1 change needs the ranks of the sweep before it, so
+// that one runs full as well (for its rank store alone; its old-rank read is the price of having two kernels, not three).
+int32_t ss::pr_step(ss_pr* pr, int32_t n_steps, int32_t full_tail) {
     ss_ctx* ctx = pr->g->ctx;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     SS_HIP(ctx, hipSetDevice(ctx->device));
@@ -802,8 +841,15 @@ int32_t ss_pr_step(ss_pr* pr, int32_t n_steps) {
     if (pr->persist && !pr->prm.memb && !pr->prm.aff) {
         ss::pr_multi_n_launch(pr, ctx->stream, (int)n_steps);   // the sweeps wait for each other inside the launch
     } else {
-        for (int i = 0; i < n_steps; i++) ss::pr_launch_step(pr, ctx->stream);
+        const PrParams& p = pr->prm;
+        const bool lean_ok = pr->lean && p.eps < 0.0 && !p.memb && !p.aff;
+        for (int i = 0; i < n_steps; i++) {
+            const int64_t s = pr->sweeps_enq + 1 + i;                  // this sweep's number since ss_pr_begin
+            const bool lean = lean_ok && i + full_tail < n_steps && (p.max_iter <= 0 || s + 2 <= p.max_iter);
+            ss::pr_launch_step(pr, ctx->stream, lean);
+        }
     }
+    pr->sweeps_enq += n_steps;
     SS_HIP(ctx, hipEventRecord(ctx->ev[0][1], ctx->stream));
     ctx->ev_valid[0] = true;
     SS_HIP(ctx, hipGetLastError());
@@ -813,6 +859,8 @@ int32_t ss_pr_step(ss_pr* pr, int32_t n_steps) {
     }
     return SS_OK;
 }
+
+extern "C" {
 
 int32_t ss_pr_finalize(ss_pr* pr) {
     if (!pr) return SS_ERR_INVALID;

@@ -775,7 +775,8 @@ int32_t ss_pagerank_run(ss_graph* g, double damping, double eps, int32_t max_ite
         while (rc == SS_OK && n_active > 0) {
             int todo = BATCH;
             if (max_iter > 0) todo = std::min(BATCH, std::max(1, max_iter - sweeps));
-            rc = ss_pr_step(pr, todo);
+            // (a fixed-iteration run: nothing reads ranks or the L1 change between the batches, and max_iter keeps its last two sweeps full)
+            rc = ss::pr_step(pr, todo, eps < 0.0 ? 0 : 2);
             if (rc == SS_OK) rc = ss_pr_status(pr, iters_out ? iters_out + k0 : nullptr, &n_active, &sweeps, nullptr, nullptr);
         }
         if (rc == SS_OK) rc = ss_pr_read(pr, rank_out + (size_t)k0 * g->n);

@@ -64,6 +64,8 @@ struct PlanScratch {
     std::vector<double> cost, load;
     std::vector<uint32_t> owner, by_load, idx, order, bucket, woff, cnt;
     std::vector<std::pair<double, uint32_t>> key;
+    std::vector<WorkItem> lean_items;                            // plan_lean_items
+    std::vector<uint32_t> lean_woff;
 };
 inline PlanScratch& plan_scratch() {
     static thread_local PlanScratch s;
@@ -367,6 +369,39 @@ inline const std::vector<uint32_t>& place_items(Cut& cut, std::vector<uint32_t>&
     s.dealt.push_back({V_ZERO, 0, 0, 0, 0, 0, 0, 0});
     items.swap(s.dealt);
     return woff;
+}
+
+// ---- the lean sweep's walk ("pr.lean_sweeps") -------------------------------------------------------------------------------
+// A lean sweep of k_pr_sweep (pr_sweep.hip) writes neither ranks nor an L1 change, so the items of dangling rows (local row >= sl_nd:
+// no table row either) have nothing to produce in it.  The dealt table mixes the two row classes inside a (wave, class) range
+// (hub pieces and whole long rows of both in class 0, the mid rows merged by length), and the full sweep's L1 change depends on
+// that order — so the table stays as it is, and the lean sweep gets a second, shorter one: every (wave, class) range without its
+// dangling items, the others in the order place_items gave them (the contribution sums of a wave are added in the same order in
+// both sweeps), its own two pad items behind it and its own per-wave class offsets.  All pieces of a cut dangling row go together:
+// no ticket of such a row is ever taken in a lean sweep.  The waves are NOT dealt again; what a wave's lean walk costs is whatever
+// the full deal left it.
+// `dealt`, `woff`: what place_items returned (the table with its two pad items); base: where in the work table the lean items will
+// stand (the offsets count from there).
+struct LeanPlan {
+    const std::vector<WorkItem>& items;   // (the calling thread's scratch)
+    const std::vector<uint32_t>& woff;    // [nw][8]
+};
+inline LeanPlan plan_lean_items(const std::vector<WorkItem>& dealt, const std::vector<uint32_t>& woff, uint32_t nw, uint32_t sl_nd, uint32_t base) {
+    PlanScratch& s = plan_scratch();
+    auto& items = s.lean_items;
+    auto& loff = s.lean_woff;
+    items.clear();
+    loff.assign((size_t)nw * 8, base);
+    const size_t n = dealt.size() >= 2 ? dealt.size() - 2 : 0;   // without the pad items
+    for (size_t j = 0; j < (size_t)nw * 8 && j < woff.size(); j++) {
+        loff[j] = base + (uint32_t)items.size();
+        const size_t lo = std::min<size_t>(woff[j], n), hi = j + 1 < woff.size() ? std::min<size_t>(woff[j + 1], n) : n;
+        for (size_t i = lo; i < hi; i++)
+            if (dealt[i].row < sl_nd) items.push_back(dealt[i]);
+    }
+    items.push_back({V_ZERO, 0, 0, 0, 0, 0, 0, 0});              // the pipelines read two items ahead
+    items.push_back({V_ZERO, 0, 0, 0, 0, 0, 0, 0});
+    return {items, loff};
 }
 
 // "pr.class_order": six decimal digits, position by position (012345 = long rows, mid rows, the three short-row classes,

@@ -93,6 +93,8 @@ struct PrParams {
     uint32_t n_shared;        // shared rows: table rows zrow + 1 .. zrow + n_shared
     uint32_t share;           // 1: the table ends at pos_nd (+ zero row + shared rows) and in_src is the state's remapped copy
     uint32_t tab_rows;        // rows of the table that belong to a local row of their own (share: pos_nd, otherwise sl_nd)
+    // the lean sweep (option "pr.lean_sweeps", k_pr_sweep<GW, false, true> only; pr_plan.hpp: LeanPlan)
+    const uint32_t* woff_lean; // [waves][8] as woff, into the work table's second part: the same walk without the dangling rows' items
 };
 
 }  // namespace
@@ -123,6 +125,10 @@ struct ss_pr {
     ss::DevBuf<uint32_t> woff;          // k_pr_sweep: per-wave class offsets into work
     ss::DevBuf<uint32_t> src_shared;    // "pr.share_zero_rows": the state's copy of in_src, sources without in-edges -> their shared row
     ss::DevBuf<uint32_t> sh_deg;        // ... and the shared rows' out-degrees
+    ss::DevBuf<uint32_t> woff_lean;     // "pr.lean_sweeps": the lean walk's per-wave class offsets (its items stand behind the others in `work`)
+    bool lean = false;                  // ... the state has a lean walk: k_pr_sweep on one rank, option on (ss::pr_step decides per sweep)
+    int64_t sweeps_enq = 0;             // sweeps enqueued since ss_pr_begin (the host's count: what a lean launch is decided from)
+    int64_t n_lean = 0;                 // ... of them launched lean (ss_pr_lean_sweeps)
     ss::DevBuf<PrCtl> ctl;
     bool begun = false;
     bool need_finalize = false;   // world>1: a begin/step is waiting for its exchange + finalize
@@ -135,12 +141,16 @@ namespace ss {
 // pagerank.hip: launchers of its kernels; the kernel for the state's lane-group width (and teleport sets) is picked inside
 unsigned begin_blocks(const ss_pr* pr);                            // grid of k_pr_begin
 void pr_launch_begin(ss_pr* pr, hipStream_t st, unsigned nb);
-void pr_launch_step(ss_pr* pr, hipStream_t st);                    // one sweep: the one place that switches on pr->kernel
+void pr_launch_step(ss_pr* pr, hipStream_t st, bool lean = false); // one sweep: the one place that switches on pr->kernel
+// n_steps sweeps on the context's stream, as ss_pr_step (which is this with full_tail = 2).  A state in fixed-iteration mode runs
+// the sweeps whose ranks and L1 change no caller can see lean: all but the last `full_tail` of the call and the last two before
+// max_iter.  ss_pagerank_run passes 0: between its batches it reads neither, and max_iter ends its run.
+int32_t pr_step(ss_pr* pr, int32_t n_steps, int32_t full_tail);
 void pr_launch_finalize(ss_pr* pr, hipStream_t st, int is_begin);  // world > 1: behind the exchange
 // The sweep-kernel families, one file each: a launcher of one sweep over pr->nblocks blocks, which picks the instantiation for the
 // state's width, teleport sets and mode itself, and the blocks per CU the runtime admits of the family's kernel of width gw
 // (unclamped; pagerank.hip asks once per kernel and process and keeps the answer)
-void pr_sweep_launch(ss_pr* pr, hipStream_t st);                   // pr_sweep.hip: k_pr_sweep<8|16, TS>
+void pr_sweep_launch(ss_pr* pr, hipStream_t st, bool lean);        // pr_sweep.hip: k_pr_sweep<8|16, TS, LEAN>
 int pr_sweep_occupancy(int gw);
 void pr_sweep_n_launch(ss_pr* pr, hipStream_t st);                 // pr_sweep_n.hip: k_pr_sweep_n<1|2, TS>
 int pr_sweep_n_occupancy(int gw);

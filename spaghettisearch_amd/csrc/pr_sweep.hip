@@ -1,4 +1,4 @@
-// pr_sweep.hip — k_pr_sweep<8|16, TS>: the wave-item sweep of the padded lane-group widths, the product path for K >= 3 and the
+// pr_sweep.hip — k_pr_sweep<8|16, TS, LEAN>: the wave-item sweep of the padded lane-group widths, the product path for K >= 3 and the
 // benchmark's headline kernel.  Exports ss::pr_sweep_launch and ss::pr_sweep_occupancy (and, in the SS_PR_WAVETIME
 // variant build, ss::pr_dump_wave_times).
 #include "pr_device.hpp"
@@ -29,7 +29,13 @@ __device__ __forceinline__ double tab_at(const double* __restrict__ T, uint32_t 
 
 // TS: the state holds teleport sets (ss_pr_set_teleport).  A kernel of its own, so that the reference's path carries no
 // membership loads (a load under a branch in finish_row makes the compiler drain the loads in flight: s_waitcnt vmcnt(0)).
-template <int GW, bool TS>
+// LEAN: a sweep of a fixed-iteration run whose ranks and L1 change no caller can see (ss::pr_step decides which; TS = false only).
+// It produces what the next sweep reads — the table, the contribution sum, the hub rows' contribution slots, the shared rows,
+// the control block — from the same expressions in the same order, and nothing else: no old-rank load, no rank store, no L1
+// arithmetic, and the waves walk p.woff_lean, which holds no item of a dangling row (such a row has no table row: its sum feeds
+// only its rank).  The rank array and the published L1 change are stale behind it; the host runs the last two sweeps in front of
+// anything a caller can read full.  A parameter and not a branch for the same reason as TS.
+template <int GW, bool TS, bool LEAN>
 struct SweepCtx {
     const PrParams& p;
     const double* __restrict__ T;
@@ -67,14 +73,24 @@ __device__ __forceinline__ void gather_turn(const double* __restrict__ T, const 
 // hub: the row was cut into pieces and is finished by whichever wave handed its piece in last, a different one from run to run — its
 // two terms go to the row's own slot (PrParams::hubsum, added in row order by block_reduce_and_publish), not into this wave's sums,
 // whose order of addition must not depend on who arrives when
-template <int GW, bool TS>
-__device__ __forceinline__ void finish_row(SweepCtx<GW, TS>& c, uint32_t lrow, double y, double xo, uint32_t od, double* hub = nullptr) {
+template <int GW, bool TS, bool LEAN>
+__device__ __forceinline__ void finish_row(SweepCtx<GW, TS, LEAN>& c, uint32_t lrow, double y, double xo, uint32_t od, double* hub = nullptr) {
     const PrParams& p = c.p;
     y += c.x0;
     const size_t xi = (size_t)lrow * GW + c.t;
     double tele = p.teleport;
     if constexpr (TS) tele = teleport_of(p, lrow, c.t);
     double xn = (y + tele) / c.S;                             // pagerank.go:117
+    if constexpr (LEAN) {
+        // every row of a lean walk is non-dangling, and a topic that is not active is one of the padding topics (a fixed-iteration
+        // run freezes none): its ranks are the 0.0 they were set to, which the full sweep reads back as xo
+        if (!c.act) xn = 0.0;
+        const double cc = p.d * xn / (double)od;              // pagerank.go:136
+        NT_STORE(cc, &c.Tw[xi]);
+        if (hub) __hip_atomic_store(&hub[GW + c.t], cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else c.csum += cc;                                    // pagerank.go:137
+        return;
+    }
     if (c.act) {
         NT_STORE(xn, &p.x[xi]);
         if (!hub) c.dsum += fabs(xn - xo);                    // pagerank.go:118
@@ -96,8 +112,8 @@ __device__ __forceinline__ void finish_row(SweepCtx<GW, TS>& c, uint32_t lrow, d
 // V_SEG / V_ROWW: the wave's items are long rows (or <= SEGW-edge pieces of the longest ones); turn i of an item
 // gives lane group s the edges beg + 64*i + 16*s ...  The pipeline runs across the items: the last turn of one item
 // requests the first index words of the next.
-template <int GW, bool TS>
-__device__ __forceinline__ void long_rows(SweepCtx<GW, TS>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1, int lane) {
+template <int GW, bool TS, bool LEAN>
+__device__ __forceinline__ void long_rows(SweepCtx<GW, TS, LEAN>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1, int lane) {
     constexpr int NS = 64 / GW;
     constexpr uint32_t TW = NS * CH;                          // edges per wave turn
     const PrParams& p = c.p;
@@ -112,7 +128,8 @@ __device__ __forceinline__ void long_rows(SweepCtx<GW, TS>& c, const WorkItem* _
         const WorkItem nn = work[it + 2];
         const uint32_t lrow = cur.row;
         // the row's old rank and out-degree: asked for now, used after the last turn
-        const double xo = NT_LOAD(&p.x[(size_t)lrow * GW + c.t]);
+        double xo = 0.0;
+        if constexpr (!LEAN) xo = NT_LOAD(&p.x[(size_t)lrow * GW + c.t]);
         const uint32_t od = lrow < p.sl_nd ? NT_LOAD(&p.outdeg[lrow]) : 1u;
         const uint32_t turns = (cur.end - cur.beg + TW - 1) / TW;
         const bool more = it + 1 < i1;
@@ -162,8 +179,8 @@ __device__ __forceinline__ void long_rows(SweepCtx<GW, TS>& c, const WorkItem* _
 // is walked in nch (= item.nseg) turns (its own length decides how many slots of a turn are real).  The bounds and
 // out-degrees of ALL rows of an item come in one request (lane t of group s holds row `row + t*NS + s`), one item ahead;
 // the pipeline runs across row groups and items.
-template <int GW, bool TS>
-__device__ __forceinline__ void quad_rows(SweepCtx<GW, TS>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1) {
+template <int GW, bool TS, bool LEAN>
+__device__ __forceinline__ void quad_rows(SweepCtx<GW, TS, LEAN>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1) {
     constexpr int NS = 64 / GW;
     const PrParams& p = c.p;
     if (i0 >= i1) return;
@@ -211,7 +228,8 @@ __device__ __forceinline__ void quad_rows(SweepCtx<GW, TS>& c, const WorkItem* _
         const uint32_t lrow = cur.row + q * NS + (uint32_t)c.slot;
         const bool valid = q * NS + (uint32_t)c.slot < cur.count;
         double xo = 0.0;
-        if (ends) xo = NT_LOAD(&p.x[(size_t)(valid ? lrow : cur.row) * GW + c.t]);
+        if constexpr (!LEAN)
+            if (ends) xo = NT_LOAD(&p.x[(size_t)(valid ? lrow : cur.row) * GW + c.t]);
         double v[CH];
         gather_turn<GW>(c.T, src, c.t, c.gbase, v);
 #pragma unroll
@@ -237,8 +255,8 @@ __device__ __forceinline__ void quad_rows(SweepCtx<GW, TS>& c, const WorkItem* _
 
 // V_DEG: an item = `count` rows of exactly D (= item.nseg) in-edges from `row` (their edges are contiguous from item.beg);
 // a lane group takes R rows per turn, row r of the turn at slots r*DM .. r*DM+D-1 (DM = 16/R >= D)
-template <int GW, int R, bool TS>
-__device__ __forceinline__ void deg_rows(SweepCtx<GW, TS>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1) {
+template <int GW, int R, bool TS, bool LEAN>
+__device__ __forceinline__ void deg_rows(SweepCtx<GW, TS, LEAN>& c, const WorkItem* __restrict__ work, uint32_t i0, uint32_t i1) {
     constexpr int NS = 64 / GW;
     constexpr int DM = CH / R;
     constexpr int IR = CH / GW;
@@ -272,7 +290,10 @@ __device__ __forceinline__ void deg_rows(SweepCtx<GW, TS>& c, const WorkItem* __
             // old ranks and out-degrees of the R rows travel with the gathers
             double xo[R];
 #pragma unroll
-            for (int r = 0; r < R; r++) xo[r] = NT_LOAD(&p.x[(size_t)(row0 + (rb + r < count ? rb + r : 0u)) * GW + c.t]);
+            for (int r = 0; r < R; r++) {
+                xo[r] = 0.0;
+                if constexpr (!LEAN) xo[r] = NT_LOAD(&p.x[(size_t)(row0 + (rb + r < count ? rb + r : 0u)) * GW + c.t]);
+            }
             const uint32_t myr = row0 + (rb + (uint32_t)c.t < count ? rb + (uint32_t)c.t : 0u);
             const uint32_t odv = (c.t < R && myr < p.sl_nd) ? NT_LOAD(&p.outdeg[myr]) : 1u;
             double v[CH];
@@ -299,8 +320,9 @@ __device__ __forceinline__ void deg_rows(SweepCtx<GW, TS>& c, const WorkItem* __
 // (100 MHz realtime counter), printed by ss_pr_destroy — how level the deal is in TIME, not in modelled turns
 __device__ unsigned long long g_pr_wt[65536][2];
 #endif
-template <int GW, bool TS>
+template <int GW, bool TS, bool LEAN>
 __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
+    static_assert(!(TS && LEAN), "the lean sweep exists without teleport sets only");
     constexpr int NS = 64 / GW;
     PrCtl* ctl = p.ctl;
     if (ctl->n_active == 0) return;   // every topic converged: the launch is a no-op
@@ -311,7 +333,7 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
     const int sweep = ctl->sweep;
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    SweepCtx<GW, TS> c{p, p.tab_rd[sweep & 1], p.tab_wr[sweep & 1], 0.0, 0.0, false, lane % GW, lane - lane % GW, lane / GW, 0.0, 0.0};
+    SweepCtx<GW, TS, LEAN> c{p, p.tab_rd[sweep & 1], p.tab_wr[sweep & 1], 0.0, 0.0, false, lane % GW, lane - lane % GW, lane / GW, 0.0, 0.0};
     c.S = ctl->S[c.t];
     c.act = ctl->active[c.t] != 0;
     c.x0 = sweep == 0 ? p.x0[c.t] : 0.0;      // Q4: iteration 1 accumulates onto 1/n
@@ -330,7 +352,7 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
     // This wave's items: work[off[k] .. off[k+1]) for class k.  The host dealt the items to the waves so that every wave
     // gets the same number of turns (ss_pr_create); one loop per class, so that the register allocator sees each
     // pipeline on its own instead of the union of all of them.
-    const uint32_t* __restrict__ off = p.woff + (size_t)(blockIdx.x * WAVES + wave) * 8;
+    const uint32_t* __restrict__ off = (LEAN ? p.woff_lean : p.woff) + (size_t)(blockIdx.x * WAVES + wave) * 8;
     // The ORDER in which a wave walks its classes matters more than anything tried on the deal (round 5: all 720 orders, 4 blocks per
     // CU, config 4): short rows first, long rows last — 2, 3, 5, 4, 0, 1 = rows of <= 2 in-edges, <= 4, edge-less, <= 8, long, mid —
     // 0.902-0.904 ms per sweep against 0.947 in the order the classes are numbered (worst order 0.961).  Round 4's "stagger" (the
@@ -400,7 +422,8 @@ __global__ __launch_bounds__(TPB, SS_PR_MINW) void k_pr_sweep(PrParams p) {
         if (lane == 0) { g_pr_wt[wid][0] = wt0; g_pr_wt[wid][1] = wt1; }
     }
 #endif
-    block_reduce_and_publish<GW>(p, c.dsum, c.csum, c.Tw, false);
+    // (lean: the published L1 change is not one — no row adds to it, the cut rows' slots keep an older sweep's terms)
+    block_reduce_and_publish<GW>(p, LEAN ? 0.0 : c.dsum, c.csum, c.Tw, false);
 }
 
 template __device__ void begin_caller_context<8, 16>(const PrParams&, double*);   // pr_device.hpp: keeps the helpers' code the parent file's
@@ -408,20 +431,24 @@ template __device__ void begin_caller_context<8, 16>(const PrParams&, double*); 
 }  // namespace
 
 namespace ss {
-void pr_sweep_launch(ss_pr* pr, hipStream_t st) {
+void pr_sweep_launch(ss_pr* pr, hipStream_t st, bool lean) {
     const bool ts = pr->prm.memb != nullptr;
+    lean = lean && !ts && pr->prm.woff_lean;
+    if (lean) pr->n_lean++;
     if (pr->gw == 8) {
-        if (ts) hipLaunchKernelGGL((k_pr_sweep<8, true>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
-        else hipLaunchKernelGGL((k_pr_sweep<8, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        if (ts) hipLaunchKernelGGL((k_pr_sweep<8, true, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        else if (lean) hipLaunchKernelGGL((k_pr_sweep<8, false, true>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        else hipLaunchKernelGGL((k_pr_sweep<8, false, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
     } else {
-        if (ts) hipLaunchKernelGGL((k_pr_sweep<16, true>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
-        else hipLaunchKernelGGL((k_pr_sweep<16, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        if (ts) hipLaunchKernelGGL((k_pr_sweep<16, true, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        else if (lean) hipLaunchKernelGGL((k_pr_sweep<16, false, true>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
+        else hipLaunchKernelGGL((k_pr_sweep<16, false, false>), dim3(pr->nblocks), dim3(TPB), 0, st, pr->prm);
     }
 }
 int pr_sweep_occupancy(int gw) {
     int per_cu = 8;
-    if (gw == 8) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep<8, false>, TPB, 0);
-    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep<16, false>, TPB, 0);
+    if (gw == 8) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep<8, false, false>, TPB, 0);
+    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pr_sweep<16, false, false>, TPB, 0);
     return per_cu;
 }
 

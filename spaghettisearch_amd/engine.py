@@ -373,6 +373,12 @@ class PageRankState:
     def step(self, n_steps: int = 1) -> None:
         check(self.ctx.lib.ss_pr_step(self.h, n_steps), self.ctx.h)
 
+    def lean_sweeps(self) -> int:
+        """ss_pr_lean_sweeps: sweeps of this state launched in the lean form so far (option pr.lean_sweeps)."""
+        n = C.c_int64(0)
+        check(self.ctx.lib.ss_pr_lean_sweeps(self.h, C.byref(n)), self.ctx.h)
+        return int(n.value)
+
     def finalize(self) -> None:
         check(self.ctx.lib.ss_pr_finalize(self.h), self.ctx.h)
 
