@@ -1262,6 +1262,47 @@ func (s *Scorer) RerankHitsByVector(qvec []int8, hits [][]Hit, first, k int) ([]
 	return out, outVals, nil
 }
 
+// DivInfo says why a row of a diversified page was chosen (ss_div_info): its relevance and its largest similarity to the rows chosen
+// before it (C.SS_NO_VEC_SCORE for the first row; both C.SS_NO_VEC_SCORE for a doc outside the table).
+type DivInfo struct {
+	Rel, Sim int32
+}
+
+// DiversifyHits re-ranks every window greedily: each next row is the one with the largest wRel*rel - wDiv*(largest similarity of its
+// doc vector to a row already chosen), of equal values the earlier row; rows outside the table last; page [first, first+k)
+// (ss_diversify_hits).  rel is the row's score under the query's vector, or, with qvec nil, minus its window position.  The weights
+// are integers in [0, C.SS_DIV_WEIGHT_MAX].
+func (s *Scorer) DiversifyHits(qvec []int8, hits [][]Hit, wRel, wDiv, first, k int) ([][]Hit, [][]DivInfo, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	in, nIn, kIn := vecWindow(hits)
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, info := make([]int32, nq), make([]C.ss_div_info, nq*kk)
+	rc := C.ss_diversify_hits(s.h, C.int32_t(nq), i8p(qvec), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn),
+		C.int32_t(wRel), C.int32_t(wDiv), C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits),
+		(*C.ss_div_info)(unsafe.Pointer(&info[0])))
+	if err := statusErr(s.ctx, rc, "ss_diversify_hits"); err != nil {
+		return nil, nil, err
+	}
+	out, outInfo := make([][]Hit, nq), make([][]DivInfo, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q], outInfo[q] = make([]Hit, n), make([]DivInfo, n)
+		for i := 0; i < n; i++ {
+			r := raw[q*kk+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+			outInfo[q][i] = DivInfo{int32(info[q*kk+i].rel), int32(info[q*kk+i].sim)}
+		}
+	}
+	return out, outInfo, nil
+}
+
 // FuseParams says how FuseHits / HybridTopK merge the two rankings (ss_fuse_params): Mode C.SS_FUSE_RRF (wLex/(RrfC+lexical rank) +
 // wVec/(RrfC+vector rank)) or C.SS_FUSE_WEIGHTED (wLex*FinalRank + wVec*vector score).
 type FuseParams struct {

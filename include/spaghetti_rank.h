@@ -56,7 +56,9 @@ extern "C" {
  * a lexical and a vector list fused into one ranked, paged list, and both searches plus the fusion in one call);
  * SS_MAX_VEC_LISTS, SS_NO_LIST, ss_scorer_set_vector_lists, ss_vector_assign_lists and ss_vector_topk_probed (the vector table cut into
  * lists around centroids: the exact top k over the docs of the n_probe lists nearest to a query, not over every doc);
- * ss_pr_lean_sweeps (how many sweeps of a state were launched in the lean form of option "pr.lean_sweeps"). */
+ * ss_pr_lean_sweeps (how many sweeps of a state were launched in the lean form of option "pr.lean_sweeps");
+ * SS_DIV_WEIGHT_MAX, ss_div_info and ss_diversify_hits (a window re-ranked greedily by relevance minus similarity to the rows already
+ * chosen: maximal marginal relevance over the doc vectors). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -870,6 +872,49 @@ int32_t ss_hit_vector_scores(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_
 int32_t ss_rerank_hits_by_vector(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim]*/, int32_t k_in,
                                  const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
                                  ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
+
+/* ss_diversify_hits: a window re-ranked greedily so that every next row is chosen for its relevance minus its similarity to the rows
+ * already on the page (maximal marginal relevance).  No reference counterpart.  ss_rerank_hits_by_vector and ss_hybrid_topk can put five
+ * paraphrases of one page at the top: ss_dedup_hits does not see them (they share no words) and ss_collapse_hits does not (they sit
+ * on different hosts).  Defined bit for bit; no float is involved:
+ *   Window.     As in ss_collapse_hits: hits[q * k_in .. q * k_in + n_hits[q]), in the order given; only .doc of a row is read.  n is
+ *               its length.
+ *   Classes.    A row with doc < n_docs is INSIDE, a row with doc >= n_docs OUTSIDE.  Outside rows come last, among themselves in
+ *               window order, as in ss_rerank_hits_by_vector.  No doc id makes a kernel read outside the table.
+ *   sim(i, j)   = the sum over t < dim of (int32)vec[doc_i][t] * (int32)vec[doc_j][t] of window rows i and j, exact (|sim| <= 2^24).
+ *   rel(j)      = score(q, doc_j) exactly as ss_hit_vector_scores defines it when qvec is given; -(int32)j, the window position, when
+ *               qvec is NULL: that diversifies a lexical window which keeps its own order as relevance.
+ *   Walk.       S starts empty.  While an inside row is unchosen: for every unchosen inside row j, pen(j) = the max over the chosen i
+ *               of sim(i, j), 0 while S is empty (a negative sim is a bonus), and value(j) = (int64)w_rel * rel(j) - (int64)w_div *
+ *               pen(j) (|value| < 2^42); the row of the largest value is chosen, of equal values the smaller window index j.  The same
+ *               doc twice is two rows.  Only the first min(n_inside, first + k) choices are made.
+ *   Output.     With R_0 .. = the chosen rows in order of choice, then the outside rows: hits_out[q * k + r] = the 40 bytes of
+ *               R_{first + r} (_pad included) for r < n_hits_out[q] = clamp(n - first, 0, k); info_out[q * k + r] (nullable) = {rel, pen
+ *               at the moment of choice} of that row, sim = SS_NO_VEC_SCORE for the first chosen row, {SS_NO_VEC_SCORE,
+ *               SS_NO_VEC_SCORE} for an outside row.  Entries past n_hits_out[q] are left untouched.
+ *   Weights.    w_rel and w_div are 16.16 fixed point in [0, SS_DIV_WEIGHT_MAX]; only their ratio matters.
+ * What follows from the definition: with w_div == 0, w_rel > 0 and a qvec the rows are byte for byte those of
+ * ss_rerank_hits_by_vector; with qvec == NULL and w_div == 0 the output is the window with its inside rows first, in window order.
+ * A known answer: dim 64, only coordinates 0 and 1 non-zero, docs A = (10, 0), B = (9, 1), C = (0, 8), D = (5, 5), window [A, B, C, D],
+ * q = (1, 0): rel = 10, 9, 0, 5; sims AB = 90, AC = 0, AD = 50, BC = 8, BD = 50, CD = 40.  w_rel = 2, w_div = 1 chooses A, C, D, B with
+ * info (10, NO), (0, 0), (5, 50), (9, 90); w_div = 0 chooses A, B, D, C; qvec == NULL, w_rel = 30, w_div = 1 chooses A, C, B, D.
+ * Checks, all before anything is enqueued and with the outputs untouched: those of ss_rerank_hits_by_vector, except that qvec may be
+ * NULL; w_rel or w_div outside [0, SS_DIV_WEIGHT_MAX]: SS_ERR_INVALID; no vector table registered: SS_ERR_STATE.  The Gram scratch or
+ * the relevance row cannot be had: SS_ERR_OOM.  n_q == 0 is SS_OK and does nothing.
+ * Every pointer may be host or device memory, as in ss_rerank_hits_by_vector: with every given array on the device the call only
+ * enqueues on the ctx stream and NEVER waits.  k_div_gram computes the window's Gram matrix on the int8 matrix cores (a wave per tile
+ * of 64 x 64 row pairs, both operands gathered from the table by doc id, only the tiles on and above the diagonal, both halves
+ * written) into a scratch block [queries of a group][pitch][pitch] of int32, pitch = k_in rounded up to 64; k_div_select, one
+ * workgroup per query, makes the choices: per choice one block arg-max over the 64-bit keys (value + 2^42) << 10 | (1023 - j) and one
+ * read of the chosen row of the Gram matrix.  The queries of a call run in groups whose Gram matrices fit into option
+ * "div.scratch_bytes" (default 256 MB; too small for one query: one query per group), one group after another on the ctx stream.
+ * Serialised on the ctx like every scoring call; no fused scoring form and no _submit / _collect form. */
+#define SS_DIV_WEIGHT_MAX 65536          /* weights are 16.16 fixed point in [0, 65536] */
+typedef struct ss_div_info { int32_t rel; int32_t sim; } ss_div_info;   /* 8 bytes */
+int32_t ss_diversify_hits(ss_scorer* s, int32_t n_q, const int8_t* qvec /*[n_q][dim], NULLABLE*/, int32_t k_in,
+                          const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
+                          int32_t w_rel, int32_t w_div, int32_t first, int32_t k,
+                          ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, ss_div_info* info_out /*[n_q][k], nullable*/);
 
 /* Vector lists: the docs of the vector table cut into n_lists lists around centroids (an inverted-file partition), and the search over
  * the n_probe lists nearest to a query.  No reference counterpart.  ss_vector_topk reads every doc byte for every block of queries; a

@@ -31,6 +31,7 @@ SS_MAX_RANGE_CLAUSES = 4
 SS_NO_FIELD_VALUE = -(2 ** 63)
 SS_MAX_VEC_DIM = 1024
 SS_NO_VEC_SCORE = -(2 ** 31)
+SS_DIV_WEIGHT_MAX = 65536
 SS_MAX_VEC_LISTS = 65536
 SS_NO_LIST = 0xFFFFFFFF
 SS_FUSE_RRF = 0
@@ -66,6 +67,10 @@ class SsDocRange(C.Structure):
 
 class SsVecHit(C.Structure):
     _fields_ = [("doc", C.c_uint32), ("score", C.c_int32)]
+
+
+class SsDivInfo(C.Structure):
+    _fields_ = [("rel", C.c_int32), ("sim", C.c_int32)]
 
 
 class SsFuseParams(C.Structure):
@@ -174,6 +179,7 @@ PROTOTYPES = {
     "ss_vector_topk": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ss_hit_vector_scores": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ss_rerank_hits_by_vector": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ss_diversify_hits": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_scorer_set_vector_lists": (_i32, [_vp, _i32, _vp, _vp]),
     "ss_vector_assign_lists": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "ss_vector_topk_probed": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),

@@ -367,6 +367,8 @@ static const char* const k_option_names[] = {
                             //    tests set it to 64 to put segment seams into short lists; the rows are the same bytes for every value
     "vec.list_batch_q",     // ... queries per batch of one call (default 0: what keeps the partial lists in bound); tests set it small to split a call
     "vec.assign_batch",     // ss_vector_assign_lists: doc rows per batch of the top-1 search over the centroids (default 0: vector_lists_plan.hpp)
+    "div.scratch_bytes",    // ss_diversify_hits: most bytes of Gram matrices in flight (default 256 MB: diversify_plan.hpp); the queries of a call
+                            //    run in groups that fit, one query per group if not even one does; the rows are the same bytes for every value
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

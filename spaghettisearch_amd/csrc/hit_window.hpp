@@ -1,6 +1,6 @@
 // hit_window.hpp — the HIP side of the calls that take a window of result rows (hits [n_q][k_in], n_hits [n_q], each in host or device
 // memory) and post-process it; hit_window_plan.hpp holds the pure host part.  explain.hip, passage.hip, collapse.hip, dedup.hip,
-// field.hip and vector.hip include this file.
+// field.hip, vector.hip and diversify.hip include this file.
 //
 //   host    window_check / window_stage    the window in: the host counts snapshotted and checked, then rows and snapshot uploaded
 //           rows_out_prepare / _finish     a paged call's outputs: hits_out, n_hits_out, optional n_kept_out and one per-row extra

@@ -1,6 +1,6 @@
 // hit_window_plan.hpp — the host-only part of the calls that take a window of result rows (hits [n_q][k_in], n_hits [n_q]) and
 // post-process it: ss_explain_hits, ss_best_passages, ss_collapse_hits, ss_score_topk_collapsed, ss_dedup_hits, ss_sort_hits_by_field,
-// ss_hit_fields, ss_hit_vector_scores, ss_rerank_hits_by_vector.  The paging checks, the overlap test of hits and hits_out, the search
+// ss_hit_fields, ss_hit_vector_scores, ss_rerank_hits_by_vector, ss_diversify_hits.  The paging checks, the overlap test of hits and hits_out, the search
 // for a host count outside the window, and the copy of exactly the entries a kernel wrote.  hit_window.hpp holds the HIP side.  No HIP
 // call and no HIP header: tests/hit_window_plan_harness.cpp compiles this file alone (with a sanitizer).
 #pragma once

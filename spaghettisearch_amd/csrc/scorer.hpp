@@ -227,6 +227,10 @@ struct ss_scorer {
     ss::DevBuf<ss_vec_hit> d_hyb_vec_in, d_hyb_vec_win;
     ss::DevBuf<int32_t> d_hyb_nvec_in, d_hyb_counts, d_hyb_miss_scores, d_hyb_nvec_win;
     ss::DevBuf<ss_hit> d_hyb_miss_rows, d_hyb_miss_vec_rows;
+    // ss_diversify_hits (diversify.hip), grow-only, written and read on the context's stream only: the Gram matrices of one group of
+    // queries [group][pitch][pitch] (bounded by option "div.scratch_bytes"; the groups of a call re-use it in stream order) and the
+    // rows' relevance from k_vec_hit_scores [n_q][k_in].
+    ss::DevBuf<int32_t> d_div_gram, d_div_rel;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

@@ -25,6 +25,8 @@ DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("
 
 VEC_HIT_DTYPE = np.dtype([("doc", "<u4"), ("score", "<i4")])   # ss_vec_hit
 
+DIV_INFO_DTYPE = np.dtype([("rel", "<i4"), ("sim", "<i4")])     # ss_div_info
+
 FUSED_DTYPE = np.dtype([("score", "<f8"), ("vec_score", "<i4"), ("lex_rank", "<u2"), ("vec_rank", "<u2")])   # ss_fused
 FUSE_RRF, FUSE_WEIGHTED = 0, 1                                  # SS_FUSE_RRF, SS_FUSE_WEIGHTED
 
@@ -1236,6 +1238,35 @@ class Scorer:
         if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_sc
+
+    def diversify_hits(self, qvec, hits, n_hits, k: int, w_rel: int, w_div: int, first: int = 0, k_in: Optional[int] = None, out=None,
+                       want_info: bool = True):
+        """ss_diversify_hits: every window hits[q][: n_hits[q]] re-ranked greedily, each next row the one with the largest
+        w_rel * rel - w_div * (largest similarity to a row already chosen), ties to the earlier row; rows outside the table last; page
+        [first, first + k) -> (hits [n_q][k], n_hits [n_q], info [n_q][k] DIV_INFO_DTYPE | None).  qvec: int8 [n_q][dim], rel = the
+        row's score under it, or None: rel = minus the window position.  w_rel, w_div: integers in [0, SS_DIV_WEIGHT_MAX].  hits /
+        n_hits, k_in as in collapse_hits.  out = (hits, n_hits, info | None): the caller's arrays, returned as they are; with device
+        arrays throughout the library only enqueues."""
+        if qvec is not None:
+            qvec, _ = self._qvec(qvec)
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        if qvec is not None and int(qvec.shape[0]) != n_q:
+            raise ValueError(f"{int(qvec.shape[0])} query vectors for {n_q} windows")
+        if out is None:
+            out = (np.zeros((n_q, int(k)), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                   np.zeros((n_q, int(k)), dtype=DIV_INFO_DTYPE) if want_info else None)
+        o_hits, o_n, o_info = out
+        o_n = _as(o_n, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(o_hits) < n_q * int(k) * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4
+                           or (o_info is not None and nbytes(o_info) < n_q * int(k) * DIV_INFO_DTYPE.itemsize)):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qvec, hits, n_hits, o_hits, o_n, o_info)
+        check(self.ctx.lib.ss_diversify_hits(self.h, n_q, _ptr(qvec), k_in, _ptr(hits), _ptr(n_hits), int(w_rel), int(w_div), int(first),
+                                             int(k), _ptr(o_hits), _ptr(o_n), _ptr(o_info)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_info
 
     @staticmethod
     def _fuse_params(mode: int, rrf_c: int, w_lex: float, w_vec: float):

@@ -68,6 +68,10 @@ PYBIND11_MODULE(_host, m) {
     py::class_<retrieval::VectorRerankedPage>(m, "VectorRerankedPage")
         .def_readonly("Results", &retrieval::VectorRerankedPage::Results)
         .def_readonly("Scores", &retrieval::VectorRerankedPage::Scores);
+    py::class_<retrieval::DiversifiedPage>(m, "DiversifiedPage")
+        .def_readonly("Results", &retrieval::DiversifiedPage::Results)
+        .def_readonly("Rel", &retrieval::DiversifiedPage::Rel)
+        .def_readonly("Sim", &retrieval::DiversifiedPage::Sim);
     py::class_<retrieval::HybridParams>(m, "HybridParams")
         .def(py::init<>())
         .def_readwrite("weighted", &retrieval::HybridParams::weighted)
@@ -215,6 +219,8 @@ PYBIND11_MODULE(_host, m) {
              py::arg("n_probe") = 8, py::arg("masks") = std::vector<std::string>())
         .def("RerankByVector", &retrieval::DeviceIndex::RerankByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("first") = 0,
              py::arg("k") = 50)
+        .def("DiversifyByVector", &retrieval::DeviceIndex::DiversifyByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("w_rel"),
+             py::arg("w_div"), py::arg("first") = 0, py::arg("k") = 50)
         .def("ScoreDocs", [](retrieval::DeviceIndex& di, const std::string& query, const std::vector<std::string>& docHashes) {
             return di.ScoreDocs(query, docHashes);
         }, py::arg("query"), py::arg("docHashes"))

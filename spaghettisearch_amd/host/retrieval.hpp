@@ -104,6 +104,14 @@ struct VectorRerankedPage {
     std::vector<int32_t> Scores;
 };
 
+// One page of a query's results diversified (DeviceIndex::DiversifyByVector).  Rel[i]: the relevance Results[i] was chosen with (its
+// vector score, or minus its window position when the call was by rank); Sim[i]: its largest similarity to the rows chosen before it,
+// SS_NO_VEC_SCORE for the first row.  Both SS_NO_VEC_SCORE for a row whose doc hash the index does not hold.
+struct DiversifiedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<int32_t> Rel, Sim;
+};
+
 // How DeviceIndex::HybridSearch fuses the lexical and the vector ranking (ss_fuse_params): reciprocal rank fusion,
 // w_lex / (rrf_c + lexical rank) + w_vec / (rrf_c + vector rank), or (weighted) w_lex * FinalRank + w_vec * vector score.
 struct HybridParams {
@@ -980,6 +988,48 @@ public:
             for (int i = 0; i < n_page[q]; i++) {
                 out[q].Results.push_back(rows[q][page[q * kk + i]._pad]);
                 out[q].Scores.push_back(scores[q * kk + i]);
+            }
+        return out;
+    }
+
+    // A window of result rows per query re-ranked greedily (ss_diversify_hits): every next row is the one with the largest w_rel *
+    // relevance - w_div * (largest similarity of its doc vector to a row already chosen), of equal values the earlier row; page
+    // [first, first + k).  Relevance is the row's score under the query's vector, or, with queryVectors EMPTY, minus its position in the
+    // window: that diversifies a lexical window which keeps its own order.  The weights are integers in [0, SS_DIV_WEIGHT_MAX].  Rows
+    // whose doc hash the index does not hold come last.
+    std::vector<DiversifiedPage> DiversifyByVector(const std::vector<std::vector<int8_t>>& queryVectors,
+                                                   const std::vector<std::vector<Rank_combined>>& rows, int w_rel, int w_div, int first = 0,
+                                                   int k = 50) {
+        using namespace spaghetti;
+        const bool by_rank = queryVectors.empty();
+        const std::vector<int8_t> flat = flatten_query_vectors("DiversifyByVector", queryVectors);
+        const size_t nq = rows.size(), kk = (size_t)std::max(k, 1);
+        if (!by_rank && queryVectors.size() != nq) throw std::runtime_error("DiversifyByVector: one window per query vector");
+        size_t k_in = 1;
+        for (auto& r : rows) k_in = std::max(k_in, r.size());
+        std::vector<ss_hit> win(nq * k_in), page(nq * kk);
+        std::vector<int32_t> n_rows(nq), n_page(nq);
+        std::vector<ss_div_info> info(nq * kk);
+        for (size_t q = 0; q < nq; q++) {
+            n_rows[q] = (int32_t)rows[q].size();
+            for (size_t j = 0; j < rows[q].size(); j++) {
+                const Rank_combined& r = rows[q][j];
+                auto it = docs.id.find(r.DocHash);
+                ss_hit h{};
+                h.doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;
+                h._pad = (uint32_t)j;                                     // the window position: how the page finds its row again
+                h.title = r.TitleRank; h.body = r.BodyRank; h.pagerank = r.PageRank; h.final = r.FinalRank;
+                win[q * k_in + j] = h;
+            }
+        }
+        check(ss_diversify_hits(scorer, (int32_t)nq, by_rank ? nullptr : flat.data(), (int32_t)k_in, win.data(), n_rows.data(), w_rel, w_div,
+                                first, k, page.data(), n_page.data(), info.data()), "ss_diversify_hits");
+        std::vector<DiversifiedPage> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_page[q]; i++) {
+                out[q].Results.push_back(rows[q][page[q * kk + i]._pad]);
+                out[q].Rel.push_back(info[q * kk + i].rel);
+                out[q].Sim.push_back(info[q * kk + i].sim);
             }
         return out;
     }
