@@ -64,6 +64,7 @@ type Scorer struct {
 	ctx       *Ctx
 	nDocs     uint64 // the title table's doc count when the scorer was created: sizes DocFieldMasks' words
 	nFields   int    // fields registered by SetDocFields: sizes HitFields' values
+	nMasks    int    // allow-lists registered by SetDocMasks: sizes FacetCounts' mask counts
 	vecDim    int    // dim of the table registered by SetDocVectors: sizes the query vectors
 	nVecLists int    // lists registered by SetVectorLists: sizes the probes of VectorTopKProbed
 }
@@ -549,6 +550,10 @@ func (s *Scorer) SetPrior(kTopics int, rank []float64) {
 // SetDocMasks registers allow-lists: words [nMasks][(nDocs+31)/32], bit (d & 31) of word d >> 5 = doc d allowed (nil clears).
 func (s *Scorer) SetDocMasks(nMasks int, words []uint32) {
 	check(s.ctx, C.ss_scorer_set_doc_masks(s.h, C.int32_t(nMasks), u32p(words)), "ss_scorer_set_doc_masks")
+	s.nMasks = nMasks
+	if len(words) == 0 {
+		s.nMasks = 0
+	}
 }
 
 // ScoreTopKMasked = ScoreTopKPhrase with one allow-list per query: maskID[q] (-1 = the whole index; nil = all -1); pPtr nil = no
@@ -961,6 +966,42 @@ func (s *Scorer) ScoreTopKFiltered(qPtr, qTerms, pPtr, pTerms []uint32, queryLen
 			r := raw[q*k+i]
 			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
 		}
+	}
+	return out, nil
+}
+
+// FacetCount is one query's counts from FacetCounts: the docs it matches, those of them in every registered allow-list, and those whose
+// field value lies in every bucket of the call.
+type FacetCount struct {
+	Total   uint32
+	Masks   []uint32
+	Buckets []uint32
+}
+
+// FacetCounts counts, per query, the docs ScoreTopKFiltered ranks for the same query terms, maskID, required / excluded terms and range
+// clauses (no phrase form), how many of them every allow-list of SetDocMasks holds, and how many fall into every bucket
+// (ss_facet_counts).  buckets are shared by the batch, at most C.SS_MAX_FACET_BUCKETS; nil pointer arrays = none, as in ScoreTopKFiltered.
+func (s *Scorer) FacetCounts(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange,
+	buckets []DocRange) ([]FacetCount, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	nm, nb := s.nMasks, len(buckets)
+	total := make([]uint32, nq)
+	byMask, byBucket := make([]uint32, nq*nm), make([]uint32, nq*nb)
+	rp, keepR := docRanges(rng)
+	bp, keepB := docRanges(buckets)
+	rc := C.ss_facet_counts(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr),
+		u32p(excTerms), u32p(rngPtr), rp, C.int32_t(nb), bp, u32p(total), u32p(byMask), u32p(byBucket))
+	runtime.KeepAlive(keepR)
+	runtime.KeepAlive(keepB)
+	if err := statusErr(s.ctx, rc, "ss_facet_counts"); err != nil {
+		return nil, err
+	}
+	out := make([]FacetCount, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = FacetCount{total[q], byMask[q*nm : (q+1)*nm], byBucket[q*nb : (q+1)*nb]}
 	}
 	return out, nil
 }

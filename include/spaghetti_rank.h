@@ -58,7 +58,8 @@ extern "C" {
  * lists around centroids: the exact top k over the docs of the n_probe lists nearest to a query, not over every doc);
  * ss_pr_lean_sweeps (how many sweeps of a state were launched in the lean form of option "pr.lean_sweeps");
  * SS_DIV_WEIGHT_MAX, ss_div_info and ss_diversify_hits (a window re-ranked greedily by relevance minus similarity to the rows already
- * chosen: maximal marginal relevance over the doc vectors). */
+ * chosen: maximal marginal relevance over the doc vectors);
+ * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -812,6 +813,56 @@ int32_t ss_sort_hits_by_field(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_
                               ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int64_t* values_out /*[n_q][k], nullable*/);
 int32_t ss_hit_fields(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
                       int64_t* values_out /*[n_q][k_in][n_fields]*/);
+
+/* ss_facet_counts: how many docs a query matches -- "about 1,240,000 results" --, how many of them lie in every registered allow-list
+ * -- "News (312) . Docs (4,881)" -- and how many in every bucket of a doc field -- "past day (14) . past week (230)".  No reference
+ * counterpart.  A scoring call returns at most SS_MAX_TOPK rows and says nothing about the docs behind them.  Defined bit for bit; no
+ * float is involved, counts are exact and no order of summation can show:
+ *   C(q)        = the docs d < n_docs that CONTAIN (as in ss_score_topk_constrained: a posting in the title or the body table, of any
+ *                 weight, zero included) at least one term t of q_terms[q_ptr[q] .. q_ptr[q+1]) with t < n_terms.  SS_UNKNOWN_TERM and
+ *                 every other id >= n_terms contribute nothing; a repeated term changes nothing; a query without a usable term has an
+ *                 empty C(q).
+ *   A(q)        = the allowed set ss_score_topk_filtered builds for the same mask_id, req_*, exc_* and rng_* arguments (every doc when
+ *                 all of them are NULL).
+ *   M(q)        = C(q) AND A(q): exactly the docs ss_score_topk_filtered ranks for these arguments with p_ptr NULL.  That call's
+ *                 candidates are the docs with a posting of a query term and nothing else: no score, NaN included, drops a doc, and
+ *                 query_len / topic_probs only move scores.  So n_match_out[q] >= that call's n_hits_out[q], with equality whenever
+ *                 |M(q)| <= k.
+ *   n_match_out[q]                          = |M(q)|.
+ *   mask_counts_out[q * n_masks + m]        = |M(q) AND mask_m| for every registered allow-list m (ss_scorer_set_doc_masks), bits at
+ *                 and past n_docs ignored.  NULL: not counted.  With no masks registered the pointer is ignored.
+ *   bucket_counts_out[q * n_buckets + b]    = the number of d in M(q) with buckets[b].lo <= value[buckets[b].field][d] <= buckets[b].hi
+ *                 as signed 64-bit integers.  Buckets may overlap, nest ("past day" inside "past week"), repeat and name different
+ *                 fields; a bucket with lo > hi counts 0; SS_NO_FIELD_VALUE is a value like any other; _pad is ignored.  The
+ *                 buckets [n_buckets] are shared by the whole batch.
+ * A known answer: 8 docs, 3 terms; the docs that contain t0 = {1, 2, 5} (doc 1 in both tables), t1 = {2, 3}, t2 = {6}; field 0 = 10, 20,
+ * .. 80 for docs 0 .. 7; masks m0 = {0, 1, 2, 3}, m1 = {2, 5, 6}; buckets on field 0: [20, 30], [0, 100], [30, 60], [5, 4].  The query
+ * (t0, t1, t0, SS_UNKNOWN_TERM) has C = {1, 2, 3, 5}.  Unconstrained: n_match 4, mask counts 3, 2, bucket counts 2, 4, 3, 0.  With t1
+ * required: M = {2, 3}: 2; 2, 1; 1, 2, 2, 0.  With mask_id 1 and the clause field 0 in [25, 65]: A = {2, 5}, M = {2, 5}: 2; 1, 2; 1, 2, 2, 0.
+ * Checks, all before anything is enqueued and with the outputs untouched: everything ss_score_topk_filtered checks about its query,
+ * mask, constraint and range arrays, with its codes (more than SS_MAX_QUERY_TERMS distinct usable terms in a query included:
+ * SS_ERR_UNSUPPORTED); NULL handle; n_q < 0; NULL q_ptr or n_match_out with n_q > 0; n_buckets < 0; NULL buckets or bucket_counts_out
+ * with n_buckets > 0; a bucket field outside [0, n_fields): SS_ERR_INVALID; n_buckets > SS_MAX_FACET_BUCKETS: SS_ERR_UNSUPPORTED; a
+ * bucket but no field table: SS_ERR_STATE.  n_q == 0 is SS_OK and does nothing.
+ * The query, constraint and bucket arrays are read on the host like every scoring call's (device pointers cost one blocking copy
+ * each).  The outputs may be host or device memory: when all given outputs are device memory the call only enqueues on the ctx stream
+ * and NEVER waits, so it sits beside the scoring call of the same batch; otherwise it goes through a block the scorer owns and returns
+ * when the outputs are written.  The allowed sets are built as in ss_score_topk_filtered (n_docs / 8 bytes per distinct set,
+ * SS_ERR_OOM if that cannot be had); M(q) itself is never written out.  k_facet_counts gives a workgroup one block of 32768 docs of
+ * one query: the runs of the query's lists in the block by binary search, ORed into an LDS image, ANDed with the allowed words and
+ * d < n_docs, then one popcount for the total, one popcount of image & mask per registered mask, and for the buckets one gather of
+ * value[field][d] per SET bit; the partial counts join the zeroed outputs by integer atomic adds.
+ * Serialised on the ctx like every scoring call.  There is no phrase form (no p_ptr) and no _submit / _collect form. */
+#define SS_MAX_FACET_BUCKETS 64
+int32_t ss_facet_counts(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                        const int32_t* mask_id,
+                        const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                        const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                        const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                        int32_t n_buckets, const ss_doc_range* buckets /*[n_buckets], shared by the whole batch*/,
+                        uint32_t* n_match_out /*[n_q]*/,
+                        uint32_t* mask_counts_out /*[n_q][n_masks], nullable*/,
+                        uint32_t* bucket_counts_out /*[n_q][n_buckets], NULL iff n_buckets == 0*/);
 
 /* Doc vectors: one signed 8-bit embedding per doc, the exact k nearest docs of a query vector, and a lexical result window re-ordered
  * by meaning.  No reference counterpart: every way the reference finds a page is a posting of a typed word.  Producing the embeddings

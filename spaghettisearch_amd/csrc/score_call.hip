@@ -807,6 +807,15 @@ struct PlanWriter {
     }
 };
 
+// the tables of the allowed sets' builders (the last sections of a scoring call's plan; all there is of ss::allowed_sets_into_turn's)
+void constraint_sections(PlanWriter& w, const ConstraintPlan& cons, ConstraintParams& cp, FieldParams& fp) {
+    w.add(cp.sets, cons.sets.data(), cons.sets.size());
+    w.add(cp.terms, cons.terms.data(), cons.terms.size());
+    w.add(fp.sets, cons.fsets.data(), cons.fsets.size());
+    w.add(fp.clauses, cons.fclauses.data(), cons.fclauses.size());
+    w.add(fp.group_fields, cons.fgroups.data(), cons.fgroups.size());
+}
+
 // THE list of the plan's sections: order, source, size, and whether the kernels see it.  Returns where k_score_small's table goes.
 unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, ScoreParams& p,
                              ConstraintParams& cp, FieldParams& fp) {
@@ -831,11 +840,7 @@ unsigned char* plan_sections(PlanWriter& w, const BatchInputs& in, const Constra
     w.add(p.q_fast, pl.fast.data(), n_q);
     unsigned char* const small_tab = w.reserve(p.small_tab, pl.n_small * pl.small_stride);
     w.add(p.q_mask, in.mask.data(), in.any_mask ? n_q : 0, in.any_mask);
-    w.add(cp.sets, cons.sets.data(), cons.sets.size());
-    w.add(cp.terms, cons.terms.data(), cons.terms.size());
-    w.add(fp.sets, cons.fsets.data(), cons.fsets.size());
-    w.add(fp.clauses, cons.fclauses.data(), cons.fclauses.size());
-    w.add(fp.group_fields, cons.fgroups.data(), cons.fgroups.size());
+    constraint_sections(w, cons, cp, fp);
     return small_tab;
 }
 
@@ -922,6 +927,31 @@ int32_t grow_workspaces(ss_scorer* s, const BatchInputs& in, const BatchPlan& pl
     return SS_OK;
 }
 
+// the parameters of the allowed sets' builders that are not sections of the plan: the tables' docs, the registered masks, this turn's sets
+void fill_constraint_params(ss_scorer* s, const ConstraintPlan& cons, StagedBatch& sb) {
+    const Turn& t = s->turn[sb.turn];
+    const size_t n_csets = cons.sets.size();
+    if (n_csets) {
+        ConstraintParams& cp = sb.cp;
+        cp.t_doc = s->title->post_doc.p; cp.b_doc = s->body->post_doc.p;
+        cp.reg_masks = s->masks.p; cp.reg_words = s->mask_words;
+        cp.out = t.d_sets.p;
+        cp.stride = sb.set_stride;
+        cp.n_words = (s->n_docs + 31) / 32;
+        cp.n_blocks = ss::constraint_blocks(sb.set_stride);
+    }
+    if (!cons.fsets.empty()) {
+        FieldParams& fp = sb.fp;
+        fp.values = s->fields.p;
+        fp.n_docs = s->n_docs;
+        fp.n_sets = (uint32_t)cons.fsets.size();
+        fp.reg_masks = s->masks.p; fp.reg_words = s->mask_words;
+        fp.out = t.d_sets.p;
+        fp.stride = sb.set_stride;
+        fp.n_words = (s->n_docs + 31) / 32;
+    }
+}
+
 // everything of the kernel parameters that is not a section of the plan: the index, this turn's workspaces, the outputs
 void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const ConstraintPlan& cons, const BatchPlan& pl, const Route& r,
                  StagedBatch& sb) {
@@ -957,25 +987,7 @@ void fill_params(ss_scorer* s, const CallArgs& a, const BatchInputs& in, const C
     p.n_hits = a.turn_rows ? a.turn_rows->n_hits : in.dev_out ? a.n_hits_out : sb.one_copy ? reinterpret_cast<int32_t*>(s->d_hits.p + sb.res_rows) : s->d_nhits.p;
     p.masks = n_csets ? t.d_sets.p : in.any_mask ? s->masks.p : nullptr;
     p.mask_words = n_csets ? sb.set_stride : s->mask_words;
-    if (n_csets) {
-        ConstraintParams& cp = sb.cp;
-        cp.t_doc = s->title->post_doc.p; cp.b_doc = s->body->post_doc.p;
-        cp.reg_masks = s->masks.p; cp.reg_words = s->mask_words;
-        cp.out = t.d_sets.p;
-        cp.stride = sb.set_stride;
-        cp.n_words = (s->n_docs + 31) / 32;
-        cp.n_blocks = ss::constraint_blocks(sb.set_stride);
-    }
-    if (!cons.fsets.empty()) {
-        FieldParams& fp = sb.fp;
-        fp.values = s->fields.p;
-        fp.n_docs = s->n_docs;
-        fp.n_sets = (uint32_t)cons.fsets.size();
-        fp.reg_masks = s->masks.p; fp.reg_words = s->mask_words;
-        fp.out = t.d_sets.p;
-        fp.stride = sb.set_stride;
-        fp.n_words = (s->n_docs + 31) / 32;
-    }
+    fill_constraint_params(s, cons, sb);
 }
 
 // one pinned staging buffer (one H2D copy: enqueue), the workspaces, the kernel parameters
@@ -1187,6 +1199,48 @@ int32_t ss::score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, co
     out->rows = (size_t)n_q * (size_t)k;
     out->n_q = (size_t)n_q;
     return score_impl(s, CallArgs{n_q, q_ptr, q_terms, nullptr, nullptr, query_len, topic_probs, k, nullptr, nullptr, mask_id, nullptr, out});
+}
+
+// ss_facet_counts (facet.hip): steps 1 and 2 of a scoring call for the mask ids, constraint arrays and range clauses alone, then the
+// sets' tables through the plan turn's buffers and the builders on the context's stream.  The caller holds the context's lock and
+// has set the device.
+int32_t ss::allowed_sets_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const int32_t* mask_id, const QueryConstraints* cons,
+                                   const QueryRanges* ranges, AllowedSets* out) {
+    ss_ctx* ctx = s->ctx;
+    TurnRows no_rows;                            // (stands for the outputs fetch_filter_inputs would check: this call writes no rows)
+    const CallArgs a{n_q, q_ptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, mask_id, cons, &no_rows, ranges};
+    BatchInputs in;
+    SS_TRY(fetch_filter_inputs(s, a, in));
+    const ScorerView view{s->n_docs, s->n_terms, s->title->h_term_ptr, s->body->h_term_ptr, s->prior_max, s->prior_min,
+                          s->has_combined, s->clean, s->prior_clean, ctx->cu_count};
+    PlanError err;
+    ConstraintPlan cp;
+    if (const int32_t rc = resolve_constraints(in, view, cp, err)) return ctx->fail(rc, "%s", err.msg);
+    // ---- the last check has passed
+    StagedBatch sb;
+    PlanWriter measure;
+    constraint_sections(measure, cp, sb.cp, sb.fp);
+    sb.plan_bytes = measure.o;
+    const size_t n_csets = cp.sets.size();
+    SS_TRY(acquire_turn(s, sb.plan_bytes, n_csets, nullptr, sb));
+    Turn& t = s->turn[sb.turn];
+    if (n_csets) {
+        PlanWriter w{t.h_plan.p, t.d_plan.p, 0};
+        constraint_sections(w, cp, sb.cp, sb.fp);
+        fill_constraint_params(s, cp, sb);
+        hipStream_t st = ctx->stream;
+        SS_HIP(ctx, hipMemcpyAsync(t.d_plan.p, t.h_plan.p, sb.plan_bytes, hipMemcpyHostToDevice, st));
+        ss::launch_constraint_masks(&sb.cp, (uint32_t)(n_csets - cp.n_field_only), st);
+        if (!cp.fsets.empty()) ss::launch_field_masks(&sb.fp, st);
+        SS_HIP(ctx, hipGetLastError());
+        SS_HIP(ctx, t.batch_ev.record(st));      // (the caller records again behind its own reader of the sets)
+    }
+    out->set_of.assign((size_t)n_q, -1);
+    if (in.any_mask) out->set_of = in.mask;
+    out->words = n_csets ? t.d_sets.p : in.any_mask ? s->masks.p : nullptr;
+    out->stride = n_csets ? sb.set_stride : s->mask_words;
+    out->turn = sb.turn;
+    return SS_OK;
 }
 
 extern "C" {

@@ -45,6 +45,8 @@ uint32_t field_mask_group();                    // sets that share one read of t
 void launch_field_masks(const void* params, hipStream_t st);
 }  // namespace ss
 struct ss_scorer;
+struct QueryConstraints;
+struct QueryRanges;
 namespace ss {
 // vector.hip, for hybrid.hip: the query vectors as the vector kernels load them (ss_vector_topk's staging: *staged is set when they
 // came from host memory, so the call waits before it returns), and k_vec_hit_scores as ss_hit_vector_scores launches it over rows
@@ -73,6 +75,18 @@ namespace ss {
 // score_call.hip (query_len: as ss_score_topk's, NULL = term count)
 int32_t score_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms, const double* topic_probs,
                         const int32_t* mask_id, int32_t k, TurnRows* out, const int32_t* query_len = nullptr);
+// score_call.hip, for facet.hip: the allowed sets of a batch exactly as ss_score_topk_filtered forms them for the same mask ids,
+// constraint arrays and range clauses.  Runs that call's checks (its codes, nothing enqueued on a refusal), takes the next plan turn,
+// and enqueues k_constraint_masks / k_field_masks on the context's stream into the turn's set buffer.  The sets are the turn's: whoever
+// reads them on the context's stream records the turn's batch_ev again behind the reader.
+struct AllowedSets {
+    std::vector<int32_t> set_of;                // [n_q] the row of `words` that is the query's allowed set, -1: every doc
+    const uint32_t* words = nullptr;            // device: the turn's sets, or the registered masks when no query has a constraint
+    uint64_t stride = 0;                        // words per row (bits at and past n_docs of a row may be set)
+    int turn = -1;
+};
+int32_t allowed_sets_into_turn(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const int32_t* mask_id, const QueryConstraints* cons,
+                               const QueryRanges* ranges, AllowedSets* out);
 }  // namespace ss
 
 // Everything one plan turn owns.  A scoring call takes the next turn (acquire_turn) and waits for batch_ev there, i.e. for the batch
@@ -98,6 +112,8 @@ struct Turn {
     ss::Event wave_ev;                         // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     ss::Event slice_ev;                        // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
+    ss::PinBuf h_facet;                        // ss_facet_counts: the call's list table and bucket table go up through it (one set per turn,
+    ss::DevBuf<unsigned char> d_facet;         // free after the wait for batch_ev like the plan's)
 };
 
 // ss_explain_hits / ss_best_passages: neither takes a plan turn (they score nothing), so each has TURNS turns of its own.  Per turn: the
@@ -231,6 +247,9 @@ struct ss_scorer {
     // queries [group][pitch][pitch] (bounded by option "div.scratch_bytes"; the groups of a call re-use it in stream order) and the
     // rows' relevance from k_vec_hit_scores [n_q][k_in].
     ss::DevBuf<int32_t> d_div_gram, d_div_rel;
+    // ss_facet_counts (facet.hip): the device block of HOST outputs, totals | mask counts | bucket counts (grow-only; the call waits
+    // before it returns)
+    ss::DevBuf<uint32_t> d_facet_out;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

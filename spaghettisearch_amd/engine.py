@@ -632,6 +632,7 @@ class Scorer:
         self.h = h
         self.k_topics = 0
         self.n_fields = 0
+        self.n_masks = 0
         self.vec_dim = 0
         self.n_vec_lists = 0
 
@@ -651,10 +652,12 @@ class Scorer:
         numpy or torch), or None / an empty set to clear.  Replaces the previous set once the scorer's outstanding work is done."""
         if masks is None or len(masks) == 0:
             check(self.ctx.lib.ss_scorer_set_doc_masks(self.h, 0, None), self.ctx.h)
+            self.n_masks = 0
             return
         masks = _as(masks, "uint32")
         self.ctx.ready(masks)
         check(self.ctx.lib.ss_scorer_set_doc_masks(self.h, int(masks.shape[0]), _ptr(masks)), self.ctx.h)
+        self.n_masks = int(masks.shape[0])
 
     def score_topk_masked(self, q_ptr, q_terms, mask_id, k: int, p_ptr=None, p_terms=None, query_len=None, topic_probs=None, out=None):
         """ss_score_topk_masked: query q's top-k restricted to the docs of allow-list mask_id[q] (-1: unrestricted; None: all -1).
@@ -1027,6 +1030,43 @@ class Scorer:
         if out is not None and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return hits, n_hits
+
+    def facet_counts(self, q_ptr, q_terms, ranges=None, req=None, exc=None, mask_id=None, buckets=None, want_masks: bool = True, out=None):
+        """ss_facet_counts: per query the number of docs score_topk_filtered would rank for the same q_ptr / q_terms, ranges, req, exc
+        and mask_id (no phrase form), the number of them in every registered allow-list, and the number in every bucket ->
+        (n_match [n_q], mask_counts [n_q][n_masks] | None, bucket_counts [n_q][n_buckets] | None), uint32.  buckets: DOC_RANGE_DTYPE
+        [n_buckets] or a list of (field, lo, hi), shared by the batch, at most SS_MAX_FACET_BUCKETS.  want_masks False (or no mask
+        registered): no mask counts.  out = (n_match, mask_counts | None, bucket_counts | None): the caller's arrays (numpy uint32, or
+        torch int32 device tensors: with device arrays throughout the call only enqueues), returned as they are."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        if buckets is not None and not isinstance(buckets, np.ndarray):
+            buckets = pack_doc_ranges([list(buckets)])[1]
+        buckets = None if buckets is None else np.ascontiguousarray(buckets, dtype=DOC_RANGE_DTYPE)
+        n_b = 0 if buckets is None else int(buckets.shape[0])
+        n_q = int(q_ptr.shape[0]) - 1
+        n_m = self.n_masks if want_masks else 0
+        if out is not None:
+            n_match, mask_counts, bucket_counts = out
+            nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+            if nbytes(n_match) < n_q * 4 or (mask_counts is not None and nbytes(mask_counts) < n_q * self.n_masks * 4) or \
+                    (n_b and (bucket_counts is None or nbytes(bucket_counts) < n_q * n_b * 4)):
+                raise ValueError("output buffers too small")
+        else:
+            n_match = np.zeros(n_q, dtype=np.uint32)
+            mask_counts = np.zeros((n_q, n_m), dtype=np.uint32) if n_m else None
+            bucket_counts = np.zeros((n_q, n_b), dtype=np.uint32) if n_b else None
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, n_match, mask_counts, bucket_counts)
+        check(self.ctx.lib.ss_facet_counts(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms),
+                                           _ptr(exc_ptr), _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), n_b, _ptr(buckets), _ptr(n_match),
+                                           _ptr(mask_counts), _ptr(bucket_counts)), self.ctx.h)
+        if _is_torch(n_match) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return n_match, mask_counts, bucket_counts
 
     def _window(self, hits, n_hits, k_in):
         """(hits, n_hits, n_q, k_in) of a result window as collapse_hits takes it"""

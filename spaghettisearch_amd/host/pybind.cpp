@@ -62,6 +62,10 @@ PYBIND11_MODULE(_host, m) {
     py::class_<retrieval::FieldSortedPage>(m, "FieldSortedPage")
         .def_readonly("Results", &retrieval::FieldSortedPage::Results)
         .def_readonly("Values", &retrieval::FieldSortedPage::Values);
+    py::class_<retrieval::FacetCount>(m, "FacetCount")
+        .def_readonly("Total", &retrieval::FacetCount::Total)
+        .def_readonly("Masks", &retrieval::FacetCount::Masks)
+        .def_readonly("Buckets", &retrieval::FacetCount::Buckets);
     py::class_<retrieval::VectorHit>(m, "VectorHit")
         .def_readonly("DocHash", &retrieval::VectorHit::DocHash)
         .def_readonly("Score", &retrieval::VectorHit::Score);
@@ -204,6 +208,17 @@ PYBIND11_MODULE(_host, m) {
             auto tp = topic_probs.cast<std::vector<std::map<std::string, double>>>();
             return di.RetrieveBatchFiltered(queries, rs, k, &tp, live_topic_probs);
         }, py::arg("queries"), py::arg("ranges"), py::arg("k") = 50, py::arg("topic_probs") = py::none(), py::arg("live_topic_probs") = false)
+        .def("FacetCounts", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                               const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges,
+                               const std::vector<std::tuple<int32_t, int64_t, int64_t>>& buckets) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            std::vector<retrieval::FieldRange> bs;
+            for (auto& b : buckets) bs.push_back(retrieval::FieldRange{std::get<0>(b), std::get<1>(b), std::get<2>(b)});
+            return di.FacetCounts(queries, rs, bs);
+        }, py::arg("queries"), py::arg("ranges") = std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>{},
+           py::arg("buckets") = std::vector<std::tuple<int32_t, int64_t, int64_t>>{})
         .def("SortByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int field, bool descending, int k_window,
                                int first, int k, py::object topic_probs, bool live_topic_probs) {
             if (topic_probs.is_none()) return di.SortByField(queries, field, descending, k_window, first, k, nullptr, live_topic_probs);

@@ -84,6 +84,15 @@ struct FieldRange {
     int64_t lo = 0, hi = 0;
 };
 
+// One query's counts from DeviceIndex::FacetCounts (no reference counterpart): Total = the docs the query matches under its range
+// clauses (and its "+word" / "-word" operators), Masks[name] = those of them in the named set of SetDocMasks, Buckets[b] = those whose
+// field value lies in bucket b of the call.
+struct FacetCount {
+    uint32_t Total = 0;
+    std::map<std::string, uint32_t> Masks;
+    std::vector<uint32_t> Buckets;
+};
+
 // One page of a query's results sorted by a doc field (DeviceIndex::SortByField; no reference counterpart).  Values[i]: the field's
 // value of Results[i].
 struct FieldSortedPage {
@@ -1616,6 +1625,55 @@ public:
                                      req_terms.data(), query_operators ? exc_ptr.data() : nullptr, exc_terms.data(), rng_ptr.data(), rng.data(),
                                      k, hits.data(), n_hits.data()), "ss_score_topk_filtered");
         return to_ranks(t.nq, k, hits, n_hits);
+    }
+    // How many docs every query matches (ss_facet_counts): under the clauses of ranges[q] (an empty `ranges`: none for any query), in
+    // every set of SetDocMasks, and in every bucket of `buckets` (shared by the batch; needs SetDocFields like a range clause).  The
+    // numbers are those of the docs RetrieveBatchFiltered ranks, not of the k it returns.  With SetQueryOperators "+word" / "-word" are
+    // read as in RetrieveBatchFiltered.  Quoted phrases are not counted: a query string with one is refused.
+    std::vector<FacetCount> FacetCounts(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges = {},
+                                        const std::vector<FieldRange>& buckets = {}) {
+        using namespace spaghetti;
+        if (!ranges.empty() && ranges.size() != queries.size()) throw std::runtime_error("FacetCounts: one list of ranges per query, or none");
+        std::vector<uint32_t> rng_ptr{0}, req_ptr{0}, exc_ptr{0}, req_terms, exc_terms;
+        std::vector<ss_doc_range> rng, bk;
+        for (auto& rs : ranges) {
+            for (auto& r : rs) rng.push_back(ss_doc_range{r.field, 0, r.lo, r.hi});
+            rng_ptr.push_back((uint32_t)rng.size());
+        }
+        for (auto& b : buckets) bk.push_back(ss_doc_range{b.field, 0, b.lo, b.hi});
+        if ((!rng.empty() || !bk.empty()) && !has_doc_fields) throw std::runtime_error("FacetCounts: no doc fields (SetDocFields)");
+        std::vector<std::string> rewritten;
+        const std::vector<std::string>* qs = &queries;
+        if (query_operators) {
+            auto id_of = [&](const std::string& w) -> uint32_t {
+                auto it = terms.id.find(md5::hex(w));
+                return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+            };
+            for (auto& q : queries) {
+                const QueryOperators op = parseQueryOperators(q, laundry);
+                rewritten.push_back(op.query);
+                for (auto& w : op.required) req_terms.push_back(id_of(w));
+                for (auto& w : op.excluded) exc_terms.push_back(id_of(w));
+                req_ptr.push_back((uint32_t)req_terms.size());
+                exc_ptr.push_back((uint32_t)exc_terms.size());
+            }
+            qs = &rewritten;
+        }
+        const Tokenised t = tokenise(*qs, nullptr, false);
+        if (!t.p_terms.empty()) throw std::runtime_error("FacetCounts: quoted phrases are not counted");
+        const size_t n_masks = mask_index.size(), n_b = bk.size();
+        std::vector<uint32_t> total(t.nq), by_mask((size_t)t.nq * n_masks), by_bucket((size_t)t.nq * n_b);
+        check(ss_facet_counts(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), nullptr, query_operators ? req_ptr.data() : nullptr, req_terms.data(),
+                              query_operators ? exc_ptr.data() : nullptr, exc_terms.data(), ranges.empty() ? nullptr : rng_ptr.data(), rng.data(),
+                              (int32_t)n_b, n_b ? bk.data() : nullptr, total.data(), n_masks ? by_mask.data() : nullptr,
+                              n_b ? by_bucket.data() : nullptr), "ss_facet_counts");
+        std::vector<FacetCount> out(t.nq);
+        for (int q = 0; q < t.nq; q++) {
+            out[q].Total = total[q];
+            for (auto& kv : mask_index) out[q].Masks[kv.first] = by_mask[(size_t)q * n_masks + kv.second];
+            out[q].Buckets.assign(by_bucket.begin() + (size_t)q * n_b, by_bucket.begin() + (size_t)(q + 1) * n_b);
+        }
+        return out;
     }
     // RetrieveBatch sorted by a doc field (SetDocFields): page [first, first + k) of the first k_window rows of every query's ranking,
     // sorted stably by the field, ascending or descending ("newest first": field 0, descending).  Query operators are not read here.
