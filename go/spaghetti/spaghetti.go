@@ -1006,6 +1006,47 @@ func (s *Scorer) FacetCounts(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqT
 	return out, nil
 }
 
+// FieldPage is one query's page from FieldTopK: the docs in field order, their values, and the number of docs the query matches in all.
+type FieldPage struct {
+	Docs    []uint32
+	Values  []int64
+	Matches uint32
+}
+
+// FieldTopK returns, per query, page [first, first+k) of ALL docs FacetCounts counts for the same arguments, ordered by a doc field,
+// ascending or descending, docs of equal value by ascending doc id (ss_field_topk).  first + k may not exceed C.SS_MAX_TOPK.
+func (s *Scorer) FieldTopK(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange,
+	field int, descending bool, first, k int) ([]FieldPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	desc := 0
+	if descending {
+		desc = 1
+	}
+	docs, nOut := make([]uint32, nq*kk), make([]int32, nq)
+	vals, nMatch := make([]int64, nq*kk), make([]uint32, nq)
+	rp, keepR := docRanges(rng)
+	rc := C.ss_field_topk(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr),
+		u32p(excTerms), u32p(rngPtr), rp, C.int32_t(field), C.int32_t(desc), C.int32_t(first), C.int32_t(k), u32p(docs), i32p(nOut),
+		i64p(vals), u32p(nMatch))
+	runtime.KeepAlive(keepR)
+	if err := statusErr(s.ctx, rc, "ss_field_topk"); err != nil {
+		return nil, err
+	}
+	out := make([]FieldPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nOut[q])
+		out[q] = FieldPage{docs[q*kk : q*kk+n], vals[q*kk : q*kk+n], nMatch[q]}
+	}
+	return out, nil
+}
+
 // SortHitsByField sorts every window stably by a doc field, ascending or descending, rows outside the table last, and returns page
 // [first, first+k) with the rows' values (ss_sort_hits_by_field).  Only the hits' Doc is read to decide anything.
 func (s *Scorer) SortHitsByField(hits [][]Hit, field int, descending bool, first, k int) ([][]Hit, [][]int64, error) {

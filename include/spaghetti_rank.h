@@ -59,7 +59,8 @@ extern "C" {
  * ss_pr_lean_sweeps (how many sweeps of a state were launched in the lean form of option "pr.lean_sweeps");
  * SS_DIV_WEIGHT_MAX, ss_div_info and ss_diversify_hits (a window re-ranked greedily by relevance minus similarity to the rows already
  * chosen: maximal marginal relevance over the doc vectors);
- * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket). */
+ * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket);
+ * ss_field_topk (the exact top k of ALL docs a query matches, ordered by a doc field). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -863,6 +864,50 @@ int32_t ss_facet_counts(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const 
                         uint32_t* n_match_out /*[n_q]*/,
                         uint32_t* mask_counts_out /*[n_q][n_masks], nullable*/,
                         uint32_t* bucket_counts_out /*[n_q][n_buckets], NULL iff n_buckets == 0*/);
+
+/* ss_field_topk: the docs a query matches, ordered by a doc field, over ALL matches -- "newest first", "smallest pages first", "oldest
+ * match".  No reference counterpart.  ss_sort_hits_by_field orders a window of at most SS_MAX_TOPK rows that relevance chose; this call
+ * selects among every doc of M(q).  Defined bit for bit; no float is involved:
+ *   M(q)        = exactly the set ss_facet_counts defines for the same q_*, mask_id, req_*, exc_* and rng_* arguments, which is the set
+ *                 ss_score_topk_filtered ranks with p_ptr NULL.  Unknown term ids contribute nothing, a repeated term changes nothing,
+ *                 docs at or above n_docs are never in it.
+ *   Order.      By value[field][d] as signed 64-bit integers, ascending (descending == 0) or descending (descending != 0); docs of
+ *               equal value in ascending doc id in BOTH directions.  SS_NO_FIELD_VALUE is a value like any other.  The order is total,
+ *               so no summation or arrival order can show.
+ *   Output.     With the ordered docs S_0 .. S_{n-1}, n = |M(q)|: n_out[q] = clamp(n - first, 0, k); docs_out[q * k + r] = S_{first + r}
+ *               for r < n_out[q]; values_out[q * k + r] (nullable) = that doc's value; n_match_out[q] (nullable) = n, the number
+ *               ss_facet_counts writes.  Entries past n_out[q] are left untouched.  A query without a usable term: n_out 0, n_match 0.
+ * A known answer: the 8 docs of ss_facet_counts' comment (field 0 = 10, 20, .. 80; t0 = {1, 2, 5}, t1 = {2, 3}; m1 = {2, 5, 6}) and the
+ * query (t0, t1, t0, SS_UNKNOWN_TERM), C = {1, 2, 3, 5}, n_match 4.  Field 0 ascending, first 0, k 4: docs 1, 2, 3, 5, values 20, 30, 40,
+ * 60.  Descending, first 1, k 2: docs 3, 2, values 40, 30, n_out 2.  With t1 required (M = {2, 3}), ascending: docs 2, 3, values 30, 40,
+ * n_match 2.  With mask_id 1 and the clause field 0 in [25, 65] (M = {2, 5}), descending: docs 5, 2, values 60, 30, n_match 2.  A second
+ * field 5, 7, 7, 7, 0, 7, 0, 0: descending over C gives docs 1, 2, 3, 5 -- all tie at 7 and fall back to ascending doc id.
+ * Checks, all before anything is enqueued and with the outputs untouched: everything ss_facet_counts checks about its query, mask,
+ * constraint and range arrays, with its codes; NULL handle; n_q < 0; NULL q_ptr, docs_out or n_out with n_q > 0; k < 1; first < 0; a
+ * field outside [0, n_fields): SS_ERR_INVALID; first + k > SS_MAX_TOPK (computed without overflow): SS_ERR_UNSUPPORTED -- a deeper page
+ * is asked for with a range clause on the last value seen, as "value < last" (or "> last") plus the docs that tie with it; no field
+ * table registered: SS_ERR_STATE.  n_q == 0 (with a handle) is SS_OK and does nothing, whatever the other arguments are: that rule comes
+ * first, before k, first, field and the field table are looked at.
+ * The query, constraint and range arrays are read on the host like every scoring call's.  The outputs may be host or device memory: when
+ * all given outputs are device memory the call only enqueues on the ctx stream and NEVER waits; otherwise it goes through a block the
+ * scorer owns and returns when the outputs are written.  docs_out and n_out are laid out as ss_score_docs takes docs and n_in with
+ * k_in = k, so ss_field_topk -> ss_score_docs -> explain -> passages chains on one stream without a wait.
+ * k_field_select gives a workgroup a run of consecutive 32768-doc blocks of one query: per block the match words as in k_facet_counts
+ * (the bounds of the lists' runs searched from the previous block's ends), per set bit one gather of value[field][d], and a running
+ * best first + k in LDS (a threshold and a buffer compacted by a bitonic sort when it fills); k_field_merge joins the runs' lists per
+ * query.  Runs per query: option "ftopk.runs" (0 = from the device and the batch); the partial lists are bounded by option
+ * "ftopk.scratch_bytes" (default 256 MB), the queries going in groups beyond it.  No atomics on any output.
+ * Serialised on the ctx like every scoring call.  There is no phrase form (no p_ptr) and no _submit / _collect form. */
+int32_t ss_field_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                      const int32_t* mask_id,
+                      const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                      const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                      const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                      int32_t field, int32_t descending, int32_t first, int32_t k,
+                      uint32_t* docs_out    /*[n_q][k]*/,
+                      int32_t*  n_out       /*[n_q]*/,
+                      int64_t*  values_out  /*[n_q][k], nullable*/,
+                      uint32_t* n_match_out /*[n_q], nullable*/);
 
 /* Doc vectors: one signed 8-bit embedding per doc, the exact k nearest docs of a query vector, and a lexical result window re-ordered
  * by meaning.  No reference counterpart: every way the reference finds a page is a posting of a typed word.  Producing the embeddings

@@ -11,6 +11,7 @@
 // a zeroing memset: exact and independent of the order.  The allowed sets come from the scoring path (ss::allowed_sets_into_turn).
 #include "facet_plan.hpp"
 #include "hit_window.hpp"
+#include "match_lists.hpp"
 
 namespace fp = ss::facetp;
 namespace hw = ss::hitwin;
@@ -29,8 +30,7 @@ constexpr int FC_WAVES = FC_TPB / 64;
 constexpr int FC_CHUNK = 64;                        // counters (total, masks) that share one pass through the waves' partial sums
 static_assert(FC_TPB * FC_WPT == (int)fp::BLOCK_WORDS && FC_TPB == 2 * (int)fp::MAX_LISTS, "block geometry");
 
-struct __attribute__((aligned(16))) FacetList { uint64_t b; uint32_t len, field; };   // postings [b, b + len) of the title (field 1) or body (0) table
-static_assert(sizeof(FacetList) == 16, "list table layout");
+using FacetList = ss::MatchList;               // postings [b, b + len) of the title (field 1) or body (0) table (match_lists.hpp)
 
 struct FacetParams {
     const uint32_t* t_doc;            // the tables' post_doc (strictly ascending inside a term)
@@ -212,30 +212,11 @@ int32_t facet_impl(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint3
     if (n_tok && !q_terms) return ctx->fail(SS_ERR_INVALID, "%s: q_terms is NULL", entry);
     std::vector<uint32_t> terms(n_tok);
     if (n_tok) SS_HIP(ctx, ss::copy_in(ctx->stream, terms.data(), q_terms, n_tok * sizeof(uint32_t)));
-    // the list table: per query its distinct usable terms' non-empty lists (a repeated term once; ids >= n_terms have no list)
-    const std::vector<uint64_t>& tp = s->title->h_term_ptr;
-    const std::vector<uint64_t>& bp = s->body->h_term_ptr;
-    std::vector<uint32_t> aq, lptr(1, 0u), dterm;
-    std::vector<FacetList> lists;
-    for (size_t q = 0; q < nq; q++) {
-        dterm.clear();
-        for (uint32_t i = qptr[q]; i < qptr[q + 1]; i++) {
-            const uint32_t t = terms[i];
-            if ((uint64_t)t >= s->n_terms || std::find(dterm.begin(), dterm.end(), t) != dterm.end()) continue;
-            dterm.push_back(t);
-        }
-        if (dterm.size() > SS_MAX_QUERY_TERMS) return ctx->fail(SS_ERR_UNSUPPORTED, "%s: query %zu has more than %d distinct terms", entry, q, SS_MAX_QUERY_TERMS);
-        const size_t before = lists.size();
-        for (const uint32_t t : dterm)
-            for (uint32_t field = 0; field < 2; field++) {
-                const uint64_t* const pp = field ? tp.data() : bp.data();
-                if (pp[t + 1] > pp[t]) lists.push_back(FacetList{pp[t], (uint32_t)(pp[t + 1] - pp[t]), field});   // (a list is shorter than 2^32: ss_index_create)
-            }
-        if (lists.size() > before) {
-            aq.push_back((uint32_t)q);
-            lptr.push_back((uint32_t)lists.size());
-        }
-    }
+    // the list table: per query its distinct usable terms' non-empty lists (match_lists.hpp, shared with ss_field_topk)
+    ss::MatchLists ml;
+    SS_TRY(ss::build_match_lists(s, entry, qptr.data(), terms.data(), nq, &ml));
+    const std::vector<uint32_t>&aq = ml.aq, &lptr = ml.lptr;
+    const std::vector<FacetList>& lists = ml.lists;
     // the mask ids, constraint arrays and range clauses: the scoring call's own checks, then its sets on the device
     ss::AllowedSets as;
     SS_TRY(ss::allowed_sets_into_turn(s, n_q, q_ptr, mask_id, &cons, &ranges, &as));

@@ -112,7 +112,7 @@ struct Turn {
     ss::Event wave_ev;                         // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     ss::Event slice_ev;                        // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
-    ss::PinBuf h_facet;                        // ss_facet_counts: the call's list table and bucket table go up through it (one set per turn,
+    ss::PinBuf h_facet;                        // ss_facet_counts / ss_field_topk: the call's list table (and bucket table) go up through it (one set per turn,
     ss::DevBuf<unsigned char> d_facet;         // free after the wait for batch_ev like the plan's)
 };
 
@@ -250,6 +250,10 @@ struct ss_scorer {
     // ss_facet_counts (facet.hip): the device block of HOST outputs, totals | mask counts | bucket counts (grow-only; the call waits
     // before it returns)
     ss::DevBuf<uint32_t> d_facet_out;
+    // ss_field_topk (field_topk.hip), grow-only, written and read on the context's stream only: the partial lists of one group of
+    // queries, keys | doc ids | run counts (bounded by option "ftopk.scratch_bytes"; the groups of a call re-use it in stream order), and
+    // the device block of HOST outputs, values | docs | n_out | n_match (the call waits before it returns)
+    ss::DevBuf<unsigned char> d_ftopk_part, d_ftopk_out;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

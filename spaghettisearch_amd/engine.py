@@ -1068,6 +1068,40 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return n_match, mask_counts, bucket_counts
 
+    def field_topk(self, q_ptr, q_terms, field: int, descending: bool = False, first: int = 0, k: int = 10, ranges=None, req=None, exc=None,
+                   mask_id=None, out=None):
+        """ss_field_topk: per query the page [first, first + k) of ALL docs facet_counts would count for the same q_ptr / q_terms, ranges,
+        req, exc and mask_id, ordered by value[field][doc] (ascending, or descending; equal values by ascending doc id) ->
+        (docs uint32 [n_q][k], n_out int32 [n_q], values int64 [n_q][k] | None, n_match uint32 [n_q] | None).  first + k <= SS_MAX_TOPK.
+        out = (docs, n_out, values | None, n_match | None): the caller's arrays (numpy, or torch device tensors int32 / int32 / int64 /
+        int32: with device arrays throughout the call only enqueues), returned as they are; docs and n_out are what score_docs takes."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        k = int(k)
+        if out is not None:
+            docs, n_out, values, n_match = out
+            nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+            if k >= 1 and (nbytes(docs) < n_q * k * 4 or nbytes(n_out) < n_q * 4 or (values is not None and nbytes(values) < n_q * k * 8)
+                           or (n_match is not None and nbytes(n_match) < n_q * 4)):
+                raise ValueError("output buffers too small")
+        else:
+            docs = np.zeros((n_q, max(k, 0)), dtype=np.uint32)
+            n_out = np.zeros(n_q, dtype=np.int32)
+            values = np.zeros((n_q, max(k, 0)), dtype=np.int64)
+            n_match = np.zeros(n_q, dtype=np.uint32)
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, docs, n_out, values, n_match)
+        check(self.ctx.lib.ss_field_topk(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                         _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), int(field), int(bool(descending)), int(first), k,
+                                         _ptr(docs), _ptr(n_out), _ptr(values), _ptr(n_match)), self.ctx.h)
+        if _is_torch(docs) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return docs, n_out, values, n_match
+
     def _window(self, hits, n_hits, k_in):
         """(hits, n_hits, n_q, k_in) of a result window as collapse_hits takes it"""
         n_hits = _as(n_hits, "int32")

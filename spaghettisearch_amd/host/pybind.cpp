@@ -219,6 +219,14 @@ PYBIND11_MODULE(_host, m) {
             return di.FacetCounts(queries, rs, bs);
         }, py::arg("queries"), py::arg("ranges") = std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>{},
            py::arg("buckets") = std::vector<std::tuple<int32_t, int64_t, int64_t>>{})
+        .def("RetrieveBatchByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                                        const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges, int field, bool descending,
+                                        int first, int k) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            return di.RetrieveBatchByField(queries, rs, field, descending, first, k);
+        }, py::arg("queries"), py::arg("ranges"), py::arg("field"), py::arg("descending") = false, py::arg("first") = 0, py::arg("k") = 50)
         .def("SortByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int field, bool descending, int k_window,
                                int first, int k, py::object topic_probs, bool live_topic_probs) {
             if (topic_probs.is_none()) return di.SortByField(queries, field, descending, k_window, first, k, nullptr, live_topic_probs);

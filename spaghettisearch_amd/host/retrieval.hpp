@@ -1675,6 +1675,60 @@ public:
         }
         return out;
     }
+    // The docs every query matches, ordered by a doc field over ALL matches, not over a relevance window (ss_field_topk): page
+    // [first, first + k) of the docs FacetCounts counts under the clauses of ranges[q] (an empty `ranges`: none for any query), by the
+    // field's value ascending or descending ("newest first": field 0, descending), equal values by ascending doc hash; first + k <=
+    // SS_MAX_TOPK.  Every row is the one the query's ranking holds for that doc (ss_score_docs) with the field's value beside it.  With
+    // SetQueryOperators "+word" / "-word" are read as in FacetCounts.  A query string with a quoted phrase is refused.  The host layer
+    // holds no device memory of its own: both calls go through the scorer's blocks.
+    std::vector<FieldSortedPage> RetrieveBatchByField(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges,
+                                                      int field, bool descending, int first = 0, int k = 50) {
+        using namespace spaghetti;
+        if (!has_doc_fields) throw std::runtime_error("RetrieveBatchByField: no doc fields (SetDocFields)");
+        if (!ranges.empty() && ranges.size() != queries.size()) throw std::runtime_error("RetrieveBatchByField: one list of ranges per query, or none");
+        std::vector<uint32_t> rng_ptr{0}, req_ptr{0}, exc_ptr{0}, req_terms, exc_terms;
+        std::vector<ss_doc_range> rng;
+        for (auto& rs : ranges) {
+            for (auto& r : rs) rng.push_back(ss_doc_range{r.field, 0, r.lo, r.hi});
+            rng_ptr.push_back((uint32_t)rng.size());
+        }
+        std::vector<std::string> rewritten;
+        const std::vector<std::string>* qs = &queries;
+        if (query_operators) {
+            auto id_of = [&](const std::string& w) -> uint32_t {
+                auto it = terms.id.find(md5::hex(w));
+                return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+            };
+            for (auto& q : queries) {
+                const QueryOperators op = parseQueryOperators(q, laundry);
+                rewritten.push_back(op.query);
+                for (auto& w : op.required) req_terms.push_back(id_of(w));
+                for (auto& w : op.excluded) exc_terms.push_back(id_of(w));
+                req_ptr.push_back((uint32_t)req_terms.size());
+                exc_ptr.push_back((uint32_t)exc_terms.size());
+            }
+            qs = &rewritten;
+        }
+        const Tokenised t = tokenise(*qs, nullptr, false);
+        if (!t.p_terms.empty()) throw std::runtime_error("RetrieveBatchByField: quoted phrases are not read here");
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
+        std::vector<uint32_t> ids(nq * kk);
+        std::vector<int32_t> n_page(nq);
+        std::vector<int64_t> values(nq * kk);
+        std::vector<ss_hit> page(nq * kk);
+        check(ss_field_topk(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), nullptr, query_operators ? req_ptr.data() : nullptr, req_terms.data(),
+                            query_operators ? exc_ptr.data() : nullptr, exc_terms.data(), ranges.empty() ? nullptr : rng_ptr.data(), rng.data(),
+                            field, descending ? 1 : 0, first, k, ids.data(), n_page.data(), values.data(), nullptr), "ss_field_topk");
+        check(ss_score_docs(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.q_len.data(), nullptr, k, ids.data(), n_page.data(), page.data()),
+              "ss_score_docs");
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<FieldSortedPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Values.assign(values.begin() + q * kk, values.begin() + q * kk + n_page[q]);
+        }
+        return out;
+    }
     // RetrieveBatch sorted by a doc field (SetDocFields): page [first, first + k) of the first k_window rows of every query's ranking,
     // sorted stably by the field, ascending or descending ("newest first": field 0, descending).  Query operators are not read here.
     std::vector<FieldSortedPage> SortByField(const std::vector<std::string>& queries, int field, bool descending, int k_window, int first = 0,
