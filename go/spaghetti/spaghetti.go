@@ -1047,6 +1047,72 @@ func (s *Scorer) FieldTopK(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTer
 	return out, nil
 }
 
+// GroupCount is one row of TopGroups: a value of the doc -> group table and the number of the query's matches that carry it.
+type GroupCount struct {
+	Group uint32
+	Count uint32
+}
+
+// GroupPage is one query's page from TopGroups: the groups in count order, the number of distinct groups among the matches, the matches
+// without a group (SS_NO_GROUP) and the number of docs the query matches in all.
+type GroupPage struct {
+	Rows      []GroupCount
+	Groups    uint32
+	Ungrouped uint32
+	Matches   uint32
+}
+
+// GroupValues returns the distinct values other than SS_NO_GROUP of the registered group table, ascending (ss_scorer_group_values).
+func (s *Scorer) GroupValues() ([]uint32, error) {
+	var n C.uint32_t
+	if err := statusErr(s.ctx, C.ss_scorer_group_values(s.h, &n, nil), "ss_scorer_group_values"); err != nil {
+		return nil, err
+	}
+	values := make([]uint32, int(n))
+	if n == 0 {
+		return values, nil
+	}
+	if err := statusErr(s.ctx, C.ss_scorer_group_values(s.h, nil, u32p(values)), "ss_scorer_group_values"); err != nil {
+		return nil, err
+	}
+	return values, nil
+}
+
+// TopGroups returns, per query, page [first, first+m) of the groups (SetDocGroups) that hold docs FacetCounts counts for the same
+// arguments, by the number of such docs descending, equal counts by ascending group value (ss_top_groups).  first + m may not exceed
+// C.SS_MAX_TOPK.
+func (s *Scorer) TopGroups(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange,
+	first, m int) ([]GroupPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	mm := m
+	if mm < 1 {
+		mm = 1
+	}
+	rows, nOut := make([]C.ss_group_count, nq*mm), make([]int32, nq)
+	nGroups, nUngrouped, nMatch := make([]uint32, nq), make([]uint32, nq), make([]uint32, nq)
+	rp, keepR := docRanges(rng)
+	rc := C.ss_top_groups(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr),
+		u32p(excTerms), u32p(rngPtr), rp, C.int32_t(first), C.int32_t(m), &rows[0], i32p(nOut), u32p(nGroups), u32p(nUngrouped),
+		u32p(nMatch))
+	runtime.KeepAlive(keepR)
+	if err := statusErr(s.ctx, rc, "ss_top_groups"); err != nil {
+		return nil, err
+	}
+	out := make([]GroupPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nOut[q])
+		page := make([]GroupCount, n)
+		for r := 0; r < n; r++ {
+			page[r] = GroupCount{uint32(rows[q*mm+r].group), uint32(rows[q*mm+r].count)}
+		}
+		out[q] = GroupPage{page, nGroups[q], nUngrouped[q], nMatch[q]}
+	}
+	return out, nil
+}
+
 // SortHitsByField sorts every window stably by a doc field, ascending or descending, rows outside the table last, and returns page
 // [first, first+k) with the rows' values (ss_sort_hits_by_field).  Only the hits' Doc is read to decide anything.
 func (s *Scorer) SortHitsByField(hits [][]Hit, field int, descending bool, first, k int) ([][]Hit, [][]int64, error) {

@@ -60,7 +60,8 @@ extern "C" {
  * SS_DIV_WEIGHT_MAX, ss_div_info and ss_diversify_hits (a window re-ranked greedily by relevance minus similarity to the rows already
  * chosen: maximal marginal relevance over the doc vectors);
  * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket);
- * ss_field_topk (the exact top k of ALL docs a query matches, ordered by a doc field). */
+ * ss_field_topk (the exact top k of ALL docs a query matches, ordered by a doc field);
+ * ss_group_count, ss_scorer_group_values and ss_top_groups (the m groups of the doc -> group table that hold most of a query's matches). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -908,6 +909,60 @@ int32_t ss_field_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const ui
                       int32_t*  n_out       /*[n_q]*/,
                       int64_t*  values_out  /*[n_q][k], nullable*/,
                       uint32_t* n_match_out /*[n_q], nullable*/);
+
+/* ss_top_groups: where a query's matches are -- "Results from 312 sites . example.org (4,881) . docs.example.com (1,902)", the languages
+ * of the matches, the authors: the terms facet over the doc -> group table of ss_scorer_set_doc_groups.  No reference counterpart.
+ * ss_collapse_hits sees the at most SS_MAX_TOPK rows relevance chose; this call counts every doc of M(q).  Defined bit for bit; no
+ * float is involved:
+ *   M(q)        = exactly the set ss_facet_counts defines for the same q_*, mask_id, req_*, exc_* and rng_* arguments.
+ *   cnt(q, v)   = the number of d in M(q) with group[d] == v, for v != SS_NO_GROUP.
+ *   Order.      The values v with cnt(q, v) > 0, by cnt descending, equal counts by value ascending as unsigned 32-bit.  The order is
+ *               total, so no summation or arrival order can show.
+ *   Output.     With that sequence G_0 .. G_{n-1}: n_out[q] = clamp(n - first, 0, m); groups_out[q * m + r] = {G_{first + r}, its cnt}
+ *               for r < n_out[q]; entries past n_out[q] are left untouched; n_groups_out[q] (nullable) = n; n_ungrouped_out[q]
+ *               (nullable) = the number of d in M(q) with group[d] == SS_NO_GROUP; n_match_out[q] (nullable) = |M(q)|, the number
+ *               ss_facet_counts writes.  The counts of all n groups plus n_ungrouped add up to n_match.  A query without a usable
+ *               term gets zeros everywhere.
+ * A known answer: the 8 docs of ss_facet_counts' comment (t0 = {1, 2, 5}, t1 = {2, 3}, t2 = {6}; field 0 = 10, 20, .. 80; m1 = {2, 5, 6})
+ * with the table group = 7, 7, 7, 3, 3, SS_NO_GROUP, 0xFFFFFFFE, 3, whose distinct values are 3, 7, 0xFFFFFFFE.  The query (t0, t1, t0,
+ * SS_UNKNOWN_TERM), M = {1, 2, 3, 5}: first 0, m 4 gives (7, 2), (3, 1), n_out 2, n_groups 2, n_ungrouped 1, n_match 4; first 1, m 1
+ * gives (3, 1), n_out 1, the counts as before.  With t1 required, M = {2, 3}: (3, 1), (7, 1) -- a tie, value ascending --, n_groups 2,
+ * n_ungrouped 0, n_match 2.  With mask_id 1 and the clause field 0 in [25, 65], M = {2, 5}: (7, 1), n_out 1, n_groups 1, n_ungrouped 1,
+ * n_match 2.  The query (t2), M = {6}: (0xFFFFFFFE, 1), n_groups 1, n_ungrouped 0, n_match 1.
+ * Checks, all before anything is enqueued and with the outputs untouched: everything ss_facet_counts checks about its query, mask,
+ * constraint and range arrays, with its codes; NULL handle; n_q < 0; NULL q_ptr, groups_out or n_out with n_q > 0; m < 1; first < 0:
+ * SS_ERR_INVALID; first + m > SS_MAX_TOPK (computed without overflow): SS_ERR_UNSUPPORTED; no group table registered: SS_ERR_STATE.
+ * n_q == 0 (with a handle) is SS_OK and does nothing, whatever the other arguments are: that rule comes first.
+ * The group ranks: the first call that needs them after ss_scorer_set_doc_groups sorts a copy of the table, keeps its distinct values
+ * != SS_NO_GROUP ascending and gives every doc the index of its value (4 bytes per doc + 4 per distinct value, SS_ERR_OOM if that cannot
+ * be had).  That call waits once; registering a table again, or clearing it, drops the ranks.  ss_scorer_group_values reads them out
+ * (and builds them if they are missing): *n_groups_out (nullable) = the number of distinct values, values_out (nullable, host or device
+ * memory, [n_groups]) = the values ascending.  NULL handle: SS_ERR_INVALID; no group table: SS_ERR_STATE.
+ * The query, constraint and range arrays are read on the host like every scoring call's.  The outputs may be host or device memory: when
+ * all given outputs are device memory and the ranks are built, the call only enqueues on the ctx stream and NEVER waits; otherwise it
+ * goes through a block the scorer owns and returns when the outputs are written.
+ * k_group_count gives a workgroup a run of consecutive 32768-doc blocks of one query: per block the match words as in k_field_select,
+ * per set bit one gather of the doc's rank, counted into the query's row of n_groups + 2 integer counters -- through a histogram in LDS
+ * when the table has at most option "gtopk.lds_groups" (default 8192, at most 8192, 0 = never) distinct values, by global atomic adds
+ * with consecutive equal ranks merged otherwise; both paths give the same bytes.  k_group_select, one workgroup per query, pushes the
+ * row's non-zero counters through a running best first + m and writes the page.  Runs per query: option "gtopk.runs" (0 = from the
+ * device and the batch); the counter rows are bounded by option "gtopk.scratch_bytes" (default 256 MB), the queries going in groups
+ * beyond it, at least one query per group.  Integer atomics only.
+ * Serialised on the ctx like every scoring call.  There is no phrase form (no p_ptr) and no _submit / _collect form. */
+typedef struct ss_group_count { uint32_t group; uint32_t count; } ss_group_count;   /* 8 bytes */
+int32_t ss_scorer_group_values(ss_scorer* s, uint32_t* n_groups_out /*nullable*/,
+                               uint32_t* values_out /*[n_groups] ascending, nullable; host or device*/);
+int32_t ss_top_groups(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                      const int32_t* mask_id,
+                      const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                      const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                      const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                      int32_t first, int32_t m,
+                      ss_group_count* groups_out /*[n_q][m]*/,
+                      int32_t*  n_out           /*[n_q]*/,
+                      uint32_t* n_groups_out    /*[n_q], nullable*/,
+                      uint32_t* n_ungrouped_out /*[n_q], nullable*/,
+                      uint32_t* n_match_out     /*[n_q], nullable*/);
 
 /* Doc vectors: one signed 8-bit embedding per doc, the exact k nearest docs of a query vector, and a lexical result window re-ordered
  * by meaning.  No reference counterpart: every way the reference finds a page is a posting of a typed word.  Producing the embeddings

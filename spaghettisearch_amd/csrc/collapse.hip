@@ -239,6 +239,7 @@ int32_t ss_scorer_set_doc_groups(ss_scorer* s, const uint32_t* group) {
     SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (hipStream_t ws : ctx->wave_stream)
         if (ws) SS_HIP(ctx, hipStreamSynchronize(ws));
+    s->drop_group_ranks();                          // (group_topk.hip: they describe the old table; the next call that needs them builds them)
     if (!group) {
         s->groups.release();
         s->has_groups = false;

@@ -374,6 +374,12 @@ static const char* const k_option_names[] = {
                             //    blocks; tests force it to put run seams between any two blocks; the outputs are the same bytes for every value
     "ftopk.scratch_bytes",  // ... most bytes of partial lists in flight (default 256 MB); the queries of a call run in groups that fit, one
                             //    query per group if not even one does; the outputs are the same bytes for every value
+    "gtopk.lds_groups",     // ss_top_groups: k_group_count counts through a histogram in LDS when the group table has at most this many distinct
+                            //    values (default 8192, which is also the most the histogram holds; 0: never), by global atomic adds otherwise;
+                            //    the outputs are the same bytes for every value
+    "gtopk.runs",           // ... runs of consecutive doc blocks per query, one workgroup of k_group_count each (default 0: as "ftopk.runs")
+    "gtopk.scratch_bytes",  // ... most bytes of counter rows in flight (default 256 MB); the queries of a call run in groups that fit, one
+                            //    query per group if not even one does; the outputs are the same bytes for every value
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

@@ -254,6 +254,23 @@ struct ss_scorer {
     // queries, keys | doc ids | run counts (bounded by option "ftopk.scratch_bytes"; the groups of a call re-use it in stream order), and
     // the device block of HOST outputs, values | docs | n_out | n_match (the call waits before it returns)
     ss::DevBuf<unsigned char> d_ftopk_part, d_ftopk_out;
+    // ss_top_groups / ss_scorer_group_values (group_topk.hip).  The group ranks of the registered table, built by the first call that
+    // needs them and dropped with the table (drop_group_ranks): gval [n_groups] the table's distinct values != SS_NO_GROUP ascending,
+    // grank [n_docs] the index of group[d] in gval (0xFFFFFFFF for SS_NO_GROUP).  Grow-only, written and read on the context's stream
+    // only: the counter rows of one group of queries [group][row stride] (bounded by option "gtopk.scratch_bytes"; the groups of a call
+    // re-use it in stream order) and the device block of HOST outputs, rows | n_out | n_groups | n_ungrouped | n_match (the call waits
+    // before it returns)
+    ss::DevBuf<uint32_t> gval, grank;
+    uint32_t n_groups = 0;
+    bool has_group_ranks = false;
+    void drop_group_ranks() {
+        gval.release();
+        grank.release();
+        n_groups = 0;
+        has_group_ranks = false;
+    }
+    ss::DevBuf<uint32_t> d_gtopk_rows;
+    ss::DevBuf<unsigned char> d_gtopk_out;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

@@ -25,6 +25,8 @@ DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("
 
 VEC_HIT_DTYPE = np.dtype([("doc", "<u4"), ("score", "<i4")])   # ss_vec_hit
 
+GROUP_COUNT_DTYPE = np.dtype([("group", "<u4"), ("count", "<u4")])   # ss_group_count
+
 DIV_INFO_DTYPE = np.dtype([("rel", "<i4"), ("sim", "<i4")])     # ss_div_info
 
 FUSED_DTYPE = np.dtype([("score", "<f8"), ("vec_score", "<i4"), ("lex_rank", "<u2"), ("vec_rank", "<u2")])   # ss_fused
@@ -1101,6 +1103,49 @@ class Scorer:
         if _is_torch(docs) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return docs, n_out, values, n_match
+
+    def group_values(self) -> np.ndarray:
+        """ss_scorer_group_values: the distinct values != SS_NO_GROUP of the registered group table, ascending -> uint32 [n_groups].
+        The first call after set_doc_groups builds the group ranks and waits for it."""
+        n = C.c_uint32(0)
+        check(self.ctx.lib.ss_scorer_group_values(self.h, C.byref(n), None), self.ctx.h)
+        values = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(self.ctx.lib.ss_scorer_group_values(self.h, None, _ptr(values)), self.ctx.h)
+        return values
+
+    def top_groups(self, q_ptr, q_terms, first: int = 0, m: int = 10, ranges=None, req=None, exc=None, mask_id=None, out=None):
+        """ss_top_groups: per query the page [first, first + m) of the groups (set_doc_groups) that hold docs facet_counts would count for
+        the same q_ptr / q_terms, ranges, req, exc and mask_id, ordered by the number of such docs descending, equal counts by group value
+        ascending -> (groups GROUP_COUNT_DTYPE [n_q][m], n_out int32 [n_q], n_groups uint32 [n_q], n_ungrouped uint32 [n_q], n_match
+        uint32 [n_q]).  first + m <= SS_MAX_TOPK.  out = (groups, n_out, n_groups | None, n_ungrouped | None, n_match | None): the
+        caller's arrays (numpy, or torch device tensors of int32 — groups as [n_q][m][2]: with device arrays throughout, and the group
+        ranks built, the call only enqueues), returned as they are."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        m = int(m)
+        if out is not None:
+            groups, n_out, n_groups, n_ungrouped, n_match = out
+            nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+            if m >= 1 and (nbytes(groups) < n_q * m * GROUP_COUNT_DTYPE.itemsize or nbytes(n_out) < n_q * 4
+                           or any(a is not None and nbytes(a) < n_q * 4 for a in (n_groups, n_ungrouped, n_match))):
+                raise ValueError("output buffers too small")
+        else:
+            groups = np.zeros((n_q, max(m, 0)), dtype=GROUP_COUNT_DTYPE)
+            n_out = np.zeros(n_q, dtype=np.int32)
+            n_groups, n_ungrouped, n_match = (np.zeros(n_q, dtype=np.uint32) for _ in range(3))
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, groups, n_out, n_groups, n_ungrouped, n_match)
+        check(self.ctx.lib.ss_top_groups(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                         _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), int(first), m, _ptr(groups), _ptr(n_out), _ptr(n_groups),
+                                         _ptr(n_ungrouped), _ptr(n_match)), self.ctx.h)
+        if _is_torch(groups) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return groups, n_out, n_groups, n_ungrouped, n_match
 
     def _window(self, hits, n_hits, k_in):
         """(hits, n_hits, n_q, k_in) of a result window as collapse_hits takes it"""

@@ -66,6 +66,11 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Total", &retrieval::FacetCount::Total)
         .def_readonly("Masks", &retrieval::FacetCount::Masks)
         .def_readonly("Buckets", &retrieval::FacetCount::Buckets);
+    py::class_<retrieval::GroupPage>(m, "GroupPage")
+        .def_readonly("Total", &retrieval::GroupPage::Total)
+        .def_readonly("Groups", &retrieval::GroupPage::Groups)
+        .def_readonly("Ungrouped", &retrieval::GroupPage::Ungrouped)
+        .def_readonly("Rows", &retrieval::GroupPage::Rows);
     py::class_<retrieval::VectorHit>(m, "VectorHit")
         .def_readonly("DocHash", &retrieval::VectorHit::DocHash)
         .def_readonly("Score", &retrieval::VectorHit::Score);
@@ -227,6 +232,14 @@ PYBIND11_MODULE(_host, m) {
                 for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
             return di.RetrieveBatchByField(queries, rs, field, descending, first, k);
         }, py::arg("queries"), py::arg("ranges"), py::arg("field"), py::arg("descending") = false, py::arg("first") = 0, py::arg("k") = 50)
+        .def("TopGroups", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                             const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges, int first, int m) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            return di.TopGroups(queries, rs, first, m);
+        }, py::arg("queries"), py::arg("ranges") = std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>{}, py::arg("first") = 0,
+           py::arg("m") = 10)
         .def("SortByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int field, bool descending, int k_window,
                                int first, int k, py::object topic_probs, bool live_topic_probs) {
             if (topic_probs.is_none()) return di.SortByField(queries, field, descending, k_window, first, k, nullptr, live_topic_probs);

@@ -93,6 +93,14 @@ struct FacetCount {
     std::vector<uint32_t> Buckets;
 };
 
+// One query's sites from DeviceIndex::TopGroups (no reference counterpart): Total = the docs the query matches (FacetCount::Total),
+// Groups = the distinct site keys among them, Ungrouped = the matches SetDocGroups does not name, Rows = page [first, first + m) of
+// {site key, matches} by matches descending, equal counts by ascending key.
+struct GroupPage {
+    uint32_t Total = 0, Groups = 0, Ungrouped = 0;
+    std::vector<std::pair<std::string, uint32_t>> Rows;
+};
+
 // One page of a query's results sorted by a doc field (DeviceIndex::SortByField; no reference counterpart).  Values[i]: the field's
 // value of Results[i].
 struct FieldSortedPage {
@@ -351,6 +359,7 @@ public:
     // Site keys for collapsed result pages (SetDocGroups): doc hash -> key string, kept by hash like the allow-lists and registered
     // again on every scorer this index creates.  has_doc_groups: SetDocGroups was called (an empty map is a table of SS_NO_GROUP).
     std::map<std::string, std::string> doc_group_keys;
+    std::vector<std::string> doc_group_names;       // the key behind every group number of the registered table (register_groups)
     bool has_doc_groups = false;
     // Doc fields (SetDocFields): doc hash -> {Mod_date as unix seconds, Page_size} (retrieval/util.go:28-29), kept by hash like the site
     // keys and registered again on every scorer this index creates.
@@ -813,7 +822,11 @@ public:
         std::map<std::string, uint32_t> number;
         for (auto& kv : doc_group_keys) number.emplace(kv.second, 0u);
         uint32_t next = 0;
-        for (auto& kv : number) kv.second = next++;
+        doc_group_names.clear();
+        for (auto& kv : number) {
+            kv.second = next++;
+            doc_group_names.push_back(kv.first);
+        }
         std::vector<uint32_t> group((size_t)n, SS_NO_GROUP);
         for (auto& kv : doc_group_keys) {
             auto it = docs.id.find(kv.first);
@@ -1726,6 +1739,60 @@ public:
         for (size_t q = 0; q < nq; q++) {
             out[q].Results = ranks[q];
             out[q].Values.assign(values.begin() + q * kk, values.begin() + q * kk + n_page[q]);
+        }
+        return out;
+    }
+    // Where every query's matches are (ss_top_groups): page [first, first + m) of the site keys of SetDocGroups that hold docs FacetCounts
+    // counts under the clauses of ranges[q] (an empty `ranges`: none for any query), by the number of such docs descending, equal counts
+    // by ascending key (a key's number is its rank among the distinct keys, so number order is key order); first + m <= SS_MAX_TOPK.
+    // With SetQueryOperators "+word" / "-word" are read as in FacetCounts.  A query string with a quoted phrase is refused.
+    std::vector<GroupPage> TopGroups(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges = {}, int first = 0,
+                                     int m = 10) {
+        using namespace spaghetti;
+        if (!has_doc_groups) throw std::runtime_error("TopGroups: no doc groups (SetDocGroups)");
+        if (!ranges.empty() && ranges.size() != queries.size()) throw std::runtime_error("TopGroups: one list of ranges per query, or none");
+        std::vector<uint32_t> rng_ptr{0}, req_ptr{0}, exc_ptr{0}, req_terms, exc_terms;
+        std::vector<ss_doc_range> rng;
+        for (auto& rs : ranges) {
+            for (auto& r : rs) rng.push_back(ss_doc_range{r.field, 0, r.lo, r.hi});
+            rng_ptr.push_back((uint32_t)rng.size());
+        }
+        if (!rng.empty() && !has_doc_fields) throw std::runtime_error("TopGroups: no doc fields (SetDocFields)");
+        std::vector<std::string> rewritten;
+        const std::vector<std::string>* qs = &queries;
+        if (query_operators) {
+            auto id_of = [&](const std::string& w) -> uint32_t {
+                auto it = terms.id.find(md5::hex(w));
+                return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+            };
+            for (auto& q : queries) {
+                const QueryOperators op = parseQueryOperators(q, laundry);
+                rewritten.push_back(op.query);
+                for (auto& w : op.required) req_terms.push_back(id_of(w));
+                for (auto& w : op.excluded) exc_terms.push_back(id_of(w));
+                req_ptr.push_back((uint32_t)req_terms.size());
+                exc_ptr.push_back((uint32_t)exc_terms.size());
+            }
+            qs = &rewritten;
+        }
+        const Tokenised t = tokenise(*qs, nullptr, false);
+        if (!t.p_terms.empty()) throw std::runtime_error("TopGroups: quoted phrases are not counted");
+        const size_t nq = (size_t)t.nq, mm = (size_t)std::max(m, 1);
+        std::vector<ss_group_count> rows(nq * mm);
+        std::vector<int32_t> n_page(nq);
+        std::vector<uint32_t> n_groups(nq), n_ungrouped(nq), n_match(nq);
+        check(ss_top_groups(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), nullptr, query_operators ? req_ptr.data() : nullptr, req_terms.data(),
+                            query_operators ? exc_ptr.data() : nullptr, exc_terms.data(), ranges.empty() ? nullptr : rng_ptr.data(), rng.data(),
+                            first, m, rows.data(), n_page.data(), n_groups.data(), n_ungrouped.data(), n_match.data()), "ss_top_groups");
+        std::vector<GroupPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Total = n_match[q];
+            out[q].Groups = n_groups[q];
+            out[q].Ungrouped = n_ungrouped[q];
+            for (int32_t r = 0; r < n_page[q]; r++) {
+                const ss_group_count& g = rows[q * mm + (size_t)r];
+                out[q].Rows.emplace_back(doc_group_names.at(g.group), g.count);
+            }
         }
         return out;
     }
