@@ -1844,3 +1844,39 @@ func (lx *Lexicon) Suggest(words []string, maxDist int, minFreq uint32, m int) (
 	}
 	return out, nil
 }
+
+// Completion is one word that starts with a typed prefix: its term id, the word and its freq.
+type Completion struct {
+	Term uint32
+	Word string
+	Freq uint32
+}
+
+// Complete returns per prefix up to m words that start with it and whose freq is at least minFreq, ordered by freq descending, then
+// as Go's string < orders the words, then term id (ss_lexicon_complete), and the number of words with the prefix whatever their
+// freq.  Written against the header like the rest of this file, not compiled (see the note at the top).
+func (lx *Lexicon) Complete(prefixes []string, minFreq uint32, m int) ([][]Completion, []uint64, error) {
+	nq := len(prefixes)
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	ptr, data := flattenWords(prefixes)
+	terms := make([]uint32, nq*m)
+	freq := make([]uint32, nq*m)
+	nOut := make([]int32, nq)
+	nMatch := make([]uint64, nq)
+	rc := C.ss_lexicon_complete(lx.h, C.int32_t(nq), u32p(ptr), u8p(data), C.uint32_t(minFreq), C.int32_t(m), u32p(terms), u32p(freq),
+		i32p(nOut), u64p(nMatch))
+	if err := statusErr(lx.ctx, rc, "ss_lexicon_complete"); err != nil {
+		return nil, nil, err
+	}
+	out := make([][]Completion, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Completion, nOut[q])
+		for i := range out[q] {
+			t := terms[q*m+i]
+			out[q][i] = Completion{t, lx.words[t], freq[q*m+i]}
+		}
+	}
+	return out, nMatch, nil
+}

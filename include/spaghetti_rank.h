@@ -61,7 +61,8 @@ extern "C" {
  * chosen: maximal marginal relevance over the doc vectors);
  * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket);
  * ss_field_topk (the exact top k of ALL docs a query matches, ordered by a doc field);
- * ss_group_count, ss_scorer_group_values and ss_top_groups (the m groups of the doc -> group table that hold most of a query's matches). */
+ * ss_group_count, ss_scorer_group_values and ss_top_groups (the m groups of the doc -> group table that hold most of a query's matches);
+ * SS_MAX_COMPLETE and ss_lexicon_complete (the m most frequent words that start with a prefix: word completions). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -1223,19 +1224,38 @@ int32_t ss_hybrid_topk(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const u
  *              Row q of terms_out [n_q][m] / dist_out [n_q][m] (nullable) holds the first n_out[q] = min(m, #candidates) candidates
  *              ordered by distance ascending, then freq descending, then term id ascending.  Entries past n_out[q] are left
  *              untouched.  The row does not depend on the order in which workgroups finish: there are no atomics.
+ *   Complete.  "Of the words that start with what was typed, the most used" (no reference counterpart).  Row q's matches are exactly
+ *              those of Prefix: the terms whose word starts with prefix q, a contiguous range [lb, ub) of positions in the sort
+ *              order; n_match_out[q] (nullable) = ub - lb, whatever min_freq is.  The candidates are the matches with freq >=
+ *              min_freq, ordered by freq descending, then by sort position ascending (the word in Go string order, equal words by
+ *              term id): by the single 64-bit key (~freq << 32) | position, ascending.  No two candidates have the same key, so the
+ *              row is a pure function of the input.  n_out[q] = min(m, #candidates); terms_out[q * m + r] = the term id of the
+ *              r-th candidate and freq_out[q * m + r] (nullable) its freq, for r < n_out[q].  Entries past n_out[q] are left
+ *              untouched.  No atomics, no dependence on the order in which workgroups finish.  By hand: the words (id 0 .. 5)
+ *              "car", "cat", "ca", "dog", "cat", "cab" with freq 5, 9, 5, 100, 9, 0 sort as ca, cab, car, cat (1), cat (4), dog =
+ *              ids 2, 5, 0, 1, 4, 3.  Prefix "ca", min_freq 1, m 3: range [0, 5), n_match 5, row ids 1, 4, 2 with freq 9, 9, 5
+ *              ("ca" before "car": equal freq, earlier position), n_out 3; m 64: ids 1, 4, 2, 0, n_out 4 ("cab" has freq 0 < 1);
+ *              min_freq 0: "cab" comes last, n_out 5; min_freq 10: n_out 0, n_match still 5; prefix "" with m 1: id 3 ("dog");
+ *              prefix "cow": n_match 0, n_out 0.  With every freq equal the row is that of Prefix with first 0 and k = m.
  * Checks, all before anything is enqueued and with the outputs untouched: NULL handle or NULL required output (terms_out, n_out) or
  * pointer array, n_q < 0, a p_ptr / w_ptr that decreases (as q_ptr in ss_score_topk), k < 1, m < 1, first < 0, max_dist < 0:
- * SS_ERR_INVALID; k > SS_MAX_TOPK, m > SS_MAX_SUGGEST, max_dist > SS_MAX_EDIT_DIST: SS_ERR_UNSUPPORTED.  n_q == 0 is SS_OK and does
+ * SS_ERR_INVALID; k > SS_MAX_TOPK, m > SS_MAX_SUGGEST (SS_MAX_COMPLETE for Complete), max_dist > SS_MAX_EDIT_DIST:
+ * SS_ERR_UNSUPPORTED.  n_q == 0 is SS_OK and does
  * nothing; every call on a lexicon of 0 terms is SS_OK: the rows come back empty and n_out is written as 0.
  * Query bytes and pointers are read on the host like every query array.  Outputs may each be host or device memory: when all given
  * outputs are device memory the call only enqueues on the ctx stream and NEVER waits (the queries go up through turns of pinned
  * blocks the lexicon owns); otherwise it stages through blocks the lexicon owns and returns when the outputs are written.
  * ss_lexicon_suggest compares every query word with every word of the length groups len - max_dist .. len + max_dist, one workgroup
  * per (query word, chunk of option "lexicon.chunk_terms" words, default 4096, 1 .. 2^20); its temporaries are sized by m * chunks,
- * never by the number of candidates.  Calls are serialised on the ctx like the scoring calls; there is no _submit / _collect form. */
+ * never by the number of candidates.  ss_lexicon_complete cuts the range of every prefix into the same number P of near-equal parts,
+ * one workgroup per (prefix, part), each streaming its part of the frequencies held in sort order (4 B per term); P comes from n_q
+ * alone (about 4096 workgroups per call and at most 64 per prefix; option "lexicon.complete_parts" forces 1 .. 256), so its temporaries are
+ * n_q * P * m keys, never sized by a range.  The rows are the same bytes for every P.
+ * Calls are serialised on the ctx like the scoring calls; there is no _submit / _collect form. */
 #define SS_MAX_WORD_BYTES 64   /* longest word that can be a suggestion candidate or a suggest query */
 #define SS_MAX_EDIT_DIST  3
 #define SS_MAX_SUGGEST    64
+#define SS_MAX_COMPLETE   64
 typedef struct ss_lexicon ss_lexicon;
 
 int32_t ss_lexicon_create(ss_ctx* ctx, uint64_t n_terms, const uint64_t* word_ptr /*[n_terms+1]*/, const uint8_t* bytes,
@@ -1252,6 +1272,11 @@ int32_t ss_lexicon_prefix(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr /*[
 int32_t ss_lexicon_suggest(ss_lexicon* lx, int32_t n_q, const uint32_t* w_ptr /*[n_q+1]*/, const uint8_t* w_bytes,
                            int32_t max_dist, uint32_t min_freq, int32_t m,
                            uint32_t* terms_out /*[n_q][m]*/, int32_t* dist_out /*[n_q][m] nullable*/, int32_t* n_out /*[n_q]*/);
+
+int32_t ss_lexicon_complete(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr /*[n_q+1]*/, const uint8_t* p_bytes,
+                            uint32_t min_freq, int32_t m,
+                            uint32_t* terms_out /*[n_q][m]*/, uint32_t* freq_out /*[n_q][m] nullable*/,
+                            int32_t* n_out /*[n_q]*/, uint64_t* n_match_out /*[n_q] nullable*/);
 
 /* Doc-range-sharded scoring: every shard scores the same query batch against its own doc range
  * (ss_score_topk, local doc ids) and the host gathers the lists.  ss_merge_hits returns the k best

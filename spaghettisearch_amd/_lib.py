@@ -21,6 +21,7 @@ SS_NO_GROUP = 0xFFFFFFFF
 SS_MAX_WORD_BYTES = 64
 SS_MAX_EDIT_DIST = 3
 SS_MAX_SUGGEST = 64
+SS_MAX_COMPLETE = 64
 SS_MAX_SIG_SLOTS = 32
 SS_SIG_EMPTY = 0xFFFFFFFF
 SS_MAX_LINKS = 64
@@ -197,6 +198,7 @@ PROTOTYPES = {
     "ss_lexicon_destroy": (_i32, [_vp]),
     "ss_lexicon_prefix": (_i32, [_vp, _i32, _vp, _vp, C.c_int64, _i32, _vp, _vp, _vp]),
     "ss_lexicon_suggest": (_i32, [_vp, _i32, _vp, _vp, _i32, C.c_uint32, _i32, _vp, _vp, _vp]),
+    "ss_lexicon_complete": (_i32, [_vp, _i32, _vp, _vp, C.c_uint32, _i32, _vp, _vp, _vp, _vp]),
     "ss_merge_hits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ss_last_kernel_ms": (_i32, [_vp, _i32, C.POINTER(C.c_float)]),
 }

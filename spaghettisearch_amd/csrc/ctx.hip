@@ -356,6 +356,9 @@ static const char* const k_option_names[] = {
                             //    the LDS (sorted there), a longer one from global memory; the same bytes either way (default 512, 1 .. 4096; tests reach the long path)
     "lexicon.chunk_terms",  // k_lexicon_suggest: words of the query's length groups per (query word, chunk) workgroup (default 4096, 1 .. 2^20;
                             //    tests set it small to put chunk seams inside a length group); the rows are the same bytes for every value
+    "lexicon.complete_parts", // ss_lexicon_complete: parts P the range of every prefix is cut into, one wave of k_lexicon_complete each (default 0:
+                            //    from the number of prefixes, lexicon_plan.hpp; 1 .. 256 forces it; tests force it to put part seams anywhere); the
+                            //    rows are the same bytes for every value
     "links.wave_max",       // ss_graph_top_links / _hit_links: a row of at most this many edges is one work item of k_links_select (default 1024,
                             //    32 .. 4096, clamped: links_plan.hpp); a longer one is cut into chunks and merged
     "links.chunk_edges",    // ... edges per chunk of such a row (default 1024, 32 .. 4096, clamped); tests set both small to reach the split

@@ -14,6 +14,13 @@
 //                              (dist << 32 | ~freq, id); the wave keeps its 64 best keys sorted, one per lane (bitonic sort of the new
 //                              keys + one bitonic merge, shuffles only: no LDS, no atomics), and writes the first m.
 //   k_lexicon_merge            one wave per query word merges its chunks' lists the same way and writes the row.
+//   k_lexicon_complete_bounds  one wave per prefix: the two bounds of k_lexicon_prefix, written as {lb, ub}.
+//   k_lexicon_complete         one wave per (prefix, part): the range [lb, ub) of every prefix is cut into P near-equal parts (P from the
+//                              number of prefixes alone, lexicon_plan.hpp).  The wave streams its part of the frequencies in sort order (16 B
+//                              per lane where the position is a multiple of 4, a ragged head and tail one dword per lane) and keeps
+//                              its best keys (~freq << 32 | position) sorted, one per lane; a step none of whose keys is below the
+//                              wave's m-th best so far costs one ballot: no sort, no merge.  Writes its first m keys.
+//   k_lexicon_complete_merge   one wave per prefix merges the P lists and writes the row, n_out and n_match_out.
 // Device outputs: the calls only enqueue on the context's stream.  Host outputs go through lexicon-owned device blocks and only the
 // entries the definition names are copied back.
 #include "common.hpp"
@@ -58,6 +65,7 @@ struct ss_lexicon {
     ss::DevBuf<uint32_t> d_off;                           // [n_terms + 1] word starts
     ss::DevBuf<uint8_t> d_bytes;
     ss::DevBuf<uint32_t> d_order;                         // [n_terms] the sort order
+    ss::DevBuf<uint32_t> d_ofreq;                         // [n_terms] freq in sort order: d_ofreq[pos] = freq[d_order[pos]]
     ss::DevBuf<uint32_t> d_gterm, d_gfreq, d_gwords;      // grouped by (length, id): ids, freq, the words at the group's stride
     ss::DevBuf<uint32_t> d_start;                         // [N_STARTS]
     ss::DevBuf<uint64_t> d_base;                          // [N_STARTS]
@@ -66,8 +74,11 @@ struct ss_lexicon {
     // the chunks' lists of a suggest call: written and read on the context's stream only (grow-only)
     ss::DevBuf<uint64_t> d_part_a;
     ss::DevBuf<uint32_t> d_part_id, d_part_n;
+    // the parts' lists and the bounds of a complete call, the same way
+    ss::DevBuf<uint64_t> d_cpl_key;
+    ss::DevBuf<uint32_t> d_cpl_bounds;
     // device blocks of HOST outputs (grow-only; a call that uses one waits before it returns)
-    ss::DevBuf<uint32_t> d_out_terms;
+    ss::DevBuf<uint32_t> d_out_terms, d_out_freq;
     ss::DevBuf<int32_t> d_out_dist, d_out_n;
     ss::DevBuf<uint64_t> d_out_match;
 };
@@ -159,6 +170,116 @@ __global__ __launch_bounds__(LX_TPB) void k_lexicon_prefix(PrefixParams p) {
     if (lane == 0) {
         p.n_out[q] = (int32_t)cnt;
         if (p.n_match_out) p.n_match_out[q] = n_match;
+    }
+}
+
+// ---- complete ---------------------------------------------------------------------------------------------------------------------
+struct CompleteParams {
+    PrefixParams lex;                                     // the lexicon, the call's table and the outputs as k_lexicon_prefix takes them (k = m)
+    const uint32_t* ofreq;                                // [n_terms] freq in sort order
+    uint32_t* bounds;                                     // [n_q] {lb, ub}
+    uint64_t* part_key;                                   // [n_q][P][m] the parts' best keys, ascending, LX_INF_A behind the last
+    uint32_t* freq_out;                                   // [n_q][m] or NULL
+    uint32_t P, min_freq;
+};
+
+// the two searches of k_lexicon_prefix: [*lb, *ub) = the sort positions whose word starts with prefix q
+__device__ __forceinline__ void prefix_bounds(const PrefixParams& p, uint32_t q, uint32_t lane, uint32_t* lb, uint32_t* ub) {
+    const uint32_t lp = p.q[2 * q + 1];
+    const uint8_t* pre = reinterpret_cast<const uint8_t*>(p.q + 2 * (size_t)p.n_q) + p.q[2 * q];
+    uint32_t lo = 0, hi = p.n_terms;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (prefix_cmp(p, mid, pre, lp, lane) < 0) lo = mid + 1; else hi = mid;
+    }
+    *lb = lo;
+    hi = p.n_terms;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (prefix_cmp(p, mid, pre, lp, lane) <= 0) lo = mid + 1; else hi = mid;
+    }
+    *ub = lo;
+}
+
+__global__ __launch_bounds__(LX_TPB) void k_lexicon_complete_bounds(CompleteParams p) {
+    uint32_t lb, ub;
+    prefix_bounds(p.lex, blockIdx.x, threadIdx.x, &lb, &ub);
+    if (threadIdx.x == 0) {
+        p.bounds[2 * (size_t)blockIdx.x] = lb;
+        p.bounds[2 * (size_t)blockIdx.x + 1] = ub;
+    }
+}
+
+// The wave's list of a complete call: its best keys ascending by lane, and `thr`, the m-th of them (LX_INF_A while there are fewer):
+// a key that is not below thr cannot be in the row.  Keys are distinct (the position is part of the key), so the id word of
+// wave_sort / wave_merge only repeats the key's low word.
+struct CompleteList {
+    uint64_t best = LX_INF_A, thr = LX_INF_A;
+    uint32_t best_id = LX_INF_ID;
+    // one key per lane (LX_INF_A: none); the whole wave calls it
+    __device__ __forceinline__ void offer(uint64_t na, uint32_t m, uint32_t lane) {
+        if (na >= thr) na = LX_INF_A;
+        if (!__any(na != LX_INF_A)) return;
+        uint32_t nid = na != LX_INF_A ? (uint32_t)na : LX_INF_ID;
+        wave_sort(na, nid, lane);
+        wave_merge(best, best_id, na, nid, lane);
+        thr = __shfl(best, (int)m - 1, 64);
+    }
+};
+__device__ __forceinline__ uint64_t complete_key(uint32_t freq, uint32_t pos, uint32_t min_freq) {
+    return freq >= min_freq ? ((uint64_t)~freq << 32) | (uint64_t)pos : LX_INF_A;
+}
+
+__global__ __launch_bounds__(LX_TPB) void k_lexicon_complete(CompleteParams p) {
+    const uint32_t wi = blockIdx.x, lane = threadIdx.x, m = p.lex.k;
+    const uint32_t q = wi / p.P, part = wi - q * p.P;
+    const uint32_t lb = p.bounds[2 * (size_t)q], ub = p.bounds[2 * (size_t)q + 1];
+    uint32_t begin, end32;
+    ss::lex::complete_part(lb, ub, p.P, part, &begin, &end32);
+    // (positions as 64-bit values: begin + 3 and pos + 256 may pass 2^32 in a lexicon of nearly 2^32 terms)
+    uint64_t pos = begin;
+    const uint64_t end = end32;
+    CompleteList list;
+    uint64_t al = (pos + 3) & ~3ull;                      // the ragged head: up to the first position that is a multiple of 4
+    if (al > end) al = end;
+    if (pos < al) {
+        const uint64_t x = pos + lane;
+        list.offer(x < al ? complete_key(p.ofreq[x], (uint32_t)x, p.min_freq) : LX_INF_A, m, lane);
+        pos = al;
+    }
+    for (; pos + 256 <= end; pos += 256) {                // 1 KiB per step: lane l holds positions pos + 4 l .. pos + 4 l + 3
+        const uint32_t x = (uint32_t)pos + 4u * lane;
+        const uint4 f = *reinterpret_cast<const uint4*>(p.ofreq + pos + 4u * lane);
+        // the lane's largest freq at its first position is a lower bound of its four keys
+        const uint32_t fmax = max(max(f.x, f.y), max(f.z, f.w));
+        if (!__any(complete_key(fmax, x, p.min_freq) < list.thr)) continue;
+        list.offer(complete_key(f.x, x, p.min_freq), m, lane);
+        list.offer(complete_key(f.y, x + 1u, p.min_freq), m, lane);
+        list.offer(complete_key(f.z, x + 2u, p.min_freq), m, lane);
+        list.offer(complete_key(f.w, x + 3u, p.min_freq), m, lane);
+    }
+    for (; pos < end; pos += 64) {                        // the tail: fewer than 256 positions
+        const uint64_t x = pos + lane;
+        list.offer(x < end ? complete_key(p.ofreq[x], (uint32_t)x, p.min_freq) : LX_INF_A, m, lane);
+    }
+    if (lane < m) p.part_key[(size_t)wi * m + lane] = list.best;
+}
+
+__global__ __launch_bounds__(LX_TPB) void k_lexicon_complete_merge(CompleteParams p) {
+    const uint32_t q = blockIdx.x, lane = threadIdx.x, m = p.lex.k;
+    const uint64_t* keys = p.part_key + (size_t)q * p.P * m;
+    const uint32_t n = p.P * m;                           // (at most 256 * 64)
+    CompleteList list;
+    for (uint32_t e = 0; e < n; e += 64) list.offer(e + lane < n ? keys[e + lane] : LX_INF_A, m, lane);
+    const bool keep = lane < m && list.best != LX_INF_A;
+    const uint64_t kept = __ballot(keep);
+    if (keep) {
+        p.lex.terms_out[(size_t)q * m + lane] = p.lex.order[(uint32_t)list.best];
+        if (p.freq_out) p.freq_out[(size_t)q * m + lane] = ~(uint32_t)(list.best >> 32);
+    }
+    if (lane == 0) {
+        p.lex.n_out[q] = (int32_t)__popcll((unsigned long long)kept);
+        if (p.lex.n_match_out) p.lex.n_match_out[q] = (uint64_t)(p.bounds[2 * (size_t)q + 1] - p.bounds[2 * (size_t)q]);
     }
 }
 
@@ -319,16 +440,23 @@ __global__ __launch_bounds__(LX_TPB) void k_lexicon_merge(SuggestParams p) {
 int32_t upload_freq(ss_lexicon* lx, const uint32_t* freq) {
     ss_ctx* ctx = lx->ctx;
     hipStream_t st = ctx->stream;
-    if (!lx->n_grouped) return SS_OK;
+    if (!lx->n_terms) return SS_OK;
     if (!freq) {
-        SS_HIP(ctx, hipMemsetAsync(lx->d_gfreq.p, 0, (size_t)lx->n_grouped * sizeof(uint32_t), st));
+        if (lx->n_grouped) SS_HIP(ctx, hipMemsetAsync(lx->d_gfreq.p, 0, (size_t)lx->n_grouped * sizeof(uint32_t), st));
+        SS_HIP(ctx, hipMemsetAsync(lx->d_ofreq.p, 0, (size_t)lx->n_terms * sizeof(uint32_t), st));
         return SS_OK;
     }
     ss::DevBuf<uint32_t> tmp;
     SS_HIP(ctx, tmp.alloc((size_t)lx->n_terms));
     SS_HIP(ctx, hipMemcpyAsync(tmp.p, freq, (size_t)lx->n_terms * sizeof(uint32_t), hipMemcpyDefault, st));
-    hipLaunchKernelGGL(k_lexicon_gather_freq, dim3(ss::div_up(lx->n_grouped, 256)), dim3(256), 0, st, lx->d_gterm.p, tmp.p, lx->d_gfreq.p,
-                       lx->n_grouped);
+    if (lx->n_grouped) {
+        hipLaunchKernelGGL(k_lexicon_gather_freq, dim3(ss::div_up(lx->n_grouped, 256)), dim3(256), 0, st, lx->d_gterm.p, tmp.p, lx->d_gfreq.p,
+                           lx->n_grouped);
+        SS_HIP(ctx, hipGetLastError());
+    }
+    // ... and in sort order, for the completions: the same gather with the sort order as its index
+    hipLaunchKernelGGL(k_lexicon_gather_freq, dim3(ss::div_up((uint32_t)lx->n_terms, 256)), dim3(256), 0, st, lx->d_order.p, tmp.p,
+                       lx->d_ofreq.p, (uint32_t)lx->n_terms);
     SS_HIP(ctx, hipGetLastError());
     SS_HIP(ctx, hipStreamSynchronize(st));                // the caller's array has been read, and tmp goes
     return SS_OK;
@@ -370,6 +498,7 @@ int32_t create_impl(ss_ctx* ctx, uint64_t n_terms, const uint64_t* word_ptr, con
     if (e == hipSuccess) e = up(lx->d_gterm, grp.gterm);
     if (e == hipSuccess) e = up(lx->d_gwords, grp.gwords);
     if (e == hipSuccess) e = lx->d_gfreq.alloc(grp.gterm.size());
+    if (e == hipSuccess) e = lx->d_ofreq.alloc(order.size());
     if (e == hipSuccess) e = lx->d_start.alloc(N_STARTS);
     if (e == hipSuccess) e = lx->d_base.alloc(N_STARTS);
     if (e == hipSuccess) e = hipMemcpyAsync(lx->d_start.p, grp.start, sizeof(grp.start), hipMemcpyHostToDevice, st);
@@ -378,7 +507,7 @@ int32_t create_impl(ss_ctx* ctx, uint64_t n_terms, const uint64_t* word_ptr, con
     int32_t rc = SS_OK;
     if (e != hipSuccess) rc = ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "ss_lexicon_create: %s", hipGetErrorString(e));
     if (rc == SS_OK) rc = upload_freq(lx, freq);
-    if (rc == SS_OK && !freq && lx->n_grouped) {
+    if (rc == SS_OK && !freq && lx->n_terms) {
         if (hipStreamSynchronize(st) != hipSuccess) rc = ctx->fail(SS_ERR_HIP, "ss_lexicon_create: wait failed");
     }
     if (rc != SS_OK) {
@@ -465,6 +594,89 @@ int32_t prefix_impl(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr, const ui
             const size_t n = (size_t)std::min(std::max(h_n[q], 0), k);
             if (n) std::memcpy(terms_out + q * (size_t)k, h_t.data() + q * (size_t)k, n * sizeof(uint32_t));
         }
+    return SS_OK;
+}
+
+int32_t complete_impl(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr, const uint8_t* p_bytes, uint32_t min_freq, int32_t m,
+                      uint32_t* terms_out, uint32_t* freq_out, int32_t* n_out, uint64_t* n_match_out) {
+    ss_ctx* ctx = lx->ctx;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    // ---- the checks: nothing is enqueued and no output is touched before the last of them has passed
+    if (n_q < 0 || !p_ptr || !terms_out || !n_out) return ctx->fail(SS_ERR_INVALID, "ss_lexicon_complete: NULL argument or n_q < 0");
+    if (m < 1) return ctx->fail(SS_ERR_INVALID, "ss_lexicon_complete: m = %d, must be >= 1", m);
+    if (m > SS_MAX_COMPLETE) return ctx->fail(SS_ERR_UNSUPPORTED, "ss_lexicon_complete: m = %d exceeds SS_MAX_COMPLETE = %d", m, SS_MAX_COMPLETE);
+    if (n_q == 0) return SS_OK;
+    SS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t nq = (size_t)n_q;
+    std::vector<uint32_t> h_ptr;
+    std::vector<uint8_t> h_bytes;
+    SS_TRY(fetch_words(ctx, "ss_lexicon_complete", "p", n_q, p_ptr, p_bytes, h_ptr, h_bytes));
+    // parts per prefix from n_q alone: the scratch is n_q * P * m keys (at most about COMPLETE_WAVES * m unless P is forced)
+    const uint32_t P = ss::lex::complete_parts((uint64_t)n_q, ctx->opt("lexicon.complete_parts", 0));
+    if (nq * P >= (1ull << 31))
+        return ctx->fail(SS_ERR_UNSUPPORTED, "ss_lexicon_complete: the batch makes 2^31 (prefix, part) pairs or more: lower \"lexicon.complete_parts\" or split it");
+    const bool dev_t = ss::on_device(terms_out), dev_n = ss::on_device(n_out), dev_f = !freq_out || ss::on_device(freq_out),
+               dev_m = !n_match_out || ss::on_device(n_match_out);
+    // ---- the call's table in the pinned block of the next turn, as ss_lexicon_prefix lays it out: {offset, length} [n_q] | prefix bytes
+    LexTurn& turn = lx->turn[lx->next_turn];
+    SS_HIP(ctx, turn.ev.wait());                          // the call LX_TURNS calls ago has read this turn's blocks
+    const size_t q_words = 2 * nq + (h_bytes.size() + 3) / 4;
+    SS_HIP(ctx, turn.h_q.ensure(q_words * sizeof(uint32_t)));
+    uint32_t* const hq = turn.h_q.as<uint32_t>();
+    for (size_t q = 0; q < nq; q++) {
+        hq[2 * q] = h_ptr[q] - h_ptr[0];
+        hq[2 * q + 1] = h_ptr[q + 1] - h_ptr[q];
+    }
+    if (!h_bytes.empty()) std::memcpy(hq + 2 * nq, h_bytes.data(), h_bytes.size());
+    SS_HIP(ctx, ensure(turn.d_q, q_words));
+    SS_HIP(ctx, ensure(lx->d_cpl_key, nq * P * (size_t)m));
+    SS_HIP(ctx, ensure(lx->d_cpl_bounds, 2 * nq));
+    if (!dev_t) SS_HIP(ctx, ensure(lx->d_out_terms, nq * (size_t)m));
+    if (!dev_f) SS_HIP(ctx, ensure(lx->d_out_freq, nq * (size_t)m));
+    if (!dev_n) SS_HIP(ctx, ensure(lx->d_out_n, nq));
+    if (!dev_m) SS_HIP(ctx, ensure(lx->d_out_match, nq));
+    lx->next_turn = (lx->next_turn + 1) % LX_TURNS;
+    // ---- the pipeline
+    SS_HIP(ctx, hipMemcpyAsync(turn.d_q.p, hq, q_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CompleteParams p{};
+    p.lex.off = lx->d_off.p; p.lex.bytes = lx->d_bytes.p; p.lex.order = lx->d_order.p;
+    p.lex.q = turn.d_q.p;
+    p.lex.n_terms = (uint32_t)lx->n_terms; p.lex.n_q = (uint32_t)n_q; p.lex.k = (uint32_t)m;
+    p.lex.terms_out = dev_t ? terms_out : lx->d_out_terms.p;
+    p.lex.n_out = dev_n ? n_out : lx->d_out_n.p;
+    p.lex.n_match_out = !n_match_out ? nullptr : dev_m ? n_match_out : lx->d_out_match.p;
+    p.ofreq = lx->d_ofreq.p;
+    p.bounds = lx->d_cpl_bounds.p;
+    p.part_key = lx->d_cpl_key.p;
+    p.freq_out = !freq_out ? nullptr : dev_f ? freq_out : lx->d_out_freq.p;
+    p.P = P; p.min_freq = min_freq;
+    const dim3 waves((unsigned)(nq * P)), rows((unsigned)n_q), block(LX_TPB);
+    hipLaunchKernelGGL(k_lexicon_complete_bounds, rows, block, 0, st, p);
+    SS_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lexicon_complete, waves, block, 0, st, p);
+    SS_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lexicon_complete_merge, rows, block, 0, st, p);
+    SS_HIP(ctx, hipGetLastError());
+    SS_HIP(ctx, turn.ev.record(st));                      // the turn's pinned block and its device copy are read until here
+    if (dev_t && dev_n && dev_f && dev_m) return SS_OK;   // ordered on the ctx stream; nothing comes back, nothing is waited for
+    // ---- staged: wait; host rows get exactly the entries the kernel wrote
+    std::vector<int32_t> h_n(nq);
+    std::vector<uint32_t> h_t(dev_t ? 0 : nq * (size_t)m), h_f(dev_f ? 0 : nq * (size_t)m);
+    std::vector<uint64_t> h_m(dev_m ? 0 : nq);
+    SS_HIP(ctx, hipMemcpyAsync(h_n.data(), p.lex.n_out, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (!dev_t) SS_HIP(ctx, hipMemcpyAsync(h_t.data(), p.lex.terms_out, h_t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!dev_f) SS_HIP(ctx, hipMemcpyAsync(h_f.data(), p.freq_out, h_f.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!dev_m) SS_HIP(ctx, hipMemcpyAsync(h_m.data(), p.lex.n_match_out, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(ctx, hipStreamSynchronize(st));
+    if (!dev_n) std::memcpy(n_out, h_n.data(), nq * sizeof(int32_t));
+    if (!dev_m) std::memcpy(n_match_out, h_m.data(), nq * sizeof(uint64_t));
+    for (size_t q = 0; q < nq; q++) {
+        const size_t n = (size_t)std::min(std::max(h_n[q], 0), m);
+        if (!n) continue;
+        if (!dev_t) std::memcpy(terms_out + q * (size_t)m, h_t.data() + q * (size_t)m, n * sizeof(uint32_t));
+        if (!dev_f) std::memcpy(freq_out + q * (size_t)m, h_f.data() + q * (size_t)m, n * sizeof(uint32_t));
+    }
     return SS_OK;
 }
 
@@ -624,6 +836,16 @@ int32_t ss_lexicon_prefix(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr, co
         return prefix_impl(lx, n_q, p_ptr, p_bytes, first, k, terms_out, n_out, n_match_out);
     } catch (const std::bad_alloc&) {
         return lx->ctx->fail(SS_ERR_OOM, "ss_lexicon_prefix: host allocation failed");
+    }
+}
+
+int32_t ss_lexicon_complete(ss_lexicon* lx, int32_t n_q, const uint32_t* p_ptr, const uint8_t* p_bytes, uint32_t min_freq, int32_t m,
+                            uint32_t* terms_out, uint32_t* freq_out, int32_t* n_out, uint64_t* n_match_out) {
+    if (!lx) return SS_ERR_INVALID;
+    try {
+        return complete_impl(lx, n_q, p_ptr, p_bytes, min_freq, m, terms_out, freq_out, n_out, n_match_out);
+    } catch (const std::bad_alloc&) {
+        return lx->ctx->fail(SS_ERR_OOM, "ss_lexicon_complete: host allocation failed");
     }
 }
 

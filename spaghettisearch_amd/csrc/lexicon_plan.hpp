@@ -91,5 +91,31 @@ inline void suggest_range(const uint32_t* start, uint64_t len, uint32_t max_dist
 }
 inline uint64_t n_chunks(uint32_t lo, uint32_t hi, uint32_t chunk) { return ((uint64_t)(hi - lo) + chunk - 1) / chunk; }
 
+// ---- completions (ss_lexicon_complete): the range [lb, ub) of sort positions of every prefix of a call is cut into the same number
+// P of near-equal parts, one wave each.  P comes from the number of prefixes alone (the ranges are known on the device only): about
+// COMPLETE_WAVES waves per call, so 1024 prefixes make a few thousand waves, and at most DEFAULT_COMPLETE_PARTS parts for a few
+// prefixes: more parts stream a long range faster but make the merge of a short one slower (measured: DESIGN.md K4k).
+#if defined(__HIPCC__)
+#define SS_LEX_HD __host__ __device__
+#else
+#define SS_LEX_HD
+#endif
+constexpr uint32_t MAX_COMPLETE_PARTS = 256;
+constexpr uint32_t DEFAULT_COMPLETE_PARTS = 64;
+constexpr uint64_t COMPLETE_WAVES = 4096;
+// forced = option "lexicon.complete_parts": a value in 1 .. MAX_COMPLETE_PARTS is taken as it is, any other means "from n_q"
+SS_LEX_HD inline uint32_t complete_parts(uint64_t n_q, int64_t forced) {
+    if (forced >= 1 && forced <= (int64_t)MAX_COMPLETE_PARTS) return (uint32_t)forced;
+    const uint64_t p = n_q ? COMPLETE_WAVES / n_q : DEFAULT_COMPLETE_PARTS;
+    return p < 1 ? 1u : p > DEFAULT_COMPLETE_PARTS ? DEFAULT_COMPLETE_PARTS : (uint32_t)p;
+}
+// part `part` of P covers positions [*begin, *end) of [lb, ub): the parts tile the range in order, their lengths differ by at most
+// one (len < 2^32 and part <= 256: the products stay below 2^41)
+SS_LEX_HD inline void complete_part(uint32_t lb, uint32_t ub, uint32_t P, uint32_t part, uint32_t* begin, uint32_t* end) {
+    const uint64_t len = ub - lb;
+    *begin = lb + (uint32_t)(len * part / P);
+    *end = lb + (uint32_t)(len * (part + 1) / P);
+}
+
 }  // namespace lex
 }  // namespace ss

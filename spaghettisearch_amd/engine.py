@@ -1632,6 +1632,32 @@ class Lexicon:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return terms, n_out, n_match
 
+    def complete(self, prefixes, m: int = 10, min_freq: int = 1, out=None):
+        """ss_lexicon_complete: per prefix the m most frequent of the words that start with it and whose freq is at least min_freq,
+        ordered by freq descending, then by sort position -> (terms uint32 [n_q][m], freq uint32 [n_q][m], n_out int32 [n_q],
+        n_match uint64 [n_q]: the words with the prefix, whatever their freq); entries past n_out[q] keep what the arrays held (zeros
+        here).  out = (terms, freq | None, n_out, n_match | None): the caller's arrays (numpy, or torch int32 / int32 / int32 / int64
+        device tensors); with device tensors the library only enqueues."""
+        p_ptr, p_bytes = _flatten_words(prefixes, "uint32")
+        n_q = int(p_ptr.shape[0]) - 1
+        count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+        if out is not None:
+            terms, freq, n_out, n_match = _as(out[0], "uint32"), _as(out[1], "uint32"), _as(out[2], "int32"), _as(out[3], "uint64")
+            if (count(terms) < n_q * m or (freq is not None and count(freq) < n_q * m) or count(n_out) < n_q
+                    or (n_match is not None and count(n_match) < n_q)):
+                raise ValueError("output buffers too small")
+        else:
+            terms = np.zeros((n_q, max(int(m), 0)), dtype=np.uint32)
+            freq = np.zeros((n_q, max(int(m), 0)), dtype=np.uint32)
+            n_out = np.zeros(n_q, dtype=np.int32)
+            n_match = np.zeros(n_q, dtype=np.uint64)
+        self.ctx.ready(p_ptr, p_bytes, terms, freq, n_out, n_match)
+        check(self.ctx.lib.ss_lexicon_complete(self.h, n_q, _ptr(p_ptr), _ptr(p_bytes), int(min_freq), int(m), _ptr(terms), _ptr(freq),
+                                               _ptr(n_out), _ptr(n_match)), self.ctx.h)
+        if out is not None and _is_torch(terms) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return terms, freq, n_out, n_match
+
     def suggest(self, words, max_dist: int = 2, m: int = 10, min_freq: int = 1, out=None):
         """ss_lexicon_suggest: per query word the m known words within max_dist edits (optimal string alignment over bytes: insert,
         delete, substitute, swap of adjacent bytes) whose freq is at least min_freq, ordered by distance, then freq descending, then

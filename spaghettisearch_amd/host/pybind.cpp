@@ -47,6 +47,9 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Words", &retrieval::WordSuggestion::Words)
         .def_readonly("Distances", &retrieval::WordSuggestion::Distances)
         .def_readonly("Freqs", &retrieval::WordSuggestion::Freqs);
+    py::class_<retrieval::WordCompletion>(m, "WordCompletion")
+        .def_readonly("Word", &retrieval::WordCompletion::Word)
+        .def_readonly("Freq", &retrieval::WordCompletion::Freq);
     py::class_<retrieval::ResultExplanation>(m, "ResultExplanation")
         .def_readonly("TitleWords", &retrieval::ResultExplanation::TitleWords)
         .def_readonly("BodyWords", &retrieval::ResultExplanation::BodyWords)
@@ -297,6 +300,8 @@ PYBIND11_MODULE(_host, m) {
             return out;
         }, py::arg("pre"), py::arg("first") = 0, py::arg("k") = 50)
         .def("SuggestWords", &retrieval::DeviceIndex::SuggestWords, py::arg("query"), py::arg("max_dist") = 2, py::arg("m") = 5)
+        .def("Complete", &retrieval::DeviceIndex::Complete, py::arg("pre"), py::arg("m") = 10, py::arg("min_freq") = 1)
+        .def("SetPrefixQueries", &retrieval::DeviceIndex::SetPrefixQueries, py::arg("expansions"))
         .def("LoadTopics", [as_dbs](retrieval::DeviceIndex& di, std::vector<db::MemDB*> forw, std::vector<db::MemDB*> inv) {
             db::Context ctx;
             auto f = as_dbs(forw), i = as_dbs(inv);

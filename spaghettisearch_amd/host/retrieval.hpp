@@ -48,6 +48,13 @@ struct WordSuggestion {
     std::vector<uint32_t> Freqs;             // title + body list length of each, as the lexicon holds it
 };
 
+// One completion of what a user has typed (DeviceIndex::Complete; no reference counterpart): a word of the vocabulary that starts with
+// the prefix and its frequency, rows ordered as ss_lexicon_complete orders them (frequency descending, then the word, then term id).
+struct WordCompletion {
+    std::string Word;
+    uint32_t Freq = 0;                       // title + body list length, as the lexicon holds it
+};
+
 // Where a row's snippet should start (DeviceIndex::BestPassages; no reference counterpart, getSummary anchors at the first matched
 // word): the window of `width` body positions that holds most of the query's distinct words, then most occurrences, then starts
 // earliest.  Start / Last: the first and the last occurrence inside it (the caller cuts the cached words at [Start, Start + width));
@@ -212,6 +219,48 @@ inline QueryOperators parseQueryOperators(const std::string& query,
     return out;
 }
 
+// Prefix tokens (no reference counterpart; DeviceIndex::SetPrefixQueries, default off).  Outside quoted phrases (paired as above), a
+// whitespace-separated token that ends in '*' with at least one byte before the star is a prefix token: it is taken out of `query`,
+// the string the tokeniser sees, and its bytes without the star, ASCII lower-cased and NOT stemmed, go to `prefixes` in the order they
+// stand.  Only the trailing star counts ("a*b" is a plain token, "*" alone too).  skip_operators (the strings of SetQueryOperators):
+// a token parseQueryOperators reads as "+word" / "-word" is no prefix token, its star is left to the tokeniser as before.
+struct PrefixTokens {
+    std::string query;
+    std::vector<std::string> prefixes;
+};
+inline PrefixTokens parsePrefixTokens(const std::string& query, bool skip_operators,
+                                      const std::function<std::vector<std::string>(const std::string&)>& laundry = defaultLaundry) {
+    PrefixTokens out;
+    std::vector<size_t> quotes;
+    for (size_t i = 0; i < query.size(); i++)
+        if (query[i] == '"') quotes.push_back(i);
+    if (quotes.size() % 2) quotes.pop_back();
+    size_t qi = 0, i = 0;
+    while (i < query.size()) {
+        if (qi < quotes.size() && i == quotes[qi]) {     // a quoted phrase: copied as it is
+            out.query.append(query, i, quotes[qi + 1] + 1 - i);
+            i = quotes[qi + 1] + 1;
+            qi += 2;
+            continue;
+        }
+        if (std::isspace((unsigned char)query[i])) { out.query += query[i++]; continue; }
+        size_t j = i;
+        while (j < query.size() && !std::isspace((unsigned char)query[j]) && !(qi < quotes.size() && j == quotes[qi])) j++;
+        const std::string tok = query.substr(i, j - i);
+        const bool op = skip_operators && tok.size() > 1 && (tok[0] == '+' || tok[0] == '-') && !laundry(tok.substr(1, 1)).empty();
+        if (!op && tok.size() > 1 && tok.back() == '*') {
+            std::string pre = tok.substr(0, tok.size() - 1);
+            for (auto& c : pre)
+                if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+            out.prefixes.push_back(pre);
+        } else {
+            out.query += tok;
+        }
+        i = j;
+    }
+    return out;
+}
+
 // computeTopicProbs, retrieval/main_retrieve.go:106-159 — DISABLED in the reference (the call at :43 is commented out and
 // :87 passes a nil map, so sqd = 0); restated so that the PageRank blend of get_metadata.go:39-42,69 can be switched on.
 //   queryTokenised: md5-hex word hashes as Retrieve makes them (:33-36);
@@ -354,6 +403,7 @@ public:
     std::map<std::string, std::vector<std::string>> mask_sets;
     std::map<std::string, int32_t> mask_index;      // name -> the scorer's mask id
     bool query_operators = false;                   // SetQueryOperators: "+word" / "-word" in RetrieveBatch's query strings
+    int prefix_expansions = 0;                      // SetPrefixQueries: "word*" in query strings stands for its most frequent completions (0: off)
     bool similar_pages = false;                     // SetSimilarPages: the body table keeps its doc-major view (8 B per posting + 8 B per doc)
     bool doc_view_built = false;                    // the body table holds a view that this object built and nothing has freed since
     // Site keys for collapsed result pages (SetDocGroups): doc hash -> key string, kept by hash like the allow-lists and registered
@@ -734,6 +784,33 @@ public:
             }
         return out;
     }
+    // "Results while you type", the word half: the m most frequent words of the vocabulary that start with `pre` and whose frequency is
+    // at least min_freq, best first (ss_lexicon_complete).  `pre` is taken byte for byte: the caller lower-cases it as it sees fit.
+    std::vector<WordCompletion> Complete(const std::string& pre, int m = 10, uint32_t min_freq = 1) {
+        using namespace spaghetti;
+        if (!lexicon) throw std::runtime_error("Complete: no lexicon (SetLexicon)");
+        const uint32_t p_ptr[2] = {0u, (uint32_t)pre.size()};
+        std::vector<uint32_t> ids((size_t)std::max(m, 1)), freq((size_t)std::max(m, 1));
+        int32_t n = 0;
+        check(ss_lexicon_complete(lexicon, 1, p_ptr, reinterpret_cast<const uint8_t*>(pre.data()), min_freq, m, ids.data(), freq.data(), &n, nullptr),
+              "ss_lexicon_complete");
+        std::vector<WordCompletion> out;
+        for (int32_t i = 0; i < n; i++) out.push_back(WordCompletion{lex_words[ids[i]], freq[i]});
+        return out;
+    }
+    // ... and the query half (default 0: off, every string is read exactly as before).  With 1 <= expansions <= 32, every entry point
+    // that tokenises query strings the way RetrieveBatch does reads a token written `word*` outside quoted phrases as a prefix term:
+    // the token leaves the string the tokeniser sees (as "-word" tokens do under SetQueryOperators), its bytes are lower-cased, NOT
+    // stemmed, and the `expansions` most frequent words that start with them (frequency at least 1) join the query as plain OR terms
+    // behind its words; a prefix without a completion counts as one unknown word.  The token adds 1 to the query's length, whatever
+    // it expands to, and a query is cut at SS_MAX_QUERY_TERMS terms.  The lexicon holds the words as the indexer stemmed them, so
+    // "runn*" does not find "run": a prefix is matched against stems.  Under SetQueryOperators "+word*" and "-word*" stay operator
+    // tokens.  Entry points that refuse query operators refuse this setting too; ExplainResults, BestPassages and SuggestWords read
+    // the string without it.  Needs SetLexicon (again after load()): a prefix token without a lexicon throws.
+    void SetPrefixQueries(int expansions) {
+        if (expansions < 0 || expansions > 32) throw std::runtime_error("SetPrefixQueries: expansions must be 0 (off) or 1 .. 32");
+        prefix_expansions = expansions;
+    }
     // Per row of `results` — the Rank_combined rows Retrieve / RetrieveBatch returned for `query` — the best body window of `width`
     // word positions (ss_best_passages).  The query is tokenised as ExplainResults does it.  A row whose DocHash the index does not
     // hold has no passage.  Changes nothing unless called.
@@ -1100,6 +1177,7 @@ public:
         if (queryVectors.size() != nq) throw std::runtime_error("HybridSearch: one query vector per query");
         if (!masks.empty() && masks.size() != nq) throw std::runtime_error("HybridSearch: one mask name per query");
         if (query_operators) throw std::runtime_error("HybridSearch: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("HybridSearch: prefix queries are not read here (SetPrefixQueries(0))");
         std::vector<int32_t> mask_id(nq, -1);
         for (size_t q = 0; q < masks.size(); q++) {
             if (masks[q].empty()) continue;
@@ -1440,7 +1518,36 @@ public:
             if (topicProbs) throw std::runtime_error("RetrieveBatch: explicit and live topic probabilities are exclusive");
             if (topic_names.empty()) throw std::runtime_error("RetrieveBatch: live topic probabilities need LoadTopics");
         }
-        for (std::string query : queries) {
+        // SetPrefixQueries: the "word*" tokens leave the strings, and all of them are completed by ONE ss_lexicon_complete call (the one
+        // place the mirror waits for the lexicon); expansion[e] = the term ids of prefix token e, best first
+        std::vector<std::string> cut;
+        std::vector<uint32_t> pre_ptr{0};                // prefix tokens of the queries before q
+        std::vector<std::vector<uint32_t>> expansion;
+        if (prefix_expansions > 0) {
+            std::vector<uint32_t> p_ptr{0};
+            std::string p_bytes;
+            for (auto& q : queries) {
+                PrefixTokens pt = parsePrefixTokens(q, query_operators, laundry);
+                cut.push_back(pt.query);
+                for (auto& pre : pt.prefixes) {
+                    p_bytes += pre;
+                    p_ptr.push_back((uint32_t)p_bytes.size());
+                }
+                pre_ptr.push_back((uint32_t)(p_ptr.size() - 1));
+            }
+            const size_t np = p_ptr.size() - 1, m = (size_t)prefix_expansions;
+            if (np) {
+                if (!lexicon) throw std::runtime_error("RetrieveBatch: prefix queries need the lexicon (SetLexicon)");
+                std::vector<uint32_t> ids(np * m);
+                std::vector<int32_t> n(np);
+                check(ss_lexicon_complete(lexicon, (int32_t)np, p_ptr.data(), reinterpret_cast<const uint8_t*>(p_bytes.data()), 1u,
+                                          prefix_expansions, ids.data(), nullptr, n.data(), nullptr), "ss_lexicon_complete");
+                expansion.resize(np);
+                for (size_t e = 0; e < np; e++) expansion[e].assign(ids.begin() + e * m, ids.begin() + e * m + n[e]);
+            }
+        }
+        for (size_t qn = 0; qn < queries.size(); qn++) {
+            std::string query = cut.empty() ? queries[qn] : cut[qn];
             // main_retrieve.go:17-36
             const std::vector<std::string> phrases = getPhrase(query);
             for (auto& ph : phrases) {
@@ -1457,6 +1564,16 @@ public:
                 t.q_terms.push_back(it == terms.id.end() ? SS_UNKNOWN_TERM : it->second);   // ErrKeyNotFound tolerated (:193,:218)
             }
             if (live_topic_probs) live.push_back(liveTopicProbs(hashed));
+            // the completions of the query's prefix tokens, as plain OR terms behind its words: in the order the tokens stand, each
+            // list best first, a token without a completion as one unknown word; what would take the query past SS_MAX_QUERY_TERMS
+            // is dropped
+            const size_t n_pre = cut.empty() ? 0 : pre_ptr[qn + 1] - pre_ptr[qn];
+            for (size_t e = 0; e < n_pre; e++) {
+                const std::vector<uint32_t>& ids = expansion[pre_ptr[qn] + e];
+                const size_t room = (size_t)SS_MAX_QUERY_TERMS - std::min<size_t>(SS_MAX_QUERY_TERMS, t.q_terms.size() - t.q_ptr.back());
+                if (ids.empty() && room) t.q_terms.push_back(SS_UNKNOWN_TERM);
+                t.q_terms.insert(t.q_terms.end(), ids.begin(), ids.begin() + std::min(room, ids.size()));
+            }
             t.q_ptr.push_back((uint32_t)t.q_terms.size());
             // all quoted phrases form ONE phrase (main_retrieve.go:26), matched on the device (retrieval/phrase.go)
             for (auto& tok : phraseTokenised) {
@@ -1464,7 +1581,7 @@ public:
                 t.p_terms.push_back(it == terms.id.end() ? SS_UNKNOWN_TERM : it->second);
             }
             t.p_ptr.push_back((uint32_t)t.p_terms.size());
-            t.q_len.push_back((int32_t)(queryTokenised.size() + phraseTokenised.size()));   // :90
+            t.q_len.push_back((int32_t)(queryTokenised.size() + phraseTokenised.size() + n_pre));   // :90 (a prefix token is one typed word)
         }
         t.nq = (int)queries.size();
         const size_t K = categories.size();
@@ -1571,6 +1688,7 @@ public:
         using namespace spaghetti;
         if (!has_doc_groups) throw std::runtime_error("RetrieveBatchCollapsed: no site keys (SetDocGroups)");
         if (query_operators) throw std::runtime_error("RetrieveBatchCollapsed: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("RetrieveBatchCollapsed: prefix queries are not read here (SetPrefixQueries(0))");
         const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
         const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
         std::vector<ss_hit> page(nq * kk);
@@ -1804,6 +1922,7 @@ public:
         using namespace spaghetti;
         if (!has_doc_fields) throw std::runtime_error("SortByField: no doc fields (SetDocFields)");
         if (query_operators) throw std::runtime_error("SortByField: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("SortByField: prefix queries are not read here (SetPrefixQueries(0))");
         const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
         const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
         std::vector<ss_hit> rows(nq * (size_t)std::max(k_window, 1)), page(nq * kk);
@@ -1831,6 +1950,7 @@ public:
         using namespace spaghetti;
         if (!signatures_built) throw std::runtime_error("RetrieveBatchDeduped: no signatures (SetNearDuplicates)");
         if (query_operators) throw std::runtime_error("RetrieveBatchDeduped: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("RetrieveBatchDeduped: prefix queries are not read here (SetPrefixQueries(0))");
         const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
         const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
         std::vector<ss_hit> page(nq * kk), rows(nq * (size_t)std::max(k_window, 1));
