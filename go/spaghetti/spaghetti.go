@@ -746,6 +746,97 @@ func (s *Scorer) BestPassages(qPtr, qTerms []uint32, hits [][]Hit, width int) ([
 	return out, nil
 }
 
+// Proximity is the smallest body span of one hit that holds every query term the doc has at all (ss_proximity): Start and End are
+// the position values of its first and last occurrence, Present the distinct query terms the doc has and Occurrences the occurrences
+// inside the span; bit i of TokenMask: the query's i-th token's term is present.  Present == 0: the doc holds none of the terms.
+type Proximity struct {
+	Start       float32
+	End         float32
+	Present     uint32
+	Occurrences uint32
+	TokenMask   uint64
+}
+
+// HitProximity answers "how close do the query's words come in each result?" (ss_hit_proximity) for rows any scoring call returned.
+// Only the hits' Doc is read.  Unknown terms and doc ids the index does not hold have no occurrences.
+func (s *Scorer) HitProximity(qPtr, qTerms []uint32, hits [][]Hit) ([][]Proximity, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 || len(hits) != nq {
+		return nil, nil
+	}
+	k := 1
+	for q := 0; q < nq; q++ {
+		if len(hits[q]) > k {
+			k = len(hits[q])
+		}
+	}
+	raw := make([]C.ss_hit, nq*k)
+	nHits := make([]int32, nq)
+	for q := 0; q < nq; q++ {
+		nHits[q] = int32(len(hits[q]))
+		for j, h := range hits[q] {
+			raw[q*k+j].doc = C.uint32_t(h.Doc)
+		}
+	}
+	m := make([]C.ss_proximity, nq*k)
+	rc := C.ss_hit_proximity(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])),
+		i32p(nHits), (*C.ss_proximity)(unsafe.Pointer(&m[0])))
+	if err := statusErr(s.ctx, rc, "ss_hit_proximity"); err != nil {
+		return nil, err
+	}
+	out := make([][]Proximity, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]Proximity, len(hits[q]))
+		for j := range out[q] {
+			e := m[q*k+j]
+			out[q][j] = Proximity{float32(e.start), float32(e.end), uint32(e.n_present), uint32(e.n_occ), uint64(e.token_mask)}
+		}
+	}
+	return out, nil
+}
+
+// ProximityPage is one page of a query's results re-ranked by term proximity: Scores[i] = wRank * Final + wProx * bonus of Hits[i],
+// Spans[i] its Proximity.
+type ProximityPage struct {
+	Hits   []Hit
+	Scores []float64
+	Spans  []Proximity
+}
+
+// ScoreTopKProximity = ScoreTopKMasked without phrases at k = kWindow, then the window sorted stably by wRank * Final + wProx * bonus,
+// descending, and page [first, first+k) of it, in one library call: the window never leaves the device (ss_score_topk_proximity).
+// bonus: how close the query's terms come in the doc's body, times the share of the query's terms the doc has.  maskID nil = none.
+func (s *Scorer) ScoreTopKProximity(qPtr, qTerms []uint32, queryLen []int32, topicProbs []float64, maskID []int32, kWindow int,
+	wRank, wProx float64, first, k int) ([]ProximityPage, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, scores, m := make([]int32, nq), make([]float64, nq*kk), make([]C.ss_proximity, nq*kk)
+	rc := C.ss_score_topk_proximity(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(queryLen), f64p(topicProbs), i32p(maskID),
+		C.int32_t(kWindow), C.double(wRank), C.double(wProx), C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])),
+		i32p(nHits), f64p(scores), (*C.ss_proximity)(unsafe.Pointer(&m[0])))
+	if err := statusErr(s.ctx, rc, "ss_score_topk_proximity"); err != nil {
+		return nil, err
+	}
+	out := make([]ProximityPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q] = ProximityPage{make([]Hit, n), append([]float64(nil), scores[q*kk:q*kk+n]...), make([]Proximity, n)}
+		for i := 0; i < n; i++ {
+			r, e := raw[q*kk+i], m[q*kk+i]
+			out[q].Hits[i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+			out[q].Spans[i] = Proximity{float32(e.start), float32(e.end), uint32(e.n_present), uint32(e.n_occ), uint64(e.token_mask)}
+		}
+	}
+	return out, nil
+}
+
 // NoGroup in a group table: the doc is never collapsed with anything (SS_NO_GROUP).
 const NoGroup = uint32(C.SS_NO_GROUP)
 

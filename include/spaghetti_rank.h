@@ -62,7 +62,9 @@ extern "C" {
  * SS_MAX_FACET_BUCKETS and ss_facet_counts (how many docs a query matches: in all, per registered allow-list, per value bucket);
  * ss_field_topk (the exact top k of ALL docs a query matches, ordered by a doc field);
  * ss_group_count, ss_scorer_group_values and ss_top_groups (the m groups of the doc -> group table that hold most of a query's matches);
- * SS_MAX_COMPLETE and ss_lexicon_complete (the m most frequent words that start with a prefix: word completions). */
+ * SS_MAX_COMPLETE and ss_lexicon_complete (the m most frequent words that start with a prefix: word completions);
+ * ss_proximity, ss_hit_proximity, ss_rerank_hits_by_proximity and ss_score_topk_proximity (per result row the smallest body span that
+ * holds every query term the doc has, and a window re-ranked by it). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -627,6 +629,84 @@ typedef struct ss_passage {
 int32_t ss_best_passages(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
                          int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
                          int32_t width, ss_passage* out /*[n_q][k]*/);
+
+/* Term proximity: per hit the smallest body span that holds every query term the doc has at all, and a window re-ranked by it.  The
+ * reference's FinalRank (retrieval/get_metadata.go:57-69) is a pure OR: a page where the query stands as neighbouring words ranks like
+ * one that holds the words in unrelated paragraphs.  ss_best_passages answers another question (a window of fixed width, for a snippet)
+ * and re-orders nothing.  These calls read the same resident material, the body table's positional postings (ss_index_set_positions),
+ * and need no other per-doc data.  No reference counterpart.
+ * ss_hit_proximity.  Defined bit for bit.  Entry (q, j) = out[q * k + j] describes doc d = hits[q * k + j].doc; of a hit only .doc is read,
+ * and n_hits[q].
+ *   Occurrences.  As in ss_best_passages, except that +inf is none: for each DISTINCT term id t among the query's tokens, each value v
+ *                 of the body position list of posting (t, d) with v >= 0 and v < +inf is one occurrence (v, t); NaN, negative values
+ *                 (the -100 marker) and +inf are none.  Equal values count separately; lists need not be sorted; both zeros are
+ *                 equal.  There are no occurrences when the term id is >= n_terms (SS_UNKNOWN_TERM included), d >= n_docs, the
+ *                 posting is missing or the body table has no positions: defined, not an error; no row, whatever it holds, makes the
+ *                 kernel read outside the tables.
+ *   Present.      P = the distinct term ids with at least one occurrence; n_present = |P|; token_mask bit i is set iff the term of the
+ *                 query's i-th token (token order as given) is in P: duplicate tokens get equal bits.
+ *   Span.         Of all pairs of occurrence values a <= b such that every term of P has an occurrence with value in [a, b]: the pair
+ *                 with the smallest (double)b - (double)a, as that float64 expression evaluates; of equal differences the one with the
+ *                 smallest a as a float value; for that a the smallest such b.  start = a, end = b, a zero as +0.0; n_occ = the
+ *                 occurrences with a <= v <= b (counted modulo 2^32).  With |P| = 1 the span is the smallest occurrence alone
+ *                 (start == end).
+ *   Written.      Every entry with j < n_hits[q] is written; n_present == 0 gives 24 zero bytes.  All other entries are left untouched.
+ * Checks, staging, host / device pointers and the clamping of a device n_hits: exactly those of ss_best_passages without `width`.  Docs
+ * with more position values under the query's terms than option "proximity.lds_events" (default 512, 1 .. 4096) are answered from
+ * global memory instead of the LDS: the same bytes, more slowly.
+ * ss_rerank_hits_by_proximity: a stable, paged re-rank in the family of ss_sort_hits_by_field and ss_rerank_hits_by_vector, so that
+ * score -> dedup -> collapse -> proximity -> explain -> passages stays on one stream.  Defined bit for bit:
+ *   Window.     As in ss_collapse_hits: hits[q * k_in .. q * k_in + n_hits[q]), in the order given.  Of a row .doc and .final are read;
+ *               given rows are trusted, as in ss_fuse_hits.
+ *   Score.      For a row with doc < n_docs let E be its ss_hit_proximity entry and T the number of distinct term ids among the
+ *               query's tokens (SS_UNKNOWN_TERM counts as one id).  Every operation is rounded once, nothing is contracted:
+ *                 sp    = (double)E.end - (double)E.start
+ *                 prox  = E.n_present < 2 ? 0.0 : (double)(E.n_present - 1) / max(sp, (double)(E.n_present - 1))     (1.0: neighbours)
+ *                 cover = T ? (double)E.n_present / (double)T : 0.0
+ *                 bonus = prox * cover
+ *                 score = w_rank * row.final + w_prox * bonus
+ *   Order.      Score descending by numeric comparison (-0.0 ties 0.0); equal scores stay in window order (the sort is stable; the
+ *               same doc twice is two rows); NaN scores come after every number, among themselves in window order; rows with
+ *               doc >= n_docs come LAST of all, in window order.
+ *   Output.     With the sorted rows S_0 .. S_{n-1}: hits_out[q * k + r] = the 40 bytes of S_{first + r} (_pad included) for
+ *               r < n_hits_out[q] = clamp(n - first, 0, k); scores_out[q * k + r] (nullable) = that row's score, a NaN as
+ *               0x7FF8000000000000, which a row with doc >= n_docs gets too; prox_out[q * k + r] (nullable) = E, 24 zero bytes for a
+ *               row with doc >= n_docs.  Entries past n_hits_out[q] are left untouched.
+ * So with w_prox == 0 and w_rank > 0, on rows in FinalRank order without NaN, the output is the window with its inside rows first; with
+ * w_rank == 0 (and finite finals) the order is bonus descending, then window order.
+ * Checks, all before anything is enqueued and with the outputs untouched: those of ss_rerank_hits_by_vector (hits_out overlapping
+ * hits included; there is no table to register), those of ss_best_passages for the query arrays, w_rank or w_prox not finite:
+ * SS_ERR_INVALID; a scratch for the window's entries that cannot be had: SS_ERR_OOM.  Every pointer but the query arrays may be host
+ * or device memory: with every given array in device memory the call only enqueues on the ctx stream and NEVER waits.
+ * ss_score_topk_proximity: row q = ss_rerank_hits_by_proximity applied to the row ss_score_topk_masked returns for query q with
+ * k = k_window, this query_len, topic_probs[q] and mask_id[q].  Wired as ss_score_topk_collapsed is: the window stays inside the scorer
+ * and only the page is written.  Checks: the re-rank's plus those of ss_score_topk_collapsed.  There is no phrase or constrained form:
+ * those callers chain the re-rank.
+ * A known answer.  Query tokens (A, B, C), T = 3.  Doc X: A {3, 40}, B {5, 41, 90}, C {43, -100}: start 40, end 43, n_present 3,
+ * n_occ 3, token_mask 0b111; prox = 2 / max(3, 2) = 2.0 / 3.0, cover = 1.0.  Doc Y: A {7}, B {8}: start 7, end 8, n_present 2, n_occ 2,
+ * token_mask 0b011; prox = 1.0, cover = 2.0 / 3.0: the same bonus bits as X.  Doc Z: A {10}: start 10, end 10, n_present 1, n_occ 1,
+ * bonus 0.0.  Doc W: none of them: 24 zero bytes, bonus 0.0.  The window (W, Z, Y, X) with w_rank = 0, w_prox = 1 comes back as
+ * Y, X, W, Z: X and Y tie and keep window order, and so do W and Z. */
+typedef struct ss_proximity {
+    float    start;       /* value of the span's first occurrence; +0.0 bits when n_present == 0 */
+    float    end;         /* value of the span's last occurrence;  +0.0 bits when n_present == 0 */
+    uint32_t n_present;   /* distinct query TERM ids with an occurrence in the doc's body; 0: all 24 bytes are zero */
+    uint32_t n_occ;       /* occurrences with start <= value <= end (modulo 2^32) */
+    uint64_t token_mask;  /* bit i: the query's i-th token's term is present */
+} ss_proximity;           /* 24 bytes */
+int32_t ss_hit_proximity(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                         int32_t k, const ss_hit* hits /*[n_q][k]*/, const int32_t* n_hits /*[n_q]*/,
+                         ss_proximity* out /*[n_q][k]*/);
+int32_t ss_rerank_hits_by_proximity(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                                    int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
+                                    double w_rank, double w_prox, int32_t first, int32_t k,
+                                    ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                                    double* scores_out /*[n_q][k], nullable*/, ss_proximity* prox_out /*[n_q][k], nullable*/);
+int32_t ss_score_topk_proximity(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                                const int32_t* query_len, const double* topic_probs, const int32_t* mask_id /*NULL = none*/,
+                                int32_t k_window, double w_rank, double w_prox, int32_t first, int32_t k,
+                                ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
+                                double* scores_out /*[n_q][k], nullable*/, ss_proximity* prox_out /*[n_q][k], nullable*/);
 
 /* Collapse by group ("host crowding"): at most g rows of one site on a result page, a "more from this site" count, and pages that
  * continue where the last one stopped.  The reference ranks pages, not sites (retrieval/main_retrieve.go:99-103 cuts the sorted list at 50).

@@ -62,6 +62,10 @@ class SsPassage(C.Structure):
     _fields_ = [("start", C.c_float), ("last", C.c_float), ("n_distinct", C.c_uint32), ("n_occ", C.c_uint32), ("token_mask", C.c_uint64)]
 
 
+class SsProximity(C.Structure):
+    _fields_ = [("start", C.c_float), ("end", C.c_float), ("n_present", C.c_uint32), ("n_occ", C.c_uint32), ("token_mask", C.c_uint64)]
+
+
 class SsDocRange(C.Structure):
     _fields_ = [("field", C.c_int32), ("_pad", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
 
@@ -164,6 +168,9 @@ PROTOTYPES = {
     "ss_related_terms": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_explain_hits": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "ss_best_passages": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "ss_hit_proximity": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ss_rerank_hits_by_proximity": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_score_topk_proximity": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
     "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -271,6 +271,14 @@ struct ss_scorer {
     }
     ss::DevBuf<uint32_t> d_gtopk_rows;
     ss::DevBuf<unsigned char> d_gtopk_out;
+    // ss_hit_proximity / ss_rerank_hits_by_proximity / ss_score_topk_proximity (proximity.hip).  prx: the turns the queries' table goes
+    // up through, as exp / pas.  Grow-only, written and read on the context's stream only: the entries of a re-rank's window
+    // [n_q][k_in] as six dwords each, between k_hit_proximity and k_prox_sort_hits, and the device block of HOST scores_out / prox_out,
+    // scores | entries (the call waits before it returns)
+    QueryTurn prx[TURNS];
+    int prx_turn = 0;
+    ss::DevBuf<uint32_t> d_prx_entries;
+    ss::DevBuf<unsigned char> d_prx_out;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import SsGraphInfo, SsHit, SsPassage, SsTermMatch, check
+from ._lib import SsGraphInfo, SsHit, SsPassage, SsProximity, SsTermMatch, check
 
 HIT_DTYPE = np.dtype([("doc", "<u4"), ("_pad", "<u4"), ("title", "<f8"), ("body", "<f8"),
                       ("pagerank", "<f8"), ("final", "<f8")])
@@ -20,6 +20,7 @@ HIT_DTYPE = np.dtype([("doc", "<u4"), ("_pad", "<u4"), ("title", "<f8"), ("body"
 TERM_MATCH_DTYPE = np.dtype([("title_w", "<f4"), ("body_w", "<f4"), ("flags", "<u4"), ("body_pos", "<f4")])   # ss_term_match
 
 PASSAGE_DTYPE = np.dtype([("start", "<f4"), ("last", "<f4"), ("n_distinct", "<u4"), ("n_occ", "<u4"), ("token_mask", "<u8")])   # ss_passage
+PROXIMITY_DTYPE = np.dtype([("start", "<f4"), ("end", "<f4"), ("n_present", "<u4"), ("n_occ", "<u4"), ("token_mask", "<u8")])   # ss_proximity
 
 DOC_RANGE_DTYPE = np.dtype([("field", "<i4"), ("_pad", "<i4"), ("lo", "<i8"), ("hi", "<i8")])   # ss_doc_range
 
@@ -875,6 +876,89 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return out
 
+    def hit_proximity(self, q_ptr, q_terms, hits, n_hits, out=None, k: Optional[int] = None):
+        """ss_hit_proximity: per hit the smallest body span that holds every query term the doc has at all -> PROXIMITY_DTYPE [n_q][k]
+        (n_present == 0: the doc holds none of the query's terms).  hits / n_hits, k and out as in best_passages (out: numpy
+        PROXIMITY_DTYPE, or a torch uint8 device tensor of n_q * k * 24 bytes, returned as it is); with device hits, n_hits and out the
+        library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        n_hits = _as(n_hits, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        hits = hits.contiguous() if _is_torch(hits) else np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if k is None:
+            if n_q > 0 and nbytes(hits) % (n_q * HIT_DTYPE.itemsize):
+                raise ValueError("hits does not hold n_q rows of whole ss_hit")
+            k = nbytes(hits) // (n_q * HIT_DTYPE.itemsize) if n_q > 0 else 1
+        elif nbytes(hits) < n_q * int(k) * HIT_DTYPE.itemsize or (n_hits.numel() if _is_torch(n_hits) else n_hits.size) < n_q:
+            raise ValueError("hits / n_hits too small")
+        if out is None:
+            out = np.zeros((n_q, k), dtype=PROXIMITY_DTYPE)
+        elif nbytes(out) < n_q * k * PROXIMITY_DTYPE.itemsize:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(q_ptr, q_terms, hits, n_hits, out)
+        check(self.ctx.lib.ss_hit_proximity(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), int(k), _ptr(hits), _ptr(n_hits), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return out
+
+    def _proximity_out(self, n_q: int, k: int, out, want_scores: bool, want_prox: bool):
+        """The four output arrays of the proximity re-ranks: the caller's (hits, n_hits, scores | None, prox | None) or fresh numpy ones."""
+        if out is None:
+            return (np.zeros((n_q, k), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                    np.zeros((n_q, k), dtype=np.float64) if want_scores else None,
+                    np.zeros((n_q, k), dtype=PROXIMITY_DTYPE) if want_prox else None)
+        o_hits, o_n, o_sc, o_px = out
+        o_n, o_sc = _as(o_n, "int32"), _as(o_sc, "float64")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if k > 0 and (nbytes(o_hits) < n_q * k * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4 or (o_sc is not None and nbytes(o_sc) < n_q * k * 8)
+                      or (o_px is not None and nbytes(o_px) < n_q * k * PROXIMITY_DTYPE.itemsize)):
+            raise ValueError("output buffers too small")
+        return o_hits, o_n, o_sc, o_px
+
+    def rerank_by_proximity(self, q_ptr, q_terms, hits, n_hits, k: int, w_rank: float = 1.0, w_prox: float = 1.0, first: int = 0,
+                            k_in: Optional[int] = None, out=None, want_scores: bool = True, want_prox: bool = True):
+        """ss_rerank_hits_by_proximity: every window hits[q][: n_hits[q]] sorted stably by w_rank * final + w_prox * bonus, descending
+        (NaN scores behind every number, rows outside the table last), bonus = the closeness of the query's terms in the doc's body
+        times the share of the query's terms the doc has; page [first, first + k) -> (hits [n_q][k], n_hits [n_q], scores [n_q][k]
+        float64 | None, prox [n_q][k] PROXIMITY_DTYPE | None).  hits / n_hits, k_in as in collapse_hits.  out = (hits, n_hits, scores |
+        None, prox | None): the caller's arrays (prox: numpy PROXIMITY_DTYPE or a torch uint8 device tensor), returned as they are;
+        with device arrays throughout the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        if int(q_ptr.shape[0]) - 1 != n_q:
+            raise ValueError(f"{int(q_ptr.shape[0]) - 1} queries for {n_q} windows")
+        o_hits, o_n, o_sc, o_px = self._proximity_out(n_q, int(k), out, want_scores, want_prox)
+        self.ctx.ready(q_ptr, q_terms, hits, n_hits, o_hits, o_n, o_sc, o_px)
+        check(self.ctx.lib.ss_rerank_hits_by_proximity(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), k_in, _ptr(hits), _ptr(n_hits), float(w_rank),
+                                                       float(w_prox), int(first), int(k), _ptr(o_hits), _ptr(o_n), _ptr(o_sc), _ptr(o_px)),
+              self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sc, o_px
+
+    def score_topk_proximity(self, q_ptr, q_terms, k_window: int, k: int, w_rank: float = 1.0, w_prox: float = 1.0, first: int = 0,
+                             query_len=None, topic_probs=None, mask_id=None, out=None, want_scores: bool = True, want_prox: bool = True):
+        """ss_score_topk_proximity: rerank_by_proximity applied to the rows score_topk_masked gives at k = k_window, without the window
+        leaving the device -> (hits [n_q][k], n_hits [n_q], scores | None, prox | None).  out as in rerank_by_proximity: with device
+        arrays the library only enqueues."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        query_len = _as(query_len, "int32")
+        topic_probs = _as(topic_probs, "float64")
+        mask_id = _as(mask_id, "int32")
+        n_q = int(q_ptr.shape[0]) - 1
+        o_hits, o_n, o_sc, o_px = self._proximity_out(n_q, int(k), out, want_scores, want_prox)
+        self.ctx.ready(q_ptr, q_terms, query_len, topic_probs, mask_id, o_hits, o_n, o_sc, o_px)
+        check(self.ctx.lib.ss_score_topk_proximity(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(query_len), _ptr(topic_probs), _ptr(mask_id),
+                                                   int(k_window), float(w_rank), float(w_prox), int(first), int(k), _ptr(o_hits), _ptr(o_n),
+                                                   _ptr(o_sc), _ptr(o_px)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sc, o_px
+
     def set_doc_groups(self, group) -> None:
         """ss_scorer_set_doc_groups: register the doc -> group table (uint32 [n_docs], numpy or torch; SS_NO_GROUP = never collapsed),
         or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
@@ -1542,7 +1626,7 @@ def train_vector_lists(scorer: "Scorer", vec, n_lists: int, iters: int = 5, seed
     return centroids, lists
 
 
-__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "SsHit", "SsTermMatch", "SsPassage",
+__all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "PROXIMITY_DTYPE", "SsHit", "SsTermMatch", "SsPassage", "SsProximity",
            "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED", "NO_LIST", "train_vector_lists"]
 
 

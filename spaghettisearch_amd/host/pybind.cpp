@@ -35,6 +35,17 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("TitleRank", &retrieval::Rank_combined::TitleRank)
         .def_readonly("BodyRank", &retrieval::Rank_combined::BodyRank);
 
+    py::class_<retrieval::ResultProximity>(m, "ResultProximity")
+        .def_readonly("HasSpan", &retrieval::ResultProximity::HasSpan)
+        .def_readonly("Start", &retrieval::ResultProximity::Start)
+        .def_readonly("End", &retrieval::ResultProximity::End)
+        .def_readonly("Words", &retrieval::ResultProximity::Words)
+        .def_readonly("Present", &retrieval::ResultProximity::Present)
+        .def_readonly("Occurrences", &retrieval::ResultProximity::Occurrences);
+    py::class_<retrieval::ProximityPage>(m, "ProximityPage")
+        .def_readonly("Results", &retrieval::ProximityPage::Results)
+        .def_readonly("Scores", &retrieval::ProximityPage::Scores)
+        .def_readonly("Spans", &retrieval::ProximityPage::Spans);
     py::class_<retrieval::ResultPassage>(m, "ResultPassage")
         .def_readonly("HasPassage", &retrieval::ResultPassage::HasPassage)
         .def_readonly("Start", &retrieval::ResultPassage::Start)
@@ -288,6 +299,11 @@ PYBIND11_MODULE(_host, m) {
         .def("RelatedTerms", &retrieval::DeviceIndex::RelatedTerms, py::arg("query"), py::arg("m") = 10, py::arg("k_fb") = 10, py::arg("m_doc") = 5)
         .def("ExplainResults", &retrieval::DeviceIndex::ExplainResults, py::arg("query"), py::arg("results"))
         .def("BestPassages", &retrieval::DeviceIndex::BestPassages, py::arg("query"), py::arg("results"), py::arg("width") = 20)
+        .def("HitProximity", &retrieval::DeviceIndex::HitProximity, py::arg("query"), py::arg("results"))
+        .def("RetrieveBatchProximity", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, double w_rank,
+                                          double w_prox, int first, int k) {
+            return di.RetrieveBatchProximity(queries, k_window, w_rank, w_prox, first, k);
+        }, py::arg("queries"), py::arg("k_window"), py::arg("w_rank") = 1.0, py::arg("w_prox") = 1.0, py::arg("first") = 0, py::arg("k") = 50)
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("SetLexicon", [](retrieval::DeviceIndex& di, db::MemDB* forw0) {
             db::Context ctx;

@@ -67,6 +67,25 @@ struct ResultPassage {
     uint32_t Distinct = 0, Occurrences = 0;
 };
 
+// How close the query's words come in a row's body text (DeviceIndex::HitProximity; no reference counterpart): the smallest span of
+// body positions that holds every query word the page has at all.  Start / End: its first and last occurrence; Words: the query's
+// words the page has, as md5-hex hashes in token order and each once; Present: their number; Occurrences: the occurrences inside the
+// span.  HasSpan false (all else zero / empty): no positional postings, no such doc, or none of the words in the page's body text.
+struct ResultProximity {
+    bool HasSpan = false;
+    double Start = 0, End = 0;
+    std::vector<std::string> Words;
+    uint32_t Present = 0, Occurrences = 0;
+};
+
+// One page of a query's results re-ranked by term proximity (DeviceIndex::RetrieveBatchProximity; no reference counterpart).
+// Scores[i] = w_rank * FinalRank + w_prox * bonus of Results[i]; Spans[i]: its ResultProximity.
+struct ProximityPage {
+    std::vector<Rank_combined> Results;
+    std::vector<double> Scores;
+    std::vector<ResultProximity> Spans;
+};
+
 // One page of a query's results with at most g rows per site (DeviceIndex::RetrieveBatchCollapsed; no reference counterpart).
 // Same[i]: how many rows of the query's window are on the site of Results[i], the row itself included ("Same[i] - 1 more from this
 // site"); Kept: how many rows the whole window keeps, i.e. how far paging can go.
@@ -847,6 +866,47 @@ public:
                 if (((m[j].token_mask >> i) & 1u) && std::find(out[j].Words.begin(), out[j].Words.end(), hashed[i]) == out[j].Words.end())
                     out[j].Words.push_back(hashed[i]);
         }
+        return out;
+    }
+    // one ss_proximity entry as the host's struct; names: the query's tokens as word hashes, in token order
+    static ResultProximity to_proximity(const ss_proximity& e, const std::vector<std::string>& names) {
+        ResultProximity r;
+        if (!e.n_present) return r;
+        r.HasSpan = true;
+        r.Start = (double)e.start;
+        r.End = (double)e.end;
+        r.Present = e.n_present;
+        r.Occurrences = e.n_occ;
+        for (size_t i = 0; i < names.size() && i < 64; i++)
+            if (((e.token_mask >> i) & 1u) && std::find(r.Words.begin(), r.Words.end(), names[i]) == r.Words.end()) r.Words.push_back(names[i]);
+        return r;
+    }
+    // Per row of `results` — the Rank_combined rows Retrieve / RetrieveBatch returned for `query` — the smallest body span that holds
+    // every query word the page has (ss_hit_proximity).  The query is tokenised as ExplainResults does it.  A row whose DocHash the
+    // index does not hold has no span.  Changes nothing unless called.
+    std::vector<ResultProximity> HitProximity(const std::string& query, const std::vector<Rank_combined>& results) {
+        using namespace spaghetti;
+        const std::vector<std::string> hashed = query_word_hashes(query);
+        std::vector<ResultProximity> out(results.size());
+        if (results.empty()) return out;
+        const size_t k = results.size(), T = hashed.size();
+        if (T == 0) return out;
+        if (k > (size_t)SS_MAX_TOPK || T > (size_t)SS_MAX_QUERY_TERMS) throw std::runtime_error("HitProximity: too many rows or query words");
+        std::vector<uint32_t> q_ptr{0, (uint32_t)T}, q_terms;
+        for (auto& h : hashed) {
+            auto it = terms.id.find(h);
+            q_terms.push_back(it == terms.id.end() ? SS_UNKNOWN_TERM : it->second);
+        }
+        std::vector<ss_hit> hits(k);
+        for (size_t j = 0; j < k; j++) {
+            auto it = docs.id.find(results[j].DocHash);
+            hits[j] = ss_hit{};
+            hits[j].doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;      // no such doc: no postings
+        }
+        const int32_t n_hits = (int32_t)k;
+        std::vector<ss_proximity> m(k);
+        check(ss_hit_proximity(scorer, 1, q_ptr.data(), q_terms.data(), (int32_t)k, hits.data(), &n_hits, m.data()), "ss_hit_proximity");
+        for (size_t j = 0; j < k; j++) out[j] = to_proximity(m[j], hashed);
         return out;
     }
     // dense term ids -> word hashes (DocTopTerms, RelatedTerms)
@@ -1712,6 +1772,59 @@ public:
             out[q].Results = ranks[q];
             out[q].Same.assign(same.begin() + q * kk, same.begin() + q * kk + n_page[q]);
             out[q].Kept = n_kept[q];
+        }
+        return out;
+    }
+    // RetrieveBatch re-ranked by term proximity: page [first, first + k) of every query's first k_window rows, sorted by
+    // w_rank * FinalRank + w_prox * bonus (bonus: how close the query's words come in the page's body, times the share of the query's
+    // words the page has; k_window <= SS_MAX_TOPK).  Queries without quoted phrases are scored and re-ranked in one library call and
+    // only the pages come back (ss_score_topk_proximity); a batch with a quoted phrase is scored by ss_score_topk_phrase and its rows
+    // go through ss_rerank_hits_by_proximity, the phrases' words counting as tokens behind the others.  Query operators and prefix
+    // queries are not read here.
+    std::vector<ProximityPage> RetrieveBatchProximity(const std::vector<std::string>& queries, int k_window, double w_rank = 1.0,
+                                                      double w_prox = 1.0, int first = 0, int k = 50,
+                                                      const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                      bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (query_operators) throw std::runtime_error("RetrieveBatchProximity: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("RetrieveBatchProximity: prefix queries are not read here (SetPrefixQueries(0))");
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1);
+        std::vector<ss_hit> page(nq * kk);
+        std::vector<int32_t> n_page(nq);
+        std::vector<double> scores(nq * kk);
+        std::vector<ss_proximity> prox(nq * kk);
+        std::vector<uint32_t> w_ptr{0}, w_terms;                 // the re-rank's tokens of a batch with a quoted phrase
+        const double* probs = t.probs.empty() ? nullptr : t.probs.data();
+        if (t.p_terms.empty()) {
+            check(ss_score_topk_proximity(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.q_len.data(), probs, nullptr, k_window, w_rank, w_prox,
+                                          first, k, page.data(), n_page.data(), scores.data(), prox.data()), "ss_score_topk_proximity");
+        } else {
+            std::vector<ss_hit> rows(nq * (size_t)std::max(k_window, 1));
+            std::vector<int32_t> n_rows(nq);
+            check(ss_score_topk_phrase(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(), probs,
+                                       k_window, rows.data(), n_rows.data()), "ss_score_topk_phrase");
+            // the words of the quoted phrases count as tokens, behind the others (as query_word_hashes reads a query), up to
+            // SS_MAX_QUERY_TERMS
+            for (size_t q = 0; q < nq; q++) {
+                w_terms.insert(w_terms.end(), t.q_terms.begin() + t.q_ptr[q], t.q_terms.begin() + t.q_ptr[q + 1]);
+                for (uint32_t i = t.p_ptr[q]; i < t.p_ptr[q + 1] && w_terms.size() - w_ptr.back() < (size_t)SS_MAX_QUERY_TERMS; i++)
+                    w_terms.push_back(t.p_terms[i]);
+                w_ptr.push_back((uint32_t)w_terms.size());
+            }
+            check(ss_rerank_hits_by_proximity(scorer, t.nq, w_ptr.data(), w_terms.data(), k_window, rows.data(), n_rows.data(), w_rank, w_prox,
+                                              first, k, page.data(), n_page.data(), scores.data(), prox.data()), "ss_rerank_hits_by_proximity");
+        }
+        const std::vector<uint32_t>& tok_ptr = t.p_terms.empty() ? t.q_ptr : w_ptr;
+        const std::vector<uint32_t>& tok = t.p_terms.empty() ? t.q_terms : w_terms;
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<ProximityPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            std::vector<std::string> names;
+            for (uint32_t i = tok_ptr[q]; i < tok_ptr[q + 1]; i++) names.push_back(tok[i] < terms.name.size() ? terms.name[tok[i]] : std::string());
+            out[q].Results = ranks[q];
+            out[q].Scores.assign(scores.begin() + q * kk, scores.begin() + q * kk + n_page[q]);
+            for (int32_t r = 0; r < n_page[q]; r++) out[q].Spans.push_back(to_proximity(prox[q * kk + r], names));
         }
         return out;
     }
