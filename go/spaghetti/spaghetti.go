@@ -837,6 +837,190 @@ func (s *Scorer) ScoreTopKProximity(qPtr, qTerms []uint32, queryLen []int32, top
 	return out, nil
 }
 
+// RankNFeatures is the number of columns of HitFeatures (SS_RANK_N_FEATURES): title, body, pagerank, final, window position, query
+// length, present terms, span, prox, occurrences, vector score, fields 0..3.  An absent signal is NaN.
+const RankNFeatures = 15
+
+// TreeNode is one node of a RankModel tree (ss_tree_node): Feature >= 0 splits on that column (left iff x <= Value, a NaN x left iff
+// NanLeft), Feature -1 is a leaf whose output is Value.  Left and Right are indices inside the tree, larger than the node's own.
+type TreeNode struct {
+	Feature     int32
+	Left, Right uint32
+	NanLeft     bool
+	Value       float64
+}
+
+// RankModel is a tree ensemble over feature rows (ss_rank_model): score(x) = base + the linear part over the non-NaN columns + the
+// leaf every tree sends x to, added in tree order.
+type RankModel struct {
+	h         *C.ss_rank_model
+	ctx       *Ctx
+	nFeatures int
+}
+
+// NewRankModel uploads a trained model; the library validates all of it (children behind their parent and inside the tree, finite leaf
+// values, ...) and an invalid one is an error.  linear nil = no linear part; trees may be empty (a linear model).
+func (c *Ctx) NewRankModel(nFeatures int, linear []float64, base float64, trees [][]TreeNode) (*RankModel, error) {
+	if linear != nil && len(linear) != nFeatures {
+		return nil, fmt.Errorf("NewRankModel: %d linear weights for %d features", len(linear), nFeatures)
+	}
+	treePtr := make([]uint32, len(trees)+1)
+	var nodes []C.ss_tree_node
+	for t, tr := range trees {
+		for _, n := range tr {
+			var nl C.uint32_t
+			if n.NanLeft {
+				nl = 1
+			}
+			nodes = append(nodes, C.ss_tree_node{feature: C.int32_t(n.Feature), left: C.uint32_t(n.Left), right: C.uint32_t(n.Right),
+				nan_left: nl, value: C.double(n.Value)})
+		}
+		treePtr[t+1] = uint32(len(nodes))
+	}
+	var np *C.ss_tree_node
+	if len(nodes) > 0 {
+		np = &nodes[0]
+	}
+	m := &RankModel{ctx: c, nFeatures: nFeatures}
+	rc := C.ss_rank_model_create(c.h, C.int32_t(nFeatures), f64p(linear), C.double(base), C.int32_t(len(trees)), u32p(treePtr), np, &m.h)
+	if err := statusErr(c, rc, "ss_rank_model_create"); err != nil {
+		return nil, err
+	}
+	return m, nil
+}
+
+func (m *RankModel) Close() { C.ss_rank_model_destroy(m.h) }
+
+// Eval scores feature rows x [nRows][nFeatures] (row-major) -> [nRows] (ss_rank_model_eval).
+func (m *RankModel) Eval(x []float64) ([]float64, error) {
+	if m.nFeatures == 0 || len(x)%m.nFeatures != 0 {
+		return nil, fmt.Errorf("RankModel.Eval: %d values are not whole rows of %d features", len(x), m.nFeatures)
+	}
+	n := len(x) / m.nFeatures
+	out := make([]float64, n)
+	if n == 0 {
+		return out, nil
+	}
+	rc := C.ss_rank_model_eval(m.h, C.int64_t(n), f64p(x), f64p(out))
+	return out, statusErr(m.ctx, rc, "ss_rank_model_eval")
+}
+
+// windowOf packs per-query rows into the [nq][k] layout the window calls take.
+func windowOf(hits [][]Hit) ([]C.ss_hit, []int32, int) {
+	k := 1
+	for _, row := range hits {
+		if len(row) > k {
+			k = len(row)
+		}
+	}
+	raw := make([]C.ss_hit, len(hits)*k)
+	nHits := make([]int32, len(hits))
+	for q, row := range hits {
+		nHits[q] = int32(len(row))
+		for j, h := range row {
+			raw[q*k+j] = C.ss_hit{doc: C.uint32_t(h.Doc), title: C.double(h.Title), body: C.double(h.Body), pagerank: C.double(h.PageRank),
+				final: C.double(h.Final)}
+		}
+	}
+	return raw, nHits, k
+}
+
+// windowExtras packs the optional per-row inputs of HitFeatures / RerankByModel (nil = absent) beside a window of width k.
+func windowExtras(hits [][]Hit, k int, prox [][]Proximity, vecScores [][]int32) ([]C.ss_proximity, []int32) {
+	var px []C.ss_proximity
+	var vs []int32
+	if prox != nil {
+		px = make([]C.ss_proximity, len(hits)*k)
+		for q := range hits {
+			for j := 0; j < len(hits[q]) && j < len(prox[q]); j++ {
+				e := prox[q][j]
+				px[q*k+j] = C.ss_proximity{start: C.float(e.Start), end: C.float(e.End), n_present: C.uint32_t(e.Present),
+					n_occ: C.uint32_t(e.Occurrences), token_mask: C.uint64_t(e.TokenMask)}
+			}
+		}
+	}
+	if vecScores != nil {
+		vs = make([]int32, len(hits)*k)
+		for q := range hits {
+			copy(vs[q*k:q*k+k], vecScores[q])
+		}
+	}
+	return px, vs
+}
+
+// HitFeatures assembles the signals of every row into a feature row (ss_hit_features): out[q][j] holds RankNFeatures values for
+// hits[q][j].  prox as HitProximity returns it, vecScores as HitVectorScores, queryLen one value per query; nil = that signal is absent.
+func (s *Scorer) HitFeatures(hits [][]Hit, prox [][]Proximity, vecScores [][]int32, queryLen []int32) ([][][]float64, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	raw, nHits, k := windowOf(hits)
+	px, vs := windowExtras(hits, k, prox, vecScores)
+	var pp *C.ss_proximity
+	if px != nil {
+		pp = &px[0]
+	}
+	flat := make([]float64, nq*k*RankNFeatures)
+	rc := C.ss_hit_features(s.h, C.int32_t(nq), C.int32_t(k), &raw[0], i32p(nHits), pp, i32p(vs), i32p(queryLen), f64p(flat))
+	if err := statusErr(s.ctx, rc, "ss_hit_features"); err != nil {
+		return nil, err
+	}
+	out := make([][][]float64, nq)
+	for q := range hits {
+		out[q] = make([][]float64, len(hits[q]))
+		for j := range out[q] {
+			at := (q*k + j) * RankNFeatures
+			out[q][j] = flat[at : at+RankNFeatures : at+RankNFeatures]
+		}
+	}
+	return out, nil
+}
+
+// RankedPage is one page of a query's results re-ranked by a model: Scores[i] = the model's score of Hits[i]'s feature row.
+type RankedPage struct {
+	Hits   []Hit
+	Scores []float64
+}
+
+// RerankByModel sorts every window stably by the model's score of each row's HitFeatures entry, descending (NaN scores behind every
+// number, rows outside the table last), and returns page [first, first+k) (ss_rerank_hits_by_model).  The model must read
+// RankNFeatures columns.  prox, vecScores, queryLen as in HitFeatures.
+func (s *Scorer) RerankByModel(m *RankModel, hits [][]Hit, prox [][]Proximity, vecScores [][]int32, queryLen []int32,
+	first, k int) ([]RankedPage, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	raw, nHits, kIn := windowOf(hits)
+	px, vs := windowExtras(hits, kIn, prox, vecScores)
+	var pp *C.ss_proximity
+	if px != nil {
+		pp = &px[0]
+	}
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	page := make([]C.ss_hit, nq*kk)
+	nPage, scores := make([]int32, nq), make([]float64, nq*kk)
+	rc := C.ss_rerank_hits_by_model(s.h, m.h, C.int32_t(nq), C.int32_t(kIn), &raw[0], i32p(nHits), pp, i32p(vs), i32p(queryLen),
+		C.int32_t(first), C.int32_t(k), &page[0], i32p(nPage), f64p(scores))
+	if err := statusErr(s.ctx, rc, "ss_rerank_hits_by_model"); err != nil {
+		return nil, err
+	}
+	out := make([]RankedPage, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nPage[q])
+		out[q] = RankedPage{make([]Hit, n), append([]float64(nil), scores[q*kk:q*kk+n]...)}
+		for i := 0; i < n; i++ {
+			r := page[q*kk+i]
+			out[q].Hits[i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, nil
+}
+
 // NoGroup in a group table: the doc is never collapsed with anything (SS_NO_GROUP).
 const NoGroup = uint32(C.SS_NO_GROUP)
 

@@ -64,7 +64,10 @@ extern "C" {
  * ss_group_count, ss_scorer_group_values and ss_top_groups (the m groups of the doc -> group table that hold most of a query's matches);
  * SS_MAX_COMPLETE and ss_lexicon_complete (the m most frequent words that start with a prefix: word completions);
  * ss_proximity, ss_hit_proximity, ss_rerank_hits_by_proximity and ss_score_topk_proximity (per result row the smallest body span that
- * holds every query term the doc has, and a window re-ranked by it). */
+ * holds every query term the doc has, and a window re-ranked by it);
+ * SS_RANK_N_FEATURES, SS_MAX_RANK_FEATURES, SS_MAX_RANK_TREES, ss_tree_node, ss_rank_model, ss_rank_model_info, ss_rank_model_create /
+ * _destroy / _get_info / _eval, ss_hit_features and ss_rerank_hits_by_model (learned ranking: the signals of a window's rows as a
+ * feature matrix, a tree ensemble evaluated per row, a window re-ranked by its scores). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -707,6 +710,89 @@ int32_t ss_score_topk_proximity(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr
                                 int32_t k_window, double w_rank, double w_prox, int32_t first, int32_t k,
                                 ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/,
                                 double* scores_out /*[n_q][k], nullable*/, ss_proximity* prox_out /*[n_q][k], nullable*/);
+
+/* Learned ranking: a tree ensemble over the signals of a hit, and a window re-ranked by it.  Every re-ranker above hard-wires one signal
+ * and hand-set weights; a caller with click logs has a MODEL over all of them (a gradient-boosted forest, "learning to rank").  Training
+ * is the caller's work, as producing embeddings and tokenising are: a trained model arrives as flat arrays.  No reference counterpart.
+ * ss_rank_model_create.  A model: n_features columns, an optional linear part, a base and n_trees >= 0 trees (0: a linear model).  Tree
+ * t is nodes[tree_ptr[t] .. tree_ptr[t + 1]), its root the first of them; left / right are indices INSIDE the tree.  The arrays are host
+ * memory and are copied.  The score of a feature row x is defined bit for bit; every operation is rounded once, nothing is contracted:
+ *     acc = base
+ *     for f = 0 .. n_features-1, if linear != NULL and linear[f] != 0.0 and x[f] is not NaN:   acc = acc + linear[f] * x[f]
+ *     for t = 0 .. n_trees-1:   walk tree t from its node 0 to a leaf L;   acc = acc + L.value
+ *     score = acc               (a NaN result is written as 0x7FF8000000000000)
+ *   A walk at a split goes left iff x[feature] <= value by numeric comparison (-0.0 <= 0.0; +-inf are ordinary thresholds and values); a
+ *   NaN x[feature] goes left iff nan_left.
+ *   The whole model is validated on the host, and nothing is uploaded when it fails.  SS_ERR_INVALID: n_features < 1, n_trees < 0,
+ *   tree_ptr[0] != 0 or tree_ptr decreasing, an empty tree, a feature outside [-1, n_features), a split whose left or right is <= its own
+ *   index or >= the tree's size, nan_left > 1, a NaN split value, a leaf value, base or linear weight that is not finite, a NULL array
+ *   that is needed.  SS_ERR_UNSUPPORTED: n_features > SS_MAX_RANK_FEATURES, n_trees > SS_MAX_RANK_TREES, more than 2^24 nodes.  Because
+ *   children have larger indices than their parent every walk ends within the tree's node count: no model that passes can make a kernel
+ *   loop or read outside its arrays, on any feature values; the kernel bounds its walk by the tree's size as well.
+ * ss_rank_model_get_info: the figures of the model; max_depth = the splits on the longest path from a node 0 to a leaf.
+ * ss_rank_model_eval: scores_out[r] = the score of row x[r * n_features ..) for r < n_rows; x and scores_out host or device memory (with
+ * both in device memory the call only enqueues on the ctx stream); n_rows < 0 is SS_ERR_INVALID, n_rows >= 2^31 SS_ERR_UNSUPPORTED.
+ * The forest is walked out of the LDS in chunks of consecutive whole trees of at most option "rank.lds_nodes" nodes together (default
+ * 1024, 1 .. 1024); a tree with more nodes is walked from global memory.  The order of the additions is the tree order and the scores are
+ * the same bytes for every value.  A workgroup holds 256 rows of a model of at most 16 features, 64 rows of a wider one.
+ * ss_rank_model_destroy waits for the ctx stream first.
+ * ss_hit_features: the feature row of every row of a window, out[(q * k_in + j) * SS_RANK_N_FEATURES + c], written for j < n_hits[q]; every
+ * other entry is left untouched.  E = prox[q * k_in + j], "absent" = the quiet NaN 0x7FF8000000000000:
+ *     c 0..3    the row's title, body, pagerank, final: their 8 bytes as given (rows are trusted, as in ss_fuse_hits)
+ *     c 4       (double)j, the window position
+ *     c 5       (double)query_len[q]; absent without query_len
+ *     c 6       (double)E.n_present
+ *     c 7       sp = (double)E.end - (double)E.start
+ *     c 8       prox = E.n_present < 2 ? 0.0 : (double)(E.n_present - 1) / max(sp, (double)(E.n_present - 1)), exactly
+ *               ss_rerank_hits_by_proximity's
+ *     c 9       (double)E.n_occ; columns 6..9 are all absent without prox
+ *     c 10      (double)vec_scores[q * k_in + j]; absent without vec_scores or for SS_NO_VEC_SCORE
+ *     c 11..14  (double)value[f][doc] of field f = 0..3 (int64 -> double, round to nearest even); absent when no table is registered,
+ *               f >= n_fields, doc >= n_docs or the value is SS_NO_FIELD_VALUE
+ * No registered table is required, and no doc id makes the kernel read outside one.  Checks, staging, host / device pointers and the
+ * clamping of a device n_hits: those of ss_hit_fields without its table; prox, vec_scores and query_len may each be host or device memory.
+ * ss_rerank_hits_by_model: the score of a row = the model's score of its ss_hit_features entry; Window, Order and Output word for word
+ * those of ss_rerank_hits_by_proximity (score descending by numeric comparison, stable, NaN scores behind every number in window order,
+ * rows with doc >= n_docs last of all with score NaN, the 40 bytes of a row copied, entries past n_hits_out[q] untouched).  So with a
+ * linear model of linear[3] = 1 and nothing else, on rows in FinalRank order without NaN, the page is the window's page.  Checks, all
+ * before anything is enqueued and with the outputs untouched: those of ss_rerank_hits_by_vector without a table to register; a model
+ * with n_features != SS_RANK_N_FEATURES or of another context: SS_ERR_INVALID; the scratch for the feature matrix and the scores cannot
+ * be had: SS_ERR_OOM.  With every given array in device memory the call only enqueues on the ctx stream and NEVER waits.
+ * A known answer.  15 features, base 0.5, linear all zero but linear[3] = 2.0; T0 = [{f 8, value 0.5, nan_left 0, l 1, r 2}, leaf 0.0,
+ * leaf 1.0], T1 = [{f 11, value 100, nan_left 1, l 1, r 2}, leaf 0.25, leaf -0.25].  Row A (final 1.0, prox 1.0, field0 50): 0.5 + 2.0
+ * + 1.0 + 0.25 = 3.75.  Row B (final 1.5, no prox entry: NaN goes right; field0 SS_NO_FIELD_VALUE: NaN goes left): 0.5 + 3.0 + 1.0 +
+ * 0.25 = 4.75.  Row C (final 1.0, prox 0.25, field0 200): 0.5 + 2.0 + 0.0 - 0.25 = 2.25.  The window (A, B, C) comes back as B, A, C. */
+#define SS_RANK_N_FEATURES   15     /* columns of ss_hit_features */
+#define SS_MAX_RANK_FEATURES 64     /* columns a model may read (ss_rank_model_eval takes any n_features up to this) */
+#define SS_MAX_RANK_TREES    8192
+typedef struct ss_rank_model ss_rank_model;
+typedef struct ss_tree_node {       /* 24 bytes */
+    int32_t  feature;   /* >= 0: split on this column; -1: leaf */
+    uint32_t left;      /* node index inside the tree, > this node's own index (ignored in a leaf) */
+    uint32_t right;     /* likewise */
+    uint32_t nan_left;  /* 0 / 1: where a NaN feature value goes (ignored in a leaf) */
+    double   value;     /* split: go left iff x <= value (numeric: -0.0 <= 0.0); leaf: the tree's output */
+} ss_tree_node;
+typedef struct ss_rank_model_info {
+    int32_t  n_features, n_trees;
+    uint32_t n_nodes, max_tree_nodes;
+    uint32_t max_depth, _pad;
+} ss_rank_model_info;               /* 24 bytes */
+int32_t ss_rank_model_create(ss_ctx* ctx, int32_t n_features, const double* linear /*[n_features], nullable*/, double base,
+                             int32_t n_trees, const uint32_t* tree_ptr /*[n_trees+1]*/, const ss_tree_node* nodes,
+                             ss_rank_model** out);
+int32_t ss_rank_model_destroy(ss_rank_model* m);
+int32_t ss_rank_model_get_info(ss_rank_model* m, ss_rank_model_info* out);
+int32_t ss_rank_model_eval(ss_rank_model* m, int64_t n_rows, const double* x /*[n_rows][n_features]*/, double* scores_out /*[n_rows]*/);
+int32_t ss_hit_features(ss_scorer* s, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/,
+                        const ss_proximity* prox /*[n_q][k_in], nullable: ss_hit_proximity's output*/,
+                        const int32_t* vec_scores /*[n_q][k_in], nullable: ss_hit_vector_scores' output*/,
+                        const int32_t* query_len /*[n_q], nullable*/,
+                        double* out /*[n_q][k_in][SS_RANK_N_FEATURES]*/);
+int32_t ss_rerank_hits_by_model(ss_scorer* s, ss_rank_model* m, int32_t n_q, int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/,
+                                const int32_t* n_hits /*[n_q]*/, const ss_proximity* prox, const int32_t* vec_scores,
+                                const int32_t* query_len, int32_t first, int32_t k,
+                                ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, double* scores_out /*[n_q][k], nullable*/);
 
 /* Collapse by group ("host crowding"): at most g rows of one site on a result page, a "more from this site" count, and pages that
  * continue where the last one stopped.  The reference ranks pages, not sites (retrieval/main_retrieve.go:99-103 cuts the sorted list at 50).

@@ -171,6 +171,12 @@ PROTOTYPES = {
     "ss_hit_proximity": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ss_rerank_hits_by_proximity": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_proximity": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ss_rank_model_create": (_i32, [_vp, _i32, _vp, C.c_double, _i32, _vp, _vp, C.POINTER(_vp)]),
+    "ss_rank_model_destroy": (_i32, [_vp]),
+    "ss_rank_model_get_info": (_i32, [_vp, _vp]),
+    "ss_rank_model_eval": (_i32, [_vp, C.c_int64, _vp, _vp]),
+    "ss_hit_features": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ss_rerank_hits_by_model": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ss_scorer_set_doc_groups": (_i32, [_vp, _vp]),
     "ss_collapse_hits": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_score_topk_collapsed": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -356,6 +356,8 @@ static const char* const k_option_names[] = {
                             //    the LDS (sorted there), a longer one from global memory; the same bytes either way (default 512, 1 .. 4096; tests reach the long path)
     "proximity.lds_events", // k_hit_proximity: the same switch for the span kernel (default 512, 1 .. 4096); tests set it to 16 and 1 to reach the
                             //    padded sort and the long path on short lists; the same bytes for every value
+    "rank.lds_nodes",       // k_forest_eval: consecutive whole trees of at most this many nodes together are walked out of the LDS, a larger tree
+                            //    from global memory (default 1024, 1 .. 1024; tests set it to 16 and 1); the same bytes for every value
     "lexicon.chunk_terms",  // k_lexicon_suggest: words of the query's length groups per (query word, chunk) workgroup (default 4096, 1 .. 2^20;
                             //    tests set it small to put chunk seams inside a length group); the rows are the same bytes for every value
     "lexicon.complete_parts", // ss_lexicon_complete: parts P the range of every prefix is cut into, one wave of k_lexicon_complete each (default 0:

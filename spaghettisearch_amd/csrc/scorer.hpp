@@ -279,6 +279,11 @@ struct ss_scorer {
     int prx_turn = 0;
     ss::DevBuf<uint32_t> d_prx_entries;
     ss::DevBuf<unsigned char> d_prx_out;
+    // ss_hit_features / ss_rerank_hits_by_model (rank_model.hip).  Grow-only, written and read on the context's stream only: the
+    // feature matrix of a re-rank's window [n_q][k_in][SS_RANK_N_FEATURES] and its scores [n_q][k_in], between k_hit_features,
+    // k_forest_eval and k_model_sort_hits, and the device block of HOST prox | vec_scores | query_len (the call waits before it returns)
+    ss::DevBuf<double> d_rm_feat, d_rm_scores;
+    ss::DevBuf<unsigned char> d_rm_in;
     // ss_score_topk_submit / _collect: batches in flight whose hits go to HOST memory.  A slot: device buffers the kernels write and
     // an event behind them.
     static constexpr int INFLIGHT = SS_SCORE_INFLIGHT;

@@ -30,6 +30,9 @@ GROUP_COUNT_DTYPE = np.dtype([("group", "<u4"), ("count", "<u4")])   # ss_group_
 
 DIV_INFO_DTYPE = np.dtype([("rel", "<i4"), ("sim", "<i4")])     # ss_div_info
 
+TREE_NODE_DTYPE = np.dtype([("feature", "<i4"), ("left", "<u4"), ("right", "<u4"), ("nan_left", "<u4"), ("value", "<f8")])   # ss_tree_node
+RANK_N_FEATURES = 15                                            # SS_RANK_N_FEATURES: the columns of Scorer.hit_features
+
 FUSED_DTYPE = np.dtype([("score", "<f8"), ("vec_score", "<i4"), ("lex_rank", "<u2"), ("vec_rank", "<u2")])   # ss_fused
 FUSE_RRF, FUSE_WEIGHTED = 0, 1                                  # SS_FUSE_RRF, SS_FUSE_WEIGHTED
 
@@ -959,6 +962,55 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_sc, o_px
 
+    def _window_extras(self, n_q: int, k_in: int, prox, vec_scores, query_len):
+        """The optional per-row inputs of hit_features / rerank_by_model, checked for size: prox (numpy PROXIMITY_DTYPE or a torch
+        uint8 device tensor), vec_scores int32, query_len int32."""
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if prox is not None:
+            prox = prox.contiguous() if _is_torch(prox) else np.ascontiguousarray(prox, dtype=PROXIMITY_DTYPE)
+        vec_scores, query_len = _as(vec_scores, "int32"), _as(query_len, "int32")
+        if ((prox is not None and nbytes(prox) < n_q * k_in * PROXIMITY_DTYPE.itemsize) or (vec_scores is not None and nbytes(vec_scores) < n_q * k_in * 4)
+                or (query_len is not None and nbytes(query_len) < n_q * 4)):
+            raise ValueError("prox / vec_scores / query_len too small")
+        return prox, vec_scores, query_len
+
+    def hit_features(self, hits, n_hits, prox=None, vec_scores=None, query_len=None, k_in: Optional[int] = None, out=None):
+        """ss_hit_features: the feature row of every window row -> float64 [n_q][k_in][RANK_N_FEATURES]: title, body, pagerank, final,
+        window position, query length, n_present, span, prox, n_occ, vector score, fields 0..3; NaN where a signal is absent.  hits /
+        n_hits, k_in as in collapse_hits; prox as hit_proximity returns it, vec_scores as hit_vector_scores; out: the caller's float64
+        array (numpy or torch), returned as it is; entries past n_hits[q] keep what they held; with device arrays throughout the
+        library only enqueues."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        prox, vec_scores, query_len = self._window_extras(n_q, k_in, prox, vec_scores, query_len)
+        if out is None:
+            out = np.zeros((n_q, k_in, RANK_N_FEATURES), dtype=np.float64)
+        else:
+            out = _as(out, "float64")
+            if (out.numel() if _is_torch(out) else out.size) < n_q * k_in * RANK_N_FEATURES:
+                raise ValueError("output buffer too small")
+        self.ctx.ready(hits, n_hits, prox, vec_scores, query_len, out)
+        check(self.ctx.lib.ss_hit_features(self.h, n_q, k_in, _ptr(hits), _ptr(n_hits), _ptr(prox), _ptr(vec_scores), _ptr(query_len), _ptr(out)),
+              self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return out
+
+    def rerank_by_model(self, model: "RankModel", hits, n_hits, k: int, prox=None, vec_scores=None, query_len=None, first: int = 0,
+                        k_in: Optional[int] = None, out=None, want_scores: bool = True):
+        """ss_rerank_hits_by_model: every window hits[q][: n_hits[q]] sorted stably by the model's score of the row's hit_features entry,
+        descending (NaN scores behind every number, rows outside the table last); page [first, first + k) -> (hits [n_q][k], n_hits
+        [n_q], scores [n_q][k] float64 | None).  out = (hits, n_hits, scores | None): the caller's arrays, returned as they are; with
+        device arrays throughout the library only enqueues."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        prox, vec_scores, query_len = self._window_extras(n_q, k_in, prox, vec_scores, query_len)
+        o_hits, o_n, o_sc, _ = self._proximity_out(n_q, int(k), out if out is None else (*out, None), want_scores, False)
+        self.ctx.ready(hits, n_hits, prox, vec_scores, query_len, o_hits, o_n, o_sc)
+        check(self.ctx.lib.ss_rerank_hits_by_model(self.h, model.h, n_q, k_in, _ptr(hits), _ptr(n_hits), _ptr(prox), _ptr(vec_scores),
+                                                   _ptr(query_len), int(first), int(k), _ptr(o_hits), _ptr(o_n), _ptr(o_sc)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sc
+
     def set_doc_groups(self, group) -> None:
         """ss_scorer_set_doc_groups: register the doc -> group table (uint32 [n_docs], numpy or torch; SS_NO_GROUP = never collapsed),
         or None to clear.  Replaces the previous table once the scorer's outstanding work is done."""
@@ -1627,7 +1679,8 @@ def train_vector_lists(scorer: "Scorer", vec, n_lists: int, iters: int = 5, seed
 
 
 __all__ = ["Context", "Graph", "PageRankState", "InvertedIndex", "Scorer", "HIT_DTYPE", "TERM_MATCH_DTYPE", "PASSAGE_DTYPE", "PROXIMITY_DTYPE", "SsHit", "SsTermMatch", "SsPassage", "SsProximity",
-           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED", "NO_LIST", "train_vector_lists"]
+           "pack_doc_masks", "DOC_RANGE_DTYPE", "pack_doc_ranges", "VEC_HIT_DTYPE", "FUSED_DTYPE", "FUSE_RRF", "FUSE_WEIGHTED", "NO_LIST", "train_vector_lists",
+           "TREE_NODE_DTYPE", "RANK_N_FEATURES", "RankModel"]
 
 
 def _flatten_words(words, ptr_dtype: str):
@@ -1765,3 +1818,91 @@ class Lexicon:
         if out is not None and _is_torch(terms) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return terms, dist, n_out
+
+
+class RankModel:
+    """ss_rank_model: a tree ensemble over feature rows (learned ranking), validated by the library when it is made.
+    score(x) = base + sum of linear[f] * x[f] over the non-NaN columns + the leaf every tree sends x to, added in tree order.
+    trees: a sequence of trees, each a TREE_NODE_DTYPE array (or a sequence of (feature, left, right, nan_left, value) tuples) whose
+    node 0 is the root and whose children have larger indices than their parent; or a (tree_ptr uint32 [n_trees + 1], nodes
+    TREE_NODE_DTYPE) pair.  linear: float64 [n_features] or None."""
+
+    def __init__(self, ctx: Context, n_features: int, trees, linear=None, base: float = 0.0):
+        self.ctx = ctx
+        self.h = None
+        if isinstance(trees, tuple) and len(trees) == 2 and isinstance(trees[0], np.ndarray) and trees[0].dtype.kind in "ui":
+            tree_ptr = np.ascontiguousarray(trees[0], dtype=np.uint32)
+            nodes = np.ascontiguousarray(trees[1], dtype=TREE_NODE_DTYPE)
+        else:
+            parts = [np.asarray(t, dtype=TREE_NODE_DTYPE).reshape(-1) for t in trees]
+            tree_ptr = np.zeros(len(parts) + 1, dtype=np.uint32)
+            if parts:
+                tree_ptr[1:] = np.cumsum([p.size for p in parts])
+            nodes = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, dtype=TREE_NODE_DTYPE)
+        if linear is not None:
+            linear = np.ascontiguousarray(linear, dtype=np.float64)
+            if linear.size != int(n_features):
+                raise ValueError("linear must hold one weight per feature")
+        self.n_features = int(n_features)
+        h = C.c_void_p()
+        check(ctx.lib.ss_rank_model_create(ctx.h, self.n_features, _ptr(linear), float(base), int(tree_ptr.size) - 1, _ptr(tree_ptr), _ptr(nodes),
+                                           C.byref(h)), ctx.h)
+        self.h = h
+
+    @staticmethod
+    def flatten(tree) -> np.ndarray:
+        """A nested tree, {"f", "thr", "nan_left", "l", "r"} (nan_left optional, default False) or {"leaf"}, as a TREE_NODE_DTYPE
+        array in pre-order: a node, its whole left subtree, its whole right subtree."""
+        rows = []
+        stack = [(tree, -1, False)]                 # (node, the row of its parent, whether it is the right child)
+        while stack:
+            node, parent, is_right = stack.pop()
+            me = len(rows)
+            if parent >= 0:
+                rows[parent][2 if is_right else 1] = me
+            if "leaf" in node:
+                rows.append([-1, 0, 0, 0, float(node["leaf"])])
+            else:
+                rows.append([int(node["f"]), 0, 0, int(bool(node.get("nan_left", False))), float(node["thr"])])
+                stack.append((node["r"], me, True))
+                stack.append((node["l"], me, False))    # (popped first: the left subtree comes right behind its parent)
+        out = np.zeros(len(rows), dtype=TREE_NODE_DTYPE)
+        for i, r in enumerate(rows):
+            out[i] = tuple(r)
+        return out
+
+    @classmethod
+    def from_nested(cls, ctx: Context, n_features: int, trees, linear=None, base: float = 0.0) -> "RankModel":
+        """A model from a list of nested dicts (see flatten)."""
+        return cls(ctx, n_features, [cls.flatten(t) for t in trees], linear=linear, base=base)
+
+    def close(self) -> None:
+        if self.h:
+            check(self.ctx.lib.ss_rank_model_destroy(self.h), self.ctx.h)
+            self.h = None
+
+    def info(self) -> dict:
+        """ss_rank_model_get_info -> {n_features, n_trees, n_nodes, max_tree_nodes, max_depth}"""
+        raw = np.zeros(6, dtype=np.uint32)
+        check(self.ctx.lib.ss_rank_model_get_info(self.h, _ptr(raw)), self.ctx.h)
+        return {"n_features": int(raw[0]), "n_trees": int(raw[1]), "n_nodes": int(raw[2]), "max_tree_nodes": int(raw[3]), "max_depth": int(raw[4])}
+
+    def eval(self, x, out=None):
+        """ss_rank_model_eval: x float64 [n_rows][n_features] (numpy or torch) -> scores float64 [n_rows]; out: the caller's array,
+        returned as it is; with x and out in device memory the library only enqueues."""
+        x = _as(x, "float64")
+        count = lambda a: a.numel() if _is_torch(a) else a.size       # noqa: E731
+        if count(x) % self.n_features:
+            raise ValueError("x does not hold whole rows of n_features values")
+        n_rows = count(x) // self.n_features
+        if out is None:
+            out = np.zeros(n_rows, dtype=np.float64)
+        else:
+            out = _as(out, "float64")
+            if count(out) < n_rows:
+                raise ValueError("output buffer too small")
+        self.ctx.ready(x, out)
+        check(self.ctx.lib.ss_rank_model_eval(self.h, n_rows, _ptr(x), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and out.is_cuda and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return out

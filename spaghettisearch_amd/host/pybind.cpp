@@ -42,6 +42,9 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Words", &retrieval::ResultProximity::Words)
         .def_readonly("Present", &retrieval::ResultProximity::Present)
         .def_readonly("Occurrences", &retrieval::ResultProximity::Occurrences);
+    py::class_<retrieval::RankedPage>(m, "RankedPage")
+        .def_readonly("Results", &retrieval::RankedPage::Results)
+        .def_readonly("Scores", &retrieval::RankedPage::Scores);
     py::class_<retrieval::ProximityPage>(m, "ProximityPage")
         .def_readonly("Results", &retrieval::ProximityPage::Results)
         .def_readonly("Scores", &retrieval::ProximityPage::Scores)
@@ -304,6 +307,10 @@ PYBIND11_MODULE(_host, m) {
                                           double w_prox, int first, int k) {
             return di.RetrieveBatchProximity(queries, k_window, w_rank, w_prox, first, k);
         }, py::arg("queries"), py::arg("k_window"), py::arg("w_rank") = 1.0, py::arg("w_prox") = 1.0, py::arg("first") = 0, py::arg("k") = 50)
+        .def("SetRankModel", &retrieval::DeviceIndex::SetRankModel, py::arg("linear"), py::arg("base"), py::arg("tree_ptr"), py::arg("nodes"))
+        .def("RetrieveBatchRanked", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int k_window, int first, int k) {
+            return di.RetrieveBatchRanked(queries, k_window, first, k);
+        }, py::arg("queries"), py::arg("k_window"), py::arg("first") = 0, py::arg("k") = 50)
         .def("HasDocView", &retrieval::DeviceIndex::HasDocView)
         .def("SetLexicon", [](retrieval::DeviceIndex& di, db::MemDB* forw0) {
             db::Context ctx;

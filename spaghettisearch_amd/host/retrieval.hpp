@@ -17,6 +17,7 @@
 #include <future>
 #include <mutex>
 #include <thread>
+#include <tuple>
 
 #include "md5.hpp"
 #include "ranking.hpp"
@@ -84,6 +85,13 @@ struct ProximityPage {
     std::vector<Rank_combined> Results;
     std::vector<double> Scores;
     std::vector<ResultProximity> Spans;
+};
+
+// One page of a query's results re-ranked by a learned model (DeviceIndex::RetrieveBatchRanked; no reference counterpart).
+// Scores[i] = the model's score of Results[i]'s feature row.
+struct RankedPage {
+    std::vector<Rank_combined> Results;
+    std::vector<double> Scores;
 };
 
 // One page of a query's results with at most g rows per site (DeviceIndex::RetrieveBatchCollapsed; no reference counterpart).
@@ -450,8 +458,12 @@ public:
     std::vector<std::string> lex_words;
     std::vector<uint32_t> lex_freq;
     std::vector<bool> lex_known;                    // forw[0] held the term's hash when its word was read
+    // Learned ranking (SetRankModel): a tree ensemble over the SS_RANK_N_FEATURES columns of ss_hit_features.  It reads no table of
+    // the index, so upload() and ApplyDelta leave it alone.
+    ss_rank_model* rank_model = nullptr;
 
     ~DeviceIndex() {
+        if (rank_model) ss_rank_model_destroy(rank_model);
         if (lexicon) ss_lexicon_destroy(lexicon);
         if (scorer) ss_scorer_destroy(scorer);
         if (title) ss_index_destroy(title);
@@ -1825,6 +1837,61 @@ public:
             out[q].Results = ranks[q];
             out[q].Scores.assign(scores.begin() + q * kk, scores.begin() + q * kk + n_page[q]);
             for (int32_t r = 0; r < n_page[q]; r++) out[q].Spans.push_back(to_proximity(prox[q * kk + r], names));
+        }
+        return out;
+    }
+    // The model of RetrieveBatchRanked: linear (empty: none) and base, and the trees as ss_rank_model_create takes them (tree t =
+    // nodes [tree_ptr[t], tree_ptr[t + 1]), a node = {feature or -1, left, right, nan_left, value}).  The library validates the whole
+    // model; one it refuses leaves the previous model in place.
+    using TreeNode = std::tuple<int32_t, uint32_t, uint32_t, uint32_t, double>;
+    void SetRankModel(const std::vector<double>& linear, double base, const std::vector<uint32_t>& tree_ptr, const std::vector<TreeNode>& nodes) {
+        using namespace spaghetti;
+        if (!linear.empty() && linear.size() != (size_t)SS_RANK_N_FEATURES) throw std::runtime_error("SetRankModel: linear holds SS_RANK_N_FEATURES weights or none");
+        if (tree_ptr.empty() || tree_ptr.back() != nodes.size()) throw std::runtime_error("SetRankModel: tree_ptr must end at the number of nodes");
+        std::vector<ss_tree_node> flat_nodes;
+        for (auto& n : nodes) flat_nodes.push_back(ss_tree_node{std::get<0>(n), std::get<1>(n), std::get<2>(n), std::get<3>(n), std::get<4>(n)});
+        ss_rank_model* m = nullptr;
+        check(ss_rank_model_create(default_ctx(), SS_RANK_N_FEATURES, linear.empty() ? nullptr : linear.data(), base, (int32_t)tree_ptr.size() - 1,
+                                   tree_ptr.data(), flat_nodes.data(), &m), "ss_rank_model_create");
+        if (rank_model) ss_rank_model_destroy(rank_model);
+        rank_model = m;
+    }
+    // RetrieveBatch re-ranked by the model of SetRankModel: page [first, first + k) of every query's first k_window rows, sorted by the
+    // model's score of each row's features (ss_score_topk_masked -> ss_hit_proximity -> ss_rerank_hits_by_model; the vector score column
+    // is absent, the field columns are those of SetDocFields, query_len is the tokeniser's).  The proximity entries are over the
+    // query's words and the words of its quoted phrases behind them, as RetrieveBatchProximity counts them.  Query operators and prefix
+    // queries are not read here.
+    std::vector<RankedPage> RetrieveBatchRanked(const std::vector<std::string>& queries, int k_window, int first = 0, int k = 50,
+                                                const std::vector<std::map<std::string, double>>* topicProbs = nullptr,
+                                                bool live_topic_probs = false) {
+        using namespace spaghetti;
+        if (!rank_model) throw std::runtime_error("RetrieveBatchRanked: no model (SetRankModel)");
+        if (query_operators) throw std::runtime_error("RetrieveBatchRanked: query operators are not read here (SetQueryOperators(false))");
+        if (prefix_expansions) throw std::runtime_error("RetrieveBatchRanked: prefix queries are not read here (SetPrefixQueries(0))");
+        const Tokenised t = tokenise(queries, topicProbs, live_topic_probs);
+        const size_t nq = (size_t)t.nq, kk = (size_t)std::max(k, 1), kw = (size_t)std::max(k_window, 1);
+        std::vector<ss_hit> rows(nq * kw), page(nq * kk);
+        std::vector<int32_t> n_rows(nq), n_page(nq), mask_id(nq, -1);
+        std::vector<double> scores(nq * kk);
+        std::vector<ss_proximity> prox(nq * kw);
+        check(ss_score_topk_masked(scorer, t.nq, t.q_ptr.data(), t.q_terms.data(), t.p_ptr.data(), t.p_terms.data(), t.q_len.data(),
+                                   t.probs.empty() ? nullptr : t.probs.data(), mask_id.data(), k_window, rows.data(), n_rows.data()),
+              "ss_score_topk_masked");
+        std::vector<uint32_t> w_ptr{0}, w_terms;
+        for (size_t q = 0; q < nq; q++) {
+            w_terms.insert(w_terms.end(), t.q_terms.begin() + t.q_ptr[q], t.q_terms.begin() + t.q_ptr[q + 1]);
+            for (uint32_t i = t.p_ptr[q]; i < t.p_ptr[q + 1] && w_terms.size() - w_ptr.back() < (size_t)SS_MAX_QUERY_TERMS; i++)
+                w_terms.push_back(t.p_terms[i]);
+            w_ptr.push_back((uint32_t)w_terms.size());
+        }
+        check(ss_hit_proximity(scorer, t.nq, w_ptr.data(), w_terms.data(), k_window, rows.data(), n_rows.data(), prox.data()), "ss_hit_proximity");
+        check(ss_rerank_hits_by_model(scorer, rank_model, t.nq, k_window, rows.data(), n_rows.data(), prox.data(), nullptr, t.q_len.data(), first, k,
+                                      page.data(), n_page.data(), scores.data()), "ss_rerank_hits_by_model");
+        const std::vector<std::vector<Rank_combined>> ranks = to_ranks(t.nq, k, page, n_page);
+        std::vector<RankedPage> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Results = ranks[q];
+            out[q].Scores.assign(scores.begin() + q * kk, scores.begin() + q * kk + n_page[q]);
         }
         return out;
     }
