@@ -1685,6 +1685,95 @@ func (s *Scorer) RerankHitsByVector(qvec []int8, hits [][]Hit, first, k int) ([]
 	return out, outVals, nil
 }
 
+// SetDocTokens registers the token vectors of every doc (ss_scorer_set_doc_tokens): the tokens of doc d are rows tokPtr[d] ..
+// tokPtr[d+1] of tok, each of dim int8 values, dim a multiple of 64 up to C.SS_MAX_VEC_DIM.  dim 0 clears.  Independent of
+// SetDocVectors.  Register it again after an index update, like the vectors.
+func (s *Scorer) SetDocTokens(dim int, tokPtr []uint64, tok []int8) error {
+	if dim > 0 && len(tok) > 0 {
+		if uint64(len(tokPtr)) != s.nDocs+1 {
+			return fmt.Errorf("SetDocTokens: %d pointer entries for %d docs", len(tokPtr), s.nDocs)
+		}
+		if uint64(len(tok)) < tokPtr[s.nDocs]*uint64(dim) {
+			return fmt.Errorf("SetDocTokens: %d values for %d tokens of dim %d", len(tok), tokPtr[s.nDocs], dim)
+		}
+	}
+	rc := C.ss_scorer_set_doc_tokens(s.h, C.int32_t(dim), u64p(tokPtr), i8p(tok))
+	return statusErr(s.ctx, rc, "ss_scorer_set_doc_tokens")
+}
+
+// maxSimQueries flattens the queries' token vectors: qtPtr[q] .. qtPtr[q+1] are the rows of query q.
+func maxSimQueries(qtok [][][]int8) ([]uint32, []int8) {
+	qtPtr := make([]uint32, len(qtok)+1)
+	var flat []int8
+	for q, toks := range qtok {
+		for _, v := range toks {
+			flat = append(flat, v...)
+		}
+		qtPtr[q+1] = qtPtr[q] + uint32(len(toks))
+	}
+	return qtPtr, flat
+}
+
+// HitMaxSimScores returns the late-interaction score of every hit under its query's token vectors (ss_hit_maxsim_scores): the
+// sum, over the query's tokens, of the best dot product among the doc's tokens; C.SS_NO_VEC_SCORE for a doc outside the table or
+// without tokens.  qtok[q]: at most C.SS_MAX_QUERY_TOKENS vectors of the table's dim.
+func (s *Scorer) HitMaxSimScores(qtok [][][]int8, hits [][]Hit) ([][]int32, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil
+	}
+	if len(qtok) != nq {
+		return nil, fmt.Errorf("HitMaxSimScores: %d queries for %d windows", len(qtok), nq)
+	}
+	qtPtr, flat := maxSimQueries(qtok)
+	in, nIn, kIn := vecWindow(hits)
+	vals := make([]int32, nq*kIn)
+	rc := C.ss_hit_maxsim_scores(s.h, C.int32_t(nq), u32p(qtPtr), i8p(flat), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn), i32p(vals))
+	if err := statusErr(s.ctx, rc, "ss_hit_maxsim_scores"); err != nil {
+		return nil, err
+	}
+	out := make([][]int32, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = append([]int32(nil), vals[q*kIn:q*kIn+len(hits[q])]...)
+	}
+	return out, nil
+}
+
+// RerankByMaxSim sorts every window stably by its rows' late-interaction scores under the query's token vectors, descending, rows
+// without a score last, and returns page [first, first+k) with the rows' scores (ss_rerank_hits_by_maxsim).
+func (s *Scorer) RerankByMaxSim(qtok [][][]int8, hits [][]Hit, first, k int) ([][]Hit, [][]int32, error) {
+	nq := len(hits)
+	if nq == 0 {
+		return nil, nil, nil
+	}
+	if len(qtok) != nq {
+		return nil, nil, fmt.Errorf("RerankByMaxSim: %d queries for %d windows", len(qtok), nq)
+	}
+	qtPtr, flat := maxSimQueries(qtok)
+	in, nIn, kIn := vecWindow(hits)
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_hit, nq*kk)
+	nHits, vals := make([]int32, nq), make([]int32, nq*kk)
+	rc := C.ss_rerank_hits_by_maxsim(s.h, C.int32_t(nq), u32p(qtPtr), i8p(flat), C.int32_t(kIn), (*C.ss_hit)(unsafe.Pointer(&in[0])), i32p(nIn),
+		C.int32_t(first), C.int32_t(k), (*C.ss_hit)(unsafe.Pointer(&raw[0])), i32p(nHits), i32p(vals))
+	if err := statusErr(s.ctx, rc, "ss_rerank_hits_by_maxsim"); err != nil {
+		return nil, nil, err
+	}
+	out, outVals := make([][]Hit, nq), make([][]int32, nq)
+	for q := 0; q < nq; q++ {
+		n := int(nHits[q])
+		out[q], outVals[q] = make([]Hit, n), append([]int32(nil), vals[q*kk:q*kk+n]...)
+		for i := 0; i < n; i++ {
+			r := raw[q*kk+i]
+			out[q][i] = Hit{uint32(r.doc), float64(r.title), float64(r.body), float64(r.pagerank), float64(r.final)}
+		}
+	}
+	return out, outVals, nil
+}
+
 // DivInfo says why a row of a diversified page was chosen (ss_div_info): its relevance and its largest similarity to the rows chosen
 // before it (C.SS_NO_VEC_SCORE for the first row; both C.SS_NO_VEC_SCORE for a doc outside the table).
 type DivInfo struct {

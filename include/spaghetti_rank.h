@@ -67,7 +67,9 @@ extern "C" {
  * holds every query term the doc has, and a window re-ranked by it);
  * SS_RANK_N_FEATURES, SS_MAX_RANK_FEATURES, SS_MAX_RANK_TREES, ss_tree_node, ss_rank_model, ss_rank_model_info, ss_rank_model_create /
  * _destroy / _get_info / _eval, ss_hit_features and ss_rerank_hits_by_model (learned ranking: the signals of a window's rows as a
- * feature matrix, a tree ensemble evaluated per row, a window re-ranked by its scores). */
+ * feature matrix, a tree ensemble evaluated per row, a window re-ranked by its scores);
+ * SS_MAX_QUERY_TOKENS, ss_scorer_set_doc_tokens, ss_hit_maxsim_scores and ss_rerank_hits_by_maxsim (one int8 vector per doc token and
+ * per query token: late-interaction MaxSim scores of a window's rows, a window re-ranked by them). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -1459,6 +1461,58 @@ int32_t ss_merge_hits(ss_ctx* ctx, int32_t n_q, int32_t n_parts, int32_t k, cons
  * recorded on the ctx stream around the LAST compute call of the given kind
  * (0 = ss_pr_step batch, 1 = ss_score_topk, 2 = ss_tfidf_build). */
 int32_t ss_last_kernel_ms(ss_ctx* ctx, int32_t kind, float* ms_out);
+
+/* Token vectors: late interaction (MaxSim).  Every call above sees a doc as one point (ss_scorer_set_doc_vectors); here a doc keeps one
+ * signed 8-bit vector per token or passage, a query does too, and a doc's score is the sum, over the query's token vectors, of the
+ * best dot product any of the doc's token vectors achieves.  It is a second stage: it scores or re-ranks a window that ss_score_topk*,
+ * ss_vector_topk[_probed] + ss_score_docs or ss_hybrid_topk produced.  No reference counterpart.
+ * The table: tok_ptr [n_docs + 1] (n_docs = the scorer's) and tok [tok_ptr[n_docs]][dim], the tokens of doc d at rows tok_ptr[d] ..
+ * tok_ptr[d + 1]; host or device memory, both copied.  dim is a multiple of 64 in [64, SS_MAX_VEC_DIM]; dim = 0 or tok = NULL clears
+ * the table.  It is independent of ss_scorer_set_doc_vectors' table (its own dim; neither call touches the other's table) and has that
+ * call's lifecycle: a new table replaces the old one after the scorer's outstanding work has finished with it, it lives as long as
+ * the scorer, and a call that fails leaves the old table in place.  tok_ptr is checked on the host, so the call may wait: NULL
+ * tok_ptr (unless the call clears), tok_ptr[0] != 0, a decreasing entry or a bad dim: SS_ERR_INVALID; a doc of 2^31 or more tokens:
+ * SS_ERR_UNSUPPORTED.  tok_ptr[n_docs] * dim bytes + 8 per doc: SS_ERR_OOM if that cannot be had.  Every int8 value is an ordinary
+ * value, -128 included; a doc may have no token.
+ * Defined bit for bit, with T_d = tok_ptr[d + 1] - tok_ptr[d] and m_q = qt_ptr[q + 1] - qt_ptr[q]:
+ *   dot(q, i, d, t) = the sum over c < dim of (int32)qtok[qt_ptr[q] + i][c] * (int32)tok[tok_ptr[d] + t][c]
+ *   maxsim(q, d)    = the sum over i < m_q of the max over t < T_d of dot(q, i, d, t), in exact 32-bit integer arithmetic
+ *                     (|maxsim| <= SS_MAX_QUERY_TOKENS * 2^24 = 2^30).  m_q == 0 gives 0.  A doc with T_d == 0, or doc >= n_docs, has NO
+ *                     score: SS_NO_VEC_SCORE (never a real score).  A token a doc does not have is never a zero vector: with every
+ *                     dot product negative the score is negative.
+ * ss_hit_maxsim_scores is ss_hit_vector_scores with that score: scores_out[q * k_in + j] = maxsim(q, hits[q * k_in + j].doc) for
+ * j < n_hits[q], SS_NO_VEC_SCORE for a row without a score; rows past n_hits[q] are left untouched; only .doc of a row is read.
+ * ss_rerank_hits_by_maxsim is ss_rerank_hits_by_vector with that score, its Window, Order and Output word for word: stable and paged
+ * (first, k), rows of equal score in window order, the same doc twice is two rows, rows without a score LAST in window order, the 40
+ * bytes of a row carried through (_pad included), scores_out[q * k + r] (nullable) the row's score, entries past n_hits_out[q] left
+ * untouched.
+ * Two consequences.  (1) With a token table of exactly one token per doc, equal to its doc vector, and one token per query, both
+ * calls return the bytes of ss_hit_vector_scores / ss_rerank_hits_by_vector.  (2) By hand, dim 64 with only coordinates 0 and 1
+ * non-zero: docs A = {(10,0), (0,3)}, B = {(4,4)}, C = {} and D = {(-5,-5), (-1,-9)}, query tokens {(1,0), (0,2)}: A = max(10, 0) +
+ * max(0, 6) = 16, B = 4 + 8 = 12, D = max(-5, -1) + max(-10, -18) = -11 (not 0: no padded lane counts), C none.  The window [D, C, B,
+ * A, doc 99] of that 4-doc table re-ranks to A, B, D, C, 99 with scores 16, 12, -11, SS_NO_VEC_SCORE, SS_NO_VEC_SCORE.
+ * Checks of the two scoring calls, all before anything is enqueued and with the outputs untouched: those of ss_hit_vector_scores /
+ * ss_rerank_hits_by_vector (with qt_ptr and qtok in qvec's place; qtok may be NULL when qt_ptr[n_q] == qt_ptr[0]); a decreasing qt_ptr:
+ * SS_ERR_INVALID; an m_q above SS_MAX_QUERY_TOKENS: SS_ERR_UNSUPPORTED; no token table registered: SS_ERR_STATE.  n_q == 0 is SS_OK
+ * and does nothing.
+ * qt_ptr is read on the host like q_ptr of the scoring calls (a device pointer costs one blocking copy).  Every other pointer may be
+ * host or device memory: when all of them are device memory the calls only enqueue on the ctx stream and NEVER wait (qt_ptr goes up
+ * through a pinned block the scorer owns); otherwise they stage through blocks the scorer owns and return when the outputs are
+ * written.  qtok that is host memory or not 16-byte aligned is copied into a block the scorer owns, as qvec is.
+ * k_maxsim_scores<QT> (QT = 1, 2, 4 tiles of 16 query-token slots, from the call's largest m_q): a workgroup of four waves belongs to
+ * one query and a run of its window rows and holds the query's token vectors in LDS; a wave takes a row at a time and multiplies the
+ * doc's tokens, 64 per step straight from memory, with the query tiles on the int8 matrix cores
+ * (__builtin_amdgcn_mfma_i32_16x16x64_i8), keeps a running max per query token with slots past T_d held at INT32_MIN, and sums the
+ * maxima of the slots below m_q.  A row whose doc has at least option "maxsim.wide_tokens" tokens (default 1024) is shared by the four
+ * waves, whose maxima are joined by integer max: the scores are the same bytes for every value.  No float, no atomics.  The re-rank
+ * sorts with ss_rerank_hits_by_vector's kernel.  Serialised on the ctx like every scoring call; no _submit / _collect form. */
+#define SS_MAX_QUERY_TOKENS 64
+int32_t ss_scorer_set_doc_tokens(ss_scorer* s, int32_t dim, const uint64_t* tok_ptr /*[n_docs+1]*/, const int8_t* tok /*[tok_ptr[n_docs]][dim]; dim 0 / NULL clears*/);
+int32_t ss_hit_maxsim_scores(ss_scorer* s, int32_t n_q, const uint32_t* qt_ptr /*[n_q+1]*/, const int8_t* qtok /*[qt_ptr[n_q]][dim]*/,
+                             int32_t k_in, const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t* scores_out /*[n_q][k_in]*/);
+int32_t ss_rerank_hits_by_maxsim(ss_scorer* s, int32_t n_q, const uint32_t* qt_ptr /*[n_q+1]*/, const int8_t* qtok /*[qt_ptr[n_q]][dim]*/, int32_t k_in,
+                                 const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
+                                 ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
 
 #ifdef __cplusplus
 }

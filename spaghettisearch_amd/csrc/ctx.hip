@@ -376,6 +376,9 @@ static const char* const k_option_names[] = {
     "vec.assign_batch",     // ss_vector_assign_lists: doc rows per batch of the top-1 search over the centroids (default 0: vector_lists_plan.hpp)
     "div.scratch_bytes",    // ss_diversify_hits: most bytes of Gram matrices in flight (default 256 MB: diversify_plan.hpp); the queries of a call
                             //    run in groups that fit, one query per group if not even one does; the rows are the same bytes for every value
+    "maxsim.wide_tokens",   // ss_hit_maxsim_scores / ss_rerank_hits_by_maxsim: a window row whose doc has at least this many tokens is shared by the
+                            //    four waves of its workgroup (default 1024: maxsim_plan.hpp; below 1 = the default, clamped to 2^30); the
+                            //    scores are the same bytes for every value
     "ftopk.runs",           // ss_field_topk: runs of consecutive doc blocks per query, one workgroup of k_field_select each (default 0: from the
                             //    device's compute units and the queries with a list: field_topk_plan.hpp), clamped to 1 .. the number of doc
                             //    blocks; tests force it to put run seams between any two blocks; the outputs are the same bytes for every value

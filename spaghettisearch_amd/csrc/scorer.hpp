@@ -54,6 +54,10 @@ namespace ss {
 int32_t vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged);
 void launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in,
                            int32_t* d_out, hipStream_t st);
+// vector.hip, for maxsim.hip: k_vec_sort_hits as ss_rerank_hits_by_vector launches it, over rows, counts and the scores of the window's
+// entries [n_q][k_in] (SS_NO_VEC_SCORE: a row without a score) in device memory; d_scores_out [n_q][k] may be NULL.  Enqueues only.
+void launch_vec_sort_hits(const int32_t* d_scores, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in, int32_t first,
+                          int32_t k, ss_hit* d_hits_out, int32_t* d_n_hits_out, int32_t* d_scores_out, hipStream_t st);
 // vector.hip, for vector_lists.hip: k_vec_topk and k_vec_merge as ss_vector_topk launches them, over any table [n_rows > 0][vec_dim] of
 // int8 rows in device memory, without masks: d_qvec [n_q][vec_dim] 16-byte aligned, rows and counts to device memory.  Enqueues only.
 int32_t vec_table_topk(ss_scorer* s, const char* who, const int8_t* table, uint64_t n_rows, int32_t n_q, const int8_t* d_qvec, int32_t k,
@@ -247,6 +251,21 @@ struct ss_scorer {
     // queries [group][pitch][pitch] (bounded by option "div.scratch_bytes"; the groups of a call re-use it in stream order) and the
     // rows' relevance from k_vec_hit_scores [n_q][k_in].
     ss::DevBuf<int32_t> d_div_gram, d_div_rel;
+    // ss_scorer_set_doc_tokens (maxsim.hip): tok [tok_rows][tok_dim] signed 8-bit token vectors, doc d's at rows tok_ptr[d] ..
+    // tok_ptr[d + 1]; tok_dim 0 = no table.  Independent of vec / vec_dim.  ss_hit_maxsim_scores / ss_rerank_hits_by_maxsim, grow-only and
+    // used on the context's stream: d_ms_q, query tokens that are host memory or not 16-byte aligned; d_ms_qptr, the call's qt_ptr (up
+    // through a pinned block whose last copy ev_ms_qptr stands behind); d_ms_scores, the re-rank's scores between its two kernels; the
+    // dynamic LDS already granted to k_maxsim_scores<QT>.
+    ss::DevBuf<int8_t> tok;
+    ss::DevBuf<uint64_t> tok_ptr;
+    int32_t tok_dim = 0;
+    uint64_t tok_rows = 0;
+    ss::DevBuf<int8_t> d_ms_q;
+    ss::DevBuf<uint32_t> d_ms_qptr;
+    ss::DevBuf<int32_t> d_ms_scores;
+    ss::PinBuf h_ms_qptr;
+    ss::Event ev_ms_qptr;
+    int ms_lds_attr[5] = {0, 0, 0, 0, 0};
     // ss_facet_counts (facet.hip): the device block of HOST outputs, totals | mask counts | bucket counts (grow-only; the call waits
     // before it returns)
     ss::DevBuf<uint32_t> d_facet_out;

@@ -502,23 +502,29 @@ int32_t rerank_impl(ss_scorer* s, int32_t n_q, const int8_t* qvec, int32_t k_in,
     SS_TRY(hw::rows_out_prepare(s, (size_t)n_q, (size_t)k, hits_out, n_hits_out, nullptr, scores_out, sizeof(int32_t), &o));
     launch_hit_scores(s, d_q, w, n_q, k_in, s->d_vec_scores.p, st);
     SS_HIP(ctx, hipGetLastError());
-    VecSortParams p{};
-    p.scores = s->d_vec_scores.p;
-    p.hits = w.hits;
-    p.n_hits = w.n_hits;
-    p.hits_out = o.hits;
-    p.n_hits_out = o.n_hits;
-    p.scores_out = static_cast<int32_t*>(o.extra);
-    p.k_in = (uint32_t)k_in; p.first = (uint32_t)first; p.k = (uint32_t)k;
-    if (k_in <= VS_SMALL * VS_SMALL_PER)
-        hipLaunchKernelGGL((k_vec_sort_hits<VS_SMALL, VS_SMALL_PER>), dim3((unsigned)n_q), dim3(VS_SMALL), 0, st, p);
-    else
-        hipLaunchKernelGGL((k_vec_sort_hits<VS_LARGE, VS_LARGE_PER>), dim3((unsigned)n_q), dim3(VS_LARGE), 0, st, p);
+    ss::launch_vec_sort_hits(s->d_vec_scores.p, w.hits, w.n_hits, n_q, k_in, first, k, o.hits, o.n_hits, static_cast<int32_t*>(o.extra), st);
     SS_HIP(ctx, hipGetLastError());
     return hw::rows_out_finish(s, o, w.staged);
 }
 
 }  // namespace
+
+// for maxsim.hip (scorer.hpp): the launch of k_vec_sort_hits as ss_rerank_hits_by_vector uses it
+void ss::launch_vec_sort_hits(const int32_t* d_scores, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in, int32_t first,
+                              int32_t k, ss_hit* d_hits_out, int32_t* d_n_hits_out, int32_t* d_scores_out, hipStream_t st) {
+    VecSortParams p{};
+    p.scores = d_scores;
+    p.hits = d_hits;
+    p.n_hits = d_n_hits;
+    p.hits_out = d_hits_out;
+    p.n_hits_out = d_n_hits_out;
+    p.scores_out = d_scores_out;
+    p.k_in = (uint32_t)k_in; p.first = (uint32_t)first; p.k = (uint32_t)k;
+    if (k_in <= VS_SMALL * VS_SMALL_PER)
+        hipLaunchKernelGGL((k_vec_sort_hits<VS_SMALL, VS_SMALL_PER>), dim3((unsigned)n_q), dim3(VS_SMALL), 0, st, p);
+    else
+        hipLaunchKernelGGL((k_vec_sort_hits<VS_LARGE, VS_LARGE_PER>), dim3((unsigned)n_q), dim3(VS_LARGE), 0, st, p);
+}
 
 // for hybrid.hip (scorer.hpp): the staging of the query vectors and the launch of k_vec_hit_scores, both as the calls above use them
 int32_t ss::vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged) {

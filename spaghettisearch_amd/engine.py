@@ -1494,6 +1494,78 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_sc
 
+    def set_doc_tokens(self, tok_ptr, tok) -> None:
+        """ss_scorer_set_doc_tokens: register the token vectors of every doc: tok_ptr uint64 [n_docs + 1] (torch: int64 of the same
+        bits), tok int8 [tok_ptr[n_docs]][dim] (numpy or torch, dim a multiple of 64 up to SS_MAX_VEC_DIM), doc d's tokens at rows
+        tok_ptr[d] .. tok_ptr[d + 1]; tok None clears.  Independent of set_doc_vectors.  Replaces the previous table once the scorer's
+        outstanding work is done."""
+        if tok is None:
+            check(self.ctx.lib.ss_scorer_set_doc_tokens(self.h, 0, None, None), self.ctx.h)
+            self.tok_dim = 0
+            return
+        tok_ptr, tok = _as(tok_ptr, "uint64"), _as(tok, "int8")
+        n_ptr = int(tok_ptr.numel() if _is_torch(tok_ptr) else tok_ptr.size)
+        if n_ptr != self.title.n_docs + 1:
+            raise ValueError(f"tok_ptr must have {self.title.n_docs + 1} entries, got {n_ptr}")
+        if tok.ndim != 2 or int(tok.shape[0]) < int(tok_ptr[-1]):
+            raise ValueError(f"token table must have shape [tok_ptr[n_docs] = {int(tok_ptr[-1])}][dim], got {tuple(tok.shape)}")
+        self.ctx.ready(tok_ptr, tok)
+        check(self.ctx.lib.ss_scorer_set_doc_tokens(self.h, int(tok.shape[1]), _ptr(tok_ptr), _ptr(tok)), self.ctx.h)
+        self.tok_dim = int(tok.shape[1])
+
+    def _qtok(self, qt_ptr, qtok, n_q: int):
+        """(qt_ptr, qtok) of a MaxSim call: qt_ptr uint32 [n_q + 1], qtok int8 [qt_ptr[n_q]][dim] (None: no query has a token)"""
+        qt_ptr, qtok = _as(qt_ptr, "uint32"), _as(qtok, "int8")
+        n_ptr = int(qt_ptr.numel() if _is_torch(qt_ptr) else qt_ptr.size)
+        if n_ptr != n_q + 1:
+            raise ValueError(f"qt_ptr must have n_q + 1 = {n_q + 1} entries, got {n_ptr}")
+        if qtok is not None:
+            dim = getattr(self, "tok_dim", 0)
+            if qtok.ndim != 2 or (dim and int(qtok.shape[1]) != dim) or int(qtok.shape[0]) < int(qt_ptr[-1]):
+                raise ValueError(f"query tokens must have shape [qt_ptr[n_q] = {int(qt_ptr[-1])}][{dim}], got {tuple(qtok.shape)}")
+        return qt_ptr, qtok
+
+    def hit_maxsim_scores(self, qt_ptr, qtok, hits, n_hits, k_in: Optional[int] = None, out=None):
+        """ss_hit_maxsim_scores: the late-interaction score of every row hits[q][: n_hits[q]] under the token vectors of query q (the
+        sum over the query's tokens of the best dot product among the doc's tokens) -> int32 [n_q][k_in] (SS_NO_VEC_SCORE for a row
+        outside the table or a doc without tokens; rows past n_hits[q] keep what the array held, zeros here).  qt_ptr uint32
+        [n_q + 1], read on the host; qtok int8 [qt_ptr[n_q]][dim].  out: the caller's array."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        qt_ptr, qtok = self._qtok(qt_ptr, qtok, n_q)
+        if out is None:
+            out = np.zeros((n_q, k_in), dtype=np.int32)
+        elif (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) < n_q * k_in * 4:
+            raise ValueError("output buffer too small")
+        self.ctx.ready(qt_ptr, qtok, hits, n_hits, out)
+        check(self.ctx.lib.ss_hit_maxsim_scores(self.h, n_q, _ptr(qt_ptr), _ptr(qtok), k_in, _ptr(hits), _ptr(n_hits), _ptr(out)), self.ctx.h)
+        if _is_torch(out) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()
+        return out
+
+    def rerank_hits_by_maxsim(self, qt_ptr, qtok, hits, n_hits, k: int, first: int = 0, k_in: Optional[int] = None, out=None,
+                              want_scores: bool = True):
+        """ss_rerank_hits_by_maxsim: every window hits[q][: n_hits[q]] sorted stably by its late-interaction score under the token
+        vectors of query q, descending (rows without a score last), page [first, first + k) -> (hits [n_q][k], n_hits [n_q], scores
+        [n_q][k] int32 | None).  qt_ptr / qtok as in hit_maxsim_scores; hits / n_hits, k_in as in collapse_hits.  out = (hits, n_hits,
+        scores | None): the caller's arrays, returned as they are; with device arrays throughout the library only enqueues."""
+        hits, n_hits, n_q, k_in = self._window(hits, n_hits, k_in)
+        qt_ptr, qtok = self._qtok(qt_ptr, qtok, n_q)
+        if out is None:
+            out = (np.zeros((n_q, int(k)), dtype=HIT_DTYPE), np.zeros(n_q, dtype=np.int32),
+                   np.zeros((n_q, int(k)), dtype=np.int32) if want_scores else None)
+        o_hits, o_n, o_sc = out
+        o_n, o_sc = _as(o_n, "int32"), _as(o_sc, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(o_hits) < n_q * int(k) * HIT_DTYPE.itemsize or nbytes(o_n) < n_q * 4
+                           or (o_sc is not None and nbytes(o_sc) < n_q * int(k) * 4)):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qt_ptr, qtok, hits, n_hits, o_hits, o_n, o_sc)
+        check(self.ctx.lib.ss_rerank_hits_by_maxsim(self.h, n_q, _ptr(qt_ptr), _ptr(qtok), k_in, _ptr(hits), _ptr(n_hits), int(first), int(k),
+                                                    _ptr(o_hits), _ptr(o_n), _ptr(o_sc)), self.ctx.h)
+        if _is_torch(o_hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return o_hits, o_n, o_sc
+
     def diversify_hits(self, qvec, hits, n_hits, k: int, w_rel: int, w_div: int, first: int = 0, k_in: Optional[int] = None, out=None,
                        want_info: bool = True):
         """ss_diversify_hits: every window hits[q][: n_hits[q]] re-ranked greedily, each next row the one with the largest

@@ -148,7 +148,7 @@ struct VectorHit {
     int32_t Score = 0;
 };
 
-// One page of a query's results re-ranked by vector score (DeviceIndex::RerankByVector).  Scores[i]: the score of Results[i],
+// One page of a query's results re-ranked by vector score (DeviceIndex::RerankByVector, RerankByMaxSim).  Scores[i]: the score of Results[i],
 // SS_NO_VEC_SCORE for a row whose doc hash the index does not hold.
 struct VectorRerankedPage {
     std::vector<Rank_combined> Results;
@@ -450,6 +450,10 @@ public:
     // creates, as the vectors are; a later SetDocVectors clears them.
     std::vector<int8_t> list_centroids;
     int n_vector_lists = 0;
+    // Doc tokens (SetDocTokens): doc hash -> its token vectors, each of doc_token_dim int8 values, kept by hash and registered again on
+    // every scorer this index creates, as the vectors are; independent of them.
+    std::map<std::string, std::vector<std::vector<int8_t>>> doc_tokens;
+    int doc_token_dim = 0;
     int near_dup_slots = 0;                         // SetNearDuplicates: the body table keeps MinHash signatures of this many slots (4 B each per doc)
     bool signatures_built = false;                  // the body table holds signatures that this object built and nothing has freed since
     // Term lexicon (SetLexicon): the word of every resident term id, on the device (ss_lexicon) and here for the answers; lex_freq
@@ -562,6 +566,7 @@ public:
         register_groups();
         register_fields();
         register_vectors();
+        register_tokens();
         build_doc_view();
         build_signatures();
     }
@@ -1039,6 +1044,44 @@ public:
         check(ss_scorer_set_doc_vectors(scorer, doc_vector_dim, table.data()), "ss_scorer_set_doc_vectors");
         register_vector_lists();
     }
+    // Doc tokens for RerankByMaxSim: doc hash -> its token vectors, all of one length (a multiple of 64 up to SS_MAX_VEC_DIM).  A doc
+    // the map does not name, or names with no vector, has no token and so no score; hashes the index does not hold are ignored.  An
+    // empty map clears the table.  Independent of SetDocVectors.
+    void SetDocTokens(const std::map<std::string, std::vector<std::vector<int8_t>>>& tokens) {
+        int dim = 0;
+        for (auto& kv : tokens)
+            for (auto& v : kv.second) {
+                if (dim == 0) dim = (int)v.size();
+                if ((int)v.size() != dim) throw std::runtime_error("SetDocTokens: token vectors of different lengths");
+            }
+        if (dim != 0 && (dim < 64 || dim > SS_MAX_VEC_DIM || dim % 64))
+            throw std::runtime_error("SetDocTokens: the length must be a multiple of 64 in [64, SS_MAX_VEC_DIM]");
+        doc_tokens = tokens;
+        doc_token_dim = dim;
+        register_tokens();
+    }
+    void register_tokens() {
+        using namespace spaghetti;
+        if (!scorer || !title) return;
+        if (doc_token_dim == 0) { check(ss_scorer_set_doc_tokens(scorer, 0, nullptr, nullptr), "ss_scorer_set_doc_tokens"); return; }
+        uint64_t n = 0, nt = 0, np = 0;
+        check(ss_index_get_info(title, &n, &nt, &np), "ss_index_get_info");
+        std::vector<const std::vector<std::vector<int8_t>>*> of_doc((size_t)n, nullptr);
+        for (auto& kv : doc_tokens) {
+            auto it = docs.id.find(kv.first);
+            if (it == docs.id.end() || it->second >= n) continue;
+            of_doc[it->second] = &kv.second;
+        }
+        std::vector<uint64_t> tok_ptr((size_t)n + 1, 0);
+        for (size_t d = 0; d < (size_t)n; d++) tok_ptr[d + 1] = tok_ptr[d] + (of_doc[d] ? of_doc[d]->size() : 0);
+        std::vector<int8_t> table((size_t)tok_ptr[n] * doc_token_dim + 1, 0);    // (+ 1: never an empty array, which would clear)
+        for (size_t d = 0; d < (size_t)n; d++) {
+            if (!of_doc[d]) continue;
+            size_t row = (size_t)tok_ptr[d];
+            for (auto& v : *of_doc[d]) std::copy(v.begin(), v.end(), table.begin() + (row++) * doc_token_dim);
+        }
+        check(ss_scorer_set_doc_tokens(scorer, doc_token_dim, tok_ptr.data(), table.data()), "ss_scorer_set_doc_tokens");
+    }
     // Vector lists for VectorSearchProbed: n_lists centroids of the vectors' length.  Every doc goes to the list of the centroid with
     // the largest integer dot product (ties to the lower list), assigned on the device; no centroids clears the lists.
     void SetVectorLists(int n_lists, const std::vector<std::vector<int8_t>>& centroids) {
@@ -1154,6 +1197,52 @@ public:
         }
         check(ss_rerank_hits_by_vector(scorer, (int32_t)nq, flat.data(), (int32_t)k_in, win.data(), n_rows.data(), first, k, page.data(),
                                        n_page.data(), scores.data()), "ss_rerank_hits_by_vector");
+        std::vector<VectorRerankedPage> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_page[q]; i++) {
+                out[q].Results.push_back(rows[q][page[q * kk + i]._pad]);
+                out[q].Scores.push_back(scores[q * kk + i]);
+            }
+        return out;
+    }
+
+    // A window of result rows per query re-ordered by late-interaction score (ss_rerank_hits_by_maxsim): the sum, over the query's
+    // token vectors, of the best dot product any of the doc's token vectors reaches; descending and stable; page [first, first + k).
+    // queryTokens[q]: at most SS_MAX_QUERY_TOKENS vectors of the tokens' length.  Rows whose doc has no token, or whose doc hash the
+    // index does not hold, come last with SS_NO_VEC_SCORE.
+    std::vector<VectorRerankedPage> RerankByMaxSim(const std::vector<std::vector<std::vector<int8_t>>>& queryTokens,
+                                                   const std::vector<std::vector<Rank_combined>>& rows, int first = 0, int k = 50) {
+        using namespace spaghetti;
+        if (doc_token_dim == 0) throw std::runtime_error("RerankByMaxSim: no doc tokens (SetDocTokens)");
+        const size_t nq = queryTokens.size(), kk = (size_t)std::max(k, 1);
+        if (rows.size() != nq) throw std::runtime_error("RerankByMaxSim: one window per query");
+        std::vector<uint32_t> qt_ptr(nq + 1, 0);
+        std::vector<int8_t> flat;
+        for (size_t q = 0; q < nq; q++) {
+            for (auto& v : queryTokens[q]) {
+                if ((int)v.size() != doc_token_dim) throw std::runtime_error("RerankByMaxSim: a query token vector of the wrong length");
+                flat.insert(flat.end(), v.begin(), v.end());
+            }
+            qt_ptr[q + 1] = qt_ptr[q] + (uint32_t)queryTokens[q].size();
+        }
+        size_t k_in = 1;
+        for (auto& r : rows) k_in = std::max(k_in, r.size());
+        std::vector<ss_hit> win(nq * k_in), page(nq * kk);
+        std::vector<int32_t> n_rows(nq), n_page(nq), scores(nq * kk);
+        for (size_t q = 0; q < nq; q++) {
+            n_rows[q] = (int32_t)rows[q].size();
+            for (size_t j = 0; j < rows[q].size(); j++) {
+                const Rank_combined& r = rows[q][j];
+                auto it = docs.id.find(r.DocHash);
+                ss_hit h{};
+                h.doc = it == docs.id.end() ? 0xFFFFFFFFu : it->second;
+                h._pad = (uint32_t)j;                                     // the window position: how the page finds its row again
+                h.title = r.TitleRank; h.body = r.BodyRank; h.pagerank = r.PageRank; h.final = r.FinalRank;
+                win[q * k_in + j] = h;
+            }
+        }
+        check(ss_rerank_hits_by_maxsim(scorer, (int32_t)nq, qt_ptr.data(), flat.data(), (int32_t)k_in, win.data(), n_rows.data(), first, k,
+                                       page.data(), n_page.data(), scores.data()), "ss_rerank_hits_by_maxsim");
         std::vector<VectorRerankedPage> out(nq);
         for (size_t q = 0; q < nq; q++)
             for (int i = 0; i < n_page[q]; i++) {
@@ -1356,6 +1445,7 @@ public:
                 try { di.register_groups(); } catch (...) {}                // (RetrieveBatchCollapsed then reports the missing table)
                 try { di.register_fields(); } catch (...) {}                // (RetrieveBatchFiltered then reports the missing table)
                 try { di.register_vectors(); } catch (...) {}               // (VectorSearch then reports the missing table)
+                try { di.register_tokens(); } catch (...) {}                // (RerankByMaxSim then reports the missing table)
                 try { di.build_doc_view(); } catch (...) {}                 // (SimilarPages then reports the missing view)
                 try { di.build_signatures(); } catch (...) {}               // (RetrieveBatchDeduped then reports the missing signatures)
             }
@@ -1478,6 +1568,7 @@ public:
         register_groups();
         register_fields();
         register_vectors();
+        register_tokens();
         build_doc_view();                                                 // (the deltas freed it)
         build_signatures();
         refresh_lexicon(ctx, forw[0], t_before);                          // new term ids: a new lexicon; otherwise the frequencies only
