@@ -1774,6 +1774,39 @@ func (s *Scorer) RerankByMaxSim(qtok [][][]int8, hits [][]Hit, first, k int) ([]
 	return out, outVals, nil
 }
 
+// MaxSimTopK returns per query the exact k best docs by late-interaction score over every doc that has a token, score descending
+// then doc ascending, among the docs of the registered allow-list maskID[q] (-1 / nil: every doc) (ss_maxsim_topk).  qtok[q]: at most
+// C.SS_MAX_QUERY_TOKENS vectors of the table's dim; a query without tokens scores every doc 0.
+func (s *Scorer) MaxSimTopK(qtok [][][]int8, maskID []int32, k int) ([][]VecHit, error) {
+	nq := len(qtok)
+	if nq == 0 {
+		return nil, nil
+	}
+	if maskID != nil && len(maskID) != nq {
+		return nil, fmt.Errorf("MaxSimTopK: %d mask ids for %d queries", len(maskID), nq)
+	}
+	qtPtr, flat := maxSimQueries(qtok)
+	kk := k
+	if kk < 1 {
+		kk = 1
+	}
+	raw := make([]C.ss_vec_hit, nq*kk)
+	nHits := make([]int32, nq)
+	rc := C.ss_maxsim_topk(s.h, C.int32_t(nq), u32p(qtPtr), i8p(flat), i32p(maskID), C.int32_t(k), (*C.ss_vec_hit)(unsafe.Pointer(&raw[0])), i32p(nHits))
+	if err := statusErr(s.ctx, rc, "ss_maxsim_topk"); err != nil {
+		return nil, err
+	}
+	out := make([][]VecHit, nq)
+	for q := 0; q < nq; q++ {
+		out[q] = make([]VecHit, nHits[q])
+		for i := range out[q] {
+			r := raw[q*kk+i]
+			out[q][i] = VecHit{uint32(r.doc), int32(r.score)}
+		}
+	}
+	return out, nil
+}
+
 // DivInfo says why a row of a diversified page was chosen (ss_div_info): its relevance and its largest similarity to the rows chosen
 // before it (C.SS_NO_VEC_SCORE for the first row; both C.SS_NO_VEC_SCORE for a doc outside the table).
 type DivInfo struct {

@@ -69,7 +69,8 @@ extern "C" {
  * _destroy / _get_info / _eval, ss_hit_features and ss_rerank_hits_by_model (learned ranking: the signals of a window's rows as a
  * feature matrix, a tree ensemble evaluated per row, a window re-ranked by its scores);
  * SS_MAX_QUERY_TOKENS, ss_scorer_set_doc_tokens, ss_hit_maxsim_scores and ss_rerank_hits_by_maxsim (one int8 vector per doc token and
- * per query token: late-interaction MaxSim scores of a window's rows, a window re-ranked by them). */
+ * per query token: late-interaction MaxSim scores of a window's rows, a window re-ranked by them);
+ * ss_maxsim_topk (the exact top k by that score over every doc of the token table). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -1513,6 +1514,43 @@ int32_t ss_hit_maxsim_scores(ss_scorer* s, int32_t n_q, const uint32_t* qt_ptr /
 int32_t ss_rerank_hits_by_maxsim(ss_scorer* s, int32_t n_q, const uint32_t* qt_ptr /*[n_q+1]*/, const int8_t* qtok /*[qt_ptr[n_q]][dim]*/, int32_t k_in,
                                  const ss_hit* hits /*[n_q][k_in]*/, const int32_t* n_hits /*[n_q]*/, int32_t first, int32_t k,
                                  ss_hit* hits_out /*[n_q][k]*/, int32_t* n_hits_out /*[n_q]*/, int32_t* scores_out /*[n_q][k], nullable*/);
+
+/* ss_maxsim_topk: a first stage of its own for token vectors: the exact top k of every query by maxsim(q, d) over ALL docs of the token
+ * table, not a re-rank of a window and not an approximate search.  No reference counterpart.  Defined bit for bit, with maxsim(q, d),
+ * T_d and m_q as above:
+ *   Candidates. Every doc d < n_docs with T_d >= 1 in the REGISTERED allow-list mask_id[q] (ss_scorer_set_doc_masks; -1 = every doc;
+ *               mask_id NULL = all -1).  A doc without tokens is never a candidate and never a row: no row carries SS_NO_VEC_SCORE.
+ *   Order.      maxsim(q, d) descending, then d ascending.
+ *   Output.     Row q = the first n_hits_out[q] = min(k, number of candidates) rows of that order as ss_vec_hit; entries past that are
+ *               left untouched.
+ *   Empty query. m_q == 0 scores every candidate 0: its row is the first k candidates by doc id.
+ * Three consequences.  (1) Row q equals ss_hit_maxsim_scores over all docs of the mask, sorted by (score descending, doc ascending),
+ * rows without a score dropped, cut at k.  (2) With a token table of exactly one token per doc, equal to its doc vector, and one token
+ * per query, the call returns the bytes of ss_vector_topk under the same masks and k.  (3) The known world above (docs A, B, D, and C
+ * without tokens) gives at k = 4 n_hits = 3 and the rows (A, 16), (B, 12), (D, -11).
+ * Checks, all before anything is enqueued and with the outputs untouched: those of ss_vector_topk (NULL handle, hits_out / n_hits_out
+ * NULL with n_q > 0, n_q < 0, k < 1, a mask_id below -1 or at / above n_masks: SS_ERR_INVALID) and NULL qt_ptr with n_q > 0, a decreasing
+ * qt_ptr, qtok NULL when the call has a query token: SS_ERR_INVALID; k > SS_MAX_TOPK, an m_q above SS_MAX_QUERY_TOKENS, more blocks of
+ * queries (65535) or chunks than one launch holds, a query whose token image, k + 64 candidate keys and the select's scratch exceed the
+ * LDS of a workgroup: SS_ERR_UNSUPPORTED; no token table registered: SS_ERR_STATE; the chunks' partial lists (n_q * chunks * k * 8 bytes,
+ * bounded by 256 MB unless option "maxsim.chunk_tokens" asks for more chunks) cannot be had: SS_ERR_OOM.  n_q == 0 is SS_OK and does
+ * nothing — on a scorer that has a token table: as in ss_hit_maxsim_scores and ss_vector_topk the table is asked for first, so without
+ * one n_q == 0 is SS_ERR_STATE too.  qtok may be NULL when the call has no query token.
+ * qt_ptr and mask_id are read on the host, as in the sibling calls (a device pointer costs one blocking copy).  qtok and the outputs
+ * may be host or device memory: with all of them on the device the call only enqueues on the ctx stream and NEVER waits — its plan
+ * uses only what the host knew when the table was registered (a cut table: the first doc at or behind every 64th token) — otherwise
+ * it stages through blocks the scorer owns and returns when the outputs are written.  The rows are what ss_score_docs takes:
+ * ss_maxsim_topk -> ss_score_docs -> ss_dedup_hits -> ss_explain_hits stays on one stream.
+ * k_maxsim_topk<QT> (maxsim_topk.hip; QT as in k_maxsim_scores): a workgroup of four waves owns a block of 16 / 8 / 4 / 2 / 1 queries —
+ * the most whose token images, candidate lists and the select's scratch fit the LDS — and a chunk of consecutive docs cut at doc
+ * boundaries by token count.  A wave takes a doc at a time, loads each 16-token tile of it once, as the doc has them, and multiplies
+ * it on the int8 matrix cores with the token tiles of every query of the block that may take the doc: the table is read once per block
+ * of queries.  A doc without tokens, or that no query of the block may take, costs no load.  A doc of at least "maxsim.wide_tokens"
+ * tokens is shared by the four waves.  Keys, lists, select and merge are ss_vector_topk's: a key names its doc, so the rows do not
+ * depend on which wave finishes first, nor on either option.  Serialised on the ctx like every scoring call; no _submit / _collect form. */
+int32_t ss_maxsim_topk(ss_scorer* s, int32_t n_q, const uint32_t* qt_ptr /*[n_q+1]*/, const int8_t* qtok /*[qt_ptr[n_q]][dim]*/,
+                       const int32_t* mask_id /*[n_q], NULL = all -1*/, int32_t k, ss_vec_hit* hits_out /*[n_q][k]*/,
+                       int32_t* n_hits_out /*[n_q]*/);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,7 @@ PROTOTYPES = {
     "ss_scorer_set_doc_tokens": (_i32, [_vp, _i32, _vp, _vp]),
     "ss_hit_maxsim_scores": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ss_rerank_hits_by_maxsim": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ss_maxsim_topk": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ss_diversify_hits": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_scorer_set_vector_lists": (_i32, [_vp, _i32, _vp, _vp]),
     "ss_vector_assign_lists": (_i32, [_vp, _i32, _vp, _vp, _vp]),

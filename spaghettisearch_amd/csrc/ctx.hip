@@ -378,7 +378,10 @@ static const char* const k_option_names[] = {
                             //    run in groups that fit, one query per group if not even one does; the rows are the same bytes for every value
     "maxsim.wide_tokens",   // ss_hit_maxsim_scores / ss_rerank_hits_by_maxsim: a window row whose doc has at least this many tokens is shared by the
                             //    four waves of its workgroup (default 1024: maxsim_plan.hpp; below 1 = the default, clamped to 2^30); the
-                            //    scores are the same bytes for every value
+                            //    scores are the same bytes for every value; ss_maxsim_topk shares a doc of that many tokens likewise
+    "maxsim.chunk_tokens",  // ss_maxsim_topk: doc tokens per chunk of k_maxsim_topk, rounded up to a multiple of 64 (default 0: from the device's
+                            //    compute units, the query blocks and a bound on the partial lists: maxsim_topk_plan.hpp); tests set it to 64
+                            //    to put chunk seams between any two docs; the rows are the same bytes for every value
     "ftopk.runs",           // ss_field_topk: runs of consecutive doc blocks per query, one workgroup of k_field_select each (default 0: from the
                             //    device's compute units and the queries with a list: field_topk_plan.hpp), clamped to 1 .. the number of doc
                             //    blocks; tests force it to put run seams between any two blocks; the outputs are the same bytes for every value

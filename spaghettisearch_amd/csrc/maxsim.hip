@@ -20,6 +20,7 @@
 // paging checks and the outputs' way back are hit_window.hpp's; what needs no device is maxsim_plan.hpp's.
 #include "hit_window.hpp"
 #include "maxsim_plan.hpp"
+#include "maxsim_topk_plan.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -368,6 +369,8 @@ int32_t set_doc_tokens_impl(ss_scorer* s, int32_t dim, const uint64_t* tok_ptr, 
     ss::DevBuf<int8_t> nb;
     ss::DevBuf<uint64_t> nbp;
     std::vector<uint64_t> h_ptr;
+    ss::DevBuf<uint32_t> ncut;                                                    // ss_maxsim_topk's cut table (maxsim_topk_plan.hpp)
+    std::vector<uint32_t> h_cut;
     const size_t nd = (size_t)s->n_docs;
     size_t rows = 0, bytes = 0;
     if (!clear) {
@@ -381,6 +384,8 @@ int32_t set_doc_tokens_impl(ss_scorer* s, int32_t dim, const uint64_t* tok_ptr, 
         bytes = rows * (size_t)dim;
         hipError_t e = nb.alloc(std::max<size_t>(bytes, 16));                     // (a failure here leaves the old table in place)
         if (e == hipSuccess) e = nbp.alloc(nd + 1);
+        if (!(s->n_docs >> 32)) ss::mtp::build_cuts(h_ptr.data(), nd, &h_cut);     // (doc ids of 32 bits; without it ss_maxsim_topk refuses)
+        if (e == hipSuccess && !h_cut.empty()) e = ncut.alloc(h_cut.size());
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return ctx->fail(e == hipErrorOutOfMemory ? SS_ERR_OOM : SS_ERR_HIP, "%s: no device memory for %zu bytes", who, bytes + (nd + 1) * 8);
@@ -393,21 +398,41 @@ int32_t set_doc_tokens_impl(ss_scorer* s, int32_t dim, const uint64_t* tok_ptr, 
     if (clear) {
         s->tok.release();
         s->tok_ptr.release();
+        s->tok_cut.release();
+        s->tok_slices = 0;
         s->tok_dim = 0;
         s->tok_rows = 0;
         return SS_OK;
     }
     if (bytes) SS_HIP(ctx, hipMemcpyAsync(nb.p, tok, bytes, hipMemcpyDefault, ctx->stream));
     SS_HIP(ctx, hipMemcpyAsync(nbp.p, h_ptr.data(), (nd + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (!h_cut.empty()) SS_HIP(ctx, hipMemcpyAsync(ncut.p, h_cut.data(), h_cut.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     SS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->tok = std::move(nb);
     s->tok_ptr = std::move(nbp);
+    s->tok_cut = std::move(ncut);
+    s->tok_slices = h_cut.empty() ? 0 : h_cut.size() - 1;
     s->tok_dim = dim;
     s->tok_rows = rows;
     return SS_OK;
 }
 
 }  // namespace
+
+// for maxsim_topk.hip (scorer.hpp): the host checks and the staging of a call's query tokens, both as the calls above use them
+int32_t ss::maxsim_check_query_tokens(ss_ctx* ctx, const char* entry, int32_t n_q, const uint32_t* qt_ptr, const int8_t* qtok,
+                                      std::vector<uint32_t>* h_ptr, uint32_t* qt) {
+    QueryTokens t;
+    SS_TRY(fetch_query_tokens(ctx, entry, n_q, qt_ptr, qtok, &t));
+    *h_ptr = std::move(t.h_ptr);
+    *qt = t.qt;
+    return SS_OK;
+}
+int32_t ss::maxsim_query_tokens_to_device(ss_scorer* s, const std::vector<uint32_t>& h_ptr, const int8_t* qtok, const int8_t** d_qtok, bool* staged) {
+    QueryTokens t;
+    t.h_ptr = h_ptr;
+    return query_tokens_to_device(s, t, qtok, d_qtok, staged);
+}
 
 extern "C" {
 

@@ -58,6 +58,16 @@ void launch_vec_hit_scores(ss_scorer* s, const int8_t* d_qvec, const ss_hit* d_h
 // entries [n_q][k_in] (SS_NO_VEC_SCORE: a row without a score) in device memory; d_scores_out [n_q][k] may be NULL.  Enqueues only.
 void launch_vec_sort_hits(const int32_t* d_scores, const ss_hit* d_hits, const int32_t* d_n_hits, int32_t n_q, int32_t k_in, int32_t first,
                           int32_t k, ss_hit* d_hits_out, int32_t* d_n_hits_out, int32_t* d_scores_out, hipStream_t st);
+// vector.hip, for maxsim_topk.hip: k_vec_merge as ss_vector_topk launches it, one workgroup per query over its n_chunks * k partial keys
+// (unused slots 0) in device memory.  n_chunks * k < 2^32.  Enqueues only.
+void launch_vec_merge(const uint64_t* d_part, uint32_t n_chunks, int32_t n_q, int32_t k, ss_vec_hit* d_hits_out, int32_t* d_n_hits_out,
+                      hipStream_t st);
+// maxsim.hip, for maxsim_topk.hip: qt_ptr fetched to the host and checked with qtok as ss_hit_maxsim_scores checks them (*qt: the tiles of
+// 16 query-token slots the call's largest m_q needs; enqueues nothing that writes), and the query tokens 16-byte aligned on the device
+// with qt_ptr rebased in s->d_ms_qptr (*staged is set when they came from host memory, so the call waits before it returns)
+int32_t maxsim_check_query_tokens(ss_ctx* ctx, const char* entry, int32_t n_q, const uint32_t* qt_ptr, const int8_t* qtok,
+                                  std::vector<uint32_t>* h_ptr, uint32_t* qt);
+int32_t maxsim_query_tokens_to_device(ss_scorer* s, const std::vector<uint32_t>& h_ptr, const int8_t* qtok, const int8_t** d_qtok, bool* staged);
 // vector.hip, for vector_lists.hip: k_vec_topk and k_vec_merge as ss_vector_topk launches them, over any table [n_rows > 0][vec_dim] of
 // int8 rows in device memory, without masks: d_qvec [n_q][vec_dim] 16-byte aligned, rows and counts to device memory.  Enqueues only.
 int32_t vec_table_topk(ss_scorer* s, const char* who, const int8_t* table, uint64_t n_rows, int32_t n_q, const int8_t* d_qvec, int32_t k,
@@ -266,6 +276,17 @@ struct ss_scorer {
     ss::PinBuf h_ms_qptr;
     ss::Event ev_ms_qptr;
     int ms_lds_attr[5] = {0, 0, 0, 0, 0};
+    // ss_maxsim_topk (maxsim_topk.hip): tok_cut [tok_slices + 1], the first doc at or behind every multiple of mtp::SLICE_TOKENS tokens
+    // (maxsim_topk_plan.hpp; built, freed and replaced with the token table; tok_slices 0 = a table without a token, or none).  Grow-only
+    // and used on the context's stream: the chunks' partial key lists, the queries' mask ids (up through a
+    // pinned block whose last copy ev_mst_mid stands behind) and the device blocks of HOST hits_out / n_hits_out.
+    ss::DevBuf<uint32_t> tok_cut;
+    uint64_t tok_slices = 0;
+    ss::DevBuf<uint64_t> d_mst_part;
+    ss::DevBuf<int32_t> d_mst_mid, d_mst_n;
+    ss::DevBuf<ss_vec_hit> d_mst_hits;
+    ss::PinBuf h_mst_mid;
+    ss::Event ev_mst_mid;
     // ss_facet_counts (facet.hip): the device block of HOST outputs, totals | mask counts | bucket counts (grow-only; the call waits
     // before it returns)
     ss::DevBuf<uint32_t> d_facet_out;

@@ -526,6 +526,18 @@ void ss::launch_vec_sort_hits(const int32_t* d_scores, const ss_hit* d_hits, con
         hipLaunchKernelGGL((k_vec_sort_hits<VS_LARGE, VS_LARGE_PER>), dim3((unsigned)n_q), dim3(VS_LARGE), 0, st, p);
 }
 
+// for maxsim_topk.hip (scorer.hpp): the launch of k_vec_merge as ss_vector_topk uses it
+void ss::launch_vec_merge(const uint64_t* d_part, uint32_t n_chunks, int32_t n_q, int32_t k, ss_vec_hit* d_hits_out, int32_t* d_n_hits_out,
+                          hipStream_t st) {
+    VecMergeParams m{};
+    m.part = d_part;
+    m.n_slots = n_chunks * (uint32_t)k;
+    m.k = (uint32_t)k;
+    m.hits_out = d_hits_out;
+    m.n_hits_out = d_n_hits_out;
+    hipLaunchKernelGGL(k_vec_merge, dim3((unsigned)n_q), dim3(VM_TPB), 0, st, m);
+}
+
 // for hybrid.hip (scorer.hpp): the staging of the query vectors and the launch of k_vec_hit_scores, both as the calls above use them
 int32_t ss::vec_queries_to_device(ss_scorer* s, const int8_t* qvec, size_t bytes, const int8_t** out, bool* staged) {
     return qvec_to_device(s, qvec, bytes, out, staged);

@@ -1566,6 +1566,36 @@ class Scorer:
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return o_hits, o_n, o_sc
 
+    def maxsim_topk(self, qt_ptr, qtok, k: int, mask_id=None, device_out: bool = False, out=None):
+        """ss_maxsim_topk: per query the exact k best docs by late-interaction score over every doc of set_doc_tokens that has a
+        token (score descending, doc ascending), restricted to the registered allow-list mask_id[q] (-1 / None: every doc) ->
+        (hits VEC_HIT_DTYPE [n_q][k], n_hits int32 [n_q]).  qt_ptr uint32 [n_q + 1], read on the host; qtok int8 [qt_ptr[n_q]][dim]
+        (None: no query has a token).  device_out: torch device tensors (hits as int32 [n_q][k][2]: doc bits, score); out = (hits,
+        n_hits): the caller's arrays, returned as they are.  With device arrays throughout the library only enqueues."""
+        qt_ptr = _as(qt_ptr, "uint32")
+        n_q = int(qt_ptr.numel() if _is_torch(qt_ptr) else qt_ptr.size) - 1
+        if n_q < 0:
+            raise ValueError("qt_ptr must have n_q + 1 entries")
+        qt_ptr, qtok = self._qtok(qt_ptr, qtok, n_q)
+        mask_id = _as(mask_id, "int32")
+        if out is None:
+            if device_out:
+                import torch
+                dev = qtok.device if _is_torch(qtok) and qtok.is_cuda else torch.device("cuda", self.ctx.device_id)
+                out = (torch.zeros((n_q, int(k), 2), dtype=torch.int32, device=dev), torch.zeros(n_q, dtype=torch.int32, device=dev))
+            else:
+                out = (np.zeros((n_q, int(k)), dtype=VEC_HIT_DTYPE), np.zeros(n_q, dtype=np.int32))
+        hits, n_hits = out
+        n_hits = _as(n_hits, "int32")
+        nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+        if int(k) > 0 and (nbytes(hits) < n_q * int(k) * 8 or nbytes(n_hits) < n_q * 4):
+            raise ValueError("output buffers too small")
+        self.ctx.ready(qt_ptr, qtok, mask_id, hits, n_hits)
+        check(self.ctx.lib.ss_maxsim_topk(self.h, n_q, _ptr(qt_ptr), _ptr(qtok), _ptr(mask_id), int(k), _ptr(hits), _ptr(n_hits)), self.ctx.h)
+        if _is_torch(hits) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return hits, n_hits
+
     def diversify_hits(self, qvec, hits, n_hits, k: int, w_rel: int, w_div: int, first: int = 0, k_in: Optional[int] = None, out=None,
                        want_info: bool = True):
         """ss_diversify_hits: every window hits[q][: n_hits[q]] re-ranked greedily, each next row the one with the largest

@@ -275,6 +275,8 @@ PYBIND11_MODULE(_host, m) {
         .def("SetDocTokens", &retrieval::DeviceIndex::SetDocTokens, py::arg("tokens"))
         .def("RerankByMaxSim", &retrieval::DeviceIndex::RerankByMaxSim, py::arg("queryTokens"), py::arg("rows"), py::arg("first") = 0,
              py::arg("k") = 50)
+        .def("MaxSimSearch", &retrieval::DeviceIndex::MaxSimSearch, py::arg("queryTokens"), py::arg("k") = 50,
+             py::arg("masks") = std::vector<std::string>())
         .def("DiversifyByVector", &retrieval::DeviceIndex::DiversifyByVector, py::arg("queryVectors"), py::arg("rows"), py::arg("w_rel"),
              py::arg("w_div"), py::arg("first") = 0, py::arg("k") = 50)
         .def("ScoreDocs", [](retrieval::DeviceIndex& di, const std::string& query, const std::vector<std::string>& docHashes) {

@@ -1252,6 +1252,44 @@ public:
         return out;
     }
 
+    // The k docs with the highest late-interaction score under each query's token vectors, over every doc that has a token
+    // (ss_maxsim_topk: exact, score descending, then doc id ascending), by doc name.  queryTokens[q] as in RerankByMaxSim (an empty
+    // query scores every doc 0); masks: empty, or one name per query ("" = every doc) of a mask of SetDocMasks.
+    std::vector<std::vector<VectorHit>> MaxSimSearch(const std::vector<std::vector<std::vector<int8_t>>>& queryTokens, int k = 50,
+                                                     const std::vector<std::string>& masks = {}) {
+        using namespace spaghetti;
+        if (doc_token_dim == 0) throw std::runtime_error("MaxSimSearch: no doc tokens (SetDocTokens)");
+        const size_t nq = queryTokens.size();
+        if (!masks.empty() && masks.size() != nq) throw std::runtime_error("MaxSimSearch: one mask name per query");
+        std::vector<uint32_t> qt_ptr(nq + 1, 0);
+        std::vector<int8_t> flat;
+        for (size_t q = 0; q < nq; q++) {
+            for (auto& v : queryTokens[q]) {
+                if ((int)v.size() != doc_token_dim) throw std::runtime_error("MaxSimSearch: a query token vector of the wrong length");
+                flat.insert(flat.end(), v.begin(), v.end());
+            }
+            qt_ptr[q + 1] = qt_ptr[q] + (uint32_t)queryTokens[q].size();
+        }
+        std::vector<int32_t> mask_id(nq, -1);
+        for (size_t q = 0; q < masks.size(); q++) {
+            if (masks[q].empty()) continue;
+            auto it = mask_index.find(masks[q]);
+            if (it == mask_index.end()) throw std::runtime_error("MaxSimSearch: no doc mask named '" + masks[q] + "' (SetDocMasks)");
+            mask_id[q] = it->second;
+        }
+        std::vector<ss_vec_hit> hits(nq * (size_t)std::max(k, 1));
+        std::vector<int32_t> n_hits(nq);
+        check(ss_maxsim_topk(scorer, (int32_t)nq, qt_ptr.data(), flat.empty() ? nullptr : flat.data(), mask_id.data(), k, hits.data(),
+                             n_hits.data()), "ss_maxsim_topk");
+        std::vector<std::vector<VectorHit>> out(nq);
+        for (size_t q = 0; q < nq; q++)
+            for (int i = 0; i < n_hits[q]; i++) {
+                const ss_vec_hit& h = hits[q * (size_t)k + i];
+                out[q].push_back(VectorHit{docs.name[h.doc], h.score});
+            }
+        return out;
+    }
+
     // A window of result rows per query re-ranked greedily (ss_diversify_hits): every next row is the one with the largest w_rel *
     // relevance - w_div * (largest similarity of its doc vector to a row already chosen), of equal values the earlier row; page
     // [first, first + k).  Relevance is the row's score under the query's vector, or, with queryVectors EMPTY, minus its position in the
