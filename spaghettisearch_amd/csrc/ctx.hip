@@ -383,7 +383,7 @@ static const char* const k_option_names[] = {
                             //    compute units, the query blocks and a bound on the partial lists: maxsim_topk_plan.hpp); tests set it to 64
                             //    to put chunk seams between any two docs; the rows are the same bytes for every value
     "ftopk.runs",           // ss_field_topk: runs of consecutive doc blocks per query, one workgroup of k_field_select each (default 0: from the
-                            //    device's compute units and the queries with a list: field_topk_plan.hpp), clamped to 1 .. the number of doc
+                            //    device's compute units and the queries with a list: match_set_plan.hpp), clamped to 1 .. the number of doc
                             //    blocks; tests force it to put run seams between any two blocks; the outputs are the same bytes for every value
     "ftopk.scratch_bytes",  // ... most bytes of partial lists in flight (default 256 MB); the queries of a call run in groups that fit, one
                             //    query per group if not even one does; the outputs are the same bytes for every value

@@ -197,6 +197,24 @@ inline int32_t entries_out_finish(ss_scorer* s, const EntriesOut& o, const Windo
     return SS_OK;
 }
 
+// One output array of a call whose results came back to the host in one block (`src`: the array's place in it), to the caller's `dst` in
+// host or device memory: copy_written's entries — rows [n_q][stride] of `elem` bytes, of row q the first n_written[q] — or, n_written
+// NULL, all n_q x stride of them.  An array in device memory gets the same entries by copies that wait.
+inline hipError_t give_rows(void* dst, const unsigned char* src, size_t n_q, size_t stride, size_t elem, const int32_t* n_written) {
+    if (!ss::on_device(dst)) {
+        if (n_written) copy_written(dst, src, n_q, stride, elem, n_written);
+        else std::memcpy(dst, src, n_q * stride * elem);
+        return hipSuccess;
+    }
+    if (!n_written) return hipMemcpy(dst, src, n_q * stride * elem, hipMemcpyHostToDevice);
+    for (size_t q = 0; q < n_q; q++) {
+        const size_t o = q * stride * elem;
+        if (n_written[q] > 0)
+            if (const hipError_t e = hipMemcpy(static_cast<unsigned char*>(dst) + o, src + o, (size_t)n_written[q] * elem, hipMemcpyHostToDevice)) return e;
+    }
+    return hipSuccess;
+}
+
 // The queries' table of a call in the pinned block of `turn`: ptr [n_q + 1] rebased to 0 | the tokens | words_per_token - 1 more
 // words per token, left for the caller to fill before the upload.  Waits for the turn's last reader; enqueues nothing.
 struct QueryTable {

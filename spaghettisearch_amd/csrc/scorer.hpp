@@ -126,7 +126,7 @@ struct Turn {
     ss::Event wave_ev;                         // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     ss::Event slice_ev;                        // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
-    ss::PinBuf h_facet;                        // ss_facet_counts / ss_field_topk: the call's list table (and bucket table) go up through it (one set per turn,
+    ss::PinBuf h_facet;                        // ss_facet_counts / ss_field_topk / ss_top_groups (match_set.hpp): the list table (and bucket table) go up through it (one set per turn,
     ss::DevBuf<unsigned char> d_facet;         // free after the wait for batch_ev like the plan's)
 };
 
