@@ -1388,6 +1388,95 @@ func (s *Scorer) TopGroups(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTer
 	return out, nil
 }
 
+// FieldStat is one (query, field) entry of FieldStats: the smallest and largest value and the exact sum SumHi * 2^64 + SumLo (two's
+// complement) over the Count matches that have a value, and the Missing matches whose value is SS_NO_FIELD_VALUE.  Count 0: Min
+// math.MaxInt64, Max math.MinInt64.
+type FieldStat struct {
+	Min, Max int64
+	SumLo    uint64
+	SumHi    int64
+	Count    uint32
+	Missing  uint32
+}
+
+// FieldStatsRow is one query's entries from FieldStats, one per asked field, and the number of docs the query matches in all.
+type FieldStatsRow struct {
+	Fields  []FieldStat
+	Matches uint32
+}
+
+// FieldStats returns, per query and per field of fields (at most C.SS_MAX_DOC_FIELDS, repeats allowed), the range, the exact sum and the
+// missing count of the field over ALL docs FacetCounts counts for the same arguments (ss_field_stats).
+func (s *Scorer) FieldStats(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange,
+	fields []int32) ([]FieldStatsRow, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	nf := len(fields)
+	stats, nMatch := make([]C.ss_field_stat, nq*nf+1), make([]uint32, nq)
+	rp, keepR := docRanges(rng)
+	rc := C.ss_field_stats(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr),
+		u32p(excTerms), u32p(rngPtr), rp, C.int32_t(nf), i32p(fields), &stats[0], u32p(nMatch))
+	runtime.KeepAlive(keepR)
+	if err := statusErr(s.ctx, rc, "ss_field_stats"); err != nil {
+		return nil, err
+	}
+	out := make([]FieldStatsRow, nq)
+	for q := 0; q < nq; q++ {
+		row := make([]FieldStat, nf)
+		for i := 0; i < nf; i++ {
+			r := stats[q*nf+i]
+			row[i] = FieldStat{int64(r.min), int64(r.max), uint64(r.sum_lo), int64(r.sum_hi), uint32(r.count), uint32(r.missing)}
+		}
+		out[q] = FieldStatsRow{row, nMatch[q]}
+	}
+	return out, nil
+}
+
+// FieldHistogramRow is one query's bins from FieldHistogram: Counts per bin, the matches below the first bin, at or above the end of the
+// last one and without a value, and the number of docs the query matches in all (the sum of the others).
+type FieldHistogramRow struct {
+	Counts  []uint32
+	Below   uint32
+	Above   uint32
+	Missing uint32
+	Matches uint32
+}
+
+// FieldHistogram counts, per query, the docs FacetCounts counts for the same arguments in every bin of a doc field (ss_field_histogram).
+// edges nil: nBins bins of the given width (1 .. 2^64-1) from origin.  edges [nBins+1], strictly ascending: bin b holds
+// edges[b] <= value < edges[b+1]; origin and width are ignored.  nBins may not exceed C.SS_MAX_HIST_BINS.
+func (s *Scorer) FieldHistogram(qPtr, qTerms []uint32, maskID []int32, reqPtr, reqTerms, excPtr, excTerms, rngPtr []uint32, rng []DocRange,
+	field int, origin int64, width uint64, edges []int64, nBins int) ([]FieldHistogramRow, error) {
+	nq := len(qPtr) - 1
+	if nq <= 0 {
+		return nil, nil
+	}
+	if edges != nil && len(edges) < nBins+1 {
+		return nil, fmt.Errorf("ss_field_histogram: %d edges for %d bins", len(edges), nBins)
+	}
+	nb := nBins
+	if nb < 1 {
+		nb = 1
+	}
+	counts, tails := make([]uint32, nq*nb), make([]C.ss_hist_tail, nq)
+	rp, keepR := docRanges(rng)
+	rc := C.ss_field_histogram(s.h, C.int32_t(nq), u32p(qPtr), u32p(qTerms), i32p(maskID), u32p(reqPtr), u32p(reqTerms), u32p(excPtr),
+		u32p(excTerms), u32p(rngPtr), rp, C.int32_t(field), C.int64_t(origin), C.uint64_t(width), i64p(edges), C.int32_t(nBins),
+		u32p(counts), &tails[0])
+	runtime.KeepAlive(keepR)
+	if err := statusErr(s.ctx, rc, "ss_field_histogram"); err != nil {
+		return nil, err
+	}
+	out := make([]FieldHistogramRow, nq)
+	for q := 0; q < nq; q++ {
+		t := tails[q]
+		out[q] = FieldHistogramRow{counts[q*nb : (q+1)*nb], uint32(t.below), uint32(t.above), uint32(t.missing), uint32(t.n_match)}
+	}
+	return out, nil
+}
+
 // SortHitsByField sorts every window stably by a doc field, ascending or descending, rows outside the table last, and returns page
 // [first, first+k) with the rows' values (ss_sort_hits_by_field).  Only the hits' Doc is read to decide anything.
 func (s *Scorer) SortHitsByField(hits [][]Hit, field int, descending bool, first, k int) ([][]Hit, [][]int64, error) {

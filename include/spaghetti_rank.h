@@ -70,7 +70,9 @@ extern "C" {
  * feature matrix, a tree ensemble evaluated per row, a window re-ranked by its scores);
  * SS_MAX_QUERY_TOKENS, ss_scorer_set_doc_tokens, ss_hit_maxsim_scores and ss_rerank_hits_by_maxsim (one int8 vector per doc token and
  * per query token: late-interaction MaxSim scores of a window's rows, a window re-ranked by them);
- * ss_maxsim_topk (the exact top k by that score over every doc of the token table). */
+ * ss_maxsim_topk (the exact top k by that score over every doc of the token table);
+ * SS_MAX_HIST_BINS, ss_field_stat, ss_hist_tail, ss_field_stats and ss_field_histogram (over ALL docs a query matches: the smallest and
+ * largest value, the exact sum and the number of missing values of a doc field, and the matches per bin of a field). */
 #define SS_ABI_VERSION 4
 
 enum {
@@ -1133,6 +1135,88 @@ int32_t ss_top_groups(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const ui
                       uint32_t* n_groups_out    /*[n_q], nullable*/,
                       uint32_t* n_ungrouped_out /*[n_q], nullable*/,
                       uint32_t* n_match_out     /*[n_q], nullable*/);
+
+/* ss_field_stats and ss_field_histogram: the range, the sum and a timeline of a doc field over ALL docs a query matches -- "pages from
+ * 2009 to 2024", "sizes 2 KB to 14 MB, 61 KB on average" to size a date or size slider, "matches per month over twenty years" to draw
+ * one.  No reference counterpart.  ss_field_topk gives the smallest or largest value only as the head of a selection and no sum;
+ * ss_facet_counts stops at SS_MAX_FACET_BUCKETS nested buckets.  Both calls are defined bit for bit; no float is involved, every
+ * operation is exact and associative, and no order of arrival can show:
+ *   M(q)        = exactly the set ss_facet_counts defines for the same q_*, mask_id, req_*, exc_* and rng_* arguments.
+ *   Missing.    In THESE TWO calls SS_NO_FIELD_VALUE means "no value": a doc of M(q) whose value in the field is SS_NO_FIELD_VALUE is
+ *               counted in `missing` and takes part in nothing else -- not in min, max or sum, not in any bin, below or above, not even
+ *               with origin == INT64_MIN.  Every other field call (range clauses, ss_facet_counts' buckets, ss_field_topk,
+ *               ss_sort_hits_by_field) keeps treating it as the ordinary value INT64_MIN: a clause [INT64_MIN, x] still lets such docs
+ *               into M(q), and they are then counted here as missing.
+ *   ss_field_stats      stats_out[q * n_stat_fields + i], for field fields[i] (1 <= n_stat_fields <= SS_MAX_DOC_FIELDS; a repeated field
+ *               is allowed and gives equal entries): count = the docs of M(q) with a value, missing = those without, count + missing =
+ *               |M(q)|; min / max over the docs with a value as signed 64-bit, INT64_MAX / INT64_MIN when count == 0; sum_hi : sum_lo =
+ *               their exact sum as a 128-bit two's complement integer.  A query with an empty M(q), one without a usable term included,
+ *               gets the identity entry {INT64_MAX, INT64_MIN, 0, 0, 0, 0}.  n_match_out[q] (nullable) = |M(q)|, the number
+ *               ss_facet_counts writes.  Every entry of every query is written.
+ *   ss_field_histogram, fixed width (edges == NULL, width >= 1).  A doc with value v: v < origin as signed 64-bit counts in `below`;
+ *               otherwise u = (uint64_t)v - (uint64_t)origin (exact: the difference of two int64 fits 64 unsigned bits), b = u / width;
+ *               b >= n_bins counts in `above`, else counts_out[q * n_bins + b]++.  width may be any value up to 2^64 - 1;
+ *               origin + n_bins * width is never formed in signed arithmetic.
+ *   ss_field_histogram, explicit edges (edges != NULL; origin and width are ignored): calendar months, log-scale sizes.
+ *               edges[0 .. n_bins] is strictly ascending as signed 64-bit; bin b is edges[b] <= v < edges[b + 1]; v < edges[0] counts
+ *               in `below`, v >= edges[n_bins] in `above`.
+ *   Histogram outputs.  1 <= n_bins <= SS_MAX_HIST_BINS.  All n_bins counters of every query are written, zeros included.  tails_out[q]
+ *               (nullable) = {below, above, missing, n_match}; the counters plus below, above and missing add up to n_match, the number
+ *               ss_facet_counts writes.  A query without a usable term gets zeros everywhere.
+ * Known answers: the 8 docs of ss_facet_counts' comment (field 0 = 10, 20, .. 80 for docs 0 .. 7; t0 = {1, 2, 5}, t1 = {2, 3}; m1 = {2, 5,
+ * 6}) and the query (t0, t1, t0, SS_UNKNOWN_TERM), M = {1, 2, 3, 5} with field-0 values 20, 30, 40, 60.  Stats of field 0: count 4,
+ * missing 0, min 20, max 60, sum 150.  With t1 required, M = {2, 3}: 2, 0, 30, 40, 70.  With mask_id 1 and the clause field 0 in [25, 65],
+ * M = {2, 5}: 2, 0, 30, 60, 90.  A second field that holds INT64_MAX for docs 1, 2, 3, SS_NO_FIELD_VALUE for doc 5 and 0 elsewhere, over
+ * M = {1, 2, 3, 5}: count 3, missing 1, min = max = INT64_MAX, sum = 3 (2^63 - 1): sum_hi 1, sum_lo 0x7FFFFFFFFFFFFFFD.  Two values of
+ * -1 sum to sum_lo 0xFFFFFFFFFFFFFFFE, sum_hi -1.  Histograms of field 0 over M = {1, 2, 3, 5}: origin 15, width 20, 2 bins: counts 2, 1,
+ * below 0, above 1.  Origin 35, width 20, 2 bins: 1, 1, below 2, above 0.  Edges {20, 40, 61}: 2, 2, below 0, above 0.  Edges {25, 30,
+ * 31}: 0, 1, below 1, above 2.
+ * Checks, all before anything is enqueued and with the outputs untouched: everything ss_facet_counts checks about its query, mask,
+ * constraint and range arrays, with its codes; NULL handle; n_q < 0; NULL q_ptr, stats_out or counts_out with n_q > 0; n_stat_fields < 1
+ * or NULL fields; a field outside [0, n_fields); n_bins < 1; width == 0 with edges == NULL; edges that are not strictly ascending:
+ * SS_ERR_INVALID; n_stat_fields > SS_MAX_DOC_FIELDS; n_bins > SS_MAX_HIST_BINS: SS_ERR_UNSUPPORTED; no field table registered:
+ * SS_ERR_STATE.  n_q == 0 (with a handle) is SS_OK and does nothing, whatever the other arguments are: that rule comes first.
+ * The query, constraint and range arrays, fields and edges are read on the host like every scoring call's (device pointers cost one
+ * blocking copy each).  The outputs may be host or device memory: when all given outputs are device memory the calls only enqueue on the
+ * ctx stream and NEVER wait; otherwise they go through a block the scorer owns and return when the outputs are written.
+ * k_field_stats gives a workgroup a run of consecutive 32768-doc blocks of one query: per block the match words as in k_group_count, per
+ * set bit one gather of value[field][d] per asked field; a thread keeps min, max, a 128-bit sum (a low word with carry, a high word) and
+ * the missing count per field in registers, the workgroup reduces them by wave shuffles and through LDS and writes one partial
+ * ss_field_stat per field; k_field_stats_merge folds the runs' partials per (query, field) and writes the identity entries of the
+ * queries without a list.  No atomics touch any stats output.  k_field_hist has k_group_count's shape with the bin computed from the
+ * gathered value: a shift for a width that is a power of two, else a multiply-high by a reciprocal computed on the host plus one fix-up
+ * (exact for every 64-bit u), u >= n_bins * width decided before any of it; a binary search over the edges otherwise (an LDS copy of
+ * up to 1025 edges, the staged array beyond).  A thread walks its docs in ascending order and merges consecutive equal bins into one
+ * add; the adds go to an LDS histogram that joins the query's zeroed counter row at the end of the run when n_bins is at most option
+ * "fstats.lds_bins" (default 8192, at most 8192, 0 = never), straight to the row by global atomic adds otherwise; both paths give the
+ * same bytes.  The row has n_bins + 4 counters (below, above, missing, matches behind the bins); k_field_hist_out copies rows and tails
+ * out.  Runs per query: option "fstats.runs" (0 = from the device and the batch); the partial entries or counter rows are bounded by
+ * option "fstats.scratch_bytes" (default 256 MB), the queries going in groups beyond it, at least one query per group.
+ * Serialised on the ctx like every scoring call.  There is no phrase form (no p_ptr) and no _submit / _collect form. */
+#define SS_MAX_HIST_BINS 65536
+typedef struct ss_field_stat {         /* 40 bytes */
+    int64_t  min, max;                 /* over the docs that have a value; INT64_MAX / INT64_MIN when count == 0 */
+    uint64_t sum_lo; int64_t sum_hi;   /* the exact sum as a 128-bit two's complement integer */
+    uint32_t count, missing;           /* docs of M(q) with value != / == SS_NO_FIELD_VALUE; count + missing == |M(q)| */
+} ss_field_stat;
+typedef struct ss_hist_tail { uint32_t below, above, missing, n_match; } ss_hist_tail;   /* 16 bytes */
+int32_t ss_field_stats(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                       const int32_t* mask_id,
+                       const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                       const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                       const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                       int32_t n_stat_fields, const int32_t* fields /*[n_stat_fields], host*/,
+                       ss_field_stat* stats_out /*[n_q][n_stat_fields]*/,
+                       uint32_t* n_match_out    /*[n_q], nullable*/);
+int32_t ss_field_histogram(ss_scorer* s, int32_t n_q, const uint32_t* q_ptr, const uint32_t* q_terms,
+                           const int32_t* mask_id,
+                           const uint32_t* req_ptr /*[n_q+1], NULL = none*/, const uint32_t* req_terms,
+                           const uint32_t* exc_ptr /*[n_q+1], NULL = none*/, const uint32_t* exc_terms,
+                           const uint32_t* rng_ptr /*[n_q+1], NULL = none*/, const ss_doc_range* rng,
+                           int32_t field, int64_t origin, uint64_t width,
+                           const int64_t* edges /*[n_bins + 1] or NULL, host*/, int32_t n_bins,
+                           uint32_t* counts_out    /*[n_q][n_bins]*/,
+                           ss_hist_tail* tails_out /*[n_q], nullable*/);
 
 /* Doc vectors: one signed 8-bit embedding per doc, the exact k nearest docs of a query vector, and a lexical result window re-ordered
  * by meaning.  No reference counterpart: every way the reference finds a page is a posting of a typed word.  Producing the embeddings

@@ -191,6 +191,8 @@ PROTOTYPES = {
     "ss_field_topk": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ss_scorer_group_values": (_i32, [_vp, _vp, _vp]),
     "ss_top_groups": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ss_field_stats": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ss_field_histogram": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_int64, C.c_uint64, _vp, _i32, _vp, _vp]),
     "ss_sort_hits_by_field": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ss_hit_fields": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "ss_scorer_set_doc_vectors": (_i32, [_vp, _i32, _vp]),

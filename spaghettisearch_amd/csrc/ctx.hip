@@ -393,6 +393,17 @@ static const char* const k_option_names[] = {
     "gtopk.runs",           // ... runs of consecutive doc blocks per query, one workgroup of k_group_count each (default 0: as "ftopk.runs")
     "gtopk.scratch_bytes",  // ... most bytes of counter rows in flight (default 256 MB); the queries of a call run in groups that fit, one
                             //    query per group if not even one does; the outputs are the same bytes for every value
+    "fstats.runs",          // ss_field_stats / ss_field_histogram: runs of consecutive doc blocks per query, one workgroup of k_field_stats or
+                            //    k_field_hist each (default 0: as "gtopk.runs")
+    "fstats.lds_bins",      // ss_field_histogram: k_field_hist counts through a histogram in LDS when n_bins is at most this (default 8192, which
+                            //    is also the most the histogram holds; 0: never), by global atomic adds otherwise; the outputs are the same
+                            //    bytes for every value
+    "fstats.scratch_bytes", // ... most bytes of partial entries (ss_field_stats) or counter rows (ss_field_histogram) in flight (default 256 MB);
+                            //    the queries of a call run in groups that fit, one query per group if not even one does; the outputs are
+                            //    the same bytes for every value
+    "fstats.plain_divide",  // ss_field_histogram: 1 = the bin of a width that is no power of two by a 64-bit `/` per matched doc, not by the
+                            //    host's reciprocal (default 0; for measuring the two against each other: the outputs are the same bytes;
+                            //    measured, DESIGN.md K4z: `/` is 2.4 to 4.5 % slower at 4096 bins, 0.3 to 2.4 % at 65536 bins)
 };
 
 int32_t ss_set_option(ss_ctx* ctx, const char* name, int64_t value) {

@@ -1,8 +1,9 @@
-// match_set.hpp — the HIP side of what ss_facet_counts (facet.hip), ss_field_topk (field_topk.hip) and ss_top_groups (group_topk.hip)
-// share; match_set_plan.hpp holds the pure host part.  DESIGN.md "K4s–u shared match-set code".
+// match_set.hpp — the HIP side of what ss_facet_counts (facet.hip), ss_field_topk (field_topk.hip), ss_top_groups (group_topk.hip) and
+// ss_field_stats / ss_field_histogram (field_stats.hip) share; match_set_plan.hpp holds the pure host part.  DESIGN.md "K4s–u shared
+// match-set code".
 //
 // M(q) = (the docs with a posting of any usable query term, title or body) AND (the allowed set ss_score_topk_filtered builds for the
-// query's mask id, required / excluded terms and range clauses) AND d < n_docs.  The three calls form it by this file alone: one host
+// query's mask id, required / excluded terms and range clauses) AND d < n_docs.  These calls form it by this file alone: one host
 // prologue (open_match_call: the list table and the allowed sets), one layout of the tables a kernel reads (stage_match_tables ->
 // MatchSetArgs) and one device walk of a 32768-doc block (steps 1 to 3 below).  So they agree about M(q) by construction;
 // test_agrees_with_facet_counts* check that it stays so.

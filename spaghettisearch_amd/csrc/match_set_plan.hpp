@@ -1,9 +1,9 @@
 // match_set_plan.hpp — what the calls over a query's whole match set M(q) share and that needs no device (ss_facet_counts, ss_field_topk,
-// ss_top_groups; DESIGN.md "K4s–u shared match-set code"): the codes a check returns, the cut of the docs into 32768-doc blocks and of a
-// query's blocks into runs, the groups of queries that share a scratch block, the launches that cover a grid, and the size and order of
-// the running best-K.  facet_plan.hpp, field_topk_plan.hpp and group_topk_plan.hpp add what is their own.  The constexpr functions are
-// compiled for both sides (match_set.hpp's device code calls them; the three plan harnesses under tests/ run them on the host under
-// ASan + UBSan).  Includes nothing of HIP.
+// ss_top_groups, ss_field_stats / ss_field_histogram; DESIGN.md "K4s–u shared match-set code"): the codes a check returns, the cut of the
+// docs into 32768-doc blocks and of a query's blocks into runs, the groups of queries that share a scratch block, the launches that
+// cover a grid, and the size and order of the running best-K.  facet_plan.hpp, field_topk_plan.hpp, group_topk_plan.hpp and
+// field_stats_plan.hpp add what is their own.  The constexpr functions are compiled for both sides (match_set.hpp's device code calls
+// them; the plan harnesses under tests/ run them on the host under ASan + UBSan).  Includes nothing of HIP.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -40,7 +40,7 @@ constexpr uint32_t word_valid(uint64_t w, uint64_t n_docs) {
 
 // ---- runs.  A query's blocks [0, n_blocks) are cut into R runs of consecutive blocks, one workgroup each.  The plan's own choice
 // fills the device: WG_PER_CU workgroups per compute unit over all active queries, at most MAX_AUTO_RUNS (a merge reads R lists).
-// forced > 0 (options "ftopk.runs", "gtopk.runs") replaces it.  Always 1 <= R <= n_blocks.
+// forced > 0 (options "ftopk.runs", "gtopk.runs", "fstats.runs") replaces it.  Always 1 <= R <= n_blocks.
 constexpr uint32_t runs_per_query(uint32_t n_blocks, uint64_t n_active, uint32_t n_cu, int64_t forced) {
     if (n_blocks == 0) return 0;
     uint64_t r = 0;

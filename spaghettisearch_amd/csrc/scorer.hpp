@@ -126,7 +126,7 @@ struct Turn {
     ss::Event wave_ev;                         // "score.pipeline": behind k_score_wave on the context's wave stream; the merge on the caller's stream waits for it
     ss::Event slice_ev;                        // ... and behind the k_score_slices part of a split batch on ANOTHER wave stream
     ss::Event set_ev;                          // ... behind k_constraint_masks, when k_score_small runs on another stream
-    ss::PinBuf h_facet;                        // ss_facet_counts / ss_field_topk / ss_top_groups (match_set.hpp): the list table (and bucket table) go up through it (one set per turn,
+    ss::PinBuf h_facet;                        // ss_facet_counts / ss_field_topk / ss_top_groups / ss_field_stats / ss_field_histogram (match_set.hpp): the list table (and bucket table) go up through it (one set per turn,
     ss::DevBuf<unsigned char> d_facet;         // free after the wait for batch_ev like the plan's)
 };
 
@@ -311,6 +311,11 @@ struct ss_scorer {
     }
     ss::DevBuf<uint32_t> d_gtopk_rows;
     ss::DevBuf<unsigned char> d_gtopk_out;
+    // ss_field_stats / ss_field_histogram (field_stats.hip), grow-only, written and read on the context's stream only: the partial
+    // entries [group][runs][fields] or the counter rows [group][row stride] of one group of queries (bounded by option
+    // "fstats.scratch_bytes"; the groups of a call re-use the block in stream order) and the device block of HOST outputs, stats |
+    // n_match or counts | tails (the call waits before it returns)
+    ss::DevBuf<unsigned char> d_fstats_part, d_fstats_out;
     // ss_hit_proximity / ss_rerank_hits_by_proximity / ss_score_topk_proximity (proximity.hip).  prx: the turns the queries' table goes
     // up through, as exp / pas.  Grow-only, written and read on the context's stream only: the entries of a re-rank's window
     // [n_q][k_in] as six dwords each, between k_hit_proximity and k_prox_sort_hits, and the device block of HOST scores_out / prox_out,

@@ -28,6 +28,9 @@ VEC_HIT_DTYPE = np.dtype([("doc", "<u4"), ("score", "<i4")])   # ss_vec_hit
 
 GROUP_COUNT_DTYPE = np.dtype([("group", "<u4"), ("count", "<u4")])   # ss_group_count
 
+FIELD_STAT_DTYPE = np.dtype([("min", "<i8"), ("max", "<i8"), ("sum_lo", "<u8"), ("sum_hi", "<i8"), ("count", "<u4"), ("missing", "<u4")])   # ss_field_stat
+HIST_TAIL_DTYPE = np.dtype([("below", "<u4"), ("above", "<u4"), ("missing", "<u4"), ("n_match", "<u4")])   # ss_hist_tail
+
 DIV_INFO_DTYPE = np.dtype([("rel", "<i4"), ("sim", "<i4")])     # ss_div_info
 
 TREE_NODE_DTYPE = np.dtype([("feature", "<i4"), ("left", "<u4"), ("right", "<u4"), ("nan_left", "<u4"), ("value", "<f8")])   # ss_tree_node
@@ -1282,6 +1285,71 @@ class Scorer:
         if _is_torch(groups) and not getattr(self.ctx, "_shared_stream", False):
             self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
         return groups, n_out, n_groups, n_ungrouped, n_match
+
+    def field_stats(self, q_ptr, q_terms, fields, ranges=None, req=None, exc=None, mask_id=None, out=None):
+        """ss_field_stats: per query and per asked field the smallest and largest value, the exact 128-bit sum, and the numbers of docs
+        with and without a value (SS_NO_FIELD_VALUE = no value), over ALL docs facet_counts would count for the same q_ptr / q_terms,
+        ranges, req, exc and mask_id -> (stats FIELD_STAT_DTYPE [n_q][len(fields)], n_match uint32 [n_q]).  fields: field numbers, at
+        most SS_MAX_DOC_FIELDS, repeats allowed.  out = (stats, n_match | None): the caller's arrays (numpy, or torch device tensors —
+        stats as int64 [n_q][n][5], n_match int32: with device arrays throughout the call only enqueues), returned as they are."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        fields = np.ascontiguousarray(np.atleast_1d(fields), dtype=np.int32)
+        n_q, n_f = int(q_ptr.shape[0]) - 1, int(fields.shape[0])
+        if out is not None:
+            stats, n_match = out
+            nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+            if nbytes(stats) < n_q * n_f * FIELD_STAT_DTYPE.itemsize or (n_match is not None and nbytes(n_match) < n_q * 4):
+                raise ValueError("output buffers too small")
+        else:
+            stats = np.zeros((n_q, n_f), dtype=FIELD_STAT_DTYPE)
+            n_match = np.zeros(n_q, dtype=np.uint32)
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, stats, n_match)
+        check(self.ctx.lib.ss_field_stats(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                          _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), n_f, _ptr(fields) if n_f else None, _ptr(stats),
+                                          _ptr(n_match)), self.ctx.h)
+        if _is_torch(stats) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return stats, n_match
+
+    def field_histogram(self, q_ptr, q_terms, field: int, n_bins: int, origin: int = 0, width: int = 1, edges=None, ranges=None, req=None,
+                        exc=None, mask_id=None, out=None):
+        """ss_field_histogram: per query the number of docs facet_counts would count for the same q_ptr / q_terms, ranges, req, exc and
+        mask_id in every bin of a field -> (counts uint32 [n_q][n_bins], tails HIST_TAIL_DTYPE [n_q]: below, above, missing, n_match).
+        Fixed width (edges None): bin b holds origin + b * width <= value < origin + (b + 1) * width, width in [1, 2^64 - 1].  edges:
+        int64 [n_bins + 1] strictly ascending, bin b holds edges[b] <= value < edges[b + 1] (origin and width are ignored).  A doc
+        whose value is SS_NO_FIELD_VALUE counts as missing only.  n_bins <= SS_MAX_HIST_BINS.  out = (counts, tails | None): the
+        caller's arrays (numpy, or torch device tensors of int32 — tails as [n_q][4]: with device arrays throughout the call only
+        enqueues), returned as they are."""
+        q_ptr = _as(q_ptr, "uint32")
+        q_terms = _as(q_terms, "uint32")
+        rng_ptr, rng = (None, None) if ranges is None else (_as(ranges[0], "uint32"), np.ascontiguousarray(ranges[1], dtype=DOC_RANGE_DTYPE))
+        req_ptr, req_terms = (None, None) if req is None else (_as(req[0], "uint32"), _as(req[1], "uint32"))
+        exc_ptr, exc_terms = (None, None) if exc is None else (_as(exc[0], "uint32"), _as(exc[1], "uint32"))
+        mask_id = _as(mask_id, "int32")
+        edges = None if edges is None else np.ascontiguousarray(edges, dtype=np.int64)
+        n_q, n_bins = int(q_ptr.shape[0]) - 1, int(n_bins)
+        if edges is not None and n_bins >= 1 and edges.size < n_bins + 1:
+            raise ValueError("edges holds fewer than n_bins + 1 values")
+        if out is not None:
+            counts, tails = out
+            nbytes = lambda a: a.numel() * a.element_size() if _is_torch(a) else a.nbytes      # noqa: E731
+            if n_bins >= 1 and (nbytes(counts) < n_q * n_bins * 4 or (tails is not None and nbytes(tails) < n_q * HIST_TAIL_DTYPE.itemsize)):
+                raise ValueError("output buffers too small")
+        else:
+            counts = np.zeros((n_q, max(n_bins, 0)), dtype=np.uint32)
+            tails = np.zeros(n_q, dtype=HIST_TAIL_DTYPE)
+        self.ctx.ready(q_ptr, q_terms, req_ptr, req_terms, exc_ptr, exc_terms, mask_id, counts, tails)
+        check(self.ctx.lib.ss_field_histogram(self.h, n_q, _ptr(q_ptr), _ptr(q_terms), _ptr(mask_id), _ptr(req_ptr), _ptr(req_terms), _ptr(exc_ptr),
+                                              _ptr(exc_terms), _ptr(rng_ptr), _ptr(rng), int(field), int(origin), int(width), _ptr(edges), n_bins,
+                                              _ptr(counts), _ptr(tails)), self.ctx.h)
+        if _is_torch(counts) and not getattr(self.ctx, "_shared_stream", False):
+            self.ctx.synchronize()                  # (device outputs on the context's own stream: as score_topk)
+        return counts, tails
 
     def _window(self, hits, n_hits, k_in):
         """(hits, n_hits, n_q, k_in) of a result window as collapse_hits takes it"""

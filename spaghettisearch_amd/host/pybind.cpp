@@ -88,6 +88,23 @@ PYBIND11_MODULE(_host, m) {
         .def_readonly("Groups", &retrieval::GroupPage::Groups)
         .def_readonly("Ungrouped", &retrieval::GroupPage::Ungrouped)
         .def_readonly("Rows", &retrieval::GroupPage::Rows);
+    py::class_<retrieval::FieldStat>(m, "FieldStat")
+        .def_readonly("Min", &retrieval::FieldStat::Min)
+        .def_readonly("Max", &retrieval::FieldStat::Max)
+        .def_readonly("SumLo", &retrieval::FieldStat::SumLo)
+        .def_readonly("SumHi", &retrieval::FieldStat::SumHi)
+        .def_readonly("Count", &retrieval::FieldStat::Count)
+        .def_readonly("Missing", &retrieval::FieldStat::Missing)
+        .def("Mean", &retrieval::FieldStat::Mean);
+    py::class_<retrieval::FieldStatsRow>(m, "FieldStatsRow")
+        .def_readonly("Total", &retrieval::FieldStatsRow::Total)
+        .def_readonly("Fields", &retrieval::FieldStatsRow::Fields);
+    py::class_<retrieval::FieldHistogramRow>(m, "FieldHistogramRow")
+        .def_readonly("Total", &retrieval::FieldHistogramRow::Total)
+        .def_readonly("Below", &retrieval::FieldHistogramRow::Below)
+        .def_readonly("Above", &retrieval::FieldHistogramRow::Above)
+        .def_readonly("Missing", &retrieval::FieldHistogramRow::Missing)
+        .def_readonly("Counts", &retrieval::FieldHistogramRow::Counts);
     py::class_<retrieval::VectorHit>(m, "VectorHit")
         .def_readonly("DocHash", &retrieval::VectorHit::DocHash)
         .def_readonly("Score", &retrieval::VectorHit::Score);
@@ -257,6 +274,23 @@ PYBIND11_MODULE(_host, m) {
             return di.TopGroups(queries, rs, first, m);
         }, py::arg("queries"), py::arg("ranges") = std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>{}, py::arg("first") = 0,
            py::arg("m") = 10)
+        .def("FieldStats", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                              const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges, const std::vector<int32_t>& fields) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            return di.FieldStats(queries, rs, fields);
+        }, py::arg("queries"), py::arg("ranges"), py::arg("fields"))
+        .def("FieldHistogram", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries,
+                                  const std::vector<std::vector<std::tuple<int32_t, int64_t, int64_t>>>& ranges, int field, int64_t origin,
+                                  uint64_t width, int n_bins, py::object edges) {
+            std::vector<std::vector<retrieval::FieldRange>> rs(ranges.size());
+            for (size_t q = 0; q < ranges.size(); q++)
+                for (auto& r : ranges[q]) rs[q].push_back(retrieval::FieldRange{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+            if (edges.is_none()) return di.FieldHistogram(queries, rs, field, origin, width, n_bins);
+            return di.FieldHistogram(queries, rs, field, edges.cast<std::vector<int64_t>>());
+        }, py::arg("queries"), py::arg("ranges"), py::arg("field"), py::arg("origin") = 0, py::arg("width") = 1, py::arg("n_bins") = 1,
+           py::arg("edges") = py::none())
         .def("SortByField", [](retrieval::DeviceIndex& di, const std::vector<std::string>& queries, int field, bool descending, int k_window,
                                int first, int k, py::object topic_probs, bool live_topic_probs) {
             if (topic_probs.is_none()) return di.SortByField(queries, field, descending, k_window, first, k, nullptr, live_topic_probs);

@@ -135,6 +135,27 @@ struct GroupPage {
     std::vector<std::pair<std::string, uint32_t>> Rows;
 };
 
+// One query's numbers from DeviceIndex::FieldStats (no reference counterpart): Total = the docs the query matches (FacetCount::Total);
+// per asked field the smallest and largest value and the exact sum SumHi * 2^64 + SumLo (two's complement) over the Count matches that
+// have a value, and the Missing ones that have none (SS_NO_FIELD_VALUE); Count + Missing = Total.  Count 0: Min INT64_MAX, Max INT64_MIN.
+struct FieldStat {
+    int64_t Min = INT64_MAX, Max = INT64_MIN;
+    uint64_t SumLo = 0;
+    int64_t SumHi = 0;
+    uint32_t Count = 0, Missing = 0;
+    double Mean() const { return Count ? ((double)SumHi * 18446744073709551616.0 + (double)SumLo) / (double)Count : 0.0; }   // for display
+};
+struct FieldStatsRow {
+    uint32_t Total = 0;
+    std::vector<FieldStat> Fields;
+};
+// One query's bins from DeviceIndex::FieldHistogram: Counts [n_bins], the matches below the first and at or above the last bin, those
+// without a value, and Total = the sum of all of them = FacetCount::Total.
+struct FieldHistogramRow {
+    uint32_t Total = 0, Below = 0, Above = 0, Missing = 0;
+    std::vector<uint32_t> Counts;
+};
+
 // One page of a query's results sorted by a doc field (DeviceIndex::SortByField; no reference counterpart).  Values[i]: the field's
 // value of Results[i].
 struct FieldSortedPage {
@@ -2223,6 +2244,105 @@ public:
         }
         return out;
     }
+private:
+    // What FieldStats and FieldHistogram pass for M(q): the tokenised queries, the clauses of ranges[q] and, with SetQueryOperators, the
+    // "+word" / "-word" terms, read as in FacetCounts.  A query string with a quoted phrase is refused.
+    struct MatchQuery {
+        Tokenised t;
+        std::vector<uint32_t> rng_ptr{0}, req_ptr{0}, exc_ptr{0}, req_terms, exc_terms;
+        std::vector<ss_doc_range> rng;
+    };
+    MatchQuery match_query(const char* who, const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges) {
+        using namespace spaghetti;
+        if (!has_doc_fields) throw std::runtime_error(std::string(who) + ": no doc fields (SetDocFields)");
+        if (!ranges.empty() && ranges.size() != queries.size()) throw std::runtime_error(std::string(who) + ": one list of ranges per query, or none");
+        MatchQuery mq;
+        for (auto& rs : ranges) {
+            for (auto& r : rs) mq.rng.push_back(ss_doc_range{r.field, 0, r.lo, r.hi});
+            mq.rng_ptr.push_back((uint32_t)mq.rng.size());
+        }
+        std::vector<std::string> rewritten;
+        const std::vector<std::string>* qs = &queries;
+        if (query_operators) {
+            auto id_of = [&](const std::string& w) -> uint32_t {
+                auto it = terms.id.find(md5::hex(w));
+                return it == terms.id.end() ? SS_UNKNOWN_TERM : it->second;
+            };
+            for (auto& q : queries) {
+                const QueryOperators op = parseQueryOperators(q, laundry);
+                rewritten.push_back(op.query);
+                for (auto& w : op.required) mq.req_terms.push_back(id_of(w));
+                for (auto& w : op.excluded) mq.exc_terms.push_back(id_of(w));
+                mq.req_ptr.push_back((uint32_t)mq.req_terms.size());
+                mq.exc_ptr.push_back((uint32_t)mq.exc_terms.size());
+            }
+            qs = &rewritten;
+        }
+        mq.t = tokenise(*qs, nullptr, false);
+        if (!mq.t.p_terms.empty()) throw std::runtime_error(std::string(who) + ": quoted phrases are not counted");
+        return mq;
+    }
+public:
+    // The range, the exact sum and the missing count of doc fields over ALL docs every query matches (ss_field_stats): the docs FacetCounts
+    // counts under the clauses of ranges[q] (an empty `ranges`: none for any query); fields: at most SS_MAX_DOC_FIELDS field numbers.
+    std::vector<FieldStatsRow> FieldStats(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges,
+                                          const std::vector<int32_t>& fields) {
+        using namespace spaghetti;
+        const MatchQuery mq = match_query("FieldStats", queries, ranges);
+        const size_t nq = (size_t)mq.t.nq, nf = fields.size();
+        std::vector<ss_field_stat> stats(nq * std::max<size_t>(nf, 1));
+        std::vector<uint32_t> n_match(nq);
+        check(ss_field_stats(scorer, mq.t.nq, mq.t.q_ptr.data(), mq.t.q_terms.data(), nullptr, query_operators ? mq.req_ptr.data() : nullptr,
+                             mq.req_terms.data(), query_operators ? mq.exc_ptr.data() : nullptr, mq.exc_terms.data(),
+                             ranges.empty() ? nullptr : mq.rng_ptr.data(), mq.rng.data(), (int32_t)nf, nf ? fields.data() : nullptr, stats.data(),
+                             n_match.data()), "ss_field_stats");
+        std::vector<FieldStatsRow> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Total = n_match[q];
+            for (size_t i = 0; i < nf; i++) {
+                const ss_field_stat& s = stats[q * nf + i];
+                FieldStat f;
+                f.Min = s.min; f.Max = s.max; f.SumLo = s.sum_lo; f.SumHi = s.sum_hi; f.Count = s.count; f.Missing = s.missing;
+                out[q].Fields.push_back(f);
+            }
+        }
+        return out;
+    }
+    // The matches per bin of a doc field over ALL docs every query matches (ss_field_histogram), "matches per month": bin b holds
+    // origin + b * width <= value < origin + (b + 1) * width; with edges, edges[b] <= value < edges[b + 1] (n_bins = edges.size() - 1,
+    // strictly ascending).  n_bins <= SS_MAX_HIST_BINS.
+    std::vector<FieldHistogramRow> FieldHistogram(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges,
+                                                  int field, int64_t origin, uint64_t width, int n_bins) {
+        return field_histogram(queries, ranges, field, origin, width, nullptr, n_bins);
+    }
+    std::vector<FieldHistogramRow> FieldHistogram(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges,
+                                                  int field, const std::vector<int64_t>& edges) {
+        if (edges.size() < 2) throw std::runtime_error("FieldHistogram: at least two edges");
+        return field_histogram(queries, ranges, field, 0, 1, edges.data(), (int)(edges.size() - 1));
+    }
+private:
+    std::vector<FieldHistogramRow> field_histogram(const std::vector<std::string>& queries, const std::vector<std::vector<FieldRange>>& ranges,
+                                                   int field, int64_t origin, uint64_t width, const int64_t* edges, int n_bins) {
+        using namespace spaghetti;
+        const MatchQuery mq = match_query("FieldHistogram", queries, ranges);
+        const size_t nq = (size_t)mq.t.nq, nb = (size_t)std::max(n_bins, 1);
+        std::vector<uint32_t> counts(nq * nb);
+        std::vector<ss_hist_tail> tails(nq);
+        check(ss_field_histogram(scorer, mq.t.nq, mq.t.q_ptr.data(), mq.t.q_terms.data(), nullptr, query_operators ? mq.req_ptr.data() : nullptr,
+                                 mq.req_terms.data(), query_operators ? mq.exc_ptr.data() : nullptr, mq.exc_terms.data(),
+                                 ranges.empty() ? nullptr : mq.rng_ptr.data(), mq.rng.data(), field, origin, width, edges, n_bins, counts.data(),
+                                 tails.data()), "ss_field_histogram");
+        std::vector<FieldHistogramRow> out(nq);
+        for (size_t q = 0; q < nq; q++) {
+            out[q].Total = tails[q].n_match;
+            out[q].Below = tails[q].below;
+            out[q].Above = tails[q].above;
+            out[q].Missing = tails[q].missing;
+            out[q].Counts.assign(counts.begin() + q * nb, counts.begin() + (q + 1) * nb);
+        }
+        return out;
+    }
+public:
     // RetrieveBatch sorted by a doc field (SetDocFields): page [first, first + k) of the first k_window rows of every query's ranking,
     // sorted stably by the field, ascending or descending ("newest first": field 0, descending).  Query operators are not read here.
     std::vector<FieldSortedPage> SortByField(const std::vector<std::string>& queries, int field, bool descending, int k_window, int first = 0,
